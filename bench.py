@@ -12,10 +12,13 @@ work is fixed).  With mixers enabled and N > 1 the per-rank mixer sums are all-r
 not already running under a launcher -- the analogue of the reference's one demodulate() pthread per device shard
 (src/rtl_airband.cpp:1110-1112) -- and refuses to report anything if the world size it ends up with is not N.
 
-After the timed region, outside it: `--verify K` (default 16) re-checks K sampled dongles of the very buffers that were
+A plain run sets up, warms up, times --steps steps and reports them; `--dump-outputs DIR` then writes a fixed, seeded sample of what
+the last timed step computed as DIR/*.npy (see dump_outputs()).  Everything else the benchmark measures or checks runs only with
+`--full`, after the timed region: `--verify K` (default 16) re-checks K sampled dongles of the very buffers that were
 benchmarked against the CPU oracle (oracle/pyverify.py); `--traffic` (default on at N = 1) re-runs a few steps under
 rocprofv3 `--pmc FETCH_SIZE` / `--pmc WRITE_SIZE` (separate passes) to MEASURE the channelizer's HBM traffic in this run;
-the CPU baseline times the reference's own demodulate() on the host cores.
+the CPU baseline times the reference's own demodulate() on the host cores; the whole-handle replica check, the open-fraction
+pass, the pipelined throughput mode and `--host-path` run there too.
 
 Prints ONE JSON line on rank 0.
 """
@@ -197,6 +200,37 @@ def cpu_baseline(pkg, devices, wave_rate, mixed, seconds):
     return out
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: bytes of sampled result rows; with the index and statistics files the directory stays under 64 MB
+
+
+def dump_outputs(out_dir, hip, dongles, channels_per_dongle, n_mixers):
+    """--dump-outputs: what a caller of the timed path receives for its last batch (airband_hip_collect_channels, airband_hip_collect_mixers), for a
+    fixed seeded sample of the handle's dongles, so that two builds can be compared output for output.  Files (C = channels per dongle, B = WAVE_BATCH):
+      dongles.npy [n] float64: the sampled dongle indices, ascending
+      waveout.npy [n C, B] float32: audio rows;  iq_out.npy [n C, 2 B] float32: raw I/Q rows (only where the handle emits I/Q)
+      axcindicate.npy [n C] float32: the character codes of ' ', '*', '<', '>'
+      channel_stats.npy [n C, 12] float64: airband_hip_channel_stats, fields in declaration order without `reserved`
+      mixer_left.npy, mixer_right.npy [mixers, B] float32, mixer_signal.npy [mixers] float32: with --mixers"""
+    import numpy as np
+
+    has_iq = bool(hip.device_results()["iq_out"])
+    n = min(dongles, max(1, DUMP_BYTES // (channels_per_dongle * hip.B * 4 * (3 if has_iq else 1))))
+    picked = np.sort(np.random.default_rng(0x5EED).choice(dongles, n, replace=False))
+    rows = [hip.collect(iq=has_iq, stats=True, first_channel=int(d) * channels_per_dongle, n_channels=channels_per_dongle) for d in picked]
+    fields = [k for k in rows[0]["stats"][0] if k != "reserved"]
+    arrays = dict(dongles=picked.astype(np.float64), waveout=np.concatenate([r["waveout"] for r in rows]),
+                  axcindicate=np.concatenate([r["axc"] for r in rows]).astype(np.float32),
+                  channel_stats=np.array([[s[k] for k in fields] for r in rows for s in r["stats"]], np.float64))
+    if has_iq:
+        arrays["iq_out"] = np.concatenate([r["iq_out"] for r in rows])
+    if n_mixers:
+        left, right, signal = hip.collect_mixers()
+        arrays.update(mixer_left=left, mixer_right=right, mixer_signal=signal.astype(np.float32))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def free_port() -> int:
     with socket.socket(socket.AF_INET, socket.SOCK_STREAM) as s:
         s.bind(("127.0.0.1", 0))
@@ -367,6 +401,9 @@ def main():
                     "4^8 = 65 536 distinct groups of eight bins, one coefficient table each.  Default 1 = SURVEY 8d's fleet of identical dongles")
     ap.add_argument("--mixers", type=int, default=0, help="number of mixers (BASELINE configs[4]: 64). Default 0 at every N, so that per-GPU work is the same "
                     "from 1 to 8 GPUs (configs[1]-[3] have no exchange step); with mixers and N > 1 the per-rank sums are all-reduced over RCCL every step")
+    ap.add_argument("--full", action="store_true", help="after the timed region, also run every measurement and check the headline figure does not need -- the CPU baseline "
+                    "(--cpu-seconds), --verify, --verify-all, the open fraction, --throughput-mode, --traffic and --host-path run only with it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write a fixed seeded sample of the last step's results as DIR/<name>.npy (dump_outputs())")
     ap.add_argument("--cpu-seconds", type=float, default=16.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--verify", type=int, default=16, help="after the timed region, compare this many sampled dongles of the benchmarked handle with the CPU oracle (0 = off)")
@@ -387,6 +424,10 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="launcher check without GPUs: form the N-rank group over gloo, print the JSON skeleton")
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)  # profiled child of measure_traffic(): steps only, no extras, no JSON
     args = ap.parse_args()
+    if not args.full:  # a plain run is repeated for every measurement of a build: it does what its headline figure needs and nothing else
+        if args.host_path:
+            ap.error("--host-path is measured with --full")
+        args.verify, args.verify_all, args.traffic, args.throughput_mode, args.no_cpu_baseline = 0, False, False, False, True
 
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
@@ -546,6 +587,8 @@ def main():
     ch_ms, demod_ms, emit_ms = tt["channelizer_ms"] / nb, tt["demod_ms"] / nb, tt["emit_ms"] / nb
     hip.flush()
     sync()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, hip, D, len(chans), n_mixers)
     total_steps = args.warmup + args.steps
     if use_dist:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
@@ -637,7 +680,7 @@ def main():
         except Exception as e:  # noqa: BLE001
             out["verified_dongles"] = 0
             out["verify"] = dict(error="spot check could not run: %r" % (e,))
-    if rank == 0 and not args.pipelined:
+    if args.full and rank == 0 and not args.pipelined:
         # how busy the benchmarked signal keeps the squelches: one more pass over the resident ring (untimed), share of channels whose batch had signal
         try:
             total_ch = hip.geometry.total_channels

@@ -13,7 +13,7 @@ WORK=(); while [ $# -gt 0 ] && [ "$1" != "--" ]; do WORK+=("$1"); shift; done; [
 LIBS=("base:$GRAFT_REPO_ROOT/_base/rtlsdr-airband_amd/libairband_hip.so" "new:$L/libairband_hip.so")
 for t in "$@"; do LIBS+=("$t:$L/libairband_hip_exp_$t.so"); done
 [ -n "$TESTS" ] && { timeout 1200 python -m pytest $TESTS -m gpu -x -q > $O/parity.log 2>&1; tail -3 $O/parity.log; }
-N="--no-cpu-baseline --no-traffic --no-verify-all --verify 4 --steps 40"
+N="--full --no-cpu-baseline --no-traffic --no-verify-all --verify 4 --steps 40"
 for round in 1 2; do
   for w in "${!WORK[@]}"; do
     for l in "${LIBS[@]}"; do

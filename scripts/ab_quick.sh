@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 O=$GRAFT_REPO_ROOT/gpurun_out/abq; rm -rf $O; mkdir -p $O
 timeout 135 python -m pytest tests -m gpu -x -q > $O/parity.log 2>&1; tail -3 $O/parity.log
-N="--no-cpu-baseline --no-traffic --no-verify-all --verify 4 --steps 30 --warmup 3"
+N="--full --no-cpu-baseline --no-traffic --no-verify-all --verify 4 --steps 30 --warmup 3"
 i=0
 for l in new base new base; do
   i=$((i+1))

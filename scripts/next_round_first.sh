@@ -11,8 +11,8 @@ O=$GRAFT_REPO_ROOT/gpurun_out/first; rm -rf $O; mkdir -p $O
 (nproc; cat /sys/fs/cgroup/cpu.max) > $O/host_cpus.txt 2>&1
 timeout 1500 python -m pytest tests -x -q -m gpu --durations=8 > $O/gpu_suite.log 2>&1; tail -14 $O/gpu_suite.log
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; tail -n 1 $O/smoke.log
-timeout 900 python bench.py 2>$O/bench_cfg3.err | tail -n 1 > $O/bench_cfg3.json; cut -c1-400 $O/bench_cfg3.json; tail -2 $O/bench_cfg3.err
-N="--no-cpu-baseline --no-traffic --no-verify-all --verify 4 --steps 24"
+timeout 900 python bench.py --full 2>$O/bench_cfg3.err | tail -n 1 > $O/bench_cfg3.json; cut -c1-400 $O/bench_cfg3.json; tail -2 $O/bench_cfg3.err
+N="--full --no-cpu-baseline --no-traffic --no-verify-all --verify 4 --steps 24"
 timeout 300 python bench.py $N --sample-rate 2000000 2>/dev/null | tail -n 1 > $O/bench_cfg3_2000k.json; cut -c1-200 $O/bench_cfg3_2000k.json
 timeout 300 python bench.py $N --steps 12 --sample-format f32 --ring 1 --dongles 32768 2>/dev/null | tail -n 1 > $O/bench_f32_32768.json; cut -c1-200 $O/bench_f32_32768.json
 timeout 300 python bench.py $N --steps 12 --workload cfg2 --sample-format f32 --ring 1 --dongles 16384 2>/dev/null | tail -n 1 > $O/bench_f32_am16384.json; cut -c1-200 $O/bench_f32_am16384.json

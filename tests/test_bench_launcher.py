@@ -1,10 +1,12 @@
 """bench.py's own N-rank launch (no GPU needed): `python bench.py --gpus N` must form an N-rank job by itself -- the analogue
 of the reference starting one demodulate() thread per device shard (src/rtl_airband.cpp:1110-1112) -- report that N, and
-refuse to report anything for a different world size."""
+refuse to report anything for a different world size.  With a GPU: what a plain run reports and what --dump-outputs writes."""
 import json
 import os
 import subprocess
 import sys
+
+import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -57,3 +59,37 @@ def test_bench_uses_only_names_the_package_has():
         assert hasattr(pkg, name), "bench.py uses <package>.%s" % name
     for name in set(re.findall(r"\bhip\.([a-z_]\w*)\(", src)):
         assert hasattr(pkg.AirbandHip, name), "bench.py calls AirbandHip.%s" % name
+
+
+@pytest.mark.gpu
+def test_plain_run_times_the_steps_and_dumps_the_last_one(built, tmp_path):
+    """A plain run (no --full) times exactly --steps steps and does nothing else; --dump-outputs writes the last step's sampled results as float32 /
+    float64 .npy files of at most 64 MB, and two runs with the same arguments write the same arrays."""
+    import numpy as np
+
+    dumps = []
+    for k in range(2):
+        d = str(tmp_path / ("run%d" % k))
+        r = _run(["--gpus", "1", "--workload", "tiny", "--steps", "3", "--warmup", "1", "--dump-outputs", d], timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = _json(r.stdout)
+        assert out["steps"] == 3 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["value"] > 0
+        assert out["unit"] == "Msamples/s" and out["higher_is_better"] is True and out["dtype"]
+        assert not {"verify", "verify_all", "open_fraction", "throughput_mode", "host_path"} & set(out), sorted(out)
+        assert out["cpu_baseline"] is None and out["roofline"]["traffic"] is None
+        arrays = {f: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        assert sum(os.path.getsize(os.path.join(d, f)) for f in arrays) <= 64 << 20
+        dumps.append(arrays)
+    a, b = dumps
+    assert {"dongles.npy", "waveout.npy", "axcindicate.npy", "channel_stats.npy"} <= set(a) and set(a) == set(b)
+    assert np.array_equal(a["dongles.npy"], np.arange(64)), "the tiny workload's 64 dongles all fit the sample"
+    assert a["waveout.npy"].shape[0] == a["axcindicate.npy"].shape[0] == a["channel_stats.npy"].shape[0] == 64 * 8
+    assert np.abs(a["waveout.npy"]).max() > 0
+    for f in a:
+        assert np.array_equal(a[f], b[f], equal_nan=True), f
+
+
+def test_host_path_needs_full():
+    r = _run(["--gpus", "1", "--host-path"])
+    assert r.returncode != 0 and "--full" in r.stderr

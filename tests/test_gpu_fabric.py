@@ -225,8 +225,8 @@ def test_bench_with_two_ranks_on_one_gpu(tmp_path):
     env.update(AIRBAND_HIP_RCCL_LIB=FAKE_RCCL, FAKE_RCCL_LOG=str(tmp_path / "fake_rccl.log"), AIRBAND_BENCH_LOCAL_DEVICE="0", AIRBAND_BENCH_DIST_BACKEND="gloo",
                HSA_ENABLE_IPC_MODE_LEGACY="0")
     env.pop("AIRBAND_BENCH_SPAWNED", None)
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--mixers", "64", "--steps", "6", "--warmup", "2", "--no-cpu-baseline",
-           "--verify", "2"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--workload", "tiny", "--mixers", "64", "--steps", "6", "--warmup", "2", "--full",
+           "--no-cpu-baseline", "--verify", "2"]
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=540, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
