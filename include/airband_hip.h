@@ -183,6 +183,44 @@ typedef struct airband_hip_handle airband_hip_handle;
  * Returns 0 or a negative AIRBAND_HIP_E* code; *out is NULL on failure. */
 int airband_hip_prepare(const airband_hip_config* cfg, airband_hip_handle** out);
 
+/* ---- scan-mode devices ------------------------------------------------------------------------
+ * A scan device (reference: dev->mode == R_SCAN, src/config.cpp:361-650) has exactly one channel (:822-825) and a list of frequencies
+ * (channel->freqlist) that the controller thread hops over (src/rtl_airband.cpp:101-139: after 10 polls of 200 ms with axcindicate ==
+ * NO_SIGNAL it advances freq_idx and retunes the dongle).  demodulate() works on freqlist[freq_idx], read once per batch (:498).
+ *   freqs[0 .. freq_count) are the list's entries as parse_channels() leaves them (modulations, squelch_threshold, squelch_snr_threshold, notch,
+ *   notch_q, ctcss, bandwidth and ampfactor may each be given per frequency); freqs[0] must be byte-equal to devices[device].channels[0].
+ *   Channel-level values come from freqs[0]: afc, tau_us and has_iq_outputs must be the same in every entry, and `frequency` of freqs[0] fixes the
+ *   bin and dm_dphi (:666-667, :679-712 -- the dongle is retuned so that every entry lands on that bin); the other entries' `frequency` is
+ *   informational.  The channel needs raw I/Q if ANY entry does (needs_raw_iq, :671-678).
+ * State: what a freq_t owns (src/rtl_airband.h:223-233: agcavgfast, ampfactor, the Squelch with its CTCSS detectors and its 102-sample delay line,
+ *   active_counter, the notch and lowpass filters, the modulation) is kept per entry and frozen while the entry is not the active one; what the
+ *   channel_t owns (:234-263: the wavein / waveout history, pr, pj, prev_waveout, alpha, dm_phi, dm_dphi, axcindicate, AFC, the bin) carries on
+ *   across switches, as in the reference. */
+typedef struct airband_hip_scan_cfg {
+    int32_t device;                       /* index into cfg->devices; that device has channel_count == 1                               */
+    int32_t freq_count;                   /* >= 1                                                                                      */
+    const airband_hip_channel_cfg* freqs; /* freqlist[0 .. freq_count); freqs[0] must equal devices[device].channels[0]                */
+} airband_hip_scan_cfg;
+
+/* airband_hip_prepare() with n_scan scan lists (scan may be NULL when n_scan == 0; airband_hip_prepare(cfg, out) is exactly
+ * airband_hip_prepare_scan(cfg, NULL, 0, out)).  The lists are validated before any device is touched: AIRBAND_HIP_EINVAL for a device listed twice,
+ * a scan device whose channel_count is not 1, freq_count < 1, freqs[0] not byte-equal to the device's channel, entries that differ in afc, tau_us or
+ * has_iq_outputs, and an NFM entry at wave_rate 8000.  A handle without scan lists does exactly the work airband_hip_prepare()'s does.
+ * A list of more than one entry puts its channel in a demod wavefront of its own (an entry's squelch counts only the batches it was active in, and the
+ * demod kernels keep those counts per wavefront), and such a handle does not regroup stage 2 (AIRBAND_HIP_FLAG_REGROUP is ignored). */
+int airband_hip_prepare_scan(const airband_hip_config* cfg, const airband_hip_scan_cfg* scan, int32_t n_scan, airband_hip_handle** out);
+
+/* Makes entry freq_idx of device dev's list the one in force for every batch enqueued from now on (by airband_hip_process, _process_device or
+ * _process_bins): channel->freq_idx as the controller thread sets it (src/rtl_airband.cpp:101-139).  The index is latched per batch: on an
+ * AIRBAND_HIP_FLAG_PIPELINE handle stage 2 of a batch, which runs during the next call, uses the index that was in force when the batch was
+ * enqueued.  AIRBAND_HIP_EINVAL for a device without a scan list or an index out of range (nothing changes then). */
+int airband_hip_set_freq_index(airband_hip_handle* h, int32_t dev, int32_t freq_idx);
+
+/* Squelch / AGC statistics of entry freq_idx of device dev's list as of the last completed batch -- what the stats file prints for every entry
+ * (src/output.cpp:615-720).  Entries that were not active report the values they were frozen with.  Computed by the same code as the rows of
+ * airband_hip_collect(), bit for bit; that row of a scan channel describes the entry that was active in the batch. */
+int airband_hip_freq_stats(airband_hip_handle* h, int32_t dev, int32_t freq_idx, airband_hip_channel_stats* out);
+
 /* Optional: wire channels into mixers before the first batch (reference: src/config.cpp mixer outputs,
  * src/mixer.cpp:57-94).  mixer_count mixers, n_inputs connections. */
 int airband_hip_set_mixers(airband_hip_handle* h, int32_t mixer_count, const airband_hip_mixer_input* inputs, int32_t n_inputs);

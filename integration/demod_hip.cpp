@@ -16,10 +16,17 @@
 #include <unistd.h>
 
 #include <libconfig.h++>
+#include <map>
 #include <vector>
 
 #include "airband_hip.h"
 #include "rtl_airband.h"
+
+// The scan-mode entry points are weak references: a host that forwards only the multichannel ones still links, and runs every configuration
+// without scan-mode devices; one with such a device needs them (demodulate_hip refuses it otherwise).
+extern "C" int airband_hip_prepare_scan(const airband_hip_config* cfg, const airband_hip_scan_cfg* scan, int32_t n_scan, airband_hip_handle** out)
+    __attribute__((weak));
+extern "C" int airband_hip_set_freq_index(airband_hip_handle* h, int32_t dev, int32_t freq_idx) __attribute__((weak));
 
 extern int tui;  // rtl_airband.cpp:75 (set by -f / cleared by -F; only rtl_airband.cpp reads it in the reference)
 
@@ -38,7 +45,33 @@ static float num_of(libconfig::Setting& s) {
     libconfig::Setting& v = first_of(s);
     return v.getType() == libconfig::Setting::TypeFloat ? (float)v : (float)(int)v;
 }
+// Scan mode (config.cpp:361-650): those keys may be lists with one element per frequency.  Element f of each, for every entry of the
+// frequency list, kept in a side table keyed by channel->freqlist -- that pointer survives the XREALLOC of dev->channels (config.cpp:825).
+struct hip_freq_cfg {
+    int squelch_threshold, bandwidth;
+    float squelch_snr, notch, notch_q, ctcss;
+};
+static std::map<const freq_t*, std::vector<hip_freq_cfg> > g_scan_cfg;
+static float num_at(libconfig::Setting& s, int f) {
+    libconfig::Setting& v = s.getType() == libconfig::Setting::TypeList ? s[f] : s;
+    return v.getType() == libconfig::Setting::TypeFloat ? (float)v : (float)(int)v;
+}
+
 void demod_hip_keep_channel_cfg(libconfig::Setting& chan, channel_t* channel) {
+    std::vector<hip_freq_cfg>& fc = g_scan_cfg[channel->freqlist];
+    fc.resize(channel->freq_count);
+    for (int f = 0; f < channel->freq_count; f++) {
+        hip_freq_cfg& c = fc[f];
+        c.squelch_threshold = chan.exists("squelch_threshold") ? (int)num_at(chan["squelch_threshold"], f) : 0;
+        c.squelch_snr = chan.exists("squelch_snr_threshold") ? num_at(chan["squelch_snr_threshold"], f) : -1.0f;
+        c.notch = chan.exists("notch") ? num_at(chan["notch"], f) : 0.0f;
+        c.notch_q = chan.exists("notch_q") ? num_at(chan["notch_q"], f) : 0.0f;
+        c.ctcss = chan.exists("ctcss") ? num_at(chan["ctcss"], f) : 0.0f;
+        c.bandwidth = chan.exists("bandwidth") ? (int)num_at(chan["bandwidth"], f) : 0;
+        if (c.notch < 0) c.notch = 0;  // "invalid, ignoring" (config.cpp:541,556)
+        if (c.ctcss < 0) c.ctcss = 0;  // config.cpp:575,584
+        if (c.bandwidth < 0) c.bandwidth = 0;  // config.cpp:601,609
+    }
     channel->cfg_squelch_threshold = chan.exists("squelch_threshold") ? (int)num_of(chan["squelch_threshold"]) : 0;
     channel->cfg_squelch_snr = chan.exists("squelch_snr_threshold") ? num_of(chan["squelch_snr_threshold"]) : -1.0f;
     channel->cfg_notch = chan.exists("notch") ? num_of(chan["notch"]) : 0.0f;
@@ -73,6 +106,27 @@ static airband_hip_channel_cfg channel_cfg_of(const channel_t* ch) {
     c.ampfactor = f->ampfactor;
     c.tau_us = ch->cfg_tau;
     c.has_iq_outputs = ch->has_iq_outputs;
+    return c;
+}
+
+// Entry f of a scan channel's frequency list: the channel's own values, the freq_t's frequency / modulation / ampfactor and the per-frequency keys
+static airband_hip_channel_cfg scan_entry_of(const channel_t* ch, int f) {
+    airband_hip_channel_cfg c = channel_cfg_of(ch);
+    if (f == 0) return c;  // byte-equal to the device's channel, as airband_hip_prepare_scan() requires
+    const freq_t* fq = ch->freqlist + f;
+    c.frequency = fq->frequency;
+    c.modulation = fq->modulation == MOD_AM ? AIRBAND_MOD_AM : AIRBAND_MOD_NFM;
+    c.ampfactor = fq->ampfactor;
+    std::map<const freq_t*, std::vector<hip_freq_cfg> >::const_iterator it = g_scan_cfg.find(ch->freqlist);
+    if (it != g_scan_cfg.end() && f < (int)it->second.size()) {
+        const hip_freq_cfg& e = it->second[f];
+        c.squelch_threshold_dbfs = e.squelch_threshold;
+        c.squelch_snr_threshold_db = e.squelch_snr;
+        c.notch_freq = e.notch;
+        c.notch_q = e.notch_q;
+        c.ctcss_freq = e.ctcss;
+        c.bandwidth_hz = e.bandwidth;
+    }
     return c;
 }
 
@@ -117,6 +171,7 @@ struct hip_part {
     std::vector<float> wave, iq;
     std::vector<char> axc;
     std::vector<airband_hip_channel_stats> st;
+    std::vector<int> batch_freq;  // per device: freq_idx of its scan channel as the batch was enqueued (rtl_airband.cpp:498), 0 in multichannel mode
     bool have_batch;
 };
 
@@ -162,8 +217,23 @@ static void prepare_part(hip_part& k) {
     cfg.hip_device = k.gpu;
     cfg.device_count = n;
     cfg.devices = dv.data();
+    std::vector<std::vector<airband_hip_channel_cfg> > sf;
+    std::vector<airband_hip_scan_cfg> scan;
+    for (int i = 0; i < n; i++) {
+        device_t* dev = devices + k.devs[i];
+        if (dev->mode != R_SCAN) continue;
+        std::vector<airband_hip_channel_cfg> e;
+        for (int f = 0; f < dev->channels[0].freq_count; f++) e.push_back(scan_entry_of(dev->channels, f));
+        sf.push_back(e);
+        airband_hip_scan_cfg sc;
+        sc.device = i;
+        sc.freq_count = dev->channels[0].freq_count;
+        sc.freqs = NULL;
+        scan.push_back(sc);
+    }
+    for (size_t s = 0; s < scan.size(); s++) scan[s].freqs = sf[s].data();
     k.h = NULL;
-    switch (airband_hip_prepare(&cfg, &k.h)) {  // the convention of gpu_fft_prepare() (rtl_airband.cpp:296-310)
+    switch (scan.empty() ? airband_hip_prepare(&cfg, &k.h) : airband_hip_prepare_scan(&cfg, scan.data(), (int32_t)scan.size(), &k.h)) {  // the convention of gpu_fft_prepare() (rtl_airband.cpp:296-310)
         case AIRBAND_HIP_OK:
             break;
         case AIRBAND_HIP_ENODEV:
@@ -188,6 +258,7 @@ static void prepare_part(hip_part& k) {
     k.axc.resize(k.g.total_channels);
     k.st.resize(k.g.total_channels);
     k.parked.assign(n, 0);
+    k.batch_freq.assign(n, 0);
     k.live = n;
     k.have_batch = false;
 }
@@ -402,22 +473,29 @@ static void part_collect(hip_class* c, int p) {
             memcpy(ch->waveout, &k.wave[q * k.g.wave_batch], sizeof(float) * k.g.wave_batch);
             if (ch->has_iq_outputs) memcpy(ch->iq_out, &k.iq[q * k.g.wave_batch * 2], sizeof(float) * 2 * k.g.wave_batch);
             ch->axcindicate = (status)k.axc[q];
-            ch->freqlist->active_counter = st.active_counter;
-            ch->freqlist->agcavgfast = st.agcavgfast;
-            ch->freqlist->squelch.mirror(st.noise_level, st.signal_level, st.squelch_level, st.open_count, st.flappy_count, st.ctcss_count, st.no_ctcss_count,
+            freq_t* fq = ch->freqlist + k.batch_freq[i];  // the entry that was active in this batch
+            fq->active_counter = st.active_counter;
+            fq->agcavgfast = st.agcavgfast;
+            fq->squelch.mirror(st.noise_level, st.signal_level, st.squelch_level, st.open_count, st.flappy_count, st.ctcss_count, st.no_ctcss_count,
                                          st.signal_outside_filter != 0);
         }
     }
 }
 
 // The waterfall line of one device for the batch just published (rtl_airband.cpp:632-643) and its scroll (:663-667)
-static void tui_line(int device_num, device_t* dev) {
+static void tui_line(int device_num, device_t* dev, int freq_idx) {
     for (int i = 0; i < dev->channel_count; i++) {
         channel_t* channel = dev->channels + i;
-        freq_t* fparms = channel->freqlist;
+        freq_t* fparms = channel->freqlist + freq_idx;
         char symbol = fparms->squelch.signal_outside_filter() ? '~' : (char)channel->axcindicate;
-        GOTOXY(i * 10, device_num * 17 + dev->row + 3);
-        printf("%4.0f/%3.0f%c ", level_to_dBFS(fparms->squelch.signal_level()), level_to_dBFS(fparms->squelch.noise_level()), symbol);
+        if (dev->mode == R_SCAN) {
+            GOTOXY(0, device_num * 17 + dev->row + 3);
+            printf("%4.0f/%3.0f%c %7.3f ", level_to_dBFS(fparms->squelch.signal_level()), level_to_dBFS(fparms->squelch.noise_level()), symbol,
+                   (dev->channels[0].freqlist[freq_idx].frequency / 1000000.0));
+        } else {
+            GOTOXY(i * 10, device_num * 17 + dev->row + 3);
+            printf("%4.0f/%3.0f%c ", level_to_dBFS(fparms->squelch.signal_level()), level_to_dBFS(fparms->squelch.noise_level()), symbol);
+        }
         fflush(stdout);
     }
 }
@@ -426,8 +504,8 @@ void* demodulate_hip(void* params) {
     demod_params_t* dp = (demod_params_t*)params;  // device_start / device_end shard (rtl_airband.h demod_params_t)
     std::vector<hip_class> classes;
     for (int d = dp->device_start; d < dp->device_end; d++) {
-        if (devices[d].mode != R_MULTICHANNEL) {  // scan mode retunes the dongle between batches (rtl_airband.cpp:556-565 of the controller thread)
-            log(LOG_CRIT, "airband_hip: device %d is in scan mode; the GPU backend demodulates multichannel devices only\n", d);
+        if (devices[d].mode == R_SCAN && (!airband_hip_prepare_scan || !airband_hip_set_freq_index)) {
+            log(LOG_CRIT, "airband_hip: device %d is in scan mode and this libairband_hip has no airband_hip_prepare_scan\n", d);
             error();
         }
         size_t c = 0;
@@ -515,6 +593,12 @@ void* demodulate_hip(void* params) {
                 hip_part& k = cls.parts[p];
                 k.have_batch = false;
                 if (k.live == 0) continue;
+                for (size_t i = 0; i < k.devs.size(); i++) {  // scan mode: freq_idx is read once per batch (rtl_airband.cpp:498)
+                    device_t* dev = devices + k.devs[i];
+                    if (dev->mode != R_SCAN) continue;
+                    k.batch_freq[i] = dev->channels[0].freq_idx;
+                    hip_check(k.h, airband_hip_set_freq_index(k.h, (int32_t)i, k.batch_freq[i]), "set_freq_index");
+                }
                 const int rc = airband_hip_process(k.h);
                 if (rc == AIRBAND_HIP_EAGAIN) continue;
                 if (rc < 0) {
@@ -552,7 +636,7 @@ void* demodulate_hip(void* params) {
                 for (size_t i = 0; i < k.devs.size(); i++) {
                     device_t* dev = devices + k.devs[i];
                     if (dev->input->state != INPUT_RUNNING || k.parked[i]) continue;
-                    if (tui) tui_line(k.devs[i], dev);
+                    if (tui) tui_line(k.devs[i], dev, k.batch_freq[i]);
                     if (dev->waveavail == 1) {  // rtl_airband.cpp:649-654: the output thread has not drained the previous batch
                         dev->output_overrun_count++;
                     } else {

@@ -32,6 +32,7 @@ EXPORTS = [
     "airband_hip_device_enable", "airband_hip_gpu_count", "airband_hip_build_info", "airband_hip_dft_selftest", "airband_hip_collect_channels", "airband_hip_read_bins_channels", "airband_hip_read_trace_channels",
     "airband_hip_batch_ready", "airband_hip_mixer_set_stereo", "airband_hip_comm_unique_id", "airband_hip_comm_init_rank", "airband_hip_comm_init_all",
     "airband_hip_comm_group_begin", "airband_hip_comm_group_end", "airband_hip_allreduce_mixers", "airband_hip_add_mixers", "airband_hip_comm_destroy", "airband_hip_clear_mixers", "airband_hip_set_signal_plan_shift", "airband_hip_regrouped",
+    "airband_hip_prepare_scan", "airband_hip_set_freq_index", "airband_hip_freq_stats",
 ]
 
 _lib = None
@@ -68,6 +69,9 @@ def load_library() -> C.CDLL:
     L = C.CDLL(LIB_PATH)
     vp, i32, i64, u64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_size_t
     L.airband_hip_prepare.argtypes = [C.POINTER(capi.Config), C.POINTER(vp)]
+    L.airband_hip_prepare_scan.argtypes = [C.POINTER(capi.Config), C.POINTER(capi.ScanCfg), i32, C.POINTER(vp)]
+    L.airband_hip_set_freq_index.argtypes = [vp, i32, i32]
+    L.airband_hip_freq_stats.argtypes = [vp, i32, i32, C.POINTER(capi.ChannelStats)]
     L.airband_hip_set_mixers.argtypes = [vp, i32, C.POINTER(capi.MixerInput), i32]
     L.airband_hip_release.argtypes = [vp]
     L.airband_hip_release.restype = None
@@ -156,16 +160,51 @@ def dft_selftest(devices: Sequence[dict], *, wave_rate: int, fft_log: int = 9, w
     return float(err.value)
 
 
+def make_scan(scan: Optional[dict]):
+    """scan = {device index: [channel kwargs | ChannelCfg, ...]} -> (ScanCfg array or None, count, keepalive)."""
+    if not scan:
+        return None, 0, []
+    keep, rows = [], []
+    for dev, entries in scan.items():
+        chs = [c if isinstance(c, capi.ChannelCfg) else capi.channel_cfg(**c) for c in entries]
+        arr = (capi.ChannelCfg * len(chs))(*chs)
+        keep.append(arr)
+        rows.append(capi.ScanCfg(int(dev), len(chs), C.cast(arr, C.POINTER(capi.ChannelCfg))))
+    sarr = (capi.ScanCfg * len(rows))(*rows)
+    keep.append(sarr)
+    return C.cast(sarr, C.POINTER(capi.ScanCfg)), len(rows), keep
+
+
+def prepare_scan_rc(devices: Sequence[dict], scan: Optional[dict], *, wave_rate: int, fft_log: int = 9, fm_demod: int = 0, flags: int = 0) -> int:
+    """airband_hip_prepare_scan()'s return code for this configuration (the handle, if one was made, is released at once).  Lets tests check the
+    validation of scan lists, which happens before any device is touched."""
+    L = load_library()
+    cfg, keep = make_config(devices, wave_rate=wave_rate, fft_log=fft_log, fm_demod=fm_demod, flags=flags)
+    sptr, n, skeep = make_scan(scan)
+    h = C.c_void_p()
+    rc = L.airband_hip_prepare_scan(C.byref(cfg), sptr, n, C.byref(h))
+    if h:
+        L.airband_hip_release(h)
+    return rc
+
+
 class AirbandHip:
     """One handle = the dongles demodulated on one GPU (the reference's demodulate() thread for a device shard,
     src/rtl_airband.cpp:1052-1086)."""
 
-    def __init__(self, devices: Sequence[dict], *, wave_rate: int, fft_log: int = 9, fm_demod: int = 0, flags: int = 0, hip_device: int = 0):
+    def __init__(self, devices: Sequence[dict], *, wave_rate: int, fft_log: int = 9, fm_demod: int = 0, flags: int = 0, hip_device: int = 0,
+                 scan: Optional[dict] = None):
+        """scan = {device index: [channel kwargs, ...]}: scan-mode devices (airband_hip_prepare_scan); each list's first entry must equal the device's channel."""
         self.L = load_library()
         self.devices = list(devices)
         cfg, self._keep = make_config(devices, wave_rate=wave_rate, fft_log=fft_log, fm_demod=fm_demod, flags=flags, hip_device=hip_device)
         h = C.c_void_p()
-        rc = self.L.airband_hip_prepare(C.byref(cfg), C.byref(h))
+        if scan:
+            sptr, n, skeep = make_scan(scan)
+            self._keep.append(skeep)
+            rc = self.L.airband_hip_prepare_scan(C.byref(cfg), sptr, n, C.byref(h))
+        else:
+            rc = self.L.airband_hip_prepare(C.byref(cfg), C.byref(h))
         if rc != 0:
             raise AirbandError(rc, (self.L.airband_hip_last_error(None) or b"").decode())
         self.h = h
@@ -234,6 +273,16 @@ class AirbandHip:
         if stats:
             out["stats"] = [{f[0]: getattr(s, f[0]) for f in capi.ChannelStats._fields_} for s in st]
         return out
+
+    def set_freq_index(self, dev: int, freq_idx: int):
+        """Entry freq_idx of dongle dev's scan list is in force for every batch enqueued from now on (latched per batch)."""
+        self._check(self.L.airband_hip_set_freq_index(self.h, dev, freq_idx))
+
+    def freq_stats(self, dev: int, freq_idx: int) -> dict:
+        """Statistics of entry freq_idx of dongle dev's scan list as of the last completed batch (frozen values for inactive entries)."""
+        st = capi.ChannelStats()
+        self._check(self.L.airband_hip_freq_stats(self.h, dev, freq_idx, C.byref(st)))
+        return {f[0]: getattr(st, f[0]) for f in capi.ChannelStats._fields_}
 
     def synchronize(self):
         self._check(self.L.airband_hip_synchronize(self.h))

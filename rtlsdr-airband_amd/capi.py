@@ -30,6 +30,10 @@ class Config(C.Structure):
                 ("hip_device", C.c_int32), ("device_count", C.c_int32), ("devices", C.POINTER(DeviceCfg))]
 
 
+class ScanCfg(C.Structure):
+    _fields_ = [("device", C.c_int32), ("freq_count", C.c_int32), ("freqs", C.POINTER(ChannelCfg))]
+
+
 class MixerInput(C.Structure):
     _fields_ = [("device", C.c_int32), ("channel", C.c_int32), ("mixer", C.c_int32), ("ampfactor", C.c_float), ("balance", C.c_float)]
 

@@ -22,6 +22,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "params.h"
+#include "scan_bank.h"
 
 /* upper bound for the int8 coefficient tables of a handle -- one per distinct group of eight bins plus one per AFC group; past it prepare() picks the wavefront-FFT
  * channelizer (override for tests) */
@@ -174,6 +175,28 @@ struct airband_hip_handle {
     ncclComm_t comm = nullptr;
     hipEvent_t ev_peer = nullptr; /* airband_hip_add_mixers: "src's batch is done" for dst's stream */
 
+    /* scan-mode devices (airband_hip_prepare_scan, scan_bank.h): nothing of this exists on a handle without scan lists */
+    std::vector<int> scan_of_dev;      /* device -> its list in plan.scan, -1 */
+    std::vector<int> scan_cur;         /* by list: the entry airband_hip_set_freq_index() put in force */
+    std::vector<int> scan_latch[2];    /* by list: the entry of front batch k, at [k & 1] (stage 2 of a pipelined batch runs during the next call) */
+    int scan_first_row[2] = {0, 0};    /* the ring rows stage 1 of front batch k produced: [first_row, first_row + n_rows) */
+    int scan_n_rows[2] = {0, 0};
+    std::vector<int> scan_held;        /* by list: the entry the slot holds once every exchange enqueued so far has run */
+    DevBuf<ChanConst> d_bank_cc;
+    DevBuf<ChanState> d_bank_cs;
+    DevBuf<float> d_bank_sq;
+    DevBuf<uint32_t> d_scan_mask;      /* [AB_CS_DWORDS] ChanState masks, then [AB_CC_DWORDS] ChanConst masks */
+    DevBuf<int> d_switch[2];           /* the batch's switch list (slot, entry parked, entry brought in), two in flight */
+    int* h_switch[2] = {nullptr, nullptr}; /* pinned staging of the lists */
+    hipEvent_t ev_switch[2] = {nullptr, nullptr};
+    bool switch_used[2] = {false, false};
+    int switch_buf = 0;
+    DevBuf<int> d_scan_mix_slots;      /* slots of lists that mix AM and NFM entries (scan_mag_kernel) */
+    DevBuf<ChanConst> d_fs_cc;         /* airband_hip_freq_stats: one composed image, its stats row */
+    DevBuf<ChanState> d_fs_cs;
+    DevBuf<airband_hip_channel_stats> d_fs_stats;
+    DevBuf<int> d_fs_zero;
+
     /* synthetic dongles */
     DevBuf<int16_t> d_sin_tab;
     DevBuf<long long> d_carriers;
@@ -236,6 +259,13 @@ void destroy(airband_hip_handle* h) {
     h->d_mix_run_first.release(); h->d_mix_run_mixer.release(); h->d_mix_first_run.release();
     h->d_mix_run_left.release(); h->d_mix_run_right.release(); h->d_mix_run_signal.release();
     h->d_sin_tab.release(); h->d_carriers.release();
+    h->d_bank_cc.release(); h->d_bank_cs.release(); h->d_bank_sq.release(); h->d_scan_mask.release(); h->d_scan_mix_slots.release();
+    h->d_switch[0].release(); h->d_switch[1].release();
+    h->d_fs_cc.release(); h->d_fs_cs.release(); h->d_fs_stats.release(); h->d_fs_zero.release();
+    for (auto& p : h->h_switch)
+        if (p) (void)hipHostFree(p);
+    for (auto& e : h->ev_switch)
+        if (e) (void)hipEventDestroy(e);
     for (auto& set : h->evp)
         for (auto& e : set)
             if (e) (void)hipEventDestroy(e);
@@ -349,6 +379,70 @@ void launch_last_hop_spectrum(airband_hip_handle* h, hipStream_t s) {
     launch_channelizer_fft(ca, s);
 }
 
+ScanExchangeArgs scan_args(airband_hip_handle* h) {
+    ScanExchangeArgs a;
+    a.cc = h->d_cc.p;
+    a.cs = h->d_cs.p;
+    a.sqbuf = h->d_sqbuf.p;
+    a.bank_cc = h->d_bank_cc.p;
+    a.bank_cs = h->d_bank_cs.p;
+    a.bank_sq = h->d_bank_sq.p;
+    a.cs_mask = h->d_scan_mask.p;
+    a.cc_mask = h->d_scan_mask.p + AB_CS_DWORDS;
+    a.sw = nullptr;
+    a.n_switch = 0;
+    a.n_slots = h->n_slots;
+    a.n_entries = (int)h->plan.scan_cc.size();
+    return a;
+}
+
+/* front batch k is being enqueued: the scan entries in force now are its entries (airband_hip_set_freq_index latches per batch) */
+void scan_latch(airband_hip_handle* h, uint64_t k, int first_row, int n_rows) {
+    if (h->plan.scan.empty()) return;
+    h->scan_latch[k & 1] = h->scan_cur;
+    h->scan_first_row[k & 1] = first_row;
+    h->scan_n_rows[k & 1] = n_rows;
+}
+
+/* in front of the demod kernels of batch batches_done, on its stage-2 stream: the exchange of every scan channel whose latched entry is not the one its slot
+ * holds (one launch for all of them), and |bin| of the lists that mix AM and NFM */
+int scan_before_demod(airband_hip_handle* h, hipStream_t s) {
+    const int b = (int)(h->batches_done & 1);
+    const std::vector<int>& want = h->scan_latch[b];
+    const int q = h->switch_buf;
+    int* list = h->h_switch[q];
+    int n = 0;
+    bool waited = false;
+    for (size_t i = 0; i < h->plan.scan.size(); i++) {
+        if (want[i] == h->scan_held[i]) continue;
+        if (!waited && h->switch_used[q]) HIP_TRY(h, hipEventSynchronize(h->ev_switch[q]), AIRBAND_HIP_ERUNTIME); /* the list of two batches ago has been read */
+        waited = true;
+        const ScanList& sl = h->plan.scan[i];
+        const int slot = h->ext_to_slot[sl.ext];
+        list[3 * n] = slot;
+        list[3 * n + 1] = sl.first_entry + h->scan_held[i];
+        list[3 * n + 2] = sl.first_entry + want[i];
+        n++;
+        h->scan_held[i] = want[i];
+        /* the host copy of the slot's flags (airband_hip_device_enable rewrites the word from it) follows the entry the slot holds */
+        ChanConst& hc = h->cc_slots[slot];
+        hc.flags = (hc.flags & ~AB_SCAN_FREQ_FLAGS) | (h->plan.scan_cc[sl.first_entry + want[i]].flags & AB_SCAN_FREQ_FLAGS);
+    }
+    if (n > 0) {
+        HIP_TRY(h, hipMemcpyAsync(h->d_switch[q].p, list, (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
+        ScanExchangeArgs a = scan_args(h);
+        a.sw = h->d_switch[q].p;
+        a.n_switch = n;
+        launch_scan_exchange(a, s);
+        HIP_TRY(h, hipEventRecord(h->ev_switch[q], s), AIRBAND_HIP_ERUNTIME);
+        h->switch_used[q] = true;
+        h->switch_buf = q ^ 1;
+    }
+    if (h->d_scan_mix_slots.n > 0)
+        launch_scan_mag(h->d_scan_mix_slots.p, (int)h->d_scan_mix_slots.n, h->d_mag.p, h->d_iq.p, h->scan_first_row[b], h->scan_n_rows[b], h->row0, h->R, s);
+    return AIRBAND_HIP_OK;
+}
+
 /* stage 2 + emit (+ mixers) of the batch whose stage-1 rows are already in the rings */
 int run_back_half(airband_hip_handle* h, hipStream_t s) {
     hipEvent_t* ev = event_set(h, h->batches_done, 1);
@@ -388,6 +482,10 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
     da.regroup = h->regroup ? h->regroup_mode : 0;
     da.sq_key = h->d_sq_key.p;
     da.perm = (h->regroup && h->regroup_mode == 3) ? h->d_perm.p : nullptr;
+    if (!h->plan.scan.empty()) {
+        const int rc = scan_before_demod(h, s);
+        if (rc != AIRBAND_HIP_OK) return rc;
+    }
     launch_demod(da, h->kind_first_block, h->kind_n_blocks, s, (h->flags & AIRBAND_HIP_FLAG_SERIAL_DEMOD) ? nullptr : h->side, h->fork_ev);
     if (h->any_afc && h->afc_spectrum_valid) { /* afc.finalize(), src/rtl_airband.cpp:626-630: may turn '*' into '<' / '>' */
         const bool tables = h->use_dft || h->use_f32; /* the matrix-core channelizers: a channel's bin is baked into its coefficient columns */
@@ -486,12 +584,15 @@ int airband_hip_dft_selftest(const airband_hip_config* cfg, int32_t windows, dou
     return AIRBAND_HIP_OK;
 }
 
-int airband_hip_prepare(const airband_hip_config* cfg, airband_hip_handle** out) {
+int airband_hip_prepare(const airband_hip_config* cfg, airband_hip_handle** out) { return airband_hip_prepare_scan(cfg, nullptr, 0, out); }
+
+int airband_hip_prepare_scan(const airband_hip_config* cfg, const airband_hip_scan_cfg* scan, int32_t n_scan, airband_hip_handle** out) {
     if (!out) return fail(nullptr, AIRBAND_HIP_EINVAL, "out is NULL");
     *out = nullptr;
     airband_hip_handle* h = new (std::nothrow) airband_hip_handle();
     if (!h) return fail(nullptr, AIRBAND_HIP_ENOMEM, "host allocation failed");
     int rc = build_plan(cfg, h->plan);
+    if (rc == AIRBAND_HIP_OK) rc = build_scan(cfg, scan, n_scan, h->plan); /* before any device is touched */
     if (rc != AIRBAND_HIP_OK) {
         g_prepare_error = h->plan.error;
         delete h;
@@ -557,6 +658,25 @@ int airband_hip_prepare(const airband_hip_config* cfg, airband_hip_handle** out)
             return ct ? (int)AB_KIND_NFM_CTCSS : lp ? (int)AB_KIND_NFM_LOWPASS : (int)AB_KIND_NFM;
         };
         h->ext_to_slot.assign(p.total_ch, -1);
+        std::vector<int> kind_ext(p.total_ch);
+        for (int e = 0; e < p.total_ch; e++) kind_ext[e] = kind_of(p.cc[e]);
+        /* a scan channel's kind holds for every entry of its list: their common kind, else the generic one.  NFM + lowpass becomes generic too when the
+         * list has more than one entry: that kind recomputes the squelch's delay line from the channel's wavein carry (squelch_fsm.h, SqShadow), which
+         * after a switch belongs to another frequency; the generic kind keeps the line, and the line is banked per entry */
+        for (const ScanList& sl : p.scan) {
+            int k = kind_of(p.scan_cc[sl.first_entry]);
+            for (int f = 1; f < sl.n; f++)
+                if (kind_of(p.scan_cc[sl.first_entry + f]) != k) k = AB_KIND_GENERIC;
+            if (k == AB_KIND_NFM_LOWPASS && sl.n > 1) k = AB_KIND_GENERIC;
+            kind_ext[sl.ext] = k;
+        }
+        /* A switching scan channel gets a 64-slot block of its own.  The demod kernels hold the squelch's sample_count_ and delay-line cursors in scalar
+         * registers (squelch_fsm.h, sq_load: "the same on every channel"), which is true of channels that run every batch, but a list entry counts only
+         * the batches it was active in: at WAVE_BATCH 1 000 (= 8 mod 16) two entries' noise-floor sweeps fall 8 samples apart.  Alone in its wavefront
+         * the channel's counts are uniform again.  The cost is ring space for 63 idle slots per scan channel. */
+        std::vector<uint8_t> isolated(p.total_ch, 0);
+        for (const ScanList& sl : p.scan)
+            if (sl.n > 1) isolated[sl.ext] = 1;
         ChanConst pad_c;
         ChanState pad_s;
         std::memset(&pad_c, 0, sizeof(pad_c));
@@ -565,20 +685,25 @@ int airband_hip_prepare(const airband_hip_config* cfg, airband_hip_handle** out)
         pad_s.axc = ' ';
         for (int k = 0; k < AB_KIND_COUNT; k++) {
             bool any = false;
-            for (int e = 0; e < p.total_ch; e++) {
-                if (kind_of(p.cc[e]) != k) continue;
-                any = true;
-                h->ext_to_slot[e] = (int)cc_slots.size();
-                h->slot_to_ext.push_back(e);
-                cc_slots.push_back(p.cc[e]);
-                cs_slots.push_back(p.cs0[e]);
-            }
+            auto pad_block = [&]() {
+                while (cc_slots.size() % AB_SLOT_BLOCK) {
+                    h->slot_to_ext.push_back(-1);
+                    cc_slots.push_back(pad_c);
+                    cs_slots.push_back(pad_s);
+                }
+            };
+            for (int pass = 0; pass < 2; pass++) /* the kind's channels, then its isolated scan channels, one block each */
+                for (int e = 0; e < p.total_ch; e++) {
+                    if (kind_ext[e] != k || isolated[e] != pass) continue;
+                    any = true;
+                    if (pass) pad_block();
+                    h->ext_to_slot[e] = (int)cc_slots.size();
+                    h->slot_to_ext.push_back(e);
+                    cc_slots.push_back(p.cc[e]);
+                    cs_slots.push_back(p.cs0[e]);
+                }
             if (!any) continue;
-            while (cc_slots.size() % AB_SLOT_BLOCK) {
-                h->slot_to_ext.push_back(-1);
-                cc_slots.push_back(pad_c);
-                cs_slots.push_back(pad_s);
-            }
+            pad_block();
             h->kind_first_block[k] = (int)block_kind.size();
             while (block_kind.size() < cc_slots.size() / AB_SLOT_BLOCK) block_kind.push_back((uint8_t)k);
             h->kind_n_blocks[k] = (int)block_kind.size() - h->kind_first_block[k];
@@ -664,6 +789,9 @@ int airband_hip_prepare(const airband_hip_config* cfg, airband_hip_handle** out)
         const bool by_residency = waves_per_simd >= 2.75 && waves_per_simd <= 6.25;
         const char* e = getenv("AIRBAND_HIP_REGROUP");
         h->regroup = e && *e ? (*e != '0') : (h->flags & AIRBAND_HIP_FLAG_REGROUP) ? true : (h->flags & AIRBAND_HIP_FLAG_NO_REGROUP) ? false : by_residency;
+        /* regrouping deals a workgroup's slots out among its wavefronts: it would put isolated scan channels (above) back into one wavefront */
+        for (const ScanList& sl : p.scan)
+            if (sl.n > 1) h->regroup = false;
         h->regroup_mode = (e && *e == '2') ? 2 : (e && *e == '3') ? 3 : 1;
         if (h->regroup && h->regroup_mode == 3) PREP_TRY(h->d_perm.alloc((size_t)h->n_slots), AIRBAND_HIP_ENOMEM);
         if (h->regroup || h->ct_n_blocks > 0) { /* the front kernel's note per channel: had audio / went CLOSED in this batch (tone kernel; regrouped back kernel) */
@@ -798,6 +926,34 @@ int airband_hip_prepare(const airband_hip_config* cfg, airband_hip_handle** out)
     for (int d = 0; d < p.n_dev; d++) h->dev_enabled[d].store(1);
     h->n_enabled = p.n_dev;
     h->cc_slots = cc_slots;
+    if (!p.scan.empty()) { /* scan lists: the banks, every entry's initial image, the masks, the switch lists' staging */
+        const size_t ne = p.scan_cc.size();
+        PREP_TRY(upload(h->d_bank_cc, p.scan_cc), AIRBAND_HIP_ENOMEM);
+        PREP_TRY(upload(h->d_bank_cs, p.scan_cs0), AIRBAND_HIP_ENOMEM);
+        PREP_TRY(h->d_bank_sq.alloc(ne * AB_SQ_BUF), AIRBAND_HIP_ENOMEM);
+        PREP_TRY(hipMemset(h->d_bank_sq.p, 0, ne * AB_SQ_BUF * sizeof(float)), AIRBAND_HIP_ENOMEM);
+        const AbScanMasks mk = ab_scan_masks();
+        std::vector<uint32_t> masks(mk.cs, mk.cs + AB_CS_DWORDS);
+        masks.insert(masks.end(), mk.cc, mk.cc + AB_CC_DWORDS);
+        PREP_TRY(upload(h->d_scan_mask, masks), AIRBAND_HIP_ENOMEM);
+        const size_t nl = p.scan.size();
+        for (int q = 0; q < 2; q++) {
+            PREP_TRY(h->d_switch[q].alloc(nl * 3), AIRBAND_HIP_ENOMEM);
+            PREP_TRY(hipHostMalloc((void**)&h->h_switch[q], nl * 3 * sizeof(int), hipHostMallocDefault), AIRBAND_HIP_ENOMEM);
+            PREP_TRY(hipEventCreateWithFlags(&h->ev_switch[q], hipEventDisableTiming), AIRBAND_HIP_ENODEV);
+        }
+        std::vector<int> mix_slots;
+        h->scan_of_dev.assign(p.n_dev, -1);
+        for (size_t i = 0; i < nl; i++) {
+            h->scan_of_dev[p.scan[i].dev] = (int)i;
+            if (p.scan[i].mixed_am_nfm) mix_slots.push_back(h->ext_to_slot[p.scan[i].ext]);
+        }
+        if (!mix_slots.empty()) PREP_TRY(upload(h->d_scan_mix_slots, mix_slots), AIRBAND_HIP_ENOMEM);
+        h->scan_cur.assign(nl, 0);
+        h->scan_held.assign(nl, 0);
+        h->scan_latch[0].assign(nl, 0);
+        h->scan_latch[1].assign(nl, 0);
+    }
 #undef PREP_TRY
     *out = h;
     return AIRBAND_HIP_OK;
@@ -934,6 +1090,45 @@ int airband_hip_device_enable(airband_hip_handle* h, int32_t dev, int32_t enable
     for (size_t k = 0; k < h->mix_chan_host.size(); k++)
         if (p.cc[h->mix_chan_host[k]].dev == dev) HIP_TRY(h, write_mix_input(h, (int)k), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME); /* the host buffers above go out of scope */
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_set_freq_index(airband_hip_handle* h, int32_t dev, int32_t freq_idx) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (dev < 0 || dev >= h->plan.n_dev || h->scan_of_dev.empty() || h->scan_of_dev[dev] < 0) return fail(h, AIRBAND_HIP_EINVAL, "device has no scan list");
+    const int i = h->scan_of_dev[dev];
+    if (freq_idx < 0 || freq_idx >= h->plan.scan[i].n) return fail(h, AIRBAND_HIP_EINVAL, "frequency index out of range");
+    h->scan_cur[i] = freq_idx; /* latched by the next batch that is enqueued */
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_freq_stats(airband_hip_handle* h, int32_t dev, int32_t freq_idx, airband_hip_channel_stats* out) {
+    if (!h || !out) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    if (dev < 0 || dev >= h->plan.n_dev || h->scan_of_dev.empty() || h->scan_of_dev[dev] < 0) return fail(h, AIRBAND_HIP_EINVAL, "device has no scan list");
+    const int i = h->scan_of_dev[dev];
+    const ScanList& sl = h->plan.scan[i];
+    if (freq_idx < 0 || freq_idx >= sl.n) return fail(h, AIRBAND_HIP_EINVAL, "frequency index out of range");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    if (!h->d_fs_zero.p) {
+        HIP_TRY(h, h->d_fs_cc.alloc(1), AIRBAND_HIP_ENOMEM);
+        HIP_TRY(h, h->d_fs_cs.alloc(1), AIRBAND_HIP_ENOMEM);
+        HIP_TRY(h, h->d_fs_stats.alloc(1), AIRBAND_HIP_ENOMEM);
+        HIP_TRY(h, h->d_fs_zero.alloc(1), AIRBAND_HIP_ENOMEM);
+        HIP_TRY(h, hipMemsetAsync(h->d_fs_zero.p, 0, sizeof(int), s), AIRBAND_HIP_ERUNTIME);
+    }
+    const int slot = h->ext_to_slot[sl.ext];
+    /* the stats kernel of airband_hip_collect() on one image: the slot itself for the entry it holds, else the slot composed with the entry's bank */
+    if (freq_idx == h->scan_held[i]) {
+        launch_stats(h->d_cc.p + slot, h->d_cs.p + slot, h->d_fs_zero.p, 1, h->d_fs_stats.p, s);
+    } else {
+        launch_scan_compose(scan_args(h), slot, sl.first_entry + freq_idx, h->d_fs_cc.p, h->d_fs_cs.p, s);
+        launch_stats(h->d_fs_cc.p, h->d_fs_cs.p, h->d_fs_zero.p, 1, h->d_fs_stats.p, s);
+    }
+    HIP_TRY(h, hipGetLastError(), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipMemcpyAsync(out, h->d_fs_stats.p, sizeof(airband_hip_channel_stats), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
     return AIRBAND_HIP_OK;
 }
 
@@ -1099,6 +1294,7 @@ static int launch_front(airband_hip_handle* h, const void* d_iq, size_t stride_b
     }
     /* a refused launch (an LDS opt-in that failed, a bad grid) is this call's error, not a puzzle for whoever synchronises next */
     if (launch_err != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("channelizer launch: ") + hipGetErrorString(launch_err));
+    scan_latch(h, h->front_batches, first ? 0 : AB_AGC_EXTRA, first ? h->B + AB_AGC_EXTRA : h->B);
     h->row0_front = (h->row0_front + h->B) % h->R;
     h->front_batches++;
     return AIRBAND_HIP_OK;
@@ -1299,6 +1495,7 @@ int airband_hip_process_bins(airband_hip_handle* h, const float* wavein, const f
     h->afc_spectrum_valid = false;
     launch_scatter_bins(h->d_tmp_wavein.p, h->d_tmp_iqin.p, h->d_slot_to_ext.p, h->d_cc.p, h->d_mag.p, h->d_iq.p, h->n_slots, h->B, h->row0, h->R, s);
     (void)hipEventRecord(ev[1], s);
+    scan_latch(h, h->front_batches, AB_AGC_EXTRA, h->B); /* the caller's rows are the batch's new ones; the carry is what the rings hold */
     h->row0_front = (h->row0_front + h->B) % h->R;
     h->front_batches++;
     return run_back_half(h, s);

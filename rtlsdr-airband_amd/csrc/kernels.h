@@ -243,5 +243,22 @@ void launch_scatter_bins(const float* wavein, const float* iqin, const int* slot
 void launch_gather_channels(const float* mag, const float2* iq, const uint8_t* trace, const int* ext_to_slot, const ChanConst* cc, int first, int n, float* wavein,
                             float* iqin, uint8_t* trace_out, int wave_batch, int row0, int ring_rows, hipStream_t stream);
 
+/* scan-mode devices (scan_bank.h): the per-frequency state banks and the batch's switch list */
+struct ScanExchangeArgs {
+    ChanConst* cc;          /* live, by slot */
+    ChanState* cs;
+    float* sqbuf;           /* the squelch delay lines, ab_ring_base(slot, AB_SQ_BUF) + 64 i */
+    const ChanConst* bank_cc; /* [n_entries] read-only */
+    ChanState* bank_cs;     /* [n_entries] */
+    float* bank_sq;         /* [n_entries][AB_SQ_BUF] */
+    const uint32_t* cs_mask;/* [AB_CS_DWORDS] */
+    const uint32_t* cc_mask;/* [AB_CC_DWORDS] */
+    const int* sw;          /* [n_switch][3] (slot, entry parked, entry brought in) */
+    int n_switch, n_slots, n_entries;
+};
+void launch_scan_exchange(const ScanExchangeArgs& a, hipStream_t stream);
+void launch_scan_compose(const ScanExchangeArgs& a, int slot, int e, ChanConst* out_cc, ChanState* out_cs, hipStream_t stream);
+void launch_scan_mag(const int* slots, int n, float* mag, const float2* iq, int first_row, int n_rows, int row0, int ring_rows, hipStream_t stream);
+
 }  // namespace airband
 #endif

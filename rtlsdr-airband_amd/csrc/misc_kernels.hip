@@ -4,6 +4,7 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "scan_bank.h"
 
 namespace airband {
 
@@ -471,6 +472,93 @@ void launch_gather_channels(const float* mag, const float2* iq, const uint8_t* t
     if (n <= 0) return;
     hipLaunchKernelGGL(gather_channels_kernel, dim3(n, (wave_batch + 255) / 256), dim3(256), 0, stream, mag, iq, trace, ext_to_slot, cc, first, wavein, iqin, trace_out,
                        wave_batch, row0, ring_rows);
+}
+
+/* ---- scan-mode devices: per-frequency state banks (scan_bank.h) ------------------------------------------------------------------------------
+ * One wavefront per switching channel; its lanes stride over the dwords of ChanState, ChanConst and the squelch's 102-float delay line.  A dword
+ * whose mask is zero belongs to the channel and is neither read nor written.  On a pipelined handle stage 1 of the next batch may run beside this
+ * kernel and read ChanConst.flags (want_mag / want_iq), which IS rewritten here: that race is harmless -- the store is one aligned dword, the bits
+ * stage 1 looks at (RAW_IQ, VALID) are the channel's and keep their value, and NFM, the one per-frequency bit it reads, differs between entries
+ * only in lists that mix AM and NFM, whose |bin| scan_mag_kernel rewrites in front of stage 2 whatever stage 1 decided.
+ * Known cost: the live delay line sits in the slot-blocked layout (ab_ring_base), 64 floats between a channel's entries, so its part of the
+ * exchange touches about 102 cache lines per switch -- most of the kernel's time when tens of thousands of channels switch at once (a dongle
+ * switches at most once per controller poll of 200 ms, src/rtl_airband.cpp:101-139, so it stays off the per-batch path). */
+__global__ __launch_bounds__(64) void scan_exchange_kernel(ScanExchangeArgs a) {
+    const int k = blockIdx.x;
+    if (k >= a.n_switch) return;
+    const int slot = a.sw[3 * k], e_old = a.sw[3 * k + 1], e_new = a.sw[3 * k + 2];
+    if (slot < 0 || slot >= a.n_slots || e_old < 0 || e_old >= a.n_entries || e_new < 0 || e_new >= a.n_entries) return;
+    const int lane = threadIdx.x;
+    uint32_t* live_s = reinterpret_cast<uint32_t*>(a.cs + slot);
+    uint32_t* park_s = reinterpret_cast<uint32_t*>(a.bank_cs + e_old);
+    const uint32_t* in_s = reinterpret_cast<const uint32_t*>(a.bank_cs + e_new);
+    for (int d = lane; d < AB_CS_DWORDS; d += 64) {
+        const uint32_t m = a.cs_mask[d];
+        if (m == 0u) continue;
+        live_s[d] = ab_scan_exchange_dword(live_s[d], m, in_s[d], park_s + d);
+    }
+    uint32_t* live_c = reinterpret_cast<uint32_t*>(a.cc + slot);
+    const uint32_t* in_c = reinterpret_cast<const uint32_t*>(a.bank_cc + e_new);
+    for (int d = lane; d < AB_CC_DWORDS; d += 64) {
+        const uint32_t m = a.cc_mask[d];
+        if (m == 0u) continue;
+        live_c[d] = ab_scan_exchange_dword(live_c[d], m, in_c[d], nullptr);
+    }
+    uint32_t* live_q = reinterpret_cast<uint32_t*>(a.sqbuf + ab_ring_base(slot, AB_SQ_BUF));
+    uint32_t* park_q = reinterpret_cast<uint32_t*>(a.bank_sq + (long)e_old * AB_SQ_BUF);
+    const uint32_t* in_q = reinterpret_cast<const uint32_t*>(a.bank_sq + (long)e_new * AB_SQ_BUF);
+    for (int i = lane; i < AB_SQ_BUF; i += 64) {
+        const long o = (long)i * AB_SLOT_BLOCK;
+        live_q[o] = ab_scan_exchange_dword(live_q[o], 0xffffffffu, in_q[i], park_q + i);
+    }
+}
+
+void launch_scan_exchange(const ScanExchangeArgs& a, hipStream_t stream) {
+    if (a.n_switch <= 0) return;
+    hipLaunchKernelGGL(scan_exchange_kernel, dim3(a.n_switch), dim3(64), 0, stream, a);
+}
+
+/* entry e of a scan channel as it would stand in the slot: the live image with the bank's per-frequency part (airband_hip_freq_stats) */
+__global__ __launch_bounds__(64) void scan_compose_kernel(ScanExchangeArgs a, int slot, int e, ChanConst* out_cc, ChanState* out_cs) {
+    const int lane = threadIdx.x;
+    const uint32_t* live_s = reinterpret_cast<const uint32_t*>(a.cs + slot);
+    const uint32_t* in_s = reinterpret_cast<const uint32_t*>(a.bank_cs + e);
+    uint32_t* o_s = reinterpret_cast<uint32_t*>(out_cs);
+    for (int d = lane; d < AB_CS_DWORDS; d += 64) o_s[d] = ab_scan_exchange_dword(live_s[d], a.cs_mask[d], in_s[d], nullptr);
+    const uint32_t* live_c = reinterpret_cast<const uint32_t*>(a.cc + slot);
+    const uint32_t* in_c = reinterpret_cast<const uint32_t*>(a.bank_cc + e);
+    uint32_t* o_c = reinterpret_cast<uint32_t*>(out_cc);
+    for (int d = lane; d < AB_CC_DWORDS; d += 64) o_c[d] = ab_scan_exchange_dword(live_c[d], a.cc_mask[d], in_c[d], nullptr);
+}
+
+void launch_scan_compose(const ScanExchangeArgs& a, int slot, int e, ChanConst* out_cc, ChanState* out_cs, hipStream_t stream) {
+    hipLaunchKernelGGL(scan_compose_kernel, dim3(1), dim3(64), 0, stream, a, slot, e, out_cc, out_cs);
+}
+
+/* Scan channels whose list mixes AM and NFM entries: stage 1 stores |bin| only for channels that are not NFM (channelizer_*.hip, want_mag), and it
+ * reads the flags of the entry the slot held when it ran.  |bin| of the batch's new rows is rewritten here from the raw bin I/Q -- which such a
+ * channel always has (needs_raw_iq is the union over the list, src/config.cpp:671-678) -- the way the reference computes wavein[j]
+ * (src/rtl_airband.cpp:484-487) and gather_channels_kernel recomputes it, so that an AM entry finds its magnitudes whatever the slot held before.
+ * The square root is the correctly rounded one (__fsqrt_rn, the reference's sqrtf); the channelizers store v_sqrt_f32 (within 1 ulp) for every
+ * other AM channel, so an AM entry of a mixed list may see stage-1 magnitudes 1 ulp away from the same channel on a multichannel dongle --
+ * inside stage 1's tolerance, and if anything closer to the reference. */
+__global__ __launch_bounds__(256) void scan_mag_kernel(const int* slots, int n, float* mag, const float2* iq, int first_row, int n_rows, int row0, int ring_rows) {
+    const int k = blockIdx.x;
+    if (k >= n) return;
+    const int slot = slots[k];
+    const long base = ab_tile_base(slot, ring_rows / AB_TILE_ROWS);
+    for (int t = threadIdx.x; t < n_rows; t += 256) {
+        int row = row0 + first_row + t;
+        if (row >= ring_rows) row -= ring_rows;
+        const long off = base + ab_tile_off(row);
+        const float2 q = iq[off];
+        mag[off] = __fsqrt_rn(q.x * q.x + q.y * q.y);
+    }
+}
+
+void launch_scan_mag(const int* slots, int n, float* mag, const float2* iq, int first_row, int n_rows, int row0, int ring_rows, hipStream_t stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(scan_mag_kernel, dim3(n), dim3(256), 0, stream, slots, n, mag, iq, first_row, n_rows, row0, ring_rows);
 }
 
 }  // namespace airband

@@ -6,6 +6,7 @@
  * very same float constants.
  */
 #include "params.h"
+#include "scan_bank.h"
 #include "exact_math.h"
 
 #include <algorithm>
@@ -617,6 +618,110 @@ void channel_constants(const Plan& p, int i, double* v) {
     v[13] = (c.flags & AB_F_RAW_IQ) ? 1 : 0;
     v[14] = c.ct_slot >= 0 ? c.ct_window[0] : 0;
     v[15] = c.ct_slot >= 0 ? c.ct_window[1] : 0;
+}
+
+int build_scan(const airband_hip_config* cfg, const airband_hip_scan_cfg* scan, int n_scan, Plan& p) {
+    p.scan.clear();
+    p.scan_cc.clear();
+    p.scan_cs0.clear();
+    if (n_scan < 0 || (n_scan > 0 && !scan)) return fail(p, AIRBAND_HIP_EINVAL, "bad scan list arguments");
+    if (n_scan == 0) return AIRBAND_HIP_OK;
+    std::vector<uint8_t> listed((size_t)p.n_dev, 0);
+    size_t n_entries = 0;
+    for (int i = 0; i < n_scan; i++) {
+        const airband_hip_scan_cfg& sc = scan[i];
+        if (sc.device < 0 || sc.device >= p.n_dev) return fail(p, AIRBAND_HIP_EINVAL, "scan list: device index out of range");
+        if (listed[sc.device]) return fail(p, AIRBAND_HIP_EINVAL, "scan list: device " + std::to_string(sc.device) + " listed twice");
+        listed[sc.device] = 1;
+        const airband_hip_device_cfg& dc = cfg->devices[sc.device];
+        if (dc.channel_count != 1) return fail(p, AIRBAND_HIP_EINVAL, "scan list: a scan device has exactly one channel (src/config.cpp:822-825)");
+        if (sc.freq_count < 1 || !sc.freqs) return fail(p, AIRBAND_HIP_EINVAL, "scan list: freq_count must be >= 1");
+        if (std::memcmp(&sc.freqs[0], &dc.channels[0], sizeof(airband_hip_channel_cfg)) != 0)
+            return fail(p, AIRBAND_HIP_EINVAL, "scan list: freqs[0] must equal the device's channel");
+        for (int f = 0; f < sc.freq_count; f++) {
+            const airband_hip_channel_cfg& e = sc.freqs[f];
+            if (e.afc != sc.freqs[0].afc || e.tau_us != sc.freqs[0].tau_us || e.has_iq_outputs != sc.freqs[0].has_iq_outputs)
+                return fail(p, AIRBAND_HIP_EINVAL, "scan list: afc, tau and has_iq_outputs belong to the channel and must be the same in every entry");
+            if (e.modulation == AIRBAND_MOD_NFM && p.wave_rate != 16000) return fail(p, AIRBAND_HIP_EINVAL, "scan list: NFM entries need wave_rate 16000");
+        }
+        n_entries += (size_t)sc.freq_count;
+    }
+    /* every entry through build_plan(): one single-channel device per entry, on the scan device's dongle and at entry 0's frequency */
+    std::vector<airband_hip_channel_cfg> ech;
+    ech.reserve(n_entries);
+    std::vector<airband_hip_device_cfg> edev;
+    edev.reserve(n_entries);
+    for (int i = 0; i < n_scan; i++)
+        for (int f = 0; f < scan[i].freq_count; f++) {
+            airband_hip_channel_cfg c = scan[i].freqs[f];
+            c.frequency = scan[i].freqs[0].frequency;
+            ech.push_back(c);
+        }
+    size_t k = 0;
+    for (int i = 0; i < n_scan; i++)
+        for (int f = 0; f < scan[i].freq_count; f++, k++) {
+            airband_hip_device_cfg d = cfg->devices[scan[i].device];
+            d.channel_count = 1;
+            d.channels = &ech[k];
+            edev.push_back(d);
+        }
+    airband_hip_config ecfg = *cfg;
+    ecfg.device_count = (int32_t)n_entries;
+    ecfg.devices = edev.data();
+    Plan e;
+    const int rc = build_plan(&ecfg, e);
+    if (rc != AIRBAND_HIP_OK) return fail(p, rc == AIRBAND_HIP_EBADSIZE ? AIRBAND_HIP_EINVAL : rc, "scan list entry: " + e.error);
+
+    const AbScanMasks mk = ab_scan_masks();
+    auto merge = [](const void* live, const void* freq, void* out, const uint32_t* mask, int dwords) {
+        const uint32_t* l = (const uint32_t*)live;
+        const uint32_t* q = (const uint32_t*)freq;
+        uint32_t* o = (uint32_t*)out;
+        for (int w = 0; w < dwords; w++) o[w] = ab_scan_exchange_dword(l[w], mask[w], q[w], nullptr);
+    };
+    k = 0;
+    for (int i = 0; i < n_scan; i++) {
+        ScanList sl;
+        sl.dev = scan[i].device;
+        sl.ext = p.chan_base[sl.dev];
+        sl.first_entry = (int)p.scan_cc.size();
+        sl.n = scan[i].freq_count;
+        ChanConst& ch = p.cc[sl.ext];
+        bool any_am = false, any_nfm = false;
+        for (int f = 0; f < sl.n; f++) {
+            const ChanConst& ec = e.cc[k + f];
+            any_nfm |= (ec.flags & AB_F_NFM) != 0;
+            any_am |= (ec.flags & AB_F_NFM) == 0;
+            if ((ec.flags & AB_F_RAW_IQ) && !(ch.flags & AB_F_RAW_IQ)) { /* needs_raw_iq of the channel: the union (src/config.cpp:671-678), dm_dphi from freqlist[0] */
+                ch.flags |= AB_F_RAW_IQ;
+                ch.dm_dphi = ec.dm_dphi;
+                p.dev[sl.dev].any_raw_iq = 1;
+            }
+            if (ec.flags & AB_F_QUADRI) ch.flags |= AB_F_QUADRI; /* the global -Q; only NFM entries carry it */
+        }
+        sl.mixed_am_nfm = any_am && any_nfm;
+        for (int f = 0; f < sl.n; f++) {
+            ChanConst c;
+            ChanState st;
+            if (f == 0) { /* entry 0 is the channel as configured (its CTCSS tables included) */
+                c = ch;
+                st = p.cs0[sl.ext];
+            } else {
+                ChanConst ec = e.cc[k + f];
+                if (ec.ct_slot >= 0) { /* its own tone tables and Goertzel state: the exchange only rewrites ct_slot */
+                    p.tones.push_back(e.tones[ec.ct_slot]);
+                    ec.ct_slot = (int)p.tones.size() - 1;
+                }
+                merge(&ch, &ec, &c, mk.cc, AB_CC_DWORDS);
+                merge(&p.cs0[sl.ext], &e.cs0[k + f], &st, mk.cs, AB_CS_DWORDS);
+            }
+            p.scan_cc.push_back(c);
+            p.scan_cs0.push_back(st);
+        }
+        k += (size_t)sl.n;
+        p.scan.push_back(sl);
+    }
+    return AIRBAND_HIP_OK;
 }
 
 }  // namespace airband

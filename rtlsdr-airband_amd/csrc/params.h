@@ -18,6 +18,12 @@ struct ToneTable {               /* one CTCSS-enabled channel: two Goertzel bank
     int window[2];
 };
 
+struct ScanList {               /* a scan device's list (airband_hip_prepare_scan, scan_bank.h) */
+    int dev = 0, ext = 0;          /* the device and the external index of its one channel */
+    int first_entry = 0, n = 0;    /* its entries in the banks: [first_entry, first_entry + n) */
+    bool mixed_am_nfm = false;     /* AM and NFM entries in one list: stage 1's |bin| is rewritten from the raw I/Q (misc_kernels.hip, scan_mag_kernel) */
+};
+
 struct Plan {
     int fft_log = 0, fft_size = 0, wave_rate = 0, wave_batch = 0, fm_demod = 0;
     int n_dev = 0, total_ch = 0, max_ch = 0;
@@ -43,11 +49,20 @@ struct Plan {
     std::vector<int> bset_bins;          /* [n_bsets][8] the bin every column pair of a table is built for (-1: unused) */
     int64_t hop_bytes_max = 0;
     bool uniform_hop = true;           /* every dongle has the same sfmt / hop (needed by the batched launch) */
+    /* scan-mode devices: the lists, and every entry's constants / initial state (per-channel parts equal to the channel's) */
+    std::vector<ScanList> scan;
+    std::vector<ChanConst> scan_cc;
+    std::vector<ChanState> scan_cs0;
     std::string error;
 };
 
 /* Returns 0 or a negative AIRBAND_HIP_E* code (plan.error holds the text). No GPU needed. */
 int build_plan(const airband_hip_config* cfg, Plan& plan);
+
+/* Adds the scan lists to a plan build_plan() made from the same cfg: validates them (AIRBAND_HIP_EINVAL, see airband_hip_prepare_scan), derives
+ * every entry through build_plan()'s own code with the channel-level values of entry 0, gives each entry with a CTCSS tone its own tone tables, and
+ * merges the channel's needs_raw_iq over the list (src/config.cpp:671-678).  No GPU needed. */
+int build_scan(const airband_hip_config* cfg, const airband_hip_scan_cfg* scan, int n_scan, Plan& plan);
 
 /* Builds the int8 coefficient tables for the matrix-core channelizer.  host_private = false: tables of groups with an AFC channel are left
  * to the device (retune kernel); their slots exist (item_bset, n_bsets) but plan.bfrag / bcorr hold the shared tables only. */
