@@ -191,3 +191,227 @@ def parse_waterfall(text: str):
     for m in re.finditer(r"\x1b\[(\d+);(\d+)f\s*(-?\d+)/\s*(-?\d+)(.) ", text):
         out.append((int(m.group(1)), int(m.group(2)), int(m.group(3)), int(m.group(4)), m.group(5)))
     return out
+
+
+# ---- AFC at every format / fft size / rate ---------------------------------------------------------------------------------------------------------
+AFC_DEFAULT_SHIFTS = [+3, -2, 0, +5, -4, +1, 0, -1]   # transmitter offsets in bins OF THE CHOSEN FFT SIZE
+AFC_DEFAULT_AFCS = [2, 1, 3, 10, 2, 255, 0, 0]
+# The decision screen's margin m (see afc_format_case): 16 x the largest deviation of a bin's power between a float32 FFT and the float64 one, relative to the
+# hop's largest bin power, over the AFC hops of the parametrised configurations and the default fuzz seeds (test_afc_generator.py measures it again and asserts
+# that it stays below AFC_SCREEN_MARGIN / 16).
+AFC_FFT32_DEVIATION = 1.8e-7
+AFC_SCREEN_MARGIN = 16 * AFC_FFT32_DEVIATION
+
+
+def afc_plan(n_channels=8, afcs=AFC_DEFAULT_AFCS, shifts=AFC_DEFAULT_SHIFTS, base_bins=None):
+    """One dongle's AFC plan: [(afc, shift, base_bin)] with the lists cycled over the channels.  shift None: the channel has no transmitter of its own;
+    base_bin None: the channel's frequency comes from the spread of afc_format_case."""
+    return [(afcs[k % len(afcs)], shifts[k % len(shifts)], None if base_bins is None else base_bins[k]) for k in range(n_channels)]
+
+
+def afc_reference_bin(frequency, centerfreq, sample_rate, n_fft):
+    """src/config.cpp:666-667 (with its INTEGER sample_rate / fft_size)."""
+    import math
+
+    return int(math.ceil((frequency + sample_rate - centerfreq) / float(sample_rate // n_fft) - 1.0)) % n_fft
+
+
+def _afc_frequency_for_bin(want, sample_rate, n_fft):
+    q = sample_rate // n_fft
+    f = sg.CENTERFREQ + (want if want < n_fft // 2 else want - n_fft) * q
+    for _ in range(64):
+        got = afc_reference_bin(f, sg.CENTERFREQ, sample_rate, n_fft)
+        if got == want:
+            return f
+        diff = (want - got + n_fft // 2) % n_fft - n_fft // 2
+        f += diff * q
+    raise AssertionError("no frequency for bin %d" % want)
+
+
+def afc_last_hop_samples(iq, sfmt, fullscale, capi, n_fft, hop, B, batch):
+    """The n_fft complex samples (float64, scaled as the reference scales them) of the LAST hop of output batch `batch`: the first batch consumes B + AGC_EXTRA
+    hops, every later one B (src/rtl_airband.cpp:395-492), hop h reads the samples from h * hop on."""
+    start = ((batch + 1) * B + capi.AGC_EXTRA - 1) * hop
+    raw = np.asarray(iq[2 * start:2 * (start + n_fft)]).astype(np.float64)
+    if sfmt == capi.SFMT_U8:
+        raw = (raw - 127.5) / 127.5
+    elif sfmt == capi.SFMT_S8:
+        raw = raw / 128.0
+    elif sfmt == capi.SFMT_S16:
+        raw = raw / (fullscale if fullscale > 0 else 32766.5)
+    return raw[0::2] + 1j * raw[1::2]
+
+
+def afc_replay_walk(power, n_fft, base, afc):
+    """class AFC's walk (src/rtl_airband.cpp:180-251) over float64 bin powers.  Returns (bin, gap): the bin the walk ends on and the smallest distance from a tie
+    of any comparison it made (`value <= base_value`, `value - base_value < threshold`)."""
+    bv = power[base]
+    gap = [np.inf]
+
+    def walk(step):
+        thr, b = 0.0, base
+        while True:
+            if step < 0:
+                if b < -step:
+                    break
+            elif b + step >= n_fft:
+                break
+            v = power[b + step]
+            gap[0] = min(gap[0], abs(v - bv))
+            if v <= bv:
+                break
+            if b == base:
+                thr = (v - bv) / float(afc)
+            else:
+                gap[0] = min(gap[0], abs((v - bv) - thr))
+                if (v - bv) < thr:
+                    break
+                thr = thr + thr / 10.0
+            b += step
+        return b
+
+    b = walk(-1)
+    if b == base:
+        b = walk(+1)
+    return b, gap[0]
+
+
+def oracle_batches(orc, d, iq, n_batches):
+    """orc.run_device batch by batch, with the channels' bins after EVERY batch: dict of stacked arrays + "bin" [n_batches][C]."""
+    C = len(orc.devices[d]["channels"])
+    parts, bins = [], []
+    for b in range(n_batches):
+        r = orc.run_device(d, iq if b == 0 else iq[:0], 1)
+        assert r["n_batches"] == 1, "batch %d: the stream is too short" % b
+        parts.append(r)
+        bins.append([orc.stats(d, j)["bin"] for j in range(C)])
+    out = {k: np.concatenate([p[k] for p in parts]) for k in ("waveout", "iq_out", "axc", "trace", "raw_wavein", "raw_iq")}
+    out["bin"] = np.array(bins, np.int64)
+    out["n_batches"] = n_batches
+    return out
+
+
+def afc_format_case(pkg, sfmt, fft_log, sample_rate, wave_rate, plans, n_batches, first_dongle=0, amplitude=0.08, key=(0.625, 0.25, 0.0625), max_tries=6):
+    """format_case with AFC.  plans = one list per dongle of (afc, shift, base_bin) (afc_plan): the channel's afc value, its transmitter's offset from the bin the
+    reference LOOKS at (the oracle's constants; src/config.cpp:666-667) in bins of THIS fft size (None: no transmitter of its own), and the bin to put the channel
+    on (None: channels spread over +-0.42 of the sample rate, clear of DC).  WAVE_RATE 16000: odd channels are NFM, k % 4 == 1 with a 100 Hz CTCSS tone and notch,
+    k % 4 == 3 with a 12.5 kHz lowpass, as in the BASELINE plan.  Every third channel has I/Q outputs, so that its raw bins can be compared.
+    key = (period, on, slot) in seconds: every transmitter keys for two batches out of five, (dongle + channel) % 8 slots of half a batch late -- channels k and
+    k + 1 of a group open in the same batch, and channel k + 4 opens in the batch in which channel k returns home.
+
+    DECISION SCREEN.  AFC compares float32 bin powers; the GPU's come from a float32 wavefront FFT, the oracle's from a float64 radix-2 rounded to float, so a
+    near-tie may resolve either way.  For every batch in which the oracle opens an AFC channel the windowed spectrum of the batch's last hop is recomputed in numpy
+    float64 and the walk replayed; a dongle's stream is kept only if every comparison of every such walk clears m * P, P = that hop's largest bin power (and the
+    replayed walk must end where the oracle's did).  A stream that is not kept is replaced by the next synthetic dongle's (siggen's dongle index); the case
+    counts both.
+    m = AFC_SCREEN_MARGIN = 16 x AFC_FFT32_DEVIATION.  Measured on the CPU (tests/test_afc_generator.py, over every parametrised configuration of
+    tests/test_gpu_afc.py and the default fuzz seeds, about 650 AFC hops): the largest |P32[k] - P64[k]| / max(P64) between numpy's complex64 FFT of the
+    windowed samples and the complex128 one was 1.77e-7 (fft 512, u8); AFC_FFT32_DEVIATION = 1.8e-7, so m = 2.9e-6.
+
+    Returns dict(devices, iq, ref, base, needs_iq, generated, dropped, ups, downs, returns, together, crossed, min_gap, fft32_dev, hops): ref[d] = oracle_batches() of the kept
+    stream; ups / downs / returns count the oracle's '<', '>' and returns to the base bin; together = batches in which two channels of one group of eight
+    moved, crossed = batches in which one moved while another of its group returned."""
+    import pyoracle
+
+    capi = pkg.capi
+    n_fft, hop, B = 1 << fft_log, round(sample_rate / wave_rate), wave_rate // 8
+    mixed = wave_rate == 16000
+    devices = []
+    for d, plan in enumerate(plans):
+        chans = []
+        n = len(plan)
+        for k, (afc, shift, base_bin) in enumerate(plan):
+            if base_bin is None:
+                u = k / max(n - 1, 1)
+                frac = -0.42 + 0.78 * u if u < 0.5 else 0.03 + 0.78 * (u - 0.5)
+                freq = sg.CENTERFREQ + int(frac * sample_rate)
+            else:
+                freq = _afc_frequency_for_bin(base_bin, sample_rate, n_fft)
+            c = dict(frequency=freq, modulation=0, afc=afc, squelch_threshold_dbfs=0, squelch_snr_threshold_db=-1.0, notch_freq=0.0, notch_q=0.0, ctcss_freq=0.0,
+                     bandwidth_hz=0, ampfactor=1.0, tau_us=-1, has_iq_outputs=1 if k % 3 == 0 else 0)
+            if mixed and k % 2 == 1:
+                c["modulation"] = 1
+                if k % 4 == 1:
+                    c["ctcss_freq"] = c["notch_freq"] = 100.0
+                else:
+                    c["bandwidth_hz"] = 12500
+            chans.append(c)
+        gain = (200.0 if d % 2 == 0 else 50.0) if sfmt == capi.SFMT_S16 else 1.0
+        devices.append(dict(channels=chans, sample_rate=sample_rate, sfmt=sfmt, fullscale=0.0 if sfmt != capi.SFMT_S16 else 127.5 * gain))
+    orc = pyoracle.Oracle(devices, wave_rate=wave_rate, fft_log=fft_log)
+    try:
+        base = [[int(orc.constants(d, k)[0]) for k in range(len(p))] for d, p in enumerate(plans)]
+        needs_iq = [[bool(orc.constants(d, k)[13]) for k in range(len(p))] for d, p in enumerate(plans)]
+    finally:
+        orc.close()
+    for d, plan in enumerate(plans):
+        for k, (_, _, want) in enumerate(plan):
+            assert want is None or base[d][k] == want, (d, k, want, base[d][k])
+    window = np.array([pyoracle.lib().orc_window_coeff(n_fft, i) for i in range(n_fft)], np.float64)
+    n_samples = (n_batches * B + capi.AGC_EXTRA) * hop + n_fft + 8
+    out = dict(devices=devices, iq=[], ref=[], generated=0, dropped=0, ups=0, downs=0, returns=0, together=0, crossed=0, min_gap=np.inf, fft32_dev=0.0, hops=0,
+               base=base, needs_iq=needs_iq)
+    next_dongle = first_dongle
+    for d, plan in enumerate(plans):
+        carriers = []
+        for k, (afc, shift, _) in enumerate(plan):
+            if shift is None:
+                continue
+            b = base[d][k]
+            off = ((b if b < n_fft // 2 else b - n_fft) + shift) * sample_rate / n_fft
+            c = devices[d]["channels"][k]
+            carriers.append(sg.make_carrier(off, sample_rate, amplitude=amplitude, kind=c["modulation"], ctcss_hz=c["ctcss_freq"], key_slot=k, key_period_s=key[0],
+                                            key_on_s=key[1], key_slot_s=key[2]))
+        gain = devices[d]["fullscale"] / 127.5 if sfmt == capi.SFMT_S16 else 1.0
+        for attempt in range(max_tries):
+            iq = convert_format(sg.generate_u8(next_dongle, 0, n_samples, carriers), sfmt, capi, gain)
+            next_dongle += 1
+            out["generated"] += 1
+            orc = pyoracle.Oracle(devices, wave_rate=wave_rate, fft_log=fft_log)
+            try:
+                ref = oracle_batches(orc, d, iq, n_batches)
+            finally:
+                orc.close()
+            keep, gap_min, dev32, hops = True, np.inf, 0.0, 0
+            for b in range(n_batches):
+                opening = [k for k, (afc, _, _) in enumerate(plan) if afc and ref["axc"][b][k] != 32 and (b == 0 or ref["axc"][b - 1][k] == 32)]
+                if not opening:
+                    continue
+                x = afc_last_hop_samples(iq, sfmt, devices[d]["fullscale"], capi, n_fft, hop, B, b) * window
+                spec = np.fft.fft(x)
+                power = spec.real ** 2 + spec.imag ** 2
+                P = float(power.max())
+                s32 = np.fft.fft(x.astype(np.complex64))
+                assert s32.dtype == np.complex64
+                p32 = s32.real.astype(np.float32) ** 2 + s32.imag.astype(np.float32) ** 2
+                dev32 = max(dev32, float(np.abs(p32.astype(np.float64) - power).max()) / P)
+                hops += 1
+                for k in opening:
+                    end, gap = afc_replay_walk(power, n_fft, base[d][k], plan[k][0] & 0xff)
+                    gap_min = min(gap_min, gap / P)
+                    if gap < AFC_SCREEN_MARGIN * P:
+                        keep = False
+                    else:
+                        assert end == ref["bin"][b][k], "dongle %d batch %d channel %d: the float64 replay ends on bin %d, the oracle on %d" % (d, b, k, end, ref["bin"][b][k])
+            if keep:
+                break
+            out["dropped"] += 1
+        else:
+            raise AssertionError("dongle %d: no decision-stable stream in %d tries" % (d, max_tries))
+        out["iq"].append(iq)
+        out["ref"].append(ref)
+        out["min_gap"] = min(out["min_gap"], gap_min)
+        out["fft32_dev"] = max(out["fft32_dev"], dev32)
+        out["hops"] += hops
+        bins, home = ref["bin"], np.array(base[d])
+        prev = np.vstack([home[None, :], bins[:-1]])
+        up, down = ref["axc"] == ord("<"), ref["axc"] == ord(">")
+        back = (prev != home) & (bins == home)
+        out["ups"] += int(up.sum())
+        out["downs"] += int(down.sum())
+        out["returns"] += int(back.sum())
+        for g in range(0, len(plan), 8):
+            mv = (up | down)[:, g:g + 8].sum(axis=1)
+            out["together"] += int((mv >= 2).sum())
+            out["crossed"] += int(((mv >= 1) & (back[:, g:g + 8].sum(axis=1) >= 1)).sum())
+    return out

@@ -299,3 +299,23 @@ def test_afc_bit_exact(pkg, built):
     assert (ref["axc"] == ord(">")).any() and (ref["axc"] == ord("<")).any(), "test signal never triggered AFC"
     for j in range(8):
         assert ref["stats"][j]["bin"] == orc.stats(0, j)["bin"]
+
+
+@need_ref
+@pytest.mark.parametrize("sfmt_name,fft_log,sample_rate,wave_rate", [("SFMT_U8", 10, 2_560_000, 8000), ("SFMT_S16", 11, 2_400_000, 8000), ("SFMT_U8", 13, 2_560_000, 8000),
+                                                                      ("SFMT_F32", 12, 2_560_000, 16000)], ids=["fft1024", "fft2048_cs16", "fft8192", "fft4096_nfm_build_cf32"])
+def test_afc_bit_exact_at_other_fft_sizes(pkg, built, sfmt_name, fft_log, sample_rate, wave_rate):
+    """test_afc_bit_exact where tests/test_gpu_afc.py uses the oracle as the judge: fft 1024, 2048 (CS16, 2.4 MS/s) and 8192 on the AM build and fft 4096 on the NFM
+    build (NFM + CTCSS + lowpass channels whose bin moves), streams of helpers.afc_format_case (transmitters a few bins of THAT fft size off).  axc, audio and the
+    final bins of the oracle equal the compiled reference's."""
+    n_batches = 11
+    case = helpers.afc_format_case(pkg, getattr(pkg.capi, sfmt_name), fft_log, sample_rate, wave_rate, [helpers.afc_plan(8)], n_batches)
+    ref = _reference_run(case["devices"], case["iq"], n_batches, nfm=wave_rate == 16000, fft_log=fft_log)[0]
+    got = case["ref"][0]
+    assert ref["n_batches"] == n_batches
+    assert np.array_equal(ref["axc"], got["axc"]), "\n%s\n--\n%s" % (helpers.axc_str(ref["axc"]), helpers.axc_str(got["axc"]))
+    assert np.array_equal(ref["waveout"].view(np.uint32), got["waveout"].view(np.uint32))
+    assert np.array_equal(ref["iq_out"].view(np.uint32), got["iq_out"].view(np.uint32))
+    assert (ref["axc"] == ord(">")).any() and (ref["axc"] == ord("<")).any() and case["returns"] > 0, "test signal never triggered AFC"
+    for j in range(8):
+        assert ref["stats"][j]["bin"] == got["bin"][-1][j]
