@@ -7,7 +7,6 @@
  */
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
-#include <rccl/rccl.h> /* types and prototypes only: librccl.so is loaded on first use (airband_hip_comm_*) */
 
 #include <atomic>
 #include <cstdio>
@@ -18,10 +17,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/airband_hip.h"
-#include "common.h"
+#include "handle.h"
 #include "kernels.h"
-#include "params.h"
 #include "scan_bank.h"
 
 /* upper bound for the int8 coefficient tables of a handle -- one per distinct group of eight bins plus one per AFC group; past it prepare() picks the wavefront-FFT
@@ -40,172 +37,6 @@ using namespace airband;
 namespace {
 
 thread_local std::string g_prepare_error;
-
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t n = 0;
-    hipError_t alloc(size_t count) {
-        n = count;
-        if (count == 0) return hipSuccess;
-        return hipMalloc((void**)&p, count * sizeof(T));
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        n = 0;
-    }
-};
-
-}  // namespace
-
-struct airband_hip_handle {
-    Plan plan;
-    uint32_t flags = 0;
-    int hip_device = 0;
-    hipStream_t stream = nullptr;
-    hipStream_t side[3] = {nullptr, nullptr, nullptr}; /* fused demod kinds run beside the CTCSS chain */
-    hipEvent_t fork_ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    /* AIRBAND_HIP_FLAG_PIPELINE: stage 1 of batch k runs on `front` while stage 2 of batch k-1 runs on `stream` */
-    bool pipeline = false;
-    hipStream_t front = nullptr;
-    hipEvent_t ev_in = nullptr, ev_back = nullptr, ev_wait = nullptr, front_done[2] = {nullptr, nullptr};
-    hipStream_t last_stream = nullptr; /* stream the last sequential batch ran on (the caller's or ours) */
-    hipEvent_t ev_spec[2] = {nullptr, nullptr}; /* AFC on the matrix-core channelizer: the last hop's spectrum runs on a side stream beside stage 1 (fork, done) */
-    hipEvent_t ev_last = nullptr;      /* recorded behind every batch that ran on a CALLER's stream: collect / read_* / synchronize / release
-                                          order themselves behind it (the caller's stream itself may be gone by then, our event is not) */
-    bool ev_last_pending = false;
-    int row0_front = 0;            /* ring row of the batch stage 1 writes next (== row0 when not pipelined) */
-    uint64_t front_batches = 0;    /* batches whose stage 1 has been enqueued */
-    /* per-stage GPU time: a pool of event sets (one per process call) harvested lazily, so that nobody has to
-     * synchronise inside a run to read timings */
-    static constexpr int EV_POOL = 16;
-    hipEvent_t evp[EV_POOL][5] = {}; /* stage 1 begin / end, stage 2 begin, demod end, batch end */
-    uint8_t evp_state[EV_POOL] = {0}; /* bit 0: stage-1 pair recorded, bit 1: stage-2 pair recorded */
-    double t_sum[4] = {0, 0, 0, 0};
-    int64_t t_n[2] = {0, 0};          /* harvested stage-1 / stage-2 pairs */
-    float t_last[4] = {0, 0, 0, 0};
-    bool timings_valid = false;
-    std::string error;
-
-    /* geometry */
-    int B = 0, R = 0, N = 0;
-    int n_slots = 0;      /* demod slots: channels sorted by kind, every kind padded to whole 64-slot blocks */
-    std::vector<int> slot_to_ext, ext_to_slot;
-    int kind_first_block[AB_KIND_COUNT] = {0}, kind_n_blocks[AB_KIND_COUNT] = {0};
-    int64_t hop_bytes = 0, first_batch_bytes = 0, batch_bytes = 0, lookahead_bytes = 0;
-    int row0 = 0;
-    int wave_stride = 0;   /* floats between two channels' rows of d_out_wave */
-    uint64_t batches_done = 0;
-    bool results_ready = false;
-    uint64_t overruns = 0;
-
-    /* device memory */
-    DevBuf<DevConst> d_dev;
-    DevBuf<ChanConst> d_cc;
-    DevBuf<ChanState> d_cs;
-    DevBuf<int> d_slot_to_ext, d_ext_to_slot;
-    DevBuf<uint8_t> d_block_kind;
-    DevBuf<float> d_window, d_sin, d_cos, d_twiddle;
-    DevBuf<float> d_window_dec; /* fft_size >= 1024: the window de-interleaved by sample index mod (fft_size / 512), for the decimated wavefront FFT (channelizer_fft.hip) */
-    DevBuf<float> d_mag, d_sqbuf, d_ct_coeff, d_ct_q;
-    DevBuf<float2> d_iq, d_iq_out, d_ct_af;
-    DevBuf<unsigned long long> d_ct_mask;
-    int ct_first_block = 0, ct_n_blocks = 0, ct_pk_pitch = 0;
-    /* AIRBAND_HIP_FLAG_REGROUP: the batch's slot order (demod.hip, "regrouping") */
-    bool regroup = false;
-    int regroup_mode = 1;          /* 1: channels sorted inside lockstep workgroups; 2: line groups sorted, wavefronts free-running (demod.hip) */
-    DevBuf<int> d_perm;       /* regroup mode 3: the batch's slot permutation (demod.hip, regroup_perm_kernel) */
-    DevBuf<uint8_t> d_sq_key; /* split kinds: the front kernel's note for the back kernel (had audio in this batch) */
-    DevBuf<uint8_t> d_trace;
-    DevBuf<float> d_out_wave, d_out_iq;
-    DevBuf<uint8_t> d_out_axc;
-    DevBuf<airband_hip_channel_stats> d_stats;
-    DevBuf<float> d_tmp_wavein, d_tmp_iqin, d_spectrum;
-    bool any_afc = false, afc_spectrum_valid = false; /* process_bins() has no spectrum: AFC is skipped there */
-    DevBuf<uint8_t> d_tmp_trace;
-    int ct_stride = 0;
-    /* matrix-core channelizer */
-    bool use_f32 = false;          /* CF32 dongles on the float32 matrix pipe (channelizer_f32.hip) */
-    DevBuf<float> d_ftab;
-    bool use_dft = false;
-    DevBuf<int> d_item_dev, d_item_group, d_item_bset, d_item_private, d_item_home; /* d_item_bset: what stage 1 reads (the re-tune kernel switches AFC groups between their home and private tables) */
-    DevBuf<int8_t> d_bfrag;
-    DevBuf<double> d_bcorr;
-    DevBuf<float> d_dft_partial; /* fft_size 8192: partial sums between the two passes of eight window pieces */
-    DevBuf<int> d_bset_bin;      /* [n_bsets][8] bin each coefficient column pair is built for (AFC re-tunes private tables on the device) */
-    const void* last_iq = nullptr; /* input of the batch stage 1 ran last (AFC looks at its last hop once stage 2 has decided) */
-    size_t last_iq_stride = 0;
-    int last_n_hops = 0;
-
-    /* host-ring path: one PINNED circular buffer per dongle (row d of h_ring, ring_cap bytes).  submit() copies the caller's bytes
-     * straight into it -- the only CPU copy on the way -- and may be called for DIFFERENT dongles from several threads at once;
-     * process() ships a batch with (at most two, where the span wraps) strided DMA transfers on a copy stream into one of two
-     * device staging buffers while the kernels of the previous batch still read the other. */
-    std::atomic<uint8_t*> h_ring{nullptr};                 /* published (release) by host_path_init() once ring_cap / stage_stride / the staging buffers exist; read (acquire) by submit() and process() */
-    int64_t ring_cap = 0;                                  /* bytes per dongle */
-    std::unique_ptr<std::atomic<uint64_t>[]> ring_wr;      /* per dongle: stream bytes accepted so far */
-    uint64_t ring_rd = 0;                                  /* stream position of the next batch (common to all dongles: they advance in lockstep) */
-    std::atomic<uint64_t> ring_free{0};                    /* stream position up to which the ring may be overwritten (lags ring_rd by the batch in flight) */
-    DevBuf<uint8_t> d_stage2[2];
-    int64_t stage_stride = 0;
-    hipStream_t h2d = nullptr;
-    hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_stage_read[2] = {nullptr, nullptr};
-    uint64_t host_batches = 0;
-    std::mutex host_init_lock;
-
-    /* dongles switched off with airband_hip_device_enable(): skipped by the availability rule and by both stages */
-    std::unique_ptr<std::atomic<uint8_t>[]> dev_enabled; /* (atomic: a feeder thread's submit() reads its dongle's flag while the demod thread switches it) */
-    int n_enabled = 0;
-    std::vector<ChanConst> cc_slots; /* host copy of d_cc (slot order): the VALID bit of a dongle's slots follows its enable state */
-
-    /* mixers */
-    std::vector<int> mix_pos;       /* connection index (order of airband_hip_set_mixers) -> position in the per-mixer grouped arrays */
-    std::vector<int> mix_chan_host; /* grouped external channel indices, for re-enabling an input */
-    std::vector<uint8_t> mix_user_on; /* by position: airband_hip_mixer_enable_input()'s say; an input counts while this AND its dongle are on */
-    int n_mixers = 0;
-    int n_mix_runs = 0;
-    DevBuf<int> d_mix_chan, d_mix_first, d_mix_run_first, d_mix_run_mixer, d_mix_first_run;
-    DevBuf<float> d_mix_run_left, d_mix_run_right;
-    DevBuf<uint8_t> d_mix_run_signal;
-    DevBuf<float> d_mix_ml, d_mix_mr, d_mix_left, d_mix_right;
-    DevBuf<uint8_t> d_mix_stereo, d_mix_signal;
-
-    /* the mixer exchange (airband_hip_comm_*): this handle's rank in an RCCL communicator over the GPUs that hold the other dongles */
-    ncclComm_t comm = nullptr;
-    hipEvent_t ev_peer = nullptr; /* airband_hip_add_mixers: "src's batch is done" for dst's stream */
-
-    /* scan-mode devices (airband_hip_prepare_scan, scan_bank.h): nothing of this exists on a handle without scan lists */
-    std::vector<int> scan_of_dev;      /* device -> its list in plan.scan, -1 */
-    std::vector<int> scan_cur;         /* by list: the entry airband_hip_set_freq_index() put in force */
-    std::vector<int> scan_latch[2];    /* by list: the entry of front batch k, at [k & 1] (stage 2 of a pipelined batch runs during the next call) */
-    int scan_first_row[2] = {0, 0};    /* the ring rows stage 1 of front batch k produced: [first_row, first_row + n_rows) */
-    int scan_n_rows[2] = {0, 0};
-    std::vector<int> scan_held;        /* by list: the entry the slot holds once every exchange enqueued so far has run */
-    DevBuf<ChanConst> d_bank_cc;
-    DevBuf<ChanState> d_bank_cs;
-    DevBuf<float> d_bank_sq;
-    DevBuf<uint32_t> d_scan_mask;      /* [AB_CS_DWORDS] ChanState masks, then [AB_CC_DWORDS] ChanConst masks */
-    DevBuf<int> d_switch[2];           /* the batch's switch list (slot, entry parked, entry brought in), two in flight */
-    int* h_switch[2] = {nullptr, nullptr}; /* pinned staging of the lists */
-    hipEvent_t ev_switch[2] = {nullptr, nullptr};
-    bool switch_used[2] = {false, false};
-    int switch_buf = 0;
-    DevBuf<int> d_scan_mix_slots;      /* slots of lists that mix AM and NFM entries (scan_mag_kernel) */
-    DevBuf<ChanConst> d_fs_cc;         /* airband_hip_freq_stats: one composed image, its stats row */
-    DevBuf<ChanState> d_fs_cs;
-    DevBuf<airband_hip_channel_stats> d_fs_stats;
-    DevBuf<int> d_fs_zero;
-
-    /* synthetic dongles */
-    DevBuf<int16_t> d_sin_tab;
-    DevBuf<long long> d_carriers;
-    int n_carriers = 0, noise_q8 = 0;
-    int sig_n_plans = 1;            /* airband_hip_set_signal_plan_shift */
-    unsigned sig_shift_step = 0;
-};
-
-namespace {
 
 int fail(airband_hip_handle* h, int code, const std::string& msg) {
     if (h) h->error = msg;
@@ -227,64 +58,25 @@ hipError_t upload(DevBuf<T>& b, const std::vector<T>& v) {
     return hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
 }
 
+/* Everything in flight must be done before the handle's memory goes away (the handle's members free themselves, handle.h): a batch enqueued on a
+ * caller's stream, the front stream of a pipelined handle, the forked demod streams, the copy stream of the host ring. */
 void destroy(airband_hip_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->hip_device);
     (void)airband_hip_comm_destroy(h);
-    if (h->ev_peer) (void)hipEventDestroy(h->ev_peer);
-    /* everything in flight must be done before its memory goes away: the front stream of a pipelined handle, the forked demod streams */
-    if (h->ev_last && h->ev_last_pending) (void)hipEventSynchronize(h->ev_last); /* a batch enqueued on a caller's stream */
+    if (h->ev_last && h->ev_last_pending) (void)hipEventSynchronize(h->ev_last);
     if (h->front) (void)hipStreamSynchronize(h->front);
     for (auto& st : h->side)
         if (st) (void)hipStreamSynchronize(st);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    h->d_dev.release(); h->d_cc.release(); h->d_cs.release(); h->d_slot_to_ext.release(); h->d_ext_to_slot.release(); h->d_block_kind.release();
-    h->d_window.release(); h->d_sin.release(); h->d_cos.release(); h->d_twiddle.release(); h->d_window_dec.release();
-    h->d_mag.release(); h->d_sqbuf.release(); h->d_ct_coeff.release(); h->d_ct_q.release();
-    h->d_iq.release(); h->d_iq_out.release(); h->d_trace.release(); h->d_ct_af.release(); h->d_ct_mask.release();
-    h->d_out_wave.release(); h->d_out_iq.release(); h->d_out_axc.release(); h->d_stats.release();
-    h->d_tmp_wavein.release(); h->d_tmp_iqin.release(); h->d_tmp_trace.release(); h->d_spectrum.release();
-    h->d_sq_key.release(); h->d_perm.release();
-    h->d_ftab.release(); h->d_item_dev.release(); h->d_item_group.release(); h->d_item_bset.release(); h->d_item_private.release(); h->d_item_home.release(); h->d_bfrag.release(); h->d_bcorr.release(); h->d_dft_partial.release(); h->d_bset_bin.release();
     if (h->h2d) (void)hipStreamSynchronize(h->h2d);
-    h->d_stage2[0].release(); h->d_stage2[1].release();
-    if (h->h_ring.load()) (void)hipHostFree(h->h_ring.load());
-    for (auto& e : h->ev_h2d)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : h->ev_stage_read)
-        if (e) (void)hipEventDestroy(e);
-    if (h->h2d) (void)hipStreamDestroy(h->h2d);
-    h->d_mix_chan.release(); h->d_mix_first.release(); h->d_mix_ml.release(); h->d_mix_mr.release();
-    h->d_mix_left.release(); h->d_mix_right.release(); h->d_mix_stereo.release(); h->d_mix_signal.release();
-    h->d_mix_run_first.release(); h->d_mix_run_mixer.release(); h->d_mix_first_run.release();
-    h->d_mix_run_left.release(); h->d_mix_run_right.release(); h->d_mix_run_signal.release();
-    h->d_sin_tab.release(); h->d_carriers.release();
-    h->d_bank_cc.release(); h->d_bank_cs.release(); h->d_bank_sq.release(); h->d_scan_mask.release(); h->d_scan_mix_slots.release();
-    h->d_switch[0].release(); h->d_switch[1].release();
-    h->d_fs_cc.release(); h->d_fs_cs.release(); h->d_fs_stats.release(); h->d_fs_zero.release();
-    for (auto& p : h->h_switch)
-        if (p) (void)hipHostFree(p);
-    for (auto& e : h->ev_switch)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& set : h->evp)
-        for (auto& e : set)
-            if (e) (void)hipEventDestroy(e);
-    if (h->ev_in) (void)hipEventDestroy(h->ev_in);
-    if (h->ev_back) (void)hipEventDestroy(h->ev_back);
-    if (h->ev_wait) (void)hipEventDestroy(h->ev_wait);
-    if (h->ev_last) (void)hipEventDestroy(h->ev_last);
-    for (auto& e : h->ev_spec)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& e : h->front_done)
-        if (e) (void)hipEventDestroy(e);
-    if (h->front) (void)hipStreamDestroy(h->front);
-    for (auto& e : h->fork_ev)
-        if (e) (void)hipEventDestroy(e);
-    for (auto& st : h->side)
-        if (st) (void)hipStreamDestroy(st);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
 }
+
+/* airband_hip_prepare_scan() holds the handle it is building in one of these: every failure exit releases it the way airband_hip_release() would.
+ * Its HIP_TRY()s name PREPARING instead of the handle, which sends the message to the thread's prepare error -- the handle does not outlive a failure. */
+using HandlePtr = std::unique_ptr<airband_hip_handle, void (*)(airband_hip_handle*)>;
+constexpr airband_hip_handle* PREPARING = nullptr;
 
 /* Results of a batch that ran on a caller's stream: make the handle's own stream (on which collect / read_* / the stats kernel
  * are issued) wait for it on the GPU. */
@@ -292,11 +84,24 @@ void order_behind_last_batch(airband_hip_handle* h) {
     if (h->ev_last && h->ev_last_pending) (void)hipStreamWaitEvent(h->stream, h->ev_last, 0);
 }
 
+/* Work was enqueued on stream s.  If that is not the handle's own stream (a caller's: handed to process_device, or the one the last batch ran on), what the
+ * handle does next on its own -- collect / read_* / synchronize / release, the next batch's sums -- has to come behind it: ev_last marks the place. */
+int results_enqueued_on(airband_hip_handle* h, hipStream_t s) {
+    if (s == h->stream) return AIRBAND_HIP_OK;
+    HIP_TRY(h, h->ev_last.ensure(), AIRBAND_HIP_ENODEV);
+    HIP_TRY(h, hipEventRecord(h->ev_last, s), AIRBAND_HIP_ERUNTIME);
+    h->ev_last_pending = true;
+    return AIRBAND_HIP_OK;
+}
+
+/* the stream on which the last batch's mixer sums become final */
+hipStream_t results_stream(airband_hip_handle* h) { return h->pipeline ? h->stream : (h->last_stream ? h->last_stream : h->stream); }
+
 /* Per-stage GPU times: every batch records into its own event set; finished sets are folded into running sums here. */
 void harvest_timings(airband_hip_handle* h, bool wait) {
     for (int i = 0; i < airband_hip_handle::EV_POOL; i++) {
         if (h->evp_state[i] != 3) continue;
-        hipEvent_t* e = h->evp[i];
+        const Event* e = h->evp[i];
         if (wait) {
             if (hipEventSynchronize(e[4]) != hipSuccess || hipEventSynchronize(e[1]) != hipSuccess) continue;
         } else if (hipEventQuery(e[4]) != hipSuccess || hipEventQuery(e[1]) != hipSuccess) {
@@ -313,7 +118,7 @@ void harvest_timings(airband_hip_handle* h, bool wait) {
     }
 }
 
-hipEvent_t* event_set(airband_hip_handle* h, uint64_t batch, int half) {
+Event* event_set(airband_hip_handle* h, uint64_t batch, int half) {
     const int i = (int)(batch % airband_hip_handle::EV_POOL);
     if (half == 0 && h->evp_state[i] != 0) { /* the pool wrapped around a set nobody has read yet */
         harvest_timings(h, true);
@@ -347,22 +152,42 @@ void launch_retune_tables(airband_hip_handle* h, hipStream_t s, int epoch) {
     launch_retune(ra, s);
 }
 
-/* matrix-core handles with AFC channels: the full spectrum of the batch's LAST hop, for the dongles that have one (one wavefront FFT per
- * such dongle per batch -- afc.finalize(dev, i, fftout) runs once per batch on the output of its last FFT, src/rtl_airband.cpp:626-630) */
-void launch_last_hop_spectrum(airband_hip_handle* h, hipStream_t s) {
+/* the ring rows a batch's stage 1 produces */
+struct FrontRows {
+    int first_row, n_hops;
+};
+
+/* the first batch also produces the AGC_EXTRA lead-in hops (waveend starts at 0, src/config.cpp:805) */
+FrontRows front_rows(const airband_hip_handle* h) {
+    const bool first = h->front_batches == 0;
+    return {first ? 0 : AB_AGC_EXTRA, first ? h->B + AB_AGC_EXTRA : h->B};
+}
+
+/* what ChannelizerArgs, DftArgs and F32Args have in common: the input spans, the constants, the rings and the rows to produce in them */
+template <class Args>
+void fill_front_args(Args& a, const airband_hip_handle* h, const void* d_iq, size_t stride_bytes, int row0, FrontRows r) {
+    a.iq = (const uint8_t*)d_iq;
+    a.iq_stride = (long)stride_bytes;
+    a.dev = h->d_dev.p;
+    a.cc = h->d_cc.p;
+    a.ext_to_slot = h->d_ext_to_slot.p;
+    a.mag = h->d_mag.p;
+    a.iq_bins = h->d_iq.p;
+    a.row0 = row0;
+    a.ring_rows = h->R;
+    a.first_row = r.first_row;
+    a.n_hops = r.n_hops;
+}
+
+/* the wavefront FFT: a batch (spectrum_only 0: last_spectrum is null on a handle without AFC channels), or one hop's spectrum alone */
+ChannelizerArgs fft_args(const airband_hip_handle* h, const void* d_iq, size_t stride_bytes, int row0, FrontRows r, int spectrum_only) {
     const Plan& p = h->plan;
     ChannelizerArgs ca;
-    ca.iq = (const uint8_t*)h->last_iq + (size_t)(h->last_n_hops - 1) * (size_t)h->hop_bytes;
-    ca.iq_stride = (long)h->last_iq_stride;
-    ca.dev = h->d_dev.p;
+    fill_front_args(ca, h, d_iq, stride_bytes, row0, r);
     ca.cs = h->d_cs.p;
-    ca.cc = h->d_cc.p;
-    ca.ext_to_slot = h->d_ext_to_slot.p;
     ca.window = h->d_window.p;
     ca.window_dec = h->d_window_dec.p;
     ca.twiddle = reinterpret_cast<const float2*>(h->d_twiddle.p);
-    ca.mag = h->d_mag.p;
-    ca.iq_bins = h->d_iq.p;
     ca.last_spectrum = h->d_spectrum.p;
     ca.n_dev = p.n_dev;
     ca.fft_log = p.fft_log;
@@ -370,13 +195,90 @@ void launch_last_hop_spectrum(airband_hip_handle* h, hipStream_t s) {
     ca.bytes_per_sample = p.dev[0].bytes_per_sample;
     ca.sfmt = p.dev[0].sfmt;
     ca.scale = p.dev[0].scale;
-    ca.row0 = 0;
-    ca.ring_rows = h->R;
-    ca.first_row = 0;
-    ca.n_hops = 1;
     ca.max_ch = p.max_ch;
-    ca.spectrum_only = 1;
-    launch_channelizer_fft(ca, s);
+    ca.spectrum_only = spectrum_only;
+    return ca;
+}
+
+F32Args f32_args(const airband_hip_handle* h, const void* d_iq, size_t stride_bytes, FrontRows r) {
+    const Plan& p = h->plan;
+    F32Args a;
+    fill_front_args(a, h, d_iq, stride_bytes, h->row0_front, r);
+    a.item_dev = h->d_item_dev.p;
+    a.item_group = h->d_item_group.p;
+    a.item_bset = h->d_item_bset.p;
+    a.btab = h->d_ftab.p;
+    a.n_items = (int)p.item_dev.size();
+    a.fft_size = p.fft_size;
+    a.hop_bytes = (int)h->hop_bytes;
+    a.pad = f32_pad_bytes(p.dev[0].hop_samples);
+    a.lds_per_buf = f32_lds_per_buf(p.fft_size, p.dev[0].hop_samples);
+    a.seg = 0;
+    a.n_seg = 1;
+    a.partial = reinterpret_cast<float4*>(h->d_dft_partial.p);
+    /* enough workgroups to fill 256 CUs x 2 even with few dongles: split each dongle's tiles */
+    const int tiles = (a.n_hops + 15) / 16 + 1;
+    int splits = (2048 + a.n_items - 1) / a.n_items;
+    if (splits > tiles / 4) splits = tiles / 4;
+    if (splits < 1) splits = 1;
+    a.splits = splits;
+    return a;
+}
+
+DftArgs dft_args(const airband_hip_handle* h, const void* d_iq, size_t stride_bytes, FrontRows r) {
+    const Plan& p = h->plan;
+    DftArgs a;
+    fill_front_args(a, h, d_iq, stride_bytes, h->row0_front, r);
+    a.item_dev = h->d_item_dev.p;
+    a.item_group = h->d_item_group.p;
+    a.item_bset = h->d_item_bset.p;
+    a.bfrag = h->d_bfrag.p;
+    a.corr = h->d_bcorr.p;
+    /* table units -> sample units: u8 (b - 127.5) / 127.5; s8 i / 128; CS16 x / fullscale (the kernel multiplies by the dongle's 1 / fullscale) */
+    a.unscale = p.dev[0].sfmt == AIRBAND_SFMT_S16 ? p.b_unscale * 127.5 : p.dev[0].sfmt == AIRBAND_SFMT_S8 ? p.b_unscale * 127.5 / 128.0 : p.b_unscale;
+    a.sfmt = p.dev[0].sfmt;
+    a.edge_hi_zero = p.b_edge_hi_zero ? 1 : 0;
+    a.n_dev = p.n_dev;
+    a.n_items = (int)p.item_dev.size();
+    a.fft_size = p.fft_size;
+    a.hop_bytes = (int)h->hop_bytes;
+    /* the whole window is staged, also when it is worked on in pieces of 512 samples -- up to eight of them per launch (fft_size 8192: two passes) */
+    const int np_total = p.fft_size > 512 ? p.fft_size / 512 : 1, np = np_total > 8 ? 8 : np_total;
+    const int win_bytes = 2 * p.fft_size * p.dev[0].bytes_per_sample / np_total * np;
+    a.partial = reinterpret_cast<float4*>(h->d_dft_partial.p);
+    a.lds_per_buf = dft_lds_per_buf((int)h->hop_bytes, win_bytes, np);
+    a.nbuf = dft_nbuf((int)h->hop_bytes, win_bytes, np);
+    a.sub = dft_sub((int)h->hop_bytes, win_bytes, np);
+    /* Pipelined handles (stage 1 of this batch runs beside stage 2 of the batch before): eight channelizer wavefronts of ~250 registers ARE a CU's register file, and
+     * stage-2 wavefronts then only get onto a CU when one of them retires.  Held to FIVE per CU (it loses ~5 % alone: 7 and 6 per CU cost nothing, 4 cost 12 %,
+     * profiles/r06_occupancy/) the channelizer leaves three SIMDs a wavefront's worth of registers each: configs[2] 14.05 ms sequential, 13.77 pipelined as before,
+     * 13.05 like this (13.5 / 14.0 at 4 / 6 per CU; profiles/r06_pipelined/).  The LDS it asks for and never touches is what holds it there. */
+    a.extra_lds = 0;
+    if (h->pipeline && np_total == 1) {
+        const int used = a.nbuf * a.lds_per_buf, want = 28 * 1024; /* 160 KiB / 28 KiB = 5 */
+        if (used < want) a.extra_lds = want - used;
+    }
+    /* enough waves to fill 256 CUs x 8 waves even with few dongles: split each dongle's tiles */
+    const int steps = ((a.n_hops + 15) / 16 + 1 + a.sub - 1) / a.sub;
+    int splits = (8192 + a.n_items - 1) / a.n_items;
+    if (splits > steps / 4) splits = steps / 4;
+    if (splits < 1) splits = 1;
+    a.splits = splits;
+    return a;
+}
+
+/* Matrix-core handles with AFC channels: the full spectrum of the batch's LAST hop, for the dongles that have one (one wavefront FFT per such dongle per
+ * batch -- afc.finalize(dev, i, fftout) runs once per batch on the output of its last FFT, src/rtl_airband.cpp:626-630).  It depends on the input only, so
+ * it is computed on a side stream BESIDE stage 1 (behind the previous batch's AFC, which read the buffer it overwrites) and joined in front of afc_kernel
+ * (run_back_half). */
+int launch_last_hop_spectrum(airband_hip_handle* h, hipStream_t s) {
+    for (auto& e : h->ev_spec) HIP_TRY(h, e.ensure(), AIRBAND_HIP_ENODEV);
+    (void)hipEventRecord(h->ev_spec[0], s);
+    (void)hipStreamWaitEvent(h->side[0], h->ev_spec[0], 0);
+    const uint8_t* last_hop = (const uint8_t*)h->last_iq + (size_t)(h->last_n_hops - 1) * (size_t)h->hop_bytes;
+    launch_channelizer_fft(fft_args(h, last_hop, h->last_iq_stride, 0, FrontRows{0, 1}, 1), h->side[0]);
+    (void)hipEventRecord(h->ev_spec[1], h->side[0]);
+    return AIRBAND_HIP_OK;
 }
 
 ScanExchangeArgs scan_args(airband_hip_handle* h) {
@@ -404,13 +306,20 @@ void scan_latch(airband_hip_handle* h, uint64_t k, int first_row, int n_rows) {
     h->scan_n_rows[k & 1] = n_rows;
 }
 
+/* stage 1 of front batch front_batches is in its stream: latch its scan entries, move on to the next batch's ring rows */
+void front_enqueued(airband_hip_handle* h, int first_row, int n_rows) {
+    scan_latch(h, h->front_batches, first_row, n_rows);
+    h->row0_front = (h->row0_front + h->B) % h->R;
+    h->front_batches++;
+}
+
 /* in front of the demod kernels of batch batches_done, on its stage-2 stream: the exchange of every scan channel whose latched entry is not the one its slot
  * holds (one launch for all of them), and |bin| of the lists that mix AM and NFM */
 int scan_before_demod(airband_hip_handle* h, hipStream_t s) {
     const int b = (int)(h->batches_done & 1);
     const std::vector<int>& want = h->scan_latch[b];
     const int q = h->switch_buf;
-    int* list = h->h_switch[q];
+    int* list = h->h_switch[q].get();
     int n = 0;
     bool waited = false;
     for (size_t i = 0; i < h->plan.scan.size(); i++) {
@@ -443,9 +352,34 @@ int scan_before_demod(airband_hip_handle* h, hipStream_t s) {
     return AIRBAND_HIP_OK;
 }
 
+MixArgs mix_args(const airband_hip_handle* h) {
+    const MixerWiring& w = h->mix;
+    MixArgs ma;
+    ma.out_wave = h->d_out_wave.p + AB_OUT_PAD;
+    ma.wave_stride = h->wave_stride;
+    ma.out_axc = h->d_out_axc.p;
+    ma.in_chan = w.d_chan.p;
+    ma.in_ml = w.d_ml.p;
+    ma.in_mr = w.d_mr.p;
+    ma.run_first = w.d_run_first.p;
+    ma.run_mixer = w.d_run_mixer.p;
+    ma.mixer_first_run = w.d_first_run.p;
+    ma.mixer_stereo = w.d_stereo.p;
+    ma.run_left = w.d_run_left.p;
+    ma.run_right = w.d_run_right.p;
+    ma.run_signal = w.d_run_signal.p;
+    ma.n_runs = w.n_runs;
+    ma.left = w.d_left.p;
+    ma.right = w.d_right.p;
+    ma.has_signal = w.d_signal.p;
+    ma.n_mixers = w.n_mixers;
+    ma.wave_batch = h->B;
+    return ma;
+}
+
 /* stage 2 + emit (+ mixers) of the batch whose stage-1 rows are already in the rings */
 int run_back_half(airband_hip_handle* h, hipStream_t s) {
-    hipEvent_t* ev = event_set(h, h->batches_done, 1);
+    const Event* ev = event_set(h, h->batches_done, 1);
     (void)hipEventRecord(ev[2], s);
     DemodArgs da;
     da.cc = h->d_cc.p;
@@ -486,7 +420,9 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
         const int rc = scan_before_demod(h, s);
         if (rc != AIRBAND_HIP_OK) return rc;
     }
-    launch_demod(da, h->kind_first_block, h->kind_n_blocks, s, (h->flags & AIRBAND_HIP_FLAG_SERIAL_DEMOD) ? nullptr : h->side, h->fork_ev);
+    hipStream_t side[3] = {h->side[0], h->side[1], h->side[2]};
+    hipEvent_t fork_ev[4] = {h->fork_ev[0], h->fork_ev[1], h->fork_ev[2], h->fork_ev[3]};
+    launch_demod(da, h->kind_first_block, h->kind_n_blocks, s, (h->flags & AIRBAND_HIP_FLAG_SERIAL_DEMOD) ? nullptr : side, fork_ev);
     if (h->any_afc && h->afc_spectrum_valid) { /* afc.finalize(), src/rtl_airband.cpp:626-630: may turn '*' into '<' / '>' */
         const bool tables = h->use_dft || h->use_f32; /* the matrix-core channelizers: a channel's bin is baked into its coefficient columns */
         if (tables) (void)hipStreamWaitEvent(s, h->ev_spec[1], 0); /* the last hop's spectrum, computed beside stage 1 */
@@ -505,29 +441,7 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
         ea.wave_batch = h->B;
         launch_emit_iq(ea, s);
     }
-    if (h->n_mixers > 0) {
-        MixArgs ma;
-        ma.out_wave = h->d_out_wave.p + AB_OUT_PAD;
-        ma.wave_stride = h->wave_stride;
-        ma.out_axc = h->d_out_axc.p;
-        ma.in_chan = h->d_mix_chan.p;
-        ma.in_ml = h->d_mix_ml.p;
-        ma.in_mr = h->d_mix_mr.p;
-        ma.run_first = h->d_mix_run_first.p;
-        ma.run_mixer = h->d_mix_run_mixer.p;
-        ma.mixer_first_run = h->d_mix_first_run.p;
-        ma.mixer_stereo = h->d_mix_stereo.p;
-        ma.run_left = h->d_mix_run_left.p;
-        ma.run_right = h->d_mix_run_right.p;
-        ma.run_signal = h->d_mix_run_signal.p;
-        ma.n_runs = h->n_mix_runs;
-        ma.left = h->d_mix_left.p;
-        ma.right = h->d_mix_right.p;
-        ma.has_signal = h->d_mix_signal.p;
-        ma.n_mixers = h->n_mixers;
-        ma.wave_batch = h->B;
-        launch_mix(ma, s);
-    }
+    if (h->mix.n_mixers > 0) launch_mix(mix_args(h), s);
     (void)hipEventRecord(ev[4], s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
@@ -543,11 +457,370 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
 /* position k of the grouped mixer-input arrays: the channel it reads, or -1 while the connection (airband_hip_mixer_enable_input) or its dongle
  * (airband_hip_device_enable) is switched off -- a masked input is skipped like mixer->input_mask[i] == false (src/mixer.cpp:96-110,192) */
 hipError_t write_mix_input(airband_hip_handle* h, int k) {
-    const int ch = h->mix_chan_host[k];
-    const int v = (h->mix_user_on[k] && h->dev_enabled[h->plan.cc[ch].dev]) ? ch : -1;
-    hipError_t e = hipMemcpyAsync(h->d_mix_chan.p + k, &v, sizeof(int), hipMemcpyHostToDevice, h->stream);
+    const int ch = h->mix.chan_host[k];
+    const int v = (h->mix.user_on[k] && h->dev_enabled[h->plan.cc[ch].dev]) ? ch : -1;
+    hipError_t e = hipMemcpyAsync(h->mix.d_chan.p + k, &v, sizeof(int), hipMemcpyHostToDevice, h->stream);
     if (e != hipSuccess) return e;
     return hipStreamSynchronize(h->stream); /* `v` is a stack variable */
+}
+
+/* ---- airband_hip_prepare_scan() step by step, in the order it calls them ------------------------------------------------------------- */
+
+int prep_streams(airband_hip_handle* h) {
+    HIP_TRY(PREPARING, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    int prio_lo = 0, prio_hi = 0; /* numerically lower = more urgent */
+    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+    HIP_TRY(PREPARING, hipStreamCreateWithPriority(&h->stream.v, hipStreamNonBlocking, prio_hi), AIRBAND_HIP_ENODEV);
+    for (auto& set : h->evp)
+        for (auto& e : set) HIP_TRY(PREPARING, hipEventCreate(&e.v), AIRBAND_HIP_ENODEV);
+    if (h->pipeline) {
+        HIP_TRY(PREPARING, hipStreamCreateWithFlags(&h->front.v, hipStreamNonBlocking), AIRBAND_HIP_ENODEV);
+        HIP_TRY(PREPARING, h->ev_in.ensure(), AIRBAND_HIP_ENODEV);
+        HIP_TRY(PREPARING, h->ev_back.ensure(), AIRBAND_HIP_ENODEV);
+        for (auto& e : h->front_done) HIP_TRY(PREPARING, e.ensure(), AIRBAND_HIP_ENODEV);
+    }
+    for (auto& e : h->fork_ev) HIP_TRY(PREPARING, e.ensure(), AIRBAND_HIP_ENODEV);
+    for (auto& st : h->side) HIP_TRY(PREPARING, hipStreamCreateWithPriority(&st.v, hipStreamNonBlocking, prio_lo), AIRBAND_HIP_ENODEV);
+    return AIRBAND_HIP_OK;
+}
+
+int kind_of(const ChanConst& c) {
+    if (c.flags & AB_F_IQ_OUT) return AB_KIND_GENERIC;
+    const bool nfm = c.flags & AB_F_NFM, raw = c.flags & AB_F_RAW_IQ, lp = c.flags & AB_F_LOWPASS, ct = c.flags & AB_F_CTCSS;
+    if (!nfm) return (!raw && !ct) ? AB_KIND_AM : AB_KIND_GENERIC;
+    if (ct && lp) return AB_KIND_GENERIC;
+    return ct ? AB_KIND_NFM_CTCSS : lp ? AB_KIND_NFM_LOWPASS : AB_KIND_NFM;
+}
+
+/* the demod kind of every channel (external index) */
+std::vector<int> channel_kinds(const Plan& p) {
+    std::vector<int> kind_ext(p.total_ch);
+    for (int e = 0; e < p.total_ch; e++) kind_ext[e] = kind_of(p.cc[e]);
+    /* a scan channel's kind holds for every entry of its list: their common kind, else the generic one.  NFM + lowpass becomes generic too when the
+     * list has more than one entry: that kind recomputes the squelch's delay line from the channel's wavein carry (squelch_fsm.h, SqShadow), which
+     * after a switch belongs to another frequency; the generic kind keeps the line, and the line is banked per entry */
+    for (const ScanList& sl : p.scan) {
+        int k = kind_of(p.scan_cc[sl.first_entry]);
+        for (int f = 1; f < sl.n; f++)
+            if (kind_of(p.scan_cc[sl.first_entry + f]) != k) k = AB_KIND_GENERIC;
+        if (k == AB_KIND_NFM_LOWPASS && sl.n > 1) k = AB_KIND_GENERIC;
+        kind_ext[sl.ext] = k;
+    }
+    return kind_ext;
+}
+
+/* demod slots (pure host): sort the channels by demod kind so that a 64-lane wavefront runs ONE code path (AM, NFM,
+ * NFM+lowpass, NFM+CTCSS, everything else); kinds start on 64-slot block boundaries.  Leaves the slot images in h->cc_slots / cs_slots. */
+void prep_slots(airband_hip_handle* h, std::vector<ChanState>& cs_slots, std::vector<uint8_t>& block_kind) {
+    const Plan& p = h->plan;
+    std::vector<ChanConst>& cc_slots = h->cc_slots;
+    h->ext_to_slot.assign(p.total_ch, -1);
+    const std::vector<int> kind_ext = channel_kinds(p);
+    /* A switching scan channel gets a 64-slot block of its own.  The demod kernels hold the squelch's sample_count_ and delay-line cursors in scalar
+     * registers (squelch_fsm.h, sq_load: "the same on every channel"), which is true of channels that run every batch, but a list entry counts only
+     * the batches it was active in: at WAVE_BATCH 1 000 (= 8 mod 16) two entries' noise-floor sweeps fall 8 samples apart.  Alone in its wavefront
+     * the channel's counts are uniform again.  The cost is ring space for 63 idle slots per scan channel. */
+    std::vector<uint8_t> isolated(p.total_ch, 0);
+    for (const ScanList& sl : p.scan)
+        if (sl.n > 1) isolated[sl.ext] = 1;
+    ChanConst pad_c;
+    ChanState pad_s;
+    std::memset(&pad_c, 0, sizeof(pad_c));
+    std::memset(&pad_s, 0, sizeof(pad_s));
+    pad_c.ct_slot = -1;
+    pad_s.axc = ' ';
+    auto pad_block = [&]() {
+        while (cc_slots.size() % AB_SLOT_BLOCK) {
+            h->slot_to_ext.push_back(-1);
+            cc_slots.push_back(pad_c);
+            cs_slots.push_back(pad_s);
+        }
+    };
+    for (int k = 0; k < AB_KIND_COUNT; k++) {
+        bool any = false;
+        for (int pass = 0; pass < 2; pass++) /* the kind's channels, then its isolated scan channels, one block each */
+            for (int e = 0; e < p.total_ch; e++) {
+                if (kind_ext[e] != k || isolated[e] != pass) continue;
+                any = true;
+                if (pass) pad_block();
+                h->ext_to_slot[e] = (int)cc_slots.size();
+                h->slot_to_ext.push_back(e);
+                cc_slots.push_back(p.cc[e]);
+                cs_slots.push_back(p.cs0[e]);
+            }
+        if (!any) continue;
+        pad_block();
+        h->kind_first_block[k] = (int)block_kind.size();
+        while (block_kind.size() < cc_slots.size() / AB_SLOT_BLOCK) block_kind.push_back((uint8_t)k);
+        h->kind_n_blocks[k] = (int)block_kind.size() - h->kind_first_block[k];
+    }
+    h->n_slots = (int)cc_slots.size();
+}
+
+void prep_geometry(airband_hip_handle* h) {
+    const Plan& p = h->plan;
+    h->B = p.wave_batch;
+    /* ring rows, whole 16-row tiles: one batch plus its AGC_EXTRA carry -- or two batches deep when stage 1 of the next batch
+     * is written while stage 2 still reads this one */
+    h->R = ((h->pipeline ? 2 : 1) * p.wave_batch + AB_AGC_EXTRA + 15) / 16 * 16; /* whole 16-hop MFMA tiles (a multiple of AB_TILE_ROWS too) */
+    h->N = p.fft_size;
+    h->hop_bytes = 2LL * p.dev[0].bytes_per_sample * p.dev[0].hop_samples;
+    h->first_batch_bytes = h->hop_bytes * (h->B + AB_AGC_EXTRA);
+    h->batch_bytes = h->hop_bytes * h->B;
+    h->lookahead_bytes = 2LL * p.dev[0].bytes_per_sample * p.fft_size - h->hop_bytes;
+    if (h->lookahead_bytes < 0) h->lookahead_bytes = 0;
+    /* hops that are not multiples of 16 bytes (2.4 MS/s): the channelizer stages whole 16-byte pieces, the piece holding the span's last
+     * byte included -- make batch + look-ahead a whole number of pieces so that callers size (and fill) their spans accordingly */
+    h->lookahead_bytes += (16 - (h->batch_bytes + h->lookahead_bytes) % 16) % 16;
+}
+
+int prep_constants(airband_hip_handle* h, const std::vector<ChanState>& cs_slots, const std::vector<uint8_t>& block_kind) {
+    const Plan& p = h->plan;
+    HIP_TRY(PREPARING, upload(h->d_dev, p.dev), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, upload(h->d_cc, h->cc_slots), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, upload(h->d_cs, cs_slots), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, upload(h->d_slot_to_ext, h->slot_to_ext), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, upload(h->d_ext_to_slot, h->ext_to_slot), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, upload(h->d_block_kind, block_kind), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, upload(h->d_window, p.window), AIRBAND_HIP_ENOMEM);
+    if (p.fft_size >= 1024) { /* row n2 = the window at samples n2, n2 + M, n2 + 2 M, ... (M = fft_size / 512): what transform n2 of a decimated FFT multiplies by, contiguous */
+        const int M = p.fft_size / 512;
+        std::vector<float> dec((size_t)p.fft_size);
+        for (int n = 0; n < p.fft_size; n++) dec[(size_t)(n % M) * 512 + n / M] = p.window[n];
+        HIP_TRY(PREPARING, upload(h->d_window_dec, dec), AIRBAND_HIP_ENOMEM);
+    }
+    HIP_TRY(PREPARING, upload(h->d_sin, p.sin_lut), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, upload(h->d_twiddle, p.twiddle), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, upload(h->d_cos, p.cos_lut), AIRBAND_HIP_ENOMEM);
+    /* CTCSS tables: [ct_slot][detector][tone] coefficients and [ct_slot][detector][q1|q2][tone] Goertzel state, so
+     * that the 52 tone lanes of demod phase 2 read one contiguous run */
+    const int n_ct = (int)p.tones.size();
+    h->ct_stride = n_ct;
+    std::vector<float> coeff((size_t)(n_ct > 0 ? n_ct : 1) * 2 * AB_MAX_TONES, 0.0f);
+    for (int s = 0; s < n_ct; s++)
+        for (int k = 0; k < 2; k++)
+            for (int t = 0; t < p.tones[s].n[k]; t++) coeff[((size_t)s * 2 + k) * AB_MAX_TONES + t] = p.tones[s].coeff[k][t];
+    HIP_TRY(PREPARING, upload(h->d_ct_coeff, coeff), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, h->d_ct_q.alloc_zeroed((size_t)(n_ct > 0 ? n_ct : 1) * 4 * AB_MAX_TONES), AIRBAND_HIP_ENOMEM);
+    return AIRBAND_HIP_OK;
+}
+
+/* the rings, with the reference's config-time prefill of the lead-in (src/config.cpp:313-316), and the hand-off buffers of the split kinds */
+int prep_rings(airband_hip_handle* h) {
+    const size_t ring = (size_t)h->R * h->n_slots; /* blocked: [n_slots/64][R][64] */
+    HIP_TRY(PREPARING, h->d_mag.alloc(ring), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, h->d_iq.alloc_zeroed(ring), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, h->d_iq_out.alloc_zeroed((size_t)h->B * h->n_slots), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, h->d_sqbuf.alloc_zeroed((size_t)AB_SQ_BUF * h->n_slots), AIRBAND_HIP_ENOMEM);
+    const float lead_in = 20.0f; /* wavein[0 .. AGC_EXTRA) = 20.0f, src/config.cpp:313-316 (as a 32-bit pattern: no host copy of the rings, 4 GB at 65 536 dongles) */
+    int bits;
+    std::memcpy(&bits, &lead_in, sizeof(bits));
+    HIP_TRY(PREPARING, hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(h->d_mag.p), bits, ring), AIRBAND_HIP_ENOMEM);
+    /* hand-off buffers of the split kinds (NFM+CTCSS and generic are adjacent in slot order) */
+    h->ct_n_blocks = h->kind_n_blocks[AB_KIND_NFM_CTCSS] + h->kind_n_blocks[AB_KIND_GENERIC];
+    h->ct_first_block = h->kind_n_blocks[AB_KIND_NFM_CTCSS] ? h->kind_first_block[AB_KIND_NFM_CTCSS] : h->kind_first_block[AB_KIND_GENERIC];
+    if (h->ct_n_blocks > 0) {
+        /* one 32-bit word per sample for the NFM + CTCSS kind (rows padded to whole 128-byte lines), (audio, flags) pairs for the generic kind */
+        h->ct_pk_pitch = (h->B + 31) / 32 * 32;
+        HIP_TRY(PREPARING, h->d_ct_af.alloc((size_t)h->kind_n_blocks[AB_KIND_NFM_CTCSS] * AB_SLOT_BLOCK * h->ct_pk_pitch / 2 + (size_t)h->kind_n_blocks[AB_KIND_GENERIC] * AB_SLOT_BLOCK * h->B),
+                AIRBAND_HIP_ENOMEM);
+        HIP_TRY(PREPARING, h->d_ct_mask.alloc((size_t)h->ct_n_blocks * (h->B / 50) * AB_SLOT_BLOCK), AIRBAND_HIP_ENOMEM);
+    }
+    return AIRBAND_HIP_OK;
+}
+
+/* regrouped stage 2 (demod.hip, "regrouping") */
+int prep_regroup(airband_hip_handle* h) {
+    /* Default (neither flag, no environment override): by residency.  A regrouped workgroup's wavefronts of closed channels spend most of the batch waiting at the
+     * lockstep barriers -- without using an issue slot, but holding their registers.  While ALL of a handle's lane-per-channel wavefronts are resident at once (about
+     * four to six per SIMD) that costs nothing and the 22 % of vector instructions regrouping removes are time (32 768 dongles x 8 mixed channels: stage 2 3.42 ->
+     * 3.02 ms; 49 152: 4.53 -> 4.33); past that the waiting wavefronts keep the next round's out (65 536: 5.8 -> 6.05), and a chip that is not full is bound by ONE
+     * wavefront's dependent chain, which regrouping does not shorten (<= 16 384: 2.48 -> 2.54) -- profiles/r06_experiments.md D. */
+    int n_lane_blocks = 0;
+    for (int k = 0; k < AB_KIND_COUNT; k++) n_lane_blocks += h->kind_n_blocks[k];
+    int cus = 0, cur_dev = 0;
+    (void)hipGetDevice(&cur_dev);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cur_dev) != hipSuccess || cus <= 0) cus = 256;
+    const double waves_per_simd = (double)n_lane_blocks / (4.0 * cus);
+    const bool by_residency = waves_per_simd >= 2.75 && waves_per_simd <= 6.25;
+    const char* e = getenv("AIRBAND_HIP_REGROUP");
+    h->regroup = e && *e ? (*e != '0') : (h->flags & AIRBAND_HIP_FLAG_REGROUP) ? true : (h->flags & AIRBAND_HIP_FLAG_NO_REGROUP) ? false : by_residency;
+    /* regrouping deals a workgroup's slots out among its wavefronts: it would put isolated scan channels (prep_slots) back into one wavefront */
+    for (const ScanList& sl : h->plan.scan)
+        if (sl.n > 1) h->regroup = false;
+    h->regroup_mode = (e && *e == '2') ? 2 : (e && *e == '3') ? 3 : 1;
+    if (h->regroup && h->regroup_mode == 3) HIP_TRY(PREPARING, h->d_perm.alloc((size_t)h->n_slots), AIRBAND_HIP_ENOMEM);
+    if (h->regroup || h->ct_n_blocks > 0) { /* the front kernel's note per channel: had audio / went CLOSED in this batch (tone kernel; regrouped back kernel) */
+        HIP_TRY(PREPARING, h->d_sq_key.alloc_zeroed((size_t)h->n_slots), AIRBAND_HIP_ENOMEM);
+    }
+    return AIRBAND_HIP_OK;
+}
+
+int prep_results(airband_hip_handle* h) {
+    const Plan& p = h->plan;
+    if (h->flags & AIRBAND_HIP_FLAG_TRACE_SQUELCH) HIP_TRY(PREPARING, h->d_trace.alloc_zeroed((size_t)h->B * h->n_slots), AIRBAND_HIP_ENOMEM);
+    /* channel->waveout rows (src/rtl_airband.h:230): [AGC_EXTRA tail of the previous batch][WAVE_BATCH]; the consumer reads the first
+     * WAVE_BATCH entries.  Config-time prefill of the lead-in as in src/config.cpp:313-316 (waveout[0..AGC_EXTRA) = 0.5). */
+    h->wave_stride = (AB_OUT_PAD + AB_AGC_EXTRA + h->B + AB_OUT_RUN - 1) / AB_OUT_RUN * AB_OUT_RUN; /* whole 128-byte lines per row */
+    HIP_TRY(PREPARING, h->d_out_wave.alloc_zeroed((size_t)p.total_ch * h->wave_stride), AIRBAND_HIP_ENOMEM);
+    /* the lead-in columns, a few thousand rows per strided copy (not a host image of every row: 4.5 GB at 65 536 dongles) */
+    const int chunk = p.total_ch < 4096 ? p.total_ch : 4096;
+    const std::vector<float> lead((size_t)chunk * AB_AGC_EXTRA, 0.5f);
+    for (int c = 0; c < p.total_ch; c += chunk) {
+        const int rows = p.total_ch - c < chunk ? p.total_ch - c : chunk;
+        HIP_TRY(PREPARING, hipMemcpy2D(h->d_out_wave.p + (size_t)c * h->wave_stride + AB_OUT_PAD, (size_t)h->wave_stride * sizeof(float), lead.data(), AB_AGC_EXTRA * sizeof(float),
+                                       AB_AGC_EXTRA * sizeof(float), (size_t)rows, hipMemcpyHostToDevice),
+                AIRBAND_HIP_ENOMEM);
+    }
+    HIP_TRY(PREPARING, h->d_out_axc.alloc((size_t)p.total_ch), AIRBAND_HIP_ENOMEM);
+    bool any_iq_out = false;
+    for (const ChanConst& c : p.cc) any_iq_out |= (c.flags & AB_F_IQ_OUT) != 0;
+    if (any_iq_out) HIP_TRY(PREPARING, h->d_out_iq.alloc_zeroed((size_t)p.total_ch * h->B * 2), AIRBAND_HIP_ENOMEM);
+    return AIRBAND_HIP_OK;
+}
+
+/* the work items of the matrix-core channelizers */
+int upload_work_items(airband_hip_handle* h) {
+    const Plan& p = h->plan;
+    HIP_TRY(PREPARING, upload(h->d_item_dev, p.item_dev), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, upload(h->d_item_group, p.item_group), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, upload(h->d_item_bset, p.item_home), AIRBAND_HIP_ENOMEM); /* every channel starts on its base bin */
+    return AIRBAND_HIP_OK;
+}
+
+/* ... and what the re-tune kernel needs beside them to switch a group with an AFC channel between its home and its private table */
+int upload_retune_items(airband_hip_handle* h) {
+    const Plan& p = h->plan;
+    HIP_TRY(PREPARING, upload(h->d_item_private, p.item_bset), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, upload(h->d_item_home, p.item_home), AIRBAND_HIP_ENOMEM);
+    std::vector<int> with_epoch(p.bset_bins);
+    with_epoch.push_back(0); /* the "last moved in batch" stamp: 0 = the start-up build */
+    HIP_TRY(PREPARING, upload(h->d_bset_bin, with_epoch), AIRBAND_HIP_ENOMEM);
+    return AIRBAND_HIP_OK;
+}
+
+/* the int8 matrix-core channelizer, unless its tables are past the budget (use_dft is cleared then) */
+int prep_dft_tables(airband_hip_handle* h) {
+    const Plan& p = h->plan;
+    build_dft_tables(h->plan, false);
+    /* One table per DISTINCT group of eight bins (shared between the work items that have it: a fleet of identical dongles has one, a fleet in which every
+     * device_t derives its own bins -- src/config.cpp:666-667 -- as many as it has groups) plus one private table per group with an AFC channel.  Bounded by
+     * their bytes alone (65 536 tables are 3.2 GB at fft 512, ~51 GB at fft 8192); past the budget the handle runs on the wavefront FFT.  Round 6: a COUNT used to
+     * stand here (more than 4 096 distinct plans -> wavefront FFT, 7x slower), which contradicted the private tables of the AFC path right beside it. */
+    const int np_t = p.fft_size > 512 ? p.fft_size / 512 : 1;
+    const size_t tab_bytes = (size_t)3 * (p.fft_size > 512 ? 16 : p.fft_size / 32) * 64 * 16 * np_t;
+    if ((size_t)p.n_bsets * tab_bytes > AB_PRIVATE_TABLE_BUDGET) {
+        h->use_dft = false;
+        return AIRBAND_HIP_OK;
+    }
+    int rc = upload_work_items(h);
+    if (rc == AIRBAND_HIP_OK) rc = upload_retune_items(h);
+    if (rc != AIRBAND_HIP_OK) return rc;
+    /* the host has built the shared tables; the private ones (groups with an AFC channel) follow them, zeroed, and are built by the
+     * re-tune kernel right here: every column of theirs still stands at bin -1 */
+    HIP_TRY(PREPARING, h->d_bfrag.alloc_zeroed((size_t)p.n_bsets * tab_bytes), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, h->d_bcorr.alloc_zeroed((size_t)p.n_bsets * np_t * 16), AIRBAND_HIP_ENOMEM);
+    if (!p.bfrag.empty()) HIP_TRY(PREPARING, hipMemcpy(h->d_bfrag.p, p.bfrag.data(), p.bfrag.size(), hipMemcpyHostToDevice), AIRBAND_HIP_ENOMEM);
+    if (!p.bcorr.empty()) HIP_TRY(PREPARING, hipMemcpy(h->d_bcorr.p, p.bcorr.data(), p.bcorr.size() * sizeof(double), hipMemcpyHostToDevice), AIRBAND_HIP_ENOMEM);
+    /* shared tables the host did not build (fleets with more than a few thousand distinct channel plans), then the private ones: a private table's columns
+     * are copied from its home table, so the home tables come first */
+    launch_build_tables(h->d_bfrag.p, h->d_bcorr.p, h->d_window.p, h->d_bset_bin.p, p.n_host_bsets, p.n_shared_bsets - p.n_host_bsets, p.fft_size, h->stream);
+    if (p.n_bsets > p.n_shared_bsets) launch_retune_tables(h, h->stream, 0);
+    if (p.n_bsets > p.n_host_bsets) {
+        HIP_TRY(PREPARING, hipGetLastError(), AIRBAND_HIP_ENODEV);
+        HIP_TRY(PREPARING, hipStreamSynchronize(h->stream), AIRBAND_HIP_ENODEV);
+    }
+    if (p.fft_size > 4096) /* [work items][tiles][64 lanes] float4 */
+        HIP_TRY(PREPARING, h->d_dft_partial.alloc((size_t)p.item_dev.size() * dft_partial_tiles(h->B + AB_AGC_EXTRA) * 64 * 4), AIRBAND_HIP_ENOMEM);
+    return AIRBAND_HIP_OK;
+}
+
+/* CF32 (SoapySDR): the float32 matrix pipe, unless its tables are past their budgets (use_f32 is cleared then).  Round 6: also with AFC channels -- a group with
+ * one owns a private float table whose column pairs the re-tune kernel moves (misc_kernels.hip, build_column_pair_f32), exactly as the int8 path does; such
+ * handles stayed on the wavefront FFT before. */
+int prep_f32_tables(airband_hip_handle* h) {
+    const Plan& p = h->plan;
+    build_dft_tables(h->plan, false); /* the work items and the shared bin sets (its int8 tables are not used) */
+    /* bytes, not a count: a float table is f32_nw x (2 N / 4 / f32_nw) x 64 lanes x 4 bytes = 128 N bytes -- 64 KiB at fft 512, 256 KiB at 2048.  The shared tables are
+     * built on the host (params.cpp, build_f32_tables) and read once per work item per launch: past a budget the handle runs on the wavefront FFT rather than on a
+     * gigabyte-sized host build; the private ones (device-built) count against the budget the int8 path's private tables have */
+    const size_t ftab_each = 128u * (size_t)p.fft_size;
+    h->use_f32 = (size_t)p.n_shared_bsets * ftab_each <= AB_F32_TABLE_BUDGET && (size_t)p.n_bsets * ftab_each <= AB_PRIVATE_TABLE_BUDGET;
+    if (h->use_f32) {
+        build_f32_tables(h->plan);
+        const int rc = upload_work_items(h);
+        if (rc != AIRBAND_HIP_OK) return rc;
+        if (p.n_bsets > p.n_shared_bsets) { /* groups with an AFC channel: their private tables follow the shared ones, built by the re-tune kernel right here */
+            const int rc_afc = upload_retune_items(h);
+            if (rc_afc != AIRBAND_HIP_OK) return rc_afc;
+            HIP_TRY(PREPARING, h->d_ftab.alloc_zeroed((size_t)p.n_bsets * ftab_each / sizeof(float)), AIRBAND_HIP_ENOMEM);
+            HIP_TRY(PREPARING, hipMemcpy(h->d_ftab.p, p.ftab.data(), p.ftab.size() * sizeof(float), hipMemcpyHostToDevice), AIRBAND_HIP_ENOMEM);
+            launch_retune_tables(h, h->stream, 0);
+            HIP_TRY(PREPARING, hipGetLastError(), AIRBAND_HIP_ENODEV);
+            HIP_TRY(PREPARING, hipStreamSynchronize(h->stream), AIRBAND_HIP_ENODEV);
+        } else {
+            HIP_TRY(PREPARING, upload(h->d_ftab, p.ftab), AIRBAND_HIP_ENOMEM);
+        }
+        /* fft_size 4096 / 8192: partial sums between the launches of the window's segments (channelizer_f32.hip) */
+        if (f32_n_seg(p.fft_size) > 1) HIP_TRY(PREPARING, h->d_dft_partial.alloc((size_t)p.item_dev.size() * f32_partial_tiles(h->B + AB_AGC_EXTRA) * 64 * 4), AIRBAND_HIP_ENOMEM);
+    }
+    h->plan.bfrag.clear(); h->plan.bfrag.shrink_to_fit();
+    h->plan.ftab.clear(); h->plan.ftab.shrink_to_fit();
+    return AIRBAND_HIP_OK;
+}
+
+/* channelizer variant: matrix-core pruned DFT when the configuration qualifies, wavefront FFT otherwise */
+int prep_channelizer(airband_hip_handle* h) {
+    const Plan& p = h->plan;
+    /* AFC moves bins at run time and needs the full spectrum of each batch's last hop: that is the FFT kernel's job */
+    if (h->any_afc) HIP_TRY(PREPARING, h->d_spectrum.alloc((size_t)p.n_dev * p.fft_size * 2), AIRBAND_HIP_ENOMEM);
+    h->use_dft = !(h->flags & AIRBAND_HIP_FLAG_FORCE_FFT) && dft_supported(p.fft_size, (int)h->hop_bytes, p.dev[0].sfmt, p.max_ch);
+    if (h->use_dft) {
+        const int rc = prep_dft_tables(h);
+        if (rc != AIRBAND_HIP_OK) return rc;
+    }
+    h->use_f32 = !h->use_dft && !(h->flags & AIRBAND_HIP_FLAG_FORCE_FFT) && f32_supported(p.fft_size, p.dev[0].hop_samples, p.dev[0].sfmt);
+    if (h->use_f32) {
+        const int rc = prep_f32_tables(h);
+        if (rc != AIRBAND_HIP_OK) return rc;
+    }
+    if (!h->use_dft && !h->use_f32) {
+        const size_t lds = fft_lds_bytes(p.fft_log, p.dev[0].hop_samples, p.dev[0].bytes_per_sample);
+        if (lds > 160 * 1024) /* e.g. F32 at 20 MS/s: a 16-hop tile of raw samples does not fit a CU's LDS */
+            return fail(PREPARING, AIRBAND_HIP_EBADSIZE,
+                        "sample_rate x bytes_per_sample too large for the FFT channelizer's LDS tile (" + std::to_string(lds) + " > 163840 bytes)");
+    }
+    return AIRBAND_HIP_OK;
+}
+
+/* scan lists: the banks, every entry's initial image, the masks, the switch lists' staging */
+int prep_scan(airband_hip_handle* h) {
+    const Plan& p = h->plan;
+    HIP_TRY(PREPARING, upload(h->d_bank_cc, p.scan_cc), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, upload(h->d_bank_cs, p.scan_cs0), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(PREPARING, h->d_bank_sq.alloc_zeroed(p.scan_cc.size() * AB_SQ_BUF), AIRBAND_HIP_ENOMEM);
+    const AbScanMasks mk = ab_scan_masks();
+    std::vector<uint32_t> masks(mk.cs, mk.cs + AB_CS_DWORDS);
+    masks.insert(masks.end(), mk.cc, mk.cc + AB_CC_DWORDS);
+    HIP_TRY(PREPARING, upload(h->d_scan_mask, masks), AIRBAND_HIP_ENOMEM);
+    const size_t nl = p.scan.size();
+    for (int q = 0; q < 2; q++) {
+        HIP_TRY(PREPARING, h->d_switch[q].alloc(nl * 3), AIRBAND_HIP_ENOMEM);
+        HIP_TRY(PREPARING, h->h_switch[q].alloc(nl * 3), AIRBAND_HIP_ENOMEM);
+        HIP_TRY(PREPARING, h->ev_switch[q].ensure(), AIRBAND_HIP_ENODEV);
+    }
+    std::vector<int> mix_slots;
+    h->scan_of_dev.assign(p.n_dev, -1);
+    for (size_t i = 0; i < nl; i++) {
+        h->scan_of_dev[p.scan[i].dev] = (int)i;
+        if (p.scan[i].mixed_am_nfm) mix_slots.push_back(h->ext_to_slot[p.scan[i].ext]);
+    }
+    if (!mix_slots.empty()) HIP_TRY(PREPARING, upload(h->d_scan_mix_slots, mix_slots), AIRBAND_HIP_ENOMEM);
+    h->scan_cur.assign(nl, 0);
+    h->scan_held.assign(nl, 0);
+    h->scan_latch[0].assign(nl, 0);
+    h->scan_latch[1].assign(nl, 0);
+    return AIRBAND_HIP_OK;
 }
 
 }  // namespace
@@ -589,373 +862,44 @@ int airband_hip_prepare(const airband_hip_config* cfg, airband_hip_handle** out)
 int airband_hip_prepare_scan(const airband_hip_config* cfg, const airband_hip_scan_cfg* scan, int32_t n_scan, airband_hip_handle** out) {
     if (!out) return fail(nullptr, AIRBAND_HIP_EINVAL, "out is NULL");
     *out = nullptr;
-    airband_hip_handle* h = new (std::nothrow) airband_hip_handle();
+    HandlePtr owner(new (std::nothrow) airband_hip_handle(), destroy);
+    airband_hip_handle* const h = owner.get();
     if (!h) return fail(nullptr, AIRBAND_HIP_ENOMEM, "host allocation failed");
     int rc = build_plan(cfg, h->plan);
     if (rc == AIRBAND_HIP_OK) rc = build_scan(cfg, scan, n_scan, h->plan); /* before any device is touched */
-    if (rc != AIRBAND_HIP_OK) {
-        g_prepare_error = h->plan.error;
-        delete h;
-        return rc;
-    }
+    if (rc != AIRBAND_HIP_OK) return fail(PREPARING, rc, h->plan.error);
     const Plan& p = h->plan;
-    if (!p.uniform_hop) {
-        delete h;
-        return fail(nullptr, AIRBAND_HIP_EINVAL, "all dongles of one handle must share sample format and sample_rate/WAVE_RATE hop; use one handle per class");
-    }
-    bool any_afc = false;
-    for (const ChanConst& c : p.cc) any_afc |= c.afc != 0;
+    if (!p.uniform_hop)
+        return fail(PREPARING, AIRBAND_HIP_EINVAL, "all dongles of one handle must share sample format and sample_rate/WAVE_RATE hop; use one handle per class");
+    for (const ChanConst& c : p.cc) h->any_afc |= c.afc != 0;
     h->flags = cfg->flags;
     h->hip_device = cfg->hip_device;
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->hip_device < 0 || cfg->hip_device >= ndev) {
-        delete h;
-        return fail(nullptr, AIRBAND_HIP_ENODEV, "no usable HIP device (libairband_hip has no CPU fallback)");
-    }
-#define PREP_TRY(expr, code)                                                                 \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) {                                                              \
-            g_prepare_error = std::string(#expr) + ": " + hipGetErrorString(e_);             \
-            destroy(h);                                                                      \
-            return code;                                                                     \
-        }                                                                                    \
-    } while (0)
-    PREP_TRY(hipSetDevice(cfg->hip_device), AIRBAND_HIP_ENODEV);
-    int prio_lo = 0, prio_hi = 0; /* numerically lower = more urgent */
-    (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
-    PREP_TRY(hipStreamCreateWithPriority(&h->stream, hipStreamNonBlocking, prio_hi), AIRBAND_HIP_ENODEV);
-    for (auto& set : h->evp)
-        for (auto& e : set) PREP_TRY(hipEventCreate(&e), AIRBAND_HIP_ENODEV);
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || cfg->hip_device < 0 || cfg->hip_device >= ndev)
+        return fail(PREPARING, AIRBAND_HIP_ENODEV, "no usable HIP device (libairband_hip has no CPU fallback)");
     /* AFC needs stage 2's verdict on batch k before stage 1 of batch k+1 picks its bins (src/rtl_airband.cpp:222-251):
      * such handles stay sequential */
-    h->pipeline = (cfg->flags & AIRBAND_HIP_FLAG_PIPELINE) && !any_afc;
-    if (h->pipeline) {
-        PREP_TRY(hipStreamCreateWithFlags(&h->front, hipStreamNonBlocking), AIRBAND_HIP_ENODEV);
-        PREP_TRY(hipEventCreateWithFlags(&h->ev_in, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-        PREP_TRY(hipEventCreateWithFlags(&h->ev_back, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-        for (auto& e : h->front_done) PREP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-    }
-    for (auto& e : h->fork_ev) PREP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-    for (auto& st : h->side) PREP_TRY(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio_lo), AIRBAND_HIP_ENODEV);
-
-    h->B = p.wave_batch;
-    /* ring rows, whole 16-row tiles: one batch plus its AGC_EXTRA carry -- or two batches deep when stage 1 of the next batch
-     * is written while stage 2 still reads this one */
-    h->R = ((h->pipeline ? 2 : 1) * p.wave_batch + AB_AGC_EXTRA + 15) / 16 * 16; /* whole 16-hop MFMA tiles (a multiple of AB_TILE_ROWS too) */
-    h->N = p.fft_size;
-    /* demod slots: sort the channels by demod kind so that a 64-lane wavefront runs ONE code path (AM, NFM,
-     * NFM+lowpass, NFM+CTCSS, everything else); kinds start on 64-slot block boundaries */
-    std::vector<ChanConst> cc_slots;
+    h->pipeline = (cfg->flags & AIRBAND_HIP_FLAG_PIPELINE) && !h->any_afc;
+    rc = prep_streams(h);
+    if (rc != AIRBAND_HIP_OK) return rc;
     std::vector<ChanState> cs_slots;
     std::vector<uint8_t> block_kind;
-    {
-        auto kind_of = [](const ChanConst& c) {
-            if (c.flags & AB_F_IQ_OUT) return (int)AB_KIND_GENERIC;
-            const bool nfm = c.flags & AB_F_NFM, raw = c.flags & AB_F_RAW_IQ, lp = c.flags & AB_F_LOWPASS, ct = c.flags & AB_F_CTCSS;
-            if (!nfm) return (!raw && !ct) ? (int)AB_KIND_AM : (int)AB_KIND_GENERIC;
-            if (ct && lp) return (int)AB_KIND_GENERIC;
-            return ct ? (int)AB_KIND_NFM_CTCSS : lp ? (int)AB_KIND_NFM_LOWPASS : (int)AB_KIND_NFM;
-        };
-        h->ext_to_slot.assign(p.total_ch, -1);
-        std::vector<int> kind_ext(p.total_ch);
-        for (int e = 0; e < p.total_ch; e++) kind_ext[e] = kind_of(p.cc[e]);
-        /* a scan channel's kind holds for every entry of its list: their common kind, else the generic one.  NFM + lowpass becomes generic too when the
-         * list has more than one entry: that kind recomputes the squelch's delay line from the channel's wavein carry (squelch_fsm.h, SqShadow), which
-         * after a switch belongs to another frequency; the generic kind keeps the line, and the line is banked per entry */
-        for (const ScanList& sl : p.scan) {
-            int k = kind_of(p.scan_cc[sl.first_entry]);
-            for (int f = 1; f < sl.n; f++)
-                if (kind_of(p.scan_cc[sl.first_entry + f]) != k) k = AB_KIND_GENERIC;
-            if (k == AB_KIND_NFM_LOWPASS && sl.n > 1) k = AB_KIND_GENERIC;
-            kind_ext[sl.ext] = k;
-        }
-        /* A switching scan channel gets a 64-slot block of its own.  The demod kernels hold the squelch's sample_count_ and delay-line cursors in scalar
-         * registers (squelch_fsm.h, sq_load: "the same on every channel"), which is true of channels that run every batch, but a list entry counts only
-         * the batches it was active in: at WAVE_BATCH 1 000 (= 8 mod 16) two entries' noise-floor sweeps fall 8 samples apart.  Alone in its wavefront
-         * the channel's counts are uniform again.  The cost is ring space for 63 idle slots per scan channel. */
-        std::vector<uint8_t> isolated(p.total_ch, 0);
-        for (const ScanList& sl : p.scan)
-            if (sl.n > 1) isolated[sl.ext] = 1;
-        ChanConst pad_c;
-        ChanState pad_s;
-        std::memset(&pad_c, 0, sizeof(pad_c));
-        std::memset(&pad_s, 0, sizeof(pad_s));
-        pad_c.ct_slot = -1;
-        pad_s.axc = ' ';
-        for (int k = 0; k < AB_KIND_COUNT; k++) {
-            bool any = false;
-            auto pad_block = [&]() {
-                while (cc_slots.size() % AB_SLOT_BLOCK) {
-                    h->slot_to_ext.push_back(-1);
-                    cc_slots.push_back(pad_c);
-                    cs_slots.push_back(pad_s);
-                }
-            };
-            for (int pass = 0; pass < 2; pass++) /* the kind's channels, then its isolated scan channels, one block each */
-                for (int e = 0; e < p.total_ch; e++) {
-                    if (kind_ext[e] != k || isolated[e] != pass) continue;
-                    any = true;
-                    if (pass) pad_block();
-                    h->ext_to_slot[e] = (int)cc_slots.size();
-                    h->slot_to_ext.push_back(e);
-                    cc_slots.push_back(p.cc[e]);
-                    cs_slots.push_back(p.cs0[e]);
-                }
-            if (!any) continue;
-            pad_block();
-            h->kind_first_block[k] = (int)block_kind.size();
-            while (block_kind.size() < cc_slots.size() / AB_SLOT_BLOCK) block_kind.push_back((uint8_t)k);
-            h->kind_n_blocks[k] = (int)block_kind.size() - h->kind_first_block[k];
-        }
-        h->n_slots = (int)cc_slots.size();
-    }
-    h->hop_bytes = 2LL * p.dev[0].bytes_per_sample * p.dev[0].hop_samples;
-    h->first_batch_bytes = h->hop_bytes * (h->B + AB_AGC_EXTRA);
-    h->batch_bytes = h->hop_bytes * h->B;
-    h->lookahead_bytes = 2LL * p.dev[0].bytes_per_sample * p.fft_size - h->hop_bytes;
-    if (h->lookahead_bytes < 0) h->lookahead_bytes = 0;
-    /* hops that are not multiples of 16 bytes (2.4 MS/s): the channelizer stages whole 16-byte pieces, the piece holding the span's last
-     * byte included -- make batch + look-ahead a whole number of pieces so that callers size (and fill) their spans accordingly */
-    h->lookahead_bytes += (16 - (h->batch_bytes + h->lookahead_bytes) % 16) % 16;
-
-    /* constants */
-    PREP_TRY(upload(h->d_dev, p.dev), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(upload(h->d_cc, cc_slots), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(upload(h->d_cs, cs_slots), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(upload(h->d_slot_to_ext, h->slot_to_ext), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(upload(h->d_ext_to_slot, h->ext_to_slot), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(upload(h->d_block_kind, block_kind), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(upload(h->d_window, p.window), AIRBAND_HIP_ENOMEM);
-    if (p.fft_size >= 1024) { /* row n2 = the window at samples n2, n2 + M, n2 + 2 M, ... (M = fft_size / 512): what transform n2 of a decimated FFT multiplies by, contiguous */
-        const int M = p.fft_size / 512;
-        std::vector<float> dec((size_t)p.fft_size);
-        for (int n = 0; n < p.fft_size; n++) dec[(size_t)(n % M) * 512 + n / M] = p.window[n];
-        PREP_TRY(upload(h->d_window_dec, dec), AIRBAND_HIP_ENOMEM);
-    }
-    PREP_TRY(upload(h->d_sin, p.sin_lut), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(upload(h->d_twiddle, p.twiddle), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(upload(h->d_cos, p.cos_lut), AIRBAND_HIP_ENOMEM);
-    /* CTCSS tables: [ct_slot][detector][tone] coefficients and [ct_slot][detector][q1|q2][tone] Goertzel state, so
-     * that the 52 tone lanes of demod phase 2 read one contiguous run */
-    {
-        const int n_ct = (int)p.tones.size();
-        h->ct_stride = n_ct;
-        std::vector<float> coeff((size_t)(n_ct > 0 ? n_ct : 1) * 2 * AB_MAX_TONES, 0.0f);
-        for (int s = 0; s < n_ct; s++)
-            for (int k = 0; k < 2; k++)
-                for (int t = 0; t < p.tones[s].n[k]; t++) coeff[((size_t)s * 2 + k) * AB_MAX_TONES + t] = p.tones[s].coeff[k][t];
-        PREP_TRY(upload(h->d_ct_coeff, coeff), AIRBAND_HIP_ENOMEM);
-        PREP_TRY(h->d_ct_q.alloc((size_t)(n_ct > 0 ? n_ct : 1) * 4 * AB_MAX_TONES), AIRBAND_HIP_ENOMEM);
-        PREP_TRY(hipMemset(h->d_ct_q.p, 0, h->d_ct_q.n * sizeof(float)), AIRBAND_HIP_ENOMEM);
-    }
-    /* rings, with the reference's config-time prefill of the lead-in (src/config.cpp:313-316) */
-    const size_t ring = (size_t)h->R * h->n_slots; /* blocked: [n_slots/64][R][64] */
-    PREP_TRY(h->d_mag.alloc(ring), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(h->d_iq.alloc(ring), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(h->d_iq_out.alloc((size_t)h->B * h->n_slots), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(h->d_sqbuf.alloc((size_t)AB_SQ_BUF * h->n_slots), AIRBAND_HIP_ENOMEM);
-    {
-        const float lead_in = 20.0f; /* wavein[0 .. AGC_EXTRA) = 20.0f, src/config.cpp:313-316 (as a 32-bit pattern: no host copy of the rings, 4 GB at 65 536 dongles) */
-        int bits;
-        std::memcpy(&bits, &lead_in, sizeof(bits));
-        PREP_TRY(hipMemsetD32(reinterpret_cast<hipDeviceptr_t>(h->d_mag.p), bits, ring), AIRBAND_HIP_ENOMEM);
-    }
-    PREP_TRY(hipMemset(h->d_iq.p, 0, ring * sizeof(float2)), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(hipMemset(h->d_iq_out.p, 0, (size_t)h->B * h->n_slots * sizeof(float2)), AIRBAND_HIP_ENOMEM);
-    PREP_TRY(hipMemset(h->d_sqbuf.p, 0, (size_t)AB_SQ_BUF * h->n_slots * sizeof(float)), AIRBAND_HIP_ENOMEM);
-    /* hand-off buffers of the split kinds (NFM+CTCSS and generic are adjacent in slot order) */
-    h->ct_n_blocks = h->kind_n_blocks[AB_KIND_NFM_CTCSS] + h->kind_n_blocks[AB_KIND_GENERIC];
-    h->ct_first_block = h->kind_n_blocks[AB_KIND_NFM_CTCSS] ? h->kind_first_block[AB_KIND_NFM_CTCSS] : h->kind_first_block[AB_KIND_GENERIC];
-    if (h->ct_n_blocks > 0) {
-        /* one 32-bit word per sample for the NFM + CTCSS kind (rows padded to whole 128-byte lines), (audio, flags) pairs for the generic kind */
-        h->ct_pk_pitch = (h->B + 31) / 32 * 32;
-        PREP_TRY(h->d_ct_af.alloc((size_t)h->kind_n_blocks[AB_KIND_NFM_CTCSS] * AB_SLOT_BLOCK * h->ct_pk_pitch / 2 + (size_t)h->kind_n_blocks[AB_KIND_GENERIC] * AB_SLOT_BLOCK * h->B),
-                 AIRBAND_HIP_ENOMEM);
-        PREP_TRY(h->d_ct_mask.alloc((size_t)h->ct_n_blocks * (h->B / 50) * AB_SLOT_BLOCK), AIRBAND_HIP_ENOMEM);
-    }
-    {   /* regrouped stage 2 (demod.hip, "regrouping") */
-        /* Default (neither flag, no environment override): by residency.  A regrouped workgroup's wavefronts of closed channels spend most of the batch waiting at the
-         * lockstep barriers -- without using an issue slot, but holding their registers.  While ALL of a handle's lane-per-channel wavefronts are resident at once (about
-         * four to six per SIMD) that costs nothing and the 22 % of vector instructions regrouping removes are time (32 768 dongles x 8 mixed channels: stage 2 3.42 ->
-         * 3.02 ms; 49 152: 4.53 -> 4.33); past that the waiting wavefronts keep the next round's out (65 536: 5.8 -> 6.05), and a chip that is not full is bound by ONE
-         * wavefront's dependent chain, which regrouping does not shorten (<= 16 384: 2.48 -> 2.54) -- profiles/r06_experiments.md D. */
-        int n_lane_blocks = 0;
-        for (int k = 0; k < AB_KIND_COUNT; k++) n_lane_blocks += h->kind_n_blocks[k];
-        int cus = 0, cur_dev = 0;
-        (void)hipGetDevice(&cur_dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, cur_dev) != hipSuccess || cus <= 0) cus = 256;
-        const double waves_per_simd = (double)n_lane_blocks / (4.0 * cus);
-        const bool by_residency = waves_per_simd >= 2.75 && waves_per_simd <= 6.25;
-        const char* e = getenv("AIRBAND_HIP_REGROUP");
-        h->regroup = e && *e ? (*e != '0') : (h->flags & AIRBAND_HIP_FLAG_REGROUP) ? true : (h->flags & AIRBAND_HIP_FLAG_NO_REGROUP) ? false : by_residency;
-        /* regrouping deals a workgroup's slots out among its wavefronts: it would put isolated scan channels (above) back into one wavefront */
-        for (const ScanList& sl : p.scan)
-            if (sl.n > 1) h->regroup = false;
-        h->regroup_mode = (e && *e == '2') ? 2 : (e && *e == '3') ? 3 : 1;
-        if (h->regroup && h->regroup_mode == 3) PREP_TRY(h->d_perm.alloc((size_t)h->n_slots), AIRBAND_HIP_ENOMEM);
-        if (h->regroup || h->ct_n_blocks > 0) { /* the front kernel's note per channel: had audio / went CLOSED in this batch (tone kernel; regrouped back kernel) */
-            PREP_TRY(h->d_sq_key.alloc((size_t)h->n_slots), AIRBAND_HIP_ENOMEM);
-            PREP_TRY(hipMemset(h->d_sq_key.p, 0, (size_t)h->n_slots), AIRBAND_HIP_ENOMEM);
-        }
-    }
-    if (h->flags & AIRBAND_HIP_FLAG_TRACE_SQUELCH) {
-        PREP_TRY(h->d_trace.alloc((size_t)h->B * h->n_slots), AIRBAND_HIP_ENOMEM);
-        PREP_TRY(hipMemset(h->d_trace.p, 0, (size_t)h->B * h->n_slots), AIRBAND_HIP_ENOMEM);
-    }
-    /* results */
-    /* channel->waveout rows (src/rtl_airband.h:230): [AGC_EXTRA tail of the previous batch][WAVE_BATCH]; the consumer reads the first
-     * WAVE_BATCH entries.  Config-time prefill of the lead-in as in src/config.cpp:313-316 (waveout[0..AGC_EXTRA) = 0.5). */
-    h->wave_stride = (AB_OUT_PAD + AB_AGC_EXTRA + h->B + AB_OUT_RUN - 1) / AB_OUT_RUN * AB_OUT_RUN; /* whole 128-byte lines per row */
-    {
-        PREP_TRY(h->d_out_wave.alloc((size_t)p.total_ch * h->wave_stride), AIRBAND_HIP_ENOMEM);
-        PREP_TRY(hipMemset(h->d_out_wave.p, 0, h->d_out_wave.n * sizeof(float)), AIRBAND_HIP_ENOMEM);
-        /* the lead-in columns, a few thousand rows per strided copy (not a host image of every row: 4.5 GB at 65 536 dongles) */
-        const int chunk = p.total_ch < 4096 ? p.total_ch : 4096;
-        const std::vector<float> lead((size_t)chunk * AB_AGC_EXTRA, 0.5f);
-        for (int c = 0; c < p.total_ch; c += chunk) {
-            const int rows = p.total_ch - c < chunk ? p.total_ch - c : chunk;
-            PREP_TRY(hipMemcpy2D(h->d_out_wave.p + (size_t)c * h->wave_stride + AB_OUT_PAD, (size_t)h->wave_stride * sizeof(float), lead.data(), AB_AGC_EXTRA * sizeof(float),
-                                 AB_AGC_EXTRA * sizeof(float), (size_t)rows, hipMemcpyHostToDevice),
-                     AIRBAND_HIP_ENOMEM);
-        }
-    }
-    PREP_TRY(h->d_out_axc.alloc((size_t)p.total_ch), AIRBAND_HIP_ENOMEM);
-    bool any_iq_out = false;
-    for (const ChanConst& c : p.cc) any_iq_out |= (c.flags & AB_F_IQ_OUT) != 0;
-    if (any_iq_out) {
-        PREP_TRY(h->d_out_iq.alloc((size_t)p.total_ch * h->B * 2), AIRBAND_HIP_ENOMEM);
-        PREP_TRY(hipMemset(h->d_out_iq.p, 0, h->d_out_iq.n * sizeof(float)), AIRBAND_HIP_ENOMEM);
-    }
-    /* channelizer variant: matrix-core pruned DFT when the configuration qualifies, wavefront FFT otherwise */
-    /* AFC moves bins at run time and needs the full spectrum of each batch's last hop: that is the FFT kernel's job */
-    h->any_afc = any_afc;
-    if (any_afc) PREP_TRY(h->d_spectrum.alloc((size_t)p.n_dev * p.fft_size * 2), AIRBAND_HIP_ENOMEM);
-    h->use_dft = !(h->flags & AIRBAND_HIP_FLAG_FORCE_FFT) && dft_supported(p.fft_size, (int)h->hop_bytes, p.dev[0].sfmt, p.max_ch);
-    if (h->use_dft) {
-        build_dft_tables(h->plan, false);
-        /* One table per DISTINCT group of eight bins (shared between the work items that have it: a fleet of identical dongles has one, a fleet in which every
-         * device_t derives its own bins -- src/config.cpp:666-667 -- as many as it has groups) plus one private table per group with an AFC channel.  Bounded by
-         * their bytes alone (65 536 tables are 3.2 GB at fft 512, ~51 GB at fft 8192); past the budget the handle runs on the wavefront FFT.  Round 6: a COUNT used to
-         * stand here (more than 4 096 distinct plans -> wavefront FFT, 7x slower), which contradicted the private tables of the AFC path right beside it. */
-        const size_t tab_bytes_each = (size_t)3 * (p.fft_size > 512 ? 16 : p.fft_size / 32) * 64 * 16 * (p.fft_size > 512 ? p.fft_size / 512 : 1);
-        const size_t table_bytes = (size_t)p.n_bsets * tab_bytes_each;
-        if (table_bytes > AB_PRIVATE_TABLE_BUDGET) {
-            h->use_dft = false;
-        } else {
-            PREP_TRY(upload(h->d_item_dev, p.item_dev), AIRBAND_HIP_ENOMEM);
-            PREP_TRY(upload(h->d_item_group, p.item_group), AIRBAND_HIP_ENOMEM);
-            PREP_TRY(upload(h->d_item_bset, p.item_home), AIRBAND_HIP_ENOMEM); /* every channel starts on its base bin */
-            PREP_TRY(upload(h->d_item_private, p.item_bset), AIRBAND_HIP_ENOMEM);
-            PREP_TRY(upload(h->d_item_home, p.item_home), AIRBAND_HIP_ENOMEM);
-            /* the host has built the shared tables; the private ones (groups with an AFC channel) follow them, zeroed, and are built by the
-             * re-tune kernel right here: every column of theirs still stands at bin -1 */
-            const int np_t = p.fft_size > 512 ? p.fft_size / 512 : 1;
-            const size_t tab_bytes = (size_t)3 * (p.fft_size > 512 ? 16 : p.fft_size / 32) * 64 * 16 * np_t;
-            PREP_TRY(h->d_bfrag.alloc((size_t)p.n_bsets * tab_bytes), AIRBAND_HIP_ENOMEM);
-            PREP_TRY(h->d_bcorr.alloc((size_t)p.n_bsets * np_t * 16), AIRBAND_HIP_ENOMEM);
-            PREP_TRY(hipMemset(h->d_bfrag.p, 0, h->d_bfrag.n), AIRBAND_HIP_ENOMEM);
-            PREP_TRY(hipMemset(h->d_bcorr.p, 0, h->d_bcorr.n * sizeof(double)), AIRBAND_HIP_ENOMEM);
-            if (!p.bfrag.empty()) PREP_TRY(hipMemcpy(h->d_bfrag.p, p.bfrag.data(), p.bfrag.size(), hipMemcpyHostToDevice), AIRBAND_HIP_ENOMEM);
-            if (!p.bcorr.empty()) PREP_TRY(hipMemcpy(h->d_bcorr.p, p.bcorr.data(), p.bcorr.size() * sizeof(double), hipMemcpyHostToDevice), AIRBAND_HIP_ENOMEM);
-            {
-                std::vector<int> with_epoch(p.bset_bins);
-                with_epoch.push_back(0); /* the "last moved in batch" stamp: 0 = the start-up build below */
-                PREP_TRY(upload(h->d_bset_bin, with_epoch), AIRBAND_HIP_ENOMEM);
-            }
-            /* shared tables the host did not build (fleets with more than a few thousand distinct channel plans), then the private ones: a private table's columns
-             * are copied from its home table, so the home tables come first */
-            launch_build_tables(h->d_bfrag.p, h->d_bcorr.p, h->d_window.p, h->d_bset_bin.p, p.n_host_bsets, p.n_shared_bsets - p.n_host_bsets, p.fft_size, h->stream);
-            if (p.n_bsets > p.n_shared_bsets) launch_retune_tables(h, h->stream, 0);
-            if (p.n_bsets > p.n_host_bsets) {
-                PREP_TRY(hipGetLastError(), AIRBAND_HIP_ENODEV);
-                PREP_TRY(hipStreamSynchronize(h->stream), AIRBAND_HIP_ENODEV);
-            }
-            if (p.fft_size > 4096) /* [work items][tiles][64 lanes] float4 */
-                PREP_TRY(h->d_dft_partial.alloc((size_t)p.item_dev.size() * dft_partial_tiles(h->B + AB_AGC_EXTRA) * 64 * 4), AIRBAND_HIP_ENOMEM);
-        }
-    }
-    /* CF32 (SoapySDR): the float32 matrix pipe.  Round 6: also with AFC channels -- a group with one owns a private float table whose column pairs the re-tune kernel
-     * moves (misc_kernels.hip, build_column_pair_f32), exactly as the int8 path does; such handles stayed on the wavefront FFT before. */
-    h->use_f32 = !h->use_dft && !(h->flags & AIRBAND_HIP_FLAG_FORCE_FFT) && f32_supported(p.fft_size, p.dev[0].hop_samples, p.dev[0].sfmt);
-    if (h->use_f32) {
-        build_dft_tables(h->plan, false); /* the work items and the shared bin sets (its int8 tables are not used) */
-        /* bytes, not a count: a float table is f32_nw x (2 N / 4 / f32_nw) x 64 lanes x 4 bytes = 128 N bytes -- 64 KiB at fft 512, 256 KiB at 2048.  The shared tables are
-         * built on the host (params.cpp, build_f32_tables) and read once per work item per launch: past a budget the handle runs on the wavefront FFT rather than on a
-         * gigabyte-sized host build; the private ones (device-built) count against the budget the int8 path's private tables have */
-        const size_t ftab_each = 128u * (size_t)p.fft_size;
-        const size_t ftab_bytes = (size_t)p.n_shared_bsets * ftab_each;
-        if (ftab_bytes > AB_F32_TABLE_BUDGET || (size_t)p.n_bsets * ftab_each > AB_PRIVATE_TABLE_BUDGET) {
-            h->use_f32 = false;
-        } else {
-            build_f32_tables(h->plan);
-            PREP_TRY(upload(h->d_item_dev, p.item_dev), AIRBAND_HIP_ENOMEM);
-            PREP_TRY(upload(h->d_item_group, p.item_group), AIRBAND_HIP_ENOMEM);
-            PREP_TRY(upload(h->d_item_bset, p.item_home), AIRBAND_HIP_ENOMEM);
-            if (p.n_bsets > p.n_shared_bsets) { /* groups with an AFC channel: their private tables follow the shared ones, built by the re-tune kernel right here */
-                PREP_TRY(upload(h->d_item_private, p.item_bset), AIRBAND_HIP_ENOMEM);
-                PREP_TRY(upload(h->d_item_home, p.item_home), AIRBAND_HIP_ENOMEM);
-                std::vector<int> with_epoch(p.bset_bins);
-                with_epoch.push_back(0);
-                PREP_TRY(upload(h->d_bset_bin, with_epoch), AIRBAND_HIP_ENOMEM);
-                PREP_TRY(h->d_ftab.alloc((size_t)p.n_bsets * ftab_each / sizeof(float)), AIRBAND_HIP_ENOMEM);
-                PREP_TRY(hipMemset(h->d_ftab.p, 0, (size_t)p.n_bsets * ftab_each), AIRBAND_HIP_ENOMEM);
-                PREP_TRY(hipMemcpy(h->d_ftab.p, p.ftab.data(), p.ftab.size() * sizeof(float), hipMemcpyHostToDevice), AIRBAND_HIP_ENOMEM);
-                launch_retune_tables(h, h->stream, 0);
-                PREP_TRY(hipGetLastError(), AIRBAND_HIP_ENODEV);
-                PREP_TRY(hipStreamSynchronize(h->stream), AIRBAND_HIP_ENODEV);
-            } else
-            PREP_TRY(upload(h->d_ftab, p.ftab), AIRBAND_HIP_ENOMEM);
-            /* fft_size 4096 / 8192: partial sums between the launches of the window's segments (channelizer_f32.hip) */
-            if (f32_n_seg(p.fft_size) > 1) PREP_TRY(h->d_dft_partial.alloc((size_t)p.item_dev.size() * f32_partial_tiles(h->B + AB_AGC_EXTRA) * 64 * 4), AIRBAND_HIP_ENOMEM);
-        }
-        h->plan.bfrag.clear(); h->plan.bfrag.shrink_to_fit();
-        h->plan.ftab.clear(); h->plan.ftab.shrink_to_fit();
-    }
-    if (!h->use_dft && !h->use_f32) {
-        const size_t lds = fft_lds_bytes(p.fft_log, p.dev[0].hop_samples, p.dev[0].bytes_per_sample);
-        if (lds > 160 * 1024) { /* e.g. F32 at 20 MS/s: a 16-hop tile of raw samples does not fit a CU's LDS */
-            g_prepare_error = "sample_rate x bytes_per_sample too large for the FFT channelizer's LDS tile (" + std::to_string(lds) + " > 163840 bytes)";
-            destroy(h);
-            return AIRBAND_HIP_EBADSIZE;
-        }
-    }
+    prep_slots(h, cs_slots, block_kind);
+    prep_geometry(h);
+    rc = prep_constants(h, cs_slots, block_kind);
+    if (rc == AIRBAND_HIP_OK) rc = prep_rings(h);
+    if (rc == AIRBAND_HIP_OK) rc = prep_regroup(h);
+    if (rc == AIRBAND_HIP_OK) rc = prep_results(h);
+    if (rc == AIRBAND_HIP_OK) rc = prep_channelizer(h);
+    if (rc != AIRBAND_HIP_OK) return rc;
     h->ring_wr.reset(new std::atomic<uint64_t>[p.n_dev]);
     for (int d = 0; d < p.n_dev; d++) h->ring_wr[d].store(0);
     h->dev_enabled.reset(new std::atomic<uint8_t>[p.n_dev]);
     for (int d = 0; d < p.n_dev; d++) h->dev_enabled[d].store(1);
     h->n_enabled = p.n_dev;
-    h->cc_slots = cc_slots;
-    if (!p.scan.empty()) { /* scan lists: the banks, every entry's initial image, the masks, the switch lists' staging */
-        const size_t ne = p.scan_cc.size();
-        PREP_TRY(upload(h->d_bank_cc, p.scan_cc), AIRBAND_HIP_ENOMEM);
-        PREP_TRY(upload(h->d_bank_cs, p.scan_cs0), AIRBAND_HIP_ENOMEM);
-        PREP_TRY(h->d_bank_sq.alloc(ne * AB_SQ_BUF), AIRBAND_HIP_ENOMEM);
-        PREP_TRY(hipMemset(h->d_bank_sq.p, 0, ne * AB_SQ_BUF * sizeof(float)), AIRBAND_HIP_ENOMEM);
-        const AbScanMasks mk = ab_scan_masks();
-        std::vector<uint32_t> masks(mk.cs, mk.cs + AB_CS_DWORDS);
-        masks.insert(masks.end(), mk.cc, mk.cc + AB_CC_DWORDS);
-        PREP_TRY(upload(h->d_scan_mask, masks), AIRBAND_HIP_ENOMEM);
-        const size_t nl = p.scan.size();
-        for (int q = 0; q < 2; q++) {
-            PREP_TRY(h->d_switch[q].alloc(nl * 3), AIRBAND_HIP_ENOMEM);
-            PREP_TRY(hipHostMalloc((void**)&h->h_switch[q], nl * 3 * sizeof(int), hipHostMallocDefault), AIRBAND_HIP_ENOMEM);
-            PREP_TRY(hipEventCreateWithFlags(&h->ev_switch[q], hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-        }
-        std::vector<int> mix_slots;
-        h->scan_of_dev.assign(p.n_dev, -1);
-        for (size_t i = 0; i < nl; i++) {
-            h->scan_of_dev[p.scan[i].dev] = (int)i;
-            if (p.scan[i].mixed_am_nfm) mix_slots.push_back(h->ext_to_slot[p.scan[i].ext]);
-        }
-        if (!mix_slots.empty()) PREP_TRY(upload(h->d_scan_mix_slots, mix_slots), AIRBAND_HIP_ENOMEM);
-        h->scan_cur.assign(nl, 0);
-        h->scan_held.assign(nl, 0);
-        h->scan_latch[0].assign(nl, 0);
-        h->scan_latch[1].assign(nl, 0);
-    }
-#undef PREP_TRY
-    *out = h;
+    if (!p.scan.empty()) rc = prep_scan(h);
+    if (rc != AIRBAND_HIP_OK) return rc;
+    *out = owner.release();
     return AIRBAND_HIP_OK;
 }
 
@@ -969,7 +913,7 @@ int airband_hip_get_geometry(const airband_hip_handle* h, airband_hip_geometry* 
     g->device_count = h->plan.n_dev;
     g->total_channels = h->plan.total_ch;
     g->max_channels = h->plan.max_ch;
-    g->mixer_count = h->n_mixers;
+    g->mixer_count = h->mix.n_mixers;
     g->wave_stride = h->wave_stride;
     g->first_batch_bytes = h->first_batch_bytes;
     g->batch_bytes = h->batch_bytes;
@@ -1017,43 +961,39 @@ int airband_hip_set_mixers(airband_hip_handle* h, int32_t mixer_count, const air
     if (n_runs > 65535 || mixer_count > 65535) return fail(h, AIRBAND_HIP_EBADSIZE, "more than 65 535 mixers (or runs of 64 mixer inputs) on one handle");
     order_behind_last_batch(h);
     HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME); /* a batch under way still sums the old wiring */
-    h->n_mixers = 0; /* until the new wiring is complete: a failure below leaves a handle without mixers, not one with freed tables */
-    h->n_mix_runs = 0;
-    h->d_mix_chan.release(); h->d_mix_first.release(); h->d_mix_ml.release(); h->d_mix_mr.release();
-    h->d_mix_left.release(); h->d_mix_right.release(); h->d_mix_stereo.release(); h->d_mix_signal.release();
-    h->d_mix_run_first.release(); h->d_mix_run_mixer.release(); h->d_mix_first_run.release();
-    h->d_mix_run_left.release(); h->d_mix_run_right.release(); h->d_mix_run_signal.release();
-    HIP_TRY(h, upload(h->d_mix_run_first, run_first), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(h->d_mix_run_mixer, run_mixer), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(h->d_mix_first_run, first_run), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, h->d_mix_run_left.alloc((size_t)n_runs * h->B), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, h->d_mix_run_right.alloc((size_t)n_runs * h->B), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, h->d_mix_run_signal.alloc((size_t)n_runs), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(h->d_mix_chan, chan), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(h->d_mix_first, first), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(h->d_mix_ml, ml), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(h->d_mix_mr, mr), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(h->d_mix_stereo, stereo), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, h->d_mix_left.alloc((size_t)mixer_count * h->B), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, h->d_mix_right.alloc((size_t)mixer_count * h->B), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, h->d_mix_signal.alloc((size_t)mixer_count), AIRBAND_HIP_ENOMEM);
-    h->mix_pos = pos;
-    h->mix_chan_host = chan;
-    h->mix_user_on.assign(n_in, 1);
+    h->mix = MixerWiring(); /* n_mixers == 0 until the new wiring is complete: a failure below leaves a handle without mixers, not one with freed tables */
+    MixerWiring& w = h->mix;
+    HIP_TRY(h, upload(w.d_run_first, run_first), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_run_mixer, run_mixer), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_first_run, first_run), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, w.d_run_left.alloc((size_t)n_runs * h->B), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, w.d_run_right.alloc((size_t)n_runs * h->B), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, w.d_run_signal.alloc((size_t)n_runs), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_chan, chan), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_first, first), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_ml, ml), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_mr, mr), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_stereo, stereo), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, w.d_left.alloc((size_t)mixer_count * h->B), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, w.d_right.alloc((size_t)mixer_count * h->B), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, w.d_signal.alloc((size_t)mixer_count), AIRBAND_HIP_ENOMEM);
+    w.pos = pos;
+    w.chan_host = chan;
+    w.user_on.assign(n_in, 1);
     for (int k = 0; k < n_in; k++) /* inputs of dongles that are already switched off stay out */
         if (!h->dev_enabled[p.cc[chan[k]].dev]) HIP_TRY(h, write_mix_input(h, k), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
-    h->n_mix_runs = n_runs;
-    h->n_mixers = mixer_count;
+    w.n_runs = n_runs; /* published last */
+    w.n_mixers = mixer_count;
     return AIRBAND_HIP_OK;
 }
 
 int airband_hip_mixer_enable_input(airband_hip_handle* h, int32_t input_index, int32_t enabled) {
-    if (!h || h->n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
-    if (input_index < 0 || input_index >= (int32_t)h->mix_pos.size()) return fail(h, AIRBAND_HIP_EINVAL, "mixer input index out of range");
+    if (!h || h->mix.n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
+    if (input_index < 0 || input_index >= (int32_t)h->mix.pos.size()) return fail(h, AIRBAND_HIP_EINVAL, "mixer input index out of range");
     HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    const int k = h->mix_pos[input_index];
-    h->mix_user_on[k] = enabled ? 1 : 0;
+    const int k = h->mix.pos[input_index];
+    h->mix.user_on[k] = enabled ? 1 : 0;
     HIP_TRY(h, write_mix_input(h, k), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
     return AIRBAND_HIP_OK;
@@ -1087,8 +1027,8 @@ int airband_hip_device_enable(airband_hip_handle* h, int32_t dev, int32_t enable
     h->dev_enabled[dev].store(on, std::memory_order_release);
     h->n_enabled += on ? 1 : -1;
     /* its mixer connections: mixer_disable_input() for every output of the device, as disable_device_outputs() does (src/output.cpp, src/mixer.cpp:96-110) */
-    for (size_t k = 0; k < h->mix_chan_host.size(); k++)
-        if (p.cc[h->mix_chan_host[k]].dev == dev) HIP_TRY(h, write_mix_input(h, (int)k), AIRBAND_HIP_ERUNTIME);
+    for (size_t k = 0; k < h->mix.chan_host.size(); k++)
+        if (p.cc[h->mix.chan_host[k]].dev == dev) HIP_TRY(h, write_mix_input(h, (int)k), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME); /* the host buffers above go out of scope */
     return AIRBAND_HIP_OK;
 }
@@ -1140,163 +1080,29 @@ int airband_hip_gpu_count(void) {
 
 /* stage 1 of the next batch (index front_batches, ring rows from row0_front) on stream s */
 static int launch_front(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, hipStream_t s) {
-    const Plan& p = h->plan;
-    const bool first = h->front_batches == 0;
-    hipEvent_t* ev = event_set(h, h->front_batches, 0);
+    const FrontRows r = front_rows(h);
+    const Event* ev = event_set(h, h->front_batches, 0);
     /* hipGetLastError() is sticky: whatever an earlier, unchecked call of this thread left behind (ours or the host application's) is not this launch's error */
     (void)hipGetLastError();
-    hipError_t launch_err = hipSuccess;
-    if (h->use_f32) {
-        F32Args a;
-        a.iq = (const uint8_t*)d_iq;
-        a.iq_stride = (long)stride_bytes;
-        a.dev = h->d_dev.p;
-        a.cc = h->d_cc.p;
-        a.ext_to_slot = h->d_ext_to_slot.p;
-        a.item_dev = h->d_item_dev.p;
-        a.item_group = h->d_item_group.p;
-        a.item_bset = h->d_item_bset.p;
-        a.btab = h->d_ftab.p;
-        a.mag = h->d_mag.p;
-        a.iq_bins = h->d_iq.p;
-        a.n_items = (int)p.item_dev.size();
-        a.fft_size = p.fft_size;
-        a.hop_bytes = (int)h->hop_bytes;
-        a.pad = f32_pad_bytes(p.dev[0].hop_samples);
-        a.lds_per_buf = f32_lds_per_buf(p.fft_size, p.dev[0].hop_samples);
-        a.seg = 0;
-        a.n_seg = 1;
-        a.partial = reinterpret_cast<float4*>(h->d_dft_partial.p);
-        a.row0 = h->row0_front;
-        a.ring_rows = h->R;
-        a.first_row = first ? 0 : AB_AGC_EXTRA;
-        a.n_hops = first ? h->B + AB_AGC_EXTRA : h->B;
-        /* enough workgroups to fill 256 CUs x 2 even with few dongles: split each dongle's tiles */
-        const int tiles = (a.n_hops + 15) / 16 + 1;
-        int splits = (2048 + a.n_items - 1) / a.n_items;
-        if (splits > tiles / 4) splits = tiles / 4;
-        if (splits < 1) splits = 1;
-        a.splits = splits;
+    h->afc_spectrum_valid = h->any_afc;
+    if (h->use_f32 || h->use_dft) { /* the matrix-core channelizers leave the last hop's spectrum to the wavefront FFT */
         h->last_iq = d_iq;
         h->last_iq_stride = stride_bytes;
-        h->last_n_hops = a.n_hops;
-        h->afc_spectrum_valid = h->any_afc;
-        if (h->any_afc) { /* the spectrum of the batch's last hop, on a side stream beside stage 1 (as on the int8 path below) */
-            for (auto& e : h->ev_spec)
-                if (!e) HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-            (void)hipEventRecord(h->ev_spec[0], s);
-            (void)hipStreamWaitEvent(h->side[0], h->ev_spec[0], 0);
-            launch_last_hop_spectrum(h, h->side[0]);
-            (void)hipEventRecord(h->ev_spec[1], h->side[0]);
-        }
-        (void)hipEventRecord(ev[0], s);
-        launch_channelizer_f32(a, s);
-        launch_err = hipGetLastError(); /* right behind the launch: the event record below would mask it (or be blamed for it) */
-        (void)hipEventRecord(ev[1], s);
-    } else if (h->use_dft) {
-        DftArgs a;
-        a.iq = (const uint8_t*)d_iq;
-        a.iq_stride = (long)stride_bytes;
-        a.dev = h->d_dev.p;
-        a.cc = h->d_cc.p;
-        a.ext_to_slot = h->d_ext_to_slot.p;
-        a.item_dev = h->d_item_dev.p;
-        a.item_group = h->d_item_group.p;
-        a.item_bset = h->d_item_bset.p;
-        a.bfrag = h->d_bfrag.p;
-        a.corr = h->d_bcorr.p;
-        /* table units -> sample units: u8 (b - 127.5) / 127.5; s8 i / 128; CS16 x / fullscale (the kernel multiplies by the dongle's 1 / fullscale) */
-        a.unscale = p.dev[0].sfmt == AIRBAND_SFMT_S16 ? p.b_unscale * 127.5 : p.dev[0].sfmt == AIRBAND_SFMT_S8 ? p.b_unscale * 127.5 / 128.0 : p.b_unscale;
-        a.sfmt = p.dev[0].sfmt;
-        a.edge_hi_zero = p.b_edge_hi_zero ? 1 : 0;
-        a.mag = h->d_mag.p;
-        a.iq_bins = h->d_iq.p;
-        a.n_dev = p.n_dev;
-        a.n_items = (int)p.item_dev.size();
-        a.fft_size = p.fft_size;
-        a.hop_bytes = (int)h->hop_bytes;
-        /* the whole window is staged, also when it is worked on in pieces of 512 samples -- up to eight of them per launch (fft_size 8192: two passes) */
-        const int np_total = p.fft_size > 512 ? p.fft_size / 512 : 1, np = np_total > 8 ? 8 : np_total;
-        const int win_bytes = 2 * p.fft_size * p.dev[0].bytes_per_sample / np_total * np;
-        a.partial = reinterpret_cast<float4*>(h->d_dft_partial.p);
-        a.lds_per_buf = dft_lds_per_buf((int)h->hop_bytes, win_bytes, np);
-        a.nbuf = dft_nbuf((int)h->hop_bytes, win_bytes, np);
-        a.sub = dft_sub((int)h->hop_bytes, win_bytes, np);
-        a.row0 = h->row0_front;
-        a.ring_rows = h->R;
-        a.first_row = first ? 0 : AB_AGC_EXTRA;
-        a.n_hops = first ? h->B + AB_AGC_EXTRA : h->B;
-        /* Pipelined handles (stage 1 of this batch runs beside stage 2 of the batch before): eight channelizer wavefronts of ~250 registers ARE a CU's register file, and
-         * stage-2 wavefronts then only get onto a CU when one of them retires.  Held to FIVE per CU (it loses ~5 % alone: 7 and 6 per CU cost nothing, 4 cost 12 %,
-         * profiles/r06_occupancy/) the channelizer leaves three SIMDs a wavefront's worth of registers each: configs[2] 14.05 ms sequential, 13.77 pipelined as before,
-         * 13.05 like this (13.5 / 14.0 at 4 / 6 per CU; profiles/r06_pipelined/).  The LDS it asks for and never touches is what holds it there. */
-        a.extra_lds = 0;
-        if (h->pipeline && np_total == 1) {
-            const int used = a.nbuf * a.lds_per_buf, want = 28 * 1024; /* 160 KiB / 28 KiB = 5 */
-            if (used < want) a.extra_lds = want - used;
-        }
-        /* enough waves to fill 256 CUs x 8 waves even with few dongles: split each dongle's tiles */
-        const int steps = ((a.n_hops + 15) / 16 + 1 + a.sub - 1) / a.sub;
-        int splits = (8192 + a.n_items - 1) / a.n_items;
-        if (splits > steps / 4) splits = steps / 4;
-        if (splits < 1) splits = 1;
-        a.splits = splits;
-        h->last_iq = d_iq;
-        h->last_iq_stride = stride_bytes;
-        h->last_n_hops = a.n_hops;
-        h->afc_spectrum_valid = h->any_afc;
+        h->last_n_hops = r.n_hops;
         if (h->any_afc) {
-            /* AFC::finalize looks at the spectrum of the batch's last hop (src/rtl_airband.cpp:626-630): it depends on the input only, so it is
-             * computed on a side stream BESIDE stage 1 (behind the previous batch's AFC, which read the buffer it overwrites) and joined in
-             * front of afc_kernel (run_back_half) */
-            for (auto& e : h->ev_spec)
-                if (!e) HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-            (void)hipEventRecord(h->ev_spec[0], s);
-            (void)hipStreamWaitEvent(h->side[0], h->ev_spec[0], 0);
-            launch_last_hop_spectrum(h, h->side[0]);
-            (void)hipEventRecord(h->ev_spec[1], h->side[0]);
+            const int rc = launch_last_hop_spectrum(h, s);
+            if (rc != AIRBAND_HIP_OK) return rc;
         }
-        (void)hipEventRecord(ev[0], s);
-        launch_channelizer_dft(a, s);
-        launch_err = hipGetLastError();
-        (void)hipEventRecord(ev[1], s);
-    } else {
-        ChannelizerArgs ca;
-        ca.iq = (const uint8_t*)d_iq;
-        ca.iq_stride = (long)stride_bytes;
-        ca.dev = h->d_dev.p;
-        ca.cs = h->d_cs.p;
-        ca.cc = h->d_cc.p;
-        ca.ext_to_slot = h->d_ext_to_slot.p;
-        ca.window = h->d_window.p;
-        ca.window_dec = h->d_window_dec.p;
-        ca.twiddle = reinterpret_cast<const float2*>(h->d_twiddle.p);
-        ca.mag = h->d_mag.p;
-        ca.iq_bins = h->d_iq.p;
-        ca.last_spectrum = h->any_afc ? h->d_spectrum.p : nullptr;
-        ca.n_dev = p.n_dev;
-        ca.fft_log = p.fft_log;
-        ca.hop_samples = p.dev[0].hop_samples;
-        ca.bytes_per_sample = p.dev[0].bytes_per_sample;
-        ca.sfmt = p.dev[0].sfmt;
-        ca.scale = p.dev[0].scale;
-        ca.row0 = h->row0_front;
-        ca.ring_rows = h->R;
-        ca.first_row = first ? 0 : AB_AGC_EXTRA; /* the first batch also produces the AGC_EXTRA lead-in hops (waveend starts at 0, src/config.cpp:805) */
-        ca.n_hops = first ? h->B + AB_AGC_EXTRA : h->B;
-        ca.max_ch = p.max_ch;
-        ca.spectrum_only = 0;
-        (void)hipEventRecord(ev[0], s);
-        h->afc_spectrum_valid = h->any_afc;
-        launch_channelizer_fft(ca, s);
-        launch_err = hipGetLastError();
-        (void)hipEventRecord(ev[1], s);
     }
+    (void)hipEventRecord(ev[0], s);
+    if (h->use_f32) launch_channelizer_f32(f32_args(h, d_iq, stride_bytes, r), s);
+    else if (h->use_dft) launch_channelizer_dft(dft_args(h, d_iq, stride_bytes, r), s);
+    else launch_channelizer_fft(fft_args(h, d_iq, stride_bytes, h->row0_front, r, 0), s);
+    const hipError_t launch_err = hipGetLastError(); /* right behind the launch: the event record below would mask it (or be blamed for it) */
+    (void)hipEventRecord(ev[1], s);
     /* a refused launch (an LDS opt-in that failed, a bad grid) is this call's error, not a puzzle for whoever synchronises next */
     if (launch_err != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("channelizer launch: ") + hipGetErrorString(launch_err));
-    scan_latch(h, h->front_batches, first ? 0 : AB_AGC_EXTRA, first ? h->B + AB_AGC_EXTRA : h->B);
-    h->row0_front = (h->row0_front + h->B) % h->R;
-    h->front_batches++;
+    front_enqueued(h, r.first_row, r.n_hops);
     return AIRBAND_HIP_OK;
 }
 
@@ -1324,14 +1130,11 @@ int airband_hip_process_device(airband_hip_handle* h, const void* d_iq, size_t s
         const int rc_front = launch_front(h, d_iq, stride_bytes, s);
         if (rc_front != AIRBAND_HIP_OK) return rc_front;
         const int rc = run_back_half(h, s);
-        if (s != h->stream) { /* collect() and friends run on h->stream: give them something to wait for */
-            if (!h->ev_last) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_last, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-            HIP_TRY(h, hipEventRecord(h->ev_last, s), AIRBAND_HIP_ERUNTIME);
-            h->ev_last_pending = true;
-        } else {
-            h->ev_last_pending = false;
-        }
-        return rc;
+        /* collect() and friends run on h->stream.  A batch of its own is in order there already, and everything an earlier mark stood for lies in front of it:
+         * only a whole batch CLEARS the mark (an exchange or a clear on the handle's stream leaves it alone) */
+        if (s == h->stream) h->ev_last_pending = false;
+        const int rc_mark = results_enqueued_on(h, s);
+        return rc_mark != AIRBAND_HIP_OK ? rc_mark : rc;
     }
     /* Pipelined: stage 1 of this batch (k) goes on the front stream and runs beside stage 2 of batch k-1, which is enqueued
      * right after it on the handle's stream.  Stage 1 (k) overwrites the ring rows stage 2 (k-2) read, and may use the
@@ -1360,8 +1163,8 @@ int airband_hip_process_device(airband_hip_handle* h, const void* d_iq, size_t s
 int airband_hip_stream_wait_results(airband_hip_handle* h, void* stream) {
     if (!h || !stream) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
     HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    if (!h->ev_wait) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_wait, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-    hipStream_t res = h->pipeline ? h->stream : (h->last_stream ? h->last_stream : h->stream);
+    HIP_TRY(h, h->ev_wait.ensure(), AIRBAND_HIP_ENODEV);
+    hipStream_t res = results_stream(h);
     if (res == (hipStream_t)stream) return AIRBAND_HIP_OK;
     HIP_TRY(h, hipEventRecord(h->ev_wait, res), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipStreamWaitEvent((hipStream_t)stream, h->ev_wait, 0), AIRBAND_HIP_ERUNTIME);
@@ -1376,6 +1179,20 @@ int airband_hip_flush(airband_hip_handle* h) {
     return run_back_half(h, h->stream);
 }
 
+/* bytes of every dongle's stream the next batch consumes (the first one with its lead-in) */
+static int64_t next_batch_bytes(const airband_hip_handle* h) { return h->front_batches == 0 ? h->first_batch_bytes : h->batch_bytes; }
+
+/* The availability rule (src/rtl_airband.cpp:394-400) applied to a whole batch: every dongle has the batch and its look-ahead.  Dongles switched off (failed
+ * inputs) are not waited for: next_device() passes them by, src/rtl_airband.cpp:383-391; with every dongle switched off there is nothing to demodulate (the
+ * reference exits, src/rtl_airband.cpp:377-381). */
+static bool batch_available(const airband_hip_handle* h) {
+    if (h->n_enabled == 0) return false;
+    const int64_t need = next_batch_bytes(h) + h->lookahead_bytes;
+    for (int d = 0; d < h->plan.n_dev; d++)
+        if (h->dev_enabled[d] && (int64_t)(h->ring_wr[d].load(std::memory_order_acquire) - h->ring_rd) < need) return false;
+    return true;
+}
+
 /* first use of the host-ring path: pinned rings, device staging, copy stream */
 static int host_path_init(airband_hip_handle* h) {
     std::lock_guard<std::mutex> guard(h->host_init_lock);
@@ -1387,14 +1204,11 @@ static int host_path_init(airband_hip_handle* h) {
     h->stage_stride = (h->first_batch_bytes + h->lookahead_bytes + 255) / 256 * 256;
     for (auto& b : h->d_stage2)
         if (!b.p) HIP_TRY(h, b.alloc((size_t)h->stage_stride * h->plan.n_dev), AIRBAND_HIP_ENOMEM);
-    if (!h->h2d) HIP_TRY(h, hipStreamCreateWithFlags(&h->h2d, hipStreamNonBlocking), AIRBAND_HIP_ENODEV);
-    for (auto& e : h->ev_h2d)
-        if (!e) HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-    for (auto& e : h->ev_stage_read)
-        if (!e) HIP_TRY(h, hipEventCreateWithFlags(&e, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-    uint8_t* ring = nullptr;
-    HIP_TRY(h, hipHostMalloc((void**)&ring, (size_t)h->ring_cap * h->plan.n_dev, hipHostMallocDefault), AIRBAND_HIP_ENOMEM);
-    h->h_ring.store(ring, std::memory_order_release); /* published last: submit() / process() test this pointer without the lock */
+    if (!h->h2d) HIP_TRY(h, hipStreamCreateWithFlags(&h->h2d.v, hipStreamNonBlocking), AIRBAND_HIP_ENODEV);
+    for (auto& e : h->ev_h2d) HIP_TRY(h, e.ensure(), AIRBAND_HIP_ENODEV);
+    for (auto& e : h->ev_stage_read) HIP_TRY(h, e.ensure(), AIRBAND_HIP_ENODEV);
+    HIP_TRY(h, h->ring_mem.alloc((size_t)h->ring_cap * h->plan.n_dev), AIRBAND_HIP_ENOMEM);
+    h->h_ring.store(h->ring_mem.get(), std::memory_order_release); /* published last: submit() / process() test this pointer without the lock */
     return AIRBAND_HIP_OK;
 }
 
@@ -1425,12 +1239,8 @@ int64_t airband_hip_submit(airband_hip_handle* h, int32_t dev, const void* iq, s
  * used: OK = yes, EAGAIN = not yet (or every dongle is switched off). */
 int airband_hip_batch_ready(airband_hip_handle* h) {
     if (!h) return AIRBAND_HIP_EINVAL;
-    if (h->n_enabled == 0) return AIRBAND_HIP_EAGAIN;
     if (!h->h_ring.load(std::memory_order_acquire)) return AIRBAND_HIP_EAGAIN; /* nothing has been submitted yet */
-    const int64_t need = (h->front_batches == 0 ? h->first_batch_bytes : h->batch_bytes) + h->lookahead_bytes;
-    for (int d = 0; d < h->plan.n_dev; d++)
-        if (h->dev_enabled[d] && (int64_t)(h->ring_wr[d].load(std::memory_order_acquire) - h->ring_rd) < need) return AIRBAND_HIP_EAGAIN;
-    return AIRBAND_HIP_OK;
+    return batch_available(h) ? AIRBAND_HIP_OK : AIRBAND_HIP_EAGAIN;
 }
 
 int airband_hip_process(airband_hip_handle* h) {
@@ -1441,12 +1251,9 @@ int airband_hip_process(airband_hip_handle* h) {
         if (rc != AIRBAND_HIP_OK) return rc;
     }
     uint8_t* const ring = h->h_ring.load(std::memory_order_acquire);
-    const bool first = h->front_batches == 0;
-    const int64_t consume = first ? h->first_batch_bytes : h->batch_bytes;
-    const int64_t need = consume + h->lookahead_bytes; /* availability rule (src/rtl_airband.cpp:394-400) applied to a whole batch */
-    if (h->n_enabled == 0) return AIRBAND_HIP_EAGAIN; /* every dongle switched off: nothing to demodulate (the reference exits, src/rtl_airband.cpp:377-381) */
-    for (int d = 0; d < h->plan.n_dev; d++) /* dongles switched off (failed inputs) are not waited for: next_device() passes them by, src/rtl_airband.cpp:383-391 */
-        if (h->dev_enabled[d] && (int64_t)(h->ring_wr[d].load(std::memory_order_acquire) - h->ring_rd) < need) return AIRBAND_HIP_EAGAIN;
+    if (!batch_available(h)) return AIRBAND_HIP_EAGAIN;
+    const int64_t consume = next_batch_bytes(h);
+    const int64_t need = consume + h->lookahead_bytes;
     const int b = (int)(h->host_batches & 1);
     /* the DMA of the previous batch has left the ring: its bytes (up to the look-ahead the next batch re-reads) may be overwritten */
     if (h->host_batches > 0) {
@@ -1479,25 +1286,17 @@ int airband_hip_process_bins(airband_hip_handle* h, const float* wavein, const f
     if (h->pipeline) return fail(h, AIRBAND_HIP_EINVAL, "process_bins (stage 2 only) is not available on a pipelined handle");
     HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
     const size_t n = (size_t)h->plan.total_ch * h->B;
-    if (h->d_tmp_wavein.n < n) {
-        h->d_tmp_wavein.release();
-        HIP_TRY(h, h->d_tmp_wavein.alloc(n), AIRBAND_HIP_ENOMEM);
-    }
-    if (h->d_tmp_iqin.n < 2 * n) {
-        h->d_tmp_iqin.release();
-        HIP_TRY(h, h->d_tmp_iqin.alloc(2 * n), AIRBAND_HIP_ENOMEM);
-    }
+    HIP_TRY(h, h->d_tmp_wavein.reserve(n), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, h->d_tmp_iqin.reserve(2 * n), AIRBAND_HIP_ENOMEM);
     hipStream_t s = h->stream;
     HIP_TRY(h, hipMemcpyAsync(h->d_tmp_wavein.p, wavein, n * sizeof(float), hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipMemcpyAsync(h->d_tmp_iqin.p, iq_in, 2 * n * sizeof(float), hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
-    hipEvent_t* ev = event_set(h, h->front_batches, 0);
+    const Event* ev = event_set(h, h->front_batches, 0);
     (void)hipEventRecord(ev[0], s);
     h->afc_spectrum_valid = false;
     launch_scatter_bins(h->d_tmp_wavein.p, h->d_tmp_iqin.p, h->d_slot_to_ext.p, h->d_cc.p, h->d_mag.p, h->d_iq.p, h->n_slots, h->B, h->row0, h->R, s);
     (void)hipEventRecord(ev[1], s);
-    scan_latch(h, h->front_batches, AB_AGC_EXTRA, h->B); /* the caller's rows are the batch's new ones; the carry is what the rings hold */
-    h->row0_front = (h->row0_front + h->B) % h->R;
-    h->front_batches++;
+    front_enqueued(h, AB_AGC_EXTRA, h->B); /* the caller's rows are the batch's new ones; the carry is what the rings hold */
     return run_back_half(h, s);
 }
 
@@ -1553,14 +1352,14 @@ int airband_hip_collect_channels(airband_hip_handle* h, int64_t first_channel, i
 
 int airband_hip_collect_mixers(airband_hip_handle* h, float* left, float* right, uint8_t* has_signal) {
     if (!h) return AIRBAND_HIP_EINVAL;
-    if (h->n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
+    if (h->mix.n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
     HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
     hipStream_t s = h->stream;
     order_behind_last_batch(h);
-    const size_t n = (size_t)h->n_mixers * h->B;
-    if (left) HIP_TRY(h, hipMemcpyAsync(left, h->d_mix_left.p, n * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (right) HIP_TRY(h, hipMemcpyAsync(right, h->d_mix_right.p, n * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (has_signal) HIP_TRY(h, hipMemcpyAsync(has_signal, h->d_mix_signal.p, (size_t)h->n_mixers, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    const size_t n = (size_t)h->mix.n_mixers * h->B;
+    if (left) HIP_TRY(h, hipMemcpyAsync(left, h->mix.d_left.p, n * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (right) HIP_TRY(h, hipMemcpyAsync(right, h->mix.d_right.p, n * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (has_signal) HIP_TRY(h, hipMemcpyAsync(has_signal, h->mix.d_signal.p, (size_t)h->mix.n_mixers, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
     return AIRBAND_HIP_OK;
 }
@@ -1571,9 +1370,9 @@ int airband_hip_device_results(airband_hip_handle* h, float** d_waveout, float**
     if (d_waveout) *d_waveout = h->d_out_wave.p + AB_OUT_PAD;
     if (d_iq_out) *d_iq_out = h->d_out_iq.p;
     if (d_axc) *d_axc = h->d_out_axc.p;
-    if (d_mix_left) *d_mix_left = h->d_mix_left.p;
-    if (d_mix_right) *d_mix_right = h->d_mix_right.p;
-    if (d_mix_signal) *d_mix_signal = h->d_mix_signal.p;
+    if (d_mix_left) *d_mix_left = h->mix.d_left.p;
+    if (d_mix_right) *d_mix_right = h->mix.d_right.p;
+    if (d_mix_signal) *d_mix_signal = h->mix.d_signal.p;
     return AIRBAND_HIP_OK;
 }
 
@@ -1583,18 +1382,9 @@ static int gather_last(airband_hip_handle* h, int64_t first, int64_t nch, float*
     if (h->batches_done == 0) return fail(h, AIRBAND_HIP_EAGAIN, "no batch processed yet");
     if (nch == 0) return AIRBAND_HIP_OK;
     const size_t n = (size_t)nch * h->B;
-    if (wavein && h->d_tmp_wavein.n < n) {
-        h->d_tmp_wavein.release();
-        HIP_TRY(h, h->d_tmp_wavein.alloc(n), AIRBAND_HIP_ENOMEM);
-    }
-    if (iq_in && h->d_tmp_iqin.n < 2 * n) {
-        h->d_tmp_iqin.release();
-        HIP_TRY(h, h->d_tmp_iqin.alloc(2 * n), AIRBAND_HIP_ENOMEM);
-    }
-    if (trace && h->d_tmp_trace.n < n) {
-        h->d_tmp_trace.release();
-        HIP_TRY(h, h->d_tmp_trace.alloc(n), AIRBAND_HIP_ENOMEM);
-    }
+    if (wavein) HIP_TRY(h, h->d_tmp_wavein.reserve(n), AIRBAND_HIP_ENOMEM);
+    if (iq_in) HIP_TRY(h, h->d_tmp_iqin.reserve(2 * n), AIRBAND_HIP_ENOMEM);
+    if (trace) HIP_TRY(h, h->d_tmp_trace.reserve(n), AIRBAND_HIP_ENOMEM);
     hipStream_t s = h->stream;
     order_behind_last_batch(h);
     const int prev_row0 = (h->row0 + h->R - h->B) % h->R; /* row0 of the batch just finished */
@@ -1672,8 +1462,6 @@ const char* airband_hip_channelizer_name(const airband_hip_handle* h) {
 int airband_hip_set_signal_plan(airband_hip_handle* h, const int64_t* carriers, int32_t n_carriers, int32_t noise_q8, const int16_t* sin_table4096) {
     if (!h || !carriers || !sin_table4096 || n_carriers < 1 || n_carriers > 16) return fail(h, AIRBAND_HIP_EINVAL, "bad signal plan (1..16 carriers)");
     HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    h->d_carriers.release();
-    h->d_sin_tab.release();
     std::vector<long long> c(carriers, carriers + (size_t)n_carriers * 12);
     std::vector<int16_t> t(sin_table4096, sin_table4096 + 4096);
     HIP_TRY(h, upload(h->d_carriers, c), AIRBAND_HIP_ENOMEM);
@@ -1793,16 +1581,14 @@ Rccl* rccl() {
         if (r_ != ncclSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string(#expr ": ") + (R)->GetErrorString(r_)); \
     } while (0)
 
-/* the stream on which the last batch's mixer sums become final */
-hipStream_t results_stream(airband_hip_handle* h) { return h->pipeline ? h->stream : (h->last_stream ? h->last_stream : h->stream); }
 }  // namespace
 
 int airband_hip_mixer_set_stereo(airband_hip_handle* h, int32_t mixer, int32_t stereo) {
-    if (!h || h->n_mixers <= 0 || mixer < 0 || mixer >= h->n_mixers) return fail(h, AIRBAND_HIP_EINVAL, "mixer index out of range");
+    if (!h || h->mix.n_mixers <= 0 || mixer < 0 || mixer >= h->mix.n_mixers) return fail(h, AIRBAND_HIP_EINVAL, "mixer index out of range");
     HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
     order_behind_last_batch(h);
     const uint8_t v = stereo ? 1 : 0;
-    HIP_TRY(h, hipMemcpyAsync(h->d_mix_stereo.p + mixer, &v, 1, hipMemcpyHostToDevice, h->stream), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipMemcpyAsync(h->mix.d_stereo.p + mixer, &v, 1, hipMemcpyHostToDevice, h->stream), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
     return AIRBAND_HIP_OK;
 }
@@ -1835,7 +1621,7 @@ int airband_hip_comm_init_all(airband_hip_handle** hs, int32_t n) {
     for (int i = 0; i < n; i++) {
         if (!hs[i] || hs[i]->comm) return fail(hs[i], AIRBAND_HIP_EINVAL, "NULL handle, or a handle that already has a communicator");
         devs[i] = hs[i]->hip_device;
-        if (hs[i]->n_mixers != hs[0]->n_mixers || hs[i]->B != hs[0]->B) return fail(hs[i], AIRBAND_HIP_EINVAL, "the handles of a clique need the same mixer_count and WAVE_BATCH");
+        if (hs[i]->mix.n_mixers != hs[0]->mix.n_mixers || hs[i]->B != hs[0]->B) return fail(hs[i], AIRBAND_HIP_EINVAL, "the handles of a clique need the same mixer_count and WAVE_BATCH");
     }
     Rccl* R = rccl();
     if (!R) return fail(hs[0], AIRBAND_HIP_ENODEV, g_rccl.why);
@@ -1866,7 +1652,7 @@ int airband_hip_comm_group_end(void) {
 /* SUM of the mixer waveforms (src/mixer.cpp:133-140), MAX of the signal flags (channel->axcindicate = SIGNAL if any input had signal, :209), in place */
 int airband_hip_allreduce_mixers(airband_hip_handle* h, void* stream) {
     if (!h) return AIRBAND_HIP_EINVAL;
-    if (h->n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
+    if (h->mix.n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
     if (!h->comm) return fail(h, AIRBAND_HIP_EINVAL, "no communicator: airband_hip_comm_init_rank / _init_all first");
     Rccl* R = rccl();
     if (!R) return fail(h, AIRBAND_HIP_ENODEV, g_rccl.why);
@@ -1876,34 +1662,28 @@ int airband_hip_allreduce_mixers(airband_hip_handle* h, void* stream) {
         const int rc = airband_hip_stream_wait_results(h, stream);
         if (rc != AIRBAND_HIP_OK) return rc;
     }
-    const size_t n = (size_t)h->n_mixers * h->B;
+    const size_t n = (size_t)h->mix.n_mixers * h->B;
     RCCL_TRY(h, R, R->GroupStart());
-    RCCL_TRY(h, R, R->AllReduce(h->d_mix_left.p, h->d_mix_left.p, n, ncclFloat, ncclSum, h->comm, s));
-    RCCL_TRY(h, R, R->AllReduce(h->d_mix_right.p, h->d_mix_right.p, n, ncclFloat, ncclSum, h->comm, s));
-    RCCL_TRY(h, R, R->AllReduce(h->d_mix_signal.p, h->d_mix_signal.p, (size_t)h->n_mixers, ncclUint8, ncclMax, h->comm, s));
+    RCCL_TRY(h, R, R->AllReduce(h->mix.d_left.p, h->mix.d_left.p, n, ncclFloat, ncclSum, h->comm, s));
+    RCCL_TRY(h, R, R->AllReduce(h->mix.d_right.p, h->mix.d_right.p, n, ncclFloat, ncclSum, h->comm, s));
+    RCCL_TRY(h, R, R->AllReduce(h->mix.d_signal.p, h->mix.d_signal.p, (size_t)h->mix.n_mixers, ncclUint8, ncclMax, h->comm, s));
     RCCL_TRY(h, R, R->GroupEnd());
-    if (s != h->stream) { /* (a caller's stream, handed in here or to process_device) whatever the handle does next to these buffers (the next batch's sums, collect_mixers) comes behind the exchange */
-        if (!h->ev_last) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_last, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-        HIP_TRY(h, hipEventRecord(h->ev_last, s), AIRBAND_HIP_ERUNTIME);
-        h->ev_last_pending = true;
-    }
-    return AIRBAND_HIP_OK;
+    return results_enqueued_on(h, s); /* whatever the handle does next to these buffers (the next batch's sums, collect_mixers) comes behind the exchange */
 }
 
 int airband_hip_add_mixers(airband_hip_handle* dst, airband_hip_handle* src) {
     if (!dst || !src || dst == src) return fail(dst, AIRBAND_HIP_EINVAL, "two different handles needed");
-    if (dst->n_mixers <= 0 || dst->n_mixers != src->n_mixers || dst->B != src->B) return fail(dst, AIRBAND_HIP_EINVAL, "the handles need the same mixer_count and WAVE_BATCH");
+    if (dst->mix.n_mixers <= 0 || dst->mix.n_mixers != src->mix.n_mixers || dst->B != src->B) return fail(dst, AIRBAND_HIP_EINVAL, "the handles need the same mixer_count and WAVE_BATCH");
     if (dst->hip_device != src->hip_device) return fail(dst, AIRBAND_HIP_EINVAL, "handles on different GPUs exchange through airband_hip_allreduce_mixers");
     HIP_TRY(dst, hipSetDevice(dst->hip_device), AIRBAND_HIP_ENODEV);
-    if (!dst->ev_peer) HIP_TRY(dst, hipEventCreateWithFlags(&dst->ev_peer, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
+    HIP_TRY(dst, dst->ev_peer.ensure(), AIRBAND_HIP_ENODEV);
     hipStream_t s = results_stream(dst);
     HIP_TRY(dst, hipEventRecord(dst->ev_peer, results_stream(src)), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(dst, hipStreamWaitEvent(s, dst->ev_peer, 0), AIRBAND_HIP_ERUNTIME);
-    launch_mix_add(dst->d_mix_left.p, dst->d_mix_right.p, dst->d_mix_signal.p, src->d_mix_left.p, src->d_mix_right.p, src->d_mix_signal.p, dst->n_mixers, dst->B, s);
+    launch_mix_add(dst->mix.d_left.p, dst->mix.d_right.p, dst->mix.d_signal.p, src->mix.d_left.p, src->mix.d_right.p, src->mix.d_signal.p, dst->mix.n_mixers, dst->B, s);
     /* src's next batch must not overwrite its sums before they have been read */
-    if (!src->ev_last) HIP_TRY(src, hipEventCreateWithFlags(&src->ev_last, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-    HIP_TRY(src, hipEventRecord(src->ev_last, s), AIRBAND_HIP_ERUNTIME);
-    src->ev_last_pending = true;
+    const int rc_mark = results_enqueued_on(src, s);
+    if (rc_mark != AIRBAND_HIP_OK) return rc_mark;
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(dst, AIRBAND_HIP_ERUNTIME, std::string("mixer add launch: ") + hipGetErrorString(e));
     return AIRBAND_HIP_OK;
@@ -1914,20 +1694,15 @@ int airband_hip_add_mixers(airband_hip_handle* dst, airband_hip_handle* src) {
  * themselves: the last batch's sums are still in them, and after an in-place all-reduce the whole node's. */
 int airband_hip_clear_mixers(airband_hip_handle* h) {
     if (!h) return AIRBAND_HIP_EINVAL;
-    if (h->n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
+    if (h->mix.n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
     HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
     hipStream_t s = results_stream(h); /* behind whatever wrote or read the sums last: the handle's last batch, an exchange, add_mixers */
     if (h->ev_last && h->ev_last_pending) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_last, 0), AIRBAND_HIP_ERUNTIME); /* a peer's add_mixers still reading them */
-    const size_t n = (size_t)h->n_mixers * h->B;
-    HIP_TRY(h, hipMemsetAsync(h->d_mix_left.p, 0, n * sizeof(float), s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipMemsetAsync(h->d_mix_right.p, 0, n * sizeof(float), s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipMemsetAsync(h->d_mix_signal.p, 0, (size_t)h->n_mixers, s), AIRBAND_HIP_ERUNTIME);
-    if (s != h->stream) { /* a caller's stream (the last batch ran there): collect_mixers, or a later batch on another stream, comes behind the clear -- as behind allreduce_mixers */
-        if (!h->ev_last) HIP_TRY(h, hipEventCreateWithFlags(&h->ev_last, hipEventDisableTiming), AIRBAND_HIP_ENODEV);
-        HIP_TRY(h, hipEventRecord(h->ev_last, s), AIRBAND_HIP_ERUNTIME);
-        h->ev_last_pending = true;
-    }
-    return AIRBAND_HIP_OK;
+    const size_t n = (size_t)h->mix.n_mixers * h->B;
+    HIP_TRY(h, hipMemsetAsync(h->mix.d_left.p, 0, n * sizeof(float), s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipMemsetAsync(h->mix.d_right.p, 0, n * sizeof(float), s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipMemsetAsync(h->mix.d_signal.p, 0, (size_t)h->mix.n_mixers, s), AIRBAND_HIP_ERUNTIME);
+    return results_enqueued_on(h, s); /* collect_mixers, or a later batch on another stream, comes behind the clear -- as behind allreduce_mixers */
 }
 
 int airband_hip_comm_destroy(airband_hip_handle* h) {

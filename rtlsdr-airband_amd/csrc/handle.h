@@ -1,0 +1,237 @@
+/* csrc/handle.h -- private to airband_hip.cpp: the handle behind the C ABI and the types that own its HIP objects.
+ *
+ * Everything the handle holds on the device frees itself when the handle is deleted.  What makes that safe -- nothing of it is still in
+ * flight -- is destroy()'s job (airband_hip.cpp), not these destructors'.
+ */
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <rccl/rccl.h> /* types and prototypes only: librccl.so is loaded on first use (airband_hip_comm_*) */
+
+#include <atomic>
+#include <memory>
+#include <mutex>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "../../include/airband_hip.h"
+#include "common.h"
+#include "params.h"
+
+namespace airband {
+
+/* a HIP object that is released with its owner (move-only); converts to the plain handle where HIP wants one */
+template <class H, hipError_t (*Release)(H)>
+struct Owned {
+    H v = nullptr;
+    Owned() = default;
+    Owned(Owned&& o) noexcept : v(std::exchange(o.v, nullptr)) {}
+    Owned& operator=(Owned&& o) noexcept {
+        std::swap(v, o.v); /* what was here goes with o */
+        return *this;
+    }
+    ~Owned() {
+        if (v) (void)Release(v);
+    }
+    operator H() const { return v; }
+};
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+
+struct Event : Owned<hipEvent_t, hipEventDestroy> {
+    /* the events that only order streams; created on first use where a handle may never need them */
+    hipError_t ensure() { return v ? hipSuccess : hipEventCreateWithFlags(&v, hipEventDisableTiming); }
+};
+
+/* device memory, `n` elements at `p` */
+template <class T>
+struct DevBuf {
+    T* p = nullptr;
+    size_t n = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), n(std::exchange(o.n, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    hipError_t alloc(size_t count) {
+        release();
+        if (count == 0) return hipSuccess;
+        const hipError_t e = hipMalloc((void**)&p, count * sizeof(T));
+        if (e == hipSuccess) n = count;
+        return e;
+    }
+    hipError_t alloc_zeroed(size_t count) {
+        const hipError_t e = alloc(count);
+        return e != hipSuccess || count == 0 ? e : hipMemset(p, 0, count * sizeof(T));
+    }
+    /* room for `count` elements: what is there stays if it is large enough, its contents do not otherwise */
+    hipError_t reserve(size_t count) { return n >= count ? hipSuccess : alloc(count); }
+    void release() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
+};
+
+/* pinned host memory */
+template <class T>
+struct PinnedBuf : Owned<void*, hipHostFree> {
+    T* get() const { return static_cast<T*>(v); }
+    hipError_t alloc(size_t count) { return hipHostMalloc(&v, count * sizeof(T), hipHostMallocDefault); }
+};
+
+/* what airband_hip_set_mixers() wired up: replaced as a whole, an empty one is a handle without mixers */
+struct MixerWiring {
+    std::vector<int> pos;         /* connection index (order of airband_hip_set_mixers) -> position in the per-mixer grouped arrays */
+    std::vector<int> chan_host;   /* grouped external channel indices, for re-enabling an input */
+    std::vector<uint8_t> user_on; /* by position: airband_hip_mixer_enable_input()'s say; an input counts while this AND its dongle are on */
+    int n_mixers = 0;
+    int n_runs = 0;
+    DevBuf<int> d_chan, d_first, d_run_first, d_run_mixer, d_first_run;
+    DevBuf<float> d_run_left, d_run_right;
+    DevBuf<uint8_t> d_run_signal;
+    DevBuf<float> d_ml, d_mr, d_left, d_right;
+    DevBuf<uint8_t> d_stereo, d_signal;
+};
+
+}  // namespace airband
+
+struct airband_hip_handle {
+    airband::Plan plan;
+    uint32_t flags = 0;
+    int hip_device = 0;
+    airband::Stream stream;
+    airband::Stream side[3]; /* fused demod kinds run beside the CTCSS chain */
+    airband::Event fork_ev[4];
+    /* AIRBAND_HIP_FLAG_PIPELINE: stage 1 of batch k runs on `front` while stage 2 of batch k-1 runs on `stream` */
+    bool pipeline = false;
+    airband::Stream front;
+    airband::Event ev_in, ev_back, ev_wait, front_done[2];
+    hipStream_t last_stream = nullptr; /* stream the last sequential batch ran on (the caller's or ours; not owned) */
+    airband::Event ev_spec[2]; /* AFC on the matrix-core channelizer: the last hop's spectrum runs on a side stream beside stage 1 (fork, done) */
+    airband::Event ev_last;    /* recorded behind every batch that ran on a CALLER's stream: collect / read_* / synchronize / release
+                                  order themselves behind it (the caller's stream itself may be gone by then, our event is not) */
+    bool ev_last_pending = false;
+    int row0_front = 0;            /* ring row of the batch stage 1 writes next (== row0 when not pipelined) */
+    uint64_t front_batches = 0;    /* batches whose stage 1 has been enqueued */
+    /* per-stage GPU time: a pool of event sets (one per process call) harvested lazily, so that nobody has to
+     * synchronise inside a run to read timings */
+    static constexpr int EV_POOL = 16;
+    airband::Event evp[EV_POOL][5];   /* stage 1 begin / end, stage 2 begin, demod end, batch end */
+    uint8_t evp_state[EV_POOL] = {0}; /* bit 0: stage-1 pair recorded, bit 1: stage-2 pair recorded */
+    double t_sum[4] = {0, 0, 0, 0};
+    int64_t t_n[2] = {0, 0};          /* harvested stage-1 / stage-2 pairs */
+    float t_last[4] = {0, 0, 0, 0};
+    bool timings_valid = false;
+    std::string error;
+
+    /* geometry */
+    int B = 0, R = 0, N = 0;
+    int n_slots = 0;      /* demod slots: channels sorted by kind, every kind padded to whole 64-slot blocks */
+    std::vector<int> slot_to_ext, ext_to_slot;
+    int kind_first_block[AB_KIND_COUNT] = {0}, kind_n_blocks[AB_KIND_COUNT] = {0};
+    int64_t hop_bytes = 0, first_batch_bytes = 0, batch_bytes = 0, lookahead_bytes = 0;
+    int row0 = 0;
+    int wave_stride = 0;   /* floats between two channels' rows of d_out_wave */
+    uint64_t batches_done = 0;
+    bool results_ready = false;
+    uint64_t overruns = 0;
+
+    /* device memory */
+    airband::DevBuf<DevConst> d_dev;
+    airband::DevBuf<ChanConst> d_cc;
+    airband::DevBuf<ChanState> d_cs;
+    airband::DevBuf<int> d_slot_to_ext, d_ext_to_slot;
+    airband::DevBuf<uint8_t> d_block_kind;
+    airband::DevBuf<float> d_window, d_sin, d_cos, d_twiddle;
+    airband::DevBuf<float> d_window_dec; /* fft_size >= 1024: the window de-interleaved by sample index mod (fft_size / 512), for the decimated wavefront FFT (channelizer_fft.hip) */
+    airband::DevBuf<float> d_mag, d_sqbuf, d_ct_coeff, d_ct_q;
+    airband::DevBuf<float2> d_iq, d_iq_out, d_ct_af;
+    airband::DevBuf<unsigned long long> d_ct_mask;
+    int ct_first_block = 0, ct_n_blocks = 0, ct_pk_pitch = 0;
+    /* AIRBAND_HIP_FLAG_REGROUP: the batch's slot order (demod.hip, "regrouping") */
+    bool regroup = false;
+    int regroup_mode = 1;              /* 1: channels sorted inside lockstep workgroups; 2: line groups sorted, wavefronts free-running (demod.hip) */
+    airband::DevBuf<int> d_perm;       /* regroup mode 3: the batch's slot permutation (demod.hip, regroup_perm_kernel) */
+    airband::DevBuf<uint8_t> d_sq_key; /* split kinds: the front kernel's note for the back kernel (had audio in this batch) */
+    airband::DevBuf<uint8_t> d_trace;
+    airband::DevBuf<float> d_out_wave, d_out_iq;
+    airband::DevBuf<uint8_t> d_out_axc;
+    airband::DevBuf<airband_hip_channel_stats> d_stats;
+    airband::DevBuf<float> d_tmp_wavein, d_tmp_iqin, d_spectrum;
+    bool any_afc = false, afc_spectrum_valid = false; /* process_bins() has no spectrum: AFC is skipped there */
+    airband::DevBuf<uint8_t> d_tmp_trace;
+    int ct_stride = 0;
+    /* matrix-core channelizer */
+    bool use_f32 = false;          /* CF32 dongles on the float32 matrix pipe (channelizer_f32.hip) */
+    airband::DevBuf<float> d_ftab;
+    bool use_dft = false;
+    airband::DevBuf<int> d_item_dev, d_item_group, d_item_bset, d_item_private, d_item_home; /* d_item_bset: what stage 1 reads (the re-tune kernel switches AFC groups between their home and private tables) */
+    airband::DevBuf<int8_t> d_bfrag;
+    airband::DevBuf<double> d_bcorr;
+    airband::DevBuf<float> d_dft_partial; /* fft_size 8192: partial sums between the two passes of eight window pieces */
+    airband::DevBuf<int> d_bset_bin;      /* [n_bsets][8] bin each coefficient column pair is built for (AFC re-tunes private tables on the device) */
+    const void* last_iq = nullptr; /* input of the batch stage 1 ran last (AFC looks at its last hop once stage 2 has decided) */
+    size_t last_iq_stride = 0;
+    int last_n_hops = 0;
+
+    /* host-ring path: one PINNED circular buffer per dongle (row d of h_ring, ring_cap bytes).  submit() copies the caller's bytes
+     * straight into it -- the only CPU copy on the way -- and may be called for DIFFERENT dongles from several threads at once;
+     * process() ships a batch with (at most two, where the span wraps) strided DMA transfers on a copy stream into one of two
+     * device staging buffers while the kernels of the previous batch still read the other. */
+    airband::PinnedBuf<uint8_t> ring_mem;                  /* the rings' memory; everybody reads it through h_ring */
+    std::atomic<uint8_t*> h_ring{nullptr};                 /* published (release) by host_path_init() once ring_cap / stage_stride / the staging buffers exist; read (acquire) by submit() and process() */
+    int64_t ring_cap = 0;                                  /* bytes per dongle */
+    std::unique_ptr<std::atomic<uint64_t>[]> ring_wr;      /* per dongle: stream bytes accepted so far */
+    uint64_t ring_rd = 0;                                  /* stream position of the next batch (common to all dongles: they advance in lockstep) */
+    std::atomic<uint64_t> ring_free{0};                    /* stream position up to which the ring may be overwritten (lags ring_rd by the batch in flight) */
+    airband::DevBuf<uint8_t> d_stage2[2];
+    int64_t stage_stride = 0;
+    airband::Stream h2d;
+    airband::Event ev_h2d[2], ev_stage_read[2];
+    uint64_t host_batches = 0;
+    std::mutex host_init_lock;
+
+    /* dongles switched off with airband_hip_device_enable(): skipped by the availability rule and by both stages */
+    std::unique_ptr<std::atomic<uint8_t>[]> dev_enabled; /* (atomic: a feeder thread's submit() reads its dongle's flag while the demod thread switches it) */
+    int n_enabled = 0;
+    std::vector<ChanConst> cc_slots; /* host copy of d_cc (slot order): the VALID bit of a dongle's slots follows its enable state */
+
+    airband::MixerWiring mix;
+
+    /* the mixer exchange (airband_hip_comm_*): this handle's rank in an RCCL communicator over the GPUs that hold the other dongles */
+    ncclComm_t comm = nullptr;
+    airband::Event ev_peer; /* airband_hip_add_mixers: "src's batch is done" for dst's stream */
+
+    /* scan-mode devices (airband_hip_prepare_scan, scan_bank.h): nothing of this exists on a handle without scan lists */
+    std::vector<int> scan_of_dev;      /* device -> its list in plan.scan, -1 */
+    std::vector<int> scan_cur;         /* by list: the entry airband_hip_set_freq_index() put in force */
+    std::vector<int> scan_latch[2];    /* by list: the entry of front batch k, at [k & 1] (stage 2 of a pipelined batch runs during the next call) */
+    int scan_first_row[2] = {0, 0};    /* the ring rows stage 1 of front batch k produced: [first_row, first_row + n_rows) */
+    int scan_n_rows[2] = {0, 0};
+    std::vector<int> scan_held;        /* by list: the entry the slot holds once every exchange enqueued so far has run */
+    airband::DevBuf<ChanConst> d_bank_cc;
+    airband::DevBuf<ChanState> d_bank_cs;
+    airband::DevBuf<float> d_bank_sq;
+    airband::DevBuf<uint32_t> d_scan_mask; /* [AB_CS_DWORDS] ChanState masks, then [AB_CC_DWORDS] ChanConst masks */
+    airband::DevBuf<int> d_switch[2];      /* the batch's switch list (slot, entry parked, entry brought in), two in flight */
+    airband::PinnedBuf<int> h_switch[2];   /* pinned staging of the lists */
+    airband::Event ev_switch[2];
+    bool switch_used[2] = {false, false};
+    int switch_buf = 0;
+    airband::DevBuf<int> d_scan_mix_slots; /* slots of lists that mix AM and NFM entries (scan_mag_kernel) */
+    airband::DevBuf<ChanConst> d_fs_cc; /* airband_hip_freq_stats: one composed image, its stats row */
+    airband::DevBuf<ChanState> d_fs_cs;
+    airband::DevBuf<airband_hip_channel_stats> d_fs_stats;
+    airband::DevBuf<int> d_fs_zero;
+
+    /* synthetic dongles */
+    airband::DevBuf<int16_t> d_sin_tab;
+    airband::DevBuf<long long> d_carriers;
+    int n_carriers = 0, noise_q8 = 0;
+    int sig_n_plans = 1;            /* airband_hip_set_signal_plan_shift */
+    unsigned sig_shift_step = 0;
+};
