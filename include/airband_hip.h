@@ -357,6 +357,45 @@ int airband_hip_collect_mixers(airband_hip_handle* h, float* left, float* right,
 int airband_hip_device_results(airband_hip_handle* h, float** d_waveout, float** d_iq_out, uint8_t** d_axc, float** d_mix_left, float** d_mix_right,
                                uint8_t** d_mix_signal);
 
+/* ---- signal-gated collect ------------------------------------------------------------------------------------------------------------
+ * The reference's output thread does not consume every channel's batch: process_outputs() (src/output.cpp:456-559) skips a batch of a channel whose squelch is
+ * closed for every sink that is not `continuous` -- file and raw-file outputs (:501), UDP (:539), pulse (:552) -- and a quiet channel's row is zeros.  A handle
+ * with an output gate compacts the rows that will be consumed on the GPU, so that the host copies those instead of one row per channel.
+ * One gate byte per channel (device-major numbering as everywhere here):
+ *   AIRBAND_GATE_NEVER   never delivered (a channel whose only output is a mixer the GPU serves);
+ *   AIRBAND_GATE_SIGNAL  delivered in batch k iff axcindicate of batch k is not ' ' or axcindicate of batch k-1 was not ' ' (nothing before the first batch
+ *                        counts as ' '; AFC's '<' and '>' are signal).  The file-output rule: `continuous == false && axcindicate == NO_SIGNAL &&
+ *                        outputs[k].active == false` skips, and `active` is the last written batch's axcindicate != NO_SIGNAL (src/output.cpp:501,531) -- the one
+ *                        trailing batch carries the audio of a transmission that ended inside it;
+ *   AIRBAND_GATE_ALWAYS  delivered every batch (`continuous` sinks, anything that feeds an MP3 encoder).
+ * A channel of a dongle that is switched off (airband_hip_device_enable) is not delivered from the first batch the switch-off applies to, whatever its gate
+ * (disable_device_outputs()), and its memory of the batch before is cleared.  That memory is handle state the GPU advances once per batch behind stage 2, so the
+ * rule follows the batches in the order their results appear: on pipelined handles, with airband_hip_process_device, airband_hip_process_bins, scan lists
+ * and regrouped stage 2 alike.  A handle without a gate allocates nothing for this and launches nothing. */
+#define AIRBAND_GATE_NEVER 0
+#define AIRBAND_GATE_SIGNAL 1
+#define AIRBAND_GATE_ALWAYS 2
+
+/* gate[total_channels]; max_rows = capacity of the packed buffers (1 .. total_channels).  Before the first batch only (calling it again before then replaces the
+ * gate).  Validated before the device is touched: AIRBAND_HIP_EINVAL for NULL, a gate value above 2, max_rows out of range, a batch already enqueued;
+ * AIRBAND_HIP_ENOMEM when the buffers cannot be had -- the handle then runs on as it was. */
+int airband_hip_set_output_gate(airband_hip_handle* h, const uint8_t* gate, int64_t max_rows);
+
+/* The batch airband_hip_collect() would return, packed.  *n_active = channels the rule selected (may exceed max_rows: then only the first max_rows, in ascending
+ * channel order, were kept -- the caller's cue to fall back to airband_hip_collect_channels() for this batch).  With n = min(*n_active, max_rows):
+ *   channel_index [n]               the selected channels, ascending;
+ *   waveout       [n][wave_batch]   row i = channel channel_index[i]'s row of airband_hip_collect();
+ *   iq_out        [n][2*wave_batch] likewise (zeros on a handle without raw-I/Q outputs);
+ *   axc_all       [total_channels]  every channel's axcindicate.
+ * Arrays are sized for max_rows rows; nothing past row n is written.  Any pointer may be NULL.  Two small copies (the count, then the list) and one contiguous
+ * copy of n rows per array.  Marks the batch as collected; AIRBAND_HIP_EAGAIN as airband_hip_collect(), AIRBAND_HIP_EINVAL on a handle without a gate.
+ * airband_hip_collect() and airband_hip_collect_channels() keep returning every row on a gated handle. */
+int airband_hip_collect_active(airband_hip_handle* h, int64_t* n_active, int32_t* channel_index, float* waveout, float* iq_out, char* axc_all);
+
+/* Device-side views of the same (valid until the next process call) for consumers that stay on the GPU: d_index [max_rows], d_count [1], d_rows
+ * [max_rows][wave_batch], d_iq_rows [max_rows][2*wave_batch] or NULL on a handle without raw-I/Q outputs.  Any out-pointer may be NULL. */
+int airband_hip_device_active(airband_hip_handle* h, int32_t** d_index, int32_t** d_count, float** d_rows, float** d_iq_rows);
+
 /* Makes `stream` (a hipStream_t of a GPU-side consumer, e.g. the stream an RCCL all-reduce of the mixer sums is issued on)
  * wait for the results of the batch the last process call completed -- no host synchronisation.  The consumer hands its
  * stream to the next airband_hip_process_device() call, which then orders the overwrite of the result buffers behind it. */
@@ -410,7 +449,7 @@ int airband_hip_derive_constants(const airband_hip_config* cfg, int32_t channel_
 int airband_hip_dft_selftest(const airband_hip_config* cfg, int32_t windows, double* max_rel_err);
 
 /* Milliseconds the GPU spent on the last finished batch (HIP events on the streams the kernels run on):
- * [0] channelizer kernel, [1] demod kernels (+ per-kind emit), [2] joint emit / mixers, [3] their sum.  Waits for the
+ * [0] channelizer kernel, [1] demod kernels (+ per-kind emit), [2] joint emit / mixers (+ the output gate's select and gather), [3] their sum.  Waits for the
  * enqueued batches. */
 int airband_hip_last_timings(airband_hip_handle* h, float* ms4);
 

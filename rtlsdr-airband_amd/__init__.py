@@ -33,6 +33,7 @@ EXPORTS = [
     "airband_hip_batch_ready", "airband_hip_mixer_set_stereo", "airband_hip_comm_unique_id", "airband_hip_comm_init_rank", "airband_hip_comm_init_all",
     "airband_hip_comm_group_begin", "airband_hip_comm_group_end", "airband_hip_allreduce_mixers", "airband_hip_add_mixers", "airband_hip_comm_destroy", "airband_hip_clear_mixers", "airband_hip_set_signal_plan_shift", "airband_hip_regrouped",
     "airband_hip_prepare_scan", "airband_hip_set_freq_index", "airband_hip_freq_stats",
+    "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
 ]
 
 _lib = None
@@ -97,6 +98,9 @@ def load_library() -> C.CDLL:
     L.airband_hip_collect_channels.argtypes = [vp, i64, i64, vp, vp, vp, vp]
     L.airband_hip_read_bins_channels.argtypes = [vp, i64, i64, vp, vp]
     L.airband_hip_read_trace_channels.argtypes = [vp, i64, i64, vp]
+    L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
+    L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
+    L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
     L.airband_hip_device_results.argtypes = [vp] + [C.POINTER(vp)] * 6
     L.airband_hip_synchronize.argtypes = [vp]
@@ -214,6 +218,7 @@ class AirbandHip:
         self.B = g.wave_batch
         self.total_channels = g.total_channels
         self.n_mixers = 0
+        self.gate_rows = 0  # capacity of the packed buffers once set_output_gate() has run
 
     # ---- plumbing ------------------------------------------------------------------------------------
     def _check(self, rc: int):
@@ -273,6 +278,39 @@ class AirbandHip:
         if stats:
             out["stats"] = [{f[0]: getattr(s, f[0]) for f in capi.ChannelStats._fields_} for s in st]
         return out
+
+    def set_output_gate(self, gate, max_rows: Optional[int] = None):
+        """gate: one capi.GATE_NEVER / GATE_SIGNAL / GATE_ALWAYS byte per channel (device-major); max_rows: capacity of the packed buffers, default every
+        channel.  Before the first batch (airband_hip_set_output_gate)."""
+        gate = np.ascontiguousarray(gate, np.uint8)
+        if gate.shape != (self.total_channels,):
+            raise ValueError("gate needs one byte per channel (%d), got shape %r" % (self.total_channels, gate.shape))
+        rows = self.total_channels if max_rows is None else int(max_rows)
+        self._check(self.L.airband_hip_set_output_gate(self.h, gate.ctypes.data, rows))
+        self.gate_rows = rows
+
+    def collect_active(self, *, iq: bool = False) -> dict:
+        """The batch collect() would return, packed to the channels the gate selected (airband_hip_collect_active): n_active (may exceed the capacity: only
+        the first max_rows channels were kept then), channels [n] ascending, waveout [n][B], iq_out [n][2 B] (iq=True), axcindicate of every channel."""
+        rows, B = max(self.gate_rows, 1), self.B
+        n = C.c_int64(0)
+        idx = np.empty((rows,), np.int32)
+        wave = np.empty((rows, B), np.float32)
+        iqo = np.empty((rows, 2 * B), np.float32) if iq else None
+        axc = np.empty((self.total_channels,), np.uint8)
+        self._check(self.L.airband_hip_collect_active(self.h, C.byref(n), idx.ctypes.data, wave.ctypes.data, iqo.ctypes.data if iq else None, axc.ctypes.data))
+        kept = min(int(n.value), rows)
+        out = dict(n_active=int(n.value), channels=idx[:kept], waveout=wave[:kept], axcindicate=axc)
+        if iq:
+            out["iq_out"] = iqo[:kept]
+        return out
+
+    def device_active(self) -> dict:
+        """Device pointers of the packed results (valid until the next process call): index [max_rows] int32, count [1] int32, rows [max_rows][B] float32,
+        iq_rows [max_rows][2 B] float32 (0 on a handle without raw-I/Q outputs)."""
+        ptrs = [C.c_void_p() for _ in range(4)]
+        self._check(self.L.airband_hip_device_active(self.h, *[C.byref(p) for p in ptrs]))
+        return {k: (p.value or 0) for k, p in zip(["index", "count", "rows", "iq_rows"], ptrs)}
 
     def set_freq_index(self, dev: int, freq_idx: int):
         """Entry freq_idx of dongle dev's scan list is in force for every batch enqueued from now on (latched per batch)."""

@@ -37,6 +37,7 @@ HIP_SOURCES = {
     "channelizer_f32.hip": ["-O3"],
     "misc_kernels.hip": ["-O3", "-ffp-contract=off"],  # mixer sums: the reference's multiply-then-add, no FMA
     "demod.hip": ["-O3", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
+    "gate.hip": ["-O3"],  # signal-gated collect: integer passes and a row copy
     "airband_hip.cpp": ["-O2", "-x", "hip"],
 }
 HOST_SOURCES = {"params.cpp": ["-O2", "-ffp-contract=off", "-fno-fast-math"]}
@@ -113,6 +114,9 @@ def check_no_packed_f32(lib: str) -> int:
 
 
 def build(force: bool = False, verbose: bool = False) -> str:
+    sources = [os.path.join(CSRC, name) for name in list(HIP_SOURCES) + list(HOST_SOURCES)]
+    if not force and all(os.path.exists(s) for s in sources) and not any(_newer(s, LIB) for s in sources):
+        return LIB  # a checked library that is newer than everything it was built from: nothing to do, also where the object files did not come along
     os.makedirs(OBJ, exist_ok=True)
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     objs = []

@@ -377,7 +377,28 @@ MixArgs mix_args(const airband_hip_handle* h) {
     return ma;
 }
 
-/* stage 2 + emit (+ mixers) of the batch whose stage-1 rows are already in the rings */
+GateArgs gate_args(const airband_hip_handle* h) {
+    const OutputGate& g = h->gate;
+    GateArgs a;
+    a.gate = g.d_gate.p;
+    a.axc = h->d_out_axc.p;
+    a.prev = g.d_prev.p;
+    a.mask = g.d_mask.p;
+    a.block_count = g.d_block_count.p;
+    a.index = g.d_index.p;
+    a.count = g.d_count.p;
+    a.n_ch = h->plan.total_ch;
+    a.max_rows = g.max_rows;
+    a.out_wave = h->d_out_wave.p;
+    a.out_iq = h->d_out_iq.p;
+    a.rows = g.d_rows.p;
+    a.iq_rows = g.d_iq_rows.p;
+    a.wave_stride = h->wave_stride;
+    a.wave_batch = h->B;
+    return a;
+}
+
+/* stage 2 + emit (+ mixers, + the output gate) of the batch whose stage-1 rows are already in the rings */
 int run_back_half(airband_hip_handle* h, hipStream_t s) {
     const Event* ev = event_set(h, h->batches_done, 1);
     (void)hipEventRecord(ev[2], s);
@@ -442,6 +463,7 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
         launch_emit_iq(ea, s);
     }
     if (h->mix.n_mixers > 0) launch_mix(mix_args(h), s);
+    if (h->gate.max_rows > 0) launch_gate(gate_args(h), s); /* the batch's active channels and their rows, packed (gate.hip) */
     (void)hipEventRecord(ev[4], s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
@@ -1021,6 +1043,14 @@ int airband_hip_device_enable(airband_hip_handle* h, int32_t dev, int32_t enable
     }
     /* channel->axcindicate of a device that is not demodulated any more: NO_SIGNAL */
     if (!on) HIP_TRY(h, hipMemcpyAsync(h->d_out_axc.p + c0, blank.data(), (size_t)nc, hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
+    /* a gated handle delivers none of its rows while it is off (disable_device_outputs()); the select pass also clears the channels' "had signal in the batch before" */
+    std::vector<uint8_t> gate_bytes;
+    if (h->gate.max_rows > 0) {
+        gate_bytes.assign(h->gate.gate.begin() + c0, h->gate.gate.begin() + c0 + nc);
+        if (!on)
+            for (uint8_t& g : gate_bytes) g |= AB_GATE_OFF;
+        HIP_TRY(h, hipMemcpyAsync(h->gate.d_gate.p + c0, gate_bytes.data(), (size_t)nc, hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
+    }
     /* host-ring path: a dongle that comes back joins the others at the common stream position with an empty queue -- its write cursor is put there
      * BEFORE the dongle is published as enabled (release / acquire with submit()'s load): a feeder thread that sees it enabled never sees the stale cursor */
     if (on && h->ring_wr) h->ring_wr[dev].store(h->ring_rd, std::memory_order_release);
@@ -1348,6 +1378,80 @@ int airband_hip_collect(airband_hip_handle* h, float* waveout, float* iq_out, ch
 int airband_hip_collect_channels(airband_hip_handle* h, int64_t first_channel, int64_t n_channels, float* waveout, float* iq_out, char* axc,
                                  airband_hip_channel_stats* stats) {
     return collect_range(h, first_channel, n_channels, waveout, iq_out, axc, stats, false);
+}
+
+int airband_hip_set_output_gate(airband_hip_handle* h, const uint8_t* gate, int64_t max_rows) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!gate) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    const Plan& p = h->plan;
+    if (max_rows < 1 || max_rows > p.total_ch) return fail(h, AIRBAND_HIP_EINVAL, "max_rows must lie in 1 .. total_channels");
+    for (int c = 0; c < p.total_ch; c++)
+        if (gate[c] > AIRBAND_GATE_ALWAYS) return fail(h, AIRBAND_HIP_EINVAL, "gate byte of channel " + std::to_string(c) + " is not an AIRBAND_GATE_* value");
+    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the output gate is set before the first batch");
+    if (h->B % 4) return fail(h, AIRBAND_HIP_EBADSIZE, "the gather moves four samples per lane: WAVE_BATCH must be a multiple of four");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* built beside the handle and moved in whole: a failed allocation leaves the handle as it was */
+    OutputGate g;
+    g.gate.assign(gate, gate + p.total_ch);
+    std::vector<uint8_t> bytes(g.gate);
+    for (int c = 0; c < p.total_ch; c++)
+        if (!h->dev_enabled[p.cc[c].dev]) bytes[c] |= AB_GATE_OFF; /* dongles that are switched off already */
+    const size_t rows = (size_t)max_rows;
+    hipError_t e = upload(g.d_gate, bytes);
+    if (e == hipSuccess) e = g.d_prev.alloc_zeroed((size_t)p.total_ch);
+    if (e == hipSuccess) e = g.d_mask.alloc(((size_t)p.total_ch + 63) / 64);
+    if (e == hipSuccess) e = g.d_block_count.alloc((size_t)gate_blocks(p.total_ch));
+    if (e == hipSuccess) e = g.d_index.alloc(rows);
+    if (e == hipSuccess) e = g.d_count.alloc_zeroed(1);
+    if (e == hipSuccess) e = g.d_rows.alloc(rows * h->B);
+    if (e == hipSuccess && h->d_out_iq.p) e = g.d_iq_rows.alloc(rows * h->B * 2);
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); /* the failed allocation is this call's error, reported here: not the next launch's */
+        return fail(h, AIRBAND_HIP_ENOMEM, std::string("output gate buffers: ") + hipGetErrorString(e));
+    }
+    g.max_rows = (int)max_rows;
+    h->gate = std::move(g);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_active(airband_hip_handle* h, int64_t* n_active, int32_t* channel_index, float* waveout, float* iq_out, char* axc_all) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const OutputGate& g = h->gate;
+    if (g.max_rows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output gate (airband_hip_set_output_gate)");
+    if (!h->results_ready || h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    /* how many rows there are is on the device: the count first, then exactly those rows */
+    int count = 0;
+    HIP_TRY(h, hipMemcpyAsync(&count, g.d_count.p, sizeof(int), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (count < 0 || count > h->plan.total_ch) return fail(h, AIRBAND_HIP_ERUNTIME, "active count out of range: " + std::to_string(count));
+    const size_t n = (size_t)(count < g.max_rows ? count : g.max_rows), B = (size_t)h->B;
+    if (channel_index && n) HIP_TRY(h, hipMemcpyAsync(channel_index, g.d_index.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (waveout && n) HIP_TRY(h, hipMemcpyAsync(waveout, g.d_rows.p, n * B * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (iq_out && n) {
+        if (g.d_iq_rows.p)
+            HIP_TRY(h, hipMemcpyAsync(iq_out, g.d_iq_rows.p, n * B * 2 * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+        else
+            std::memset(iq_out, 0, n * B * 2 * sizeof(float));
+    }
+    if (axc_all) HIP_TRY(h, hipMemcpyAsync(axc_all, h->d_out_axc.p, (size_t)h->plan.total_ch, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (n_active) *n_active = count;
+    h->results_ready = false;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_device_active(airband_hip_handle* h, int32_t** d_index, int32_t** d_count, float** d_rows, float** d_iq_rows) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const OutputGate& g = h->gate;
+    if (g.max_rows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output gate (airband_hip_set_output_gate)");
+    if (d_index) *d_index = g.d_index.p;
+    if (d_count) *d_count = g.d_count.p;
+    if (d_rows) *d_rows = g.d_rows.p;
+    if (d_iq_rows) *d_iq_rows = g.d_iq_rows.p;
+    return AIRBAND_HIP_OK;
 }
 
 int airband_hip_collect_mixers(airband_hip_handle* h, float* left, float* right, uint8_t* has_signal) {

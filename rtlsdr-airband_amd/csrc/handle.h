@@ -97,6 +97,16 @@ struct MixerWiring {
     DevBuf<uint8_t> d_stereo, d_signal;
 };
 
+/* what airband_hip_set_output_gate() set up: replaced as a whole, one without max_rows is a handle without a gate (nothing allocated, nothing launched) */
+struct OutputGate {
+    int max_rows = 0;          /* capacity of the packed buffers; 0 = no gate */
+    std::vector<uint8_t> gate; /* the caller's bytes (the device copy also carries AB_GATE_OFF for the channels of dongles switched off) */
+    DevBuf<uint8_t> d_gate, d_prev;
+    DevBuf<unsigned long long> d_mask;
+    DevBuf<int> d_block_count, d_index, d_count;
+    DevBuf<float> d_rows, d_iq_rows;
+};
+
 }  // namespace airband
 
 struct airband_hip_handle {
@@ -201,6 +211,7 @@ struct airband_hip_handle {
     std::vector<ChanConst> cc_slots; /* host copy of d_cc (slot order): the VALID bit of a dongle's slots follows its enable state */
 
     airband::MixerWiring mix;
+    airband::OutputGate gate;
 
     /* the mixer exchange (airband_hip_comm_*): this handle's rank in an RCCL communicator over the GPUs that hold the other dongles */
     ncclComm_t comm = nullptr;

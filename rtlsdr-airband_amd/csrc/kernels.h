@@ -260,5 +260,25 @@ void launch_scan_exchange(const ScanExchangeArgs& a, hipStream_t stream);
 void launch_scan_compose(const ScanExchangeArgs& a, int slot, int e, ChanConst* out_cc, ChanState* out_cs, hipStream_t stream);
 void launch_scan_mag(const int* slots, int n, float* mag, const float2* iq, int first_row, int n_rows, int row0, int ring_rows, hipStream_t stream);
 
+/* signal-gated collect (gate.hip): the batch's active channels, ascending, and their rows packed */
+#define AB_GATE_OFF 0x80u /* in a device-side gate byte: the channel's dongle is switched off (airband_hip_device_enable) */
+struct GateArgs {
+    const uint8_t* gate;      /* [n_ch] AIRBAND_GATE_*, | AB_GATE_OFF */
+    const uint8_t* axc;       /* [n_ch] the batch's axcindicate */
+    uint8_t* prev;            /* [n_ch] the channel had signal in the batch before */
+    unsigned long long* mask; /* [ceil(n_ch / 64)] the verdicts, one bit per channel */
+    int* block_count;         /* [gate_blocks(n_ch)] */
+    int* index;               /* [max_rows] */
+    int* count;               /* [1] channels the rule selected (may exceed max_rows) */
+    int n_ch, max_rows;
+    const float* out_wave;    /* row starts (AB_OUT_PAD is skipped by the kernel) */
+    const float* out_iq;      /* [n_ch][2 * wave_batch], or null */
+    float* rows;              /* [max_rows][wave_batch] */
+    float* iq_rows;           /* [max_rows][2 * wave_batch], or null */
+    int wave_stride, wave_batch;
+};
+int gate_blocks(int n_ch);
+void launch_gate(const GateArgs& a, hipStream_t stream);
+
 }  // namespace airband
 #endif
