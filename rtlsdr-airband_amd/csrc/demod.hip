@@ -1170,6 +1170,9 @@ __global__ __launch_bounds__(256) AB_TONE_RESIDENCY void tone_kernel(DemodArgs a
      * standard tone set at 16 kHz), and 11 + 49 <= 64: where both banks fit the wavefront side by side -- slow tone i on lane i, fast tone i on lane n1 + i -- the
      * steady state runs ONE three-operation recurrence per sample for both detectors instead of two.  Both detectors run for the first 0.4 s of a transmission: a
      * third of the kernel's vector instructions on the BASELINE signal.  Otherwise (wave-uniform) lane i holds tone i of both banks as before. */
+    /* From build_plan, merged is always true: a bank holds the target's bin and at most one per standard tone, and the 51 standard tones fall on 11 distinct fast and 51 distinct
+     * slow bins at either wave rate, so n0 <= 12 and n1 <= 52, with n0 + n1 == 64 for a target far from the list (lane 63 then holds fast tone 11).
+     * tests/test_ctcss_sweep.py::test_bank_shapes_of_the_sweep asserts it; the `else` layouts below are unreachable from build_plan and kept as they were. */
     const bool merged = n0 + n1 <= 64;
     const int fi = merged ? lane - n1 : lane; /* the fast tone this lane holds, if any */
     const bool t0 = fi >= 0 && fi < n0, t1 = lane < n1;

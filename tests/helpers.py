@@ -415,3 +415,127 @@ def afc_format_case(pkg, sfmt, fft_log, sample_rate, wave_rate, plans, n_batches
             out["together"] += int((mv >= 2).sum())
             out["crossed"] += int(((mv >= 1) & (back[:, g:g + 8].sum(axis=1) >= 1)).sum())
     return out
+
+
+# ---- CTCSS at every tone, bank shape and wave rate -------------------------------------------------------------------------------------------------
+CTCSS_STANDARD_TONES = [67.0, 69.3, 71.9, 74.4, 77.0, 79.7, 82.5, 85.4, 88.5, 91.5, 94.8, 97.4, 100.0, 103.5, 107.2, 110.9, 114.8, 118.8, 123.0, 127.3, 131.8, 136.5,
+                        141.3, 146.2, 150.0, 151.4, 156.7, 159.8, 162.2, 165.5, 167.9, 171.3, 173.8, 177.3, 179.9, 183.5, 186.2, 189.9, 192.8, 196.6, 199.5, 203.5,
+                        206.5, 210.7, 218.1, 225.7, 229.1, 233.6, 241.8, 250.3, 254.1]  # src/ctcss.cpp:87-100
+# Off-list targets (the reference accepts any positive `ctcss`, src/config.cpp:565-590): far below and far above the list (no standard tone is left out of the
+# banks, and the target's own Goertzel bins are new ones), just outside it (nothing left out, but the fast bin is a standard tone's), and between two list tones
+# (both neighbours left out).  The bank sizes they lead to are read from the library (tests/test_ctcss_sweep.py), not assumed here.
+CTCSS_OFFLIST_TARGETS = [33.0, 60.0, 98.7, 260.0, 300.0]
+CTCSS_SWEEP_TARGETS = CTCSS_STANDARD_TONES + CTCSS_OFFLIST_TARGETS
+CTCSS_SWEEP_BATCHES = 16  # 2 s
+_ctcss_sweep_cache = {}
+
+
+def ctcss_fast_decoy(target, wave_rate):
+    """The standard tone nearest to `target` that the detector banks keep (5 Hz or more away, src/ctcss.cpp:105-122) and whose bin of the FAST window (0.05 s, 20 Hz
+    wide) is the target's: the fast detector cannot tell the two apart, the slow one (0.4 s, 2.5 Hz) can.  None where no standard tone qualifies.  The bin
+    arithmetic is the oracle's restatement of ToneDetector's (orc_tone_coeff, pinned to the reference by tests/test_oracle_vs_reference.py)."""
+    import pyoracle
+
+    L, win = pyoracle.lib(), int(wave_rate * 0.05)
+    own = L.orc_tone_coeff(target, float(wave_rate), win)
+    near = [s for s in CTCSS_STANDARD_TONES if abs(np.float32(target) - np.float32(s)) >= 5 and L.orc_tone_coeff(s, float(wave_rate), win) == own]
+    return min(near, key=lambda s: abs(s - target)) if near else None
+
+
+def ctcss_sweep_plan(wave_rate):
+    """The sweep's channels in order: [dict(target, sent, what, kind, notch, keys)].  Per target one channel for each of: the target itself, the next standard tone
+    above, the next one below (where they exist), no tone, and a `decoy` -- ctcss_fast_decoy(), or, where there is none, a transmission that starts with the
+    target's tone and changes to the nearest standard tone 5 Hz or more away after 0.17 s (`switch`): either way the fast detector finds the tone and the slow
+    one overrules it while the squelch is open.  kind: WAVE_RATE 16000 spreads the targets over "nfm" (NFM + CTCSS, the packed hand-off), "nfm_lp" (NFM + lowpass +
+    CTCSS) and "am" (AM + CTCSS, both the generic hand-off); WAVE_RATE 8000 has AM channels only.  Every third channel has a notch at its target.
+    keys: 1 = one transmission of 1 ... 1.5 s, 2 = two with a closed gap (never on the `target` and `decoy` channels, whose window counts the tests assert)."""
+    plan = []
+    for i, t in enumerate(CTCSS_SWEEP_TARGETS):
+        kind = ("nfm", "nfm_lp", "am")[i % 3] if wave_rate == 16000 else "am"
+        above = [s for s in CTCSS_STANDARD_TONES if s > t]
+        below = [s for s in CTCSS_STANDARD_TONES if s < t]
+        decoy = ctcss_fast_decoy(t, wave_rate)
+        sent = [("target", t)] + ([("above", min(above))] if above else []) + ([("below", max(below))] if below else []) + [("none", 0.0)]
+        sent.append(("decoy", decoy) if decoy is not None else ("switch", min((s for s in CTCSS_STANDARD_TONES if abs(s - t) >= 5), key=lambda s: abs(s - t))))
+        for k, (what, f) in enumerate(sent):
+            plan.append(dict(target=t, sent=f, what=what, kind=kind, notch=len(plan) % 3 == 0, keys=2 if what in ("above", "below", "none") and (i + k) % 3 == 0 else 1))
+    return plan
+
+
+def ctcss_sweep_case(wave_rate, seed=0, meta=False):
+    """(devices, B, n_batches, streams) in the shape of test_host_wave64.random_scenario: ctcss_sweep_plan()'s channels, eight to a dongle (the last one partly
+    filled), and made-up stage-1 output for them -- streams[d] = (wavein [C][n], iq [C][2 n]) -- so that everything behind it is bit-exact against
+    pyoracle.Oracle.run_bins.  meta=True: a fifth element, the plan entries per dongle.
+    Per channel, seeded: a quiet floor, then a transmission 20 ... 28 dB above it that starts at a sample offset which is no multiple of 50 (detector windows end
+    inside a step of the tone kernel) and lasts 1 ... 1.5 s -- the slow detector completes two or more windows, the fast -> slow hand-over of has_tone happens with
+    the squelch open -- or two shorter ones with a closed gap (the detectors' reset at the transition to CLOSED, the standing verdict of an idle batch).  The
+    sub-tone is a phase rotation exp(j beta sin 2 pi f t) on NFM channels (beta 1.5 ... 3) and amplitude modulation of the envelope on AM channels (depth
+    0.3 ... 0.5); a channel without one carries a steady audio tone beyond the far end of the banks (301.3 Hz; 21.3 Hz under the targets at the top) over next to no noise.  Frequencies are those of boundary_devices(): dm_dphi is 0, the derotation in front of the lowpass leaves the samples alone."""
+    key = (wave_rate, seed)
+    if key not in _ctcss_sweep_cache:
+        plan = ctcss_sweep_plan(wave_rate)
+        B, n_batches = wave_rate // 8, CTCSS_SWEEP_BATCHES
+        n = B * n_batches
+        t = np.arange(n) / wave_rate
+        devices, streams, metas = [], [], []
+        for d0 in range(0, len(plan), 8):
+            part = plan[d0:d0 + 8]
+            chans = []
+            wave = np.zeros((len(part), n), np.float32)
+            iq = np.zeros((len(part), 2 * n), np.float32)
+            for k, p in enumerate(part):
+                rng = np.random.default_rng([seed, wave_rate, d0 + k])
+                nfm = p["kind"] != "am"
+                chans.append(dict(frequency=sg.CENTERFREQ + 16000 * (k + 3), modulation=1 if nfm else 0, afc=0, squelch_threshold_dbfs=0, squelch_snr_threshold_db=-1.0,
+                                  notch_freq=p["target"] if p["notch"] else 0.0, notch_q=10.0 if p["notch"] else 0.0, ctcss_freq=p["target"],
+                                  bandwidth_hz=12500 if p["kind"] == "nfm_lp" else 0, ampfactor=1.0, tau_us=-1, has_iq_outputs=0))
+                floor = 0.2  # the squelch's noise floor comes down from 5.0 with a time constant of ~530 samples (src/squelch.cpp:477-490): it has settled by 0.35 s at either rate
+                level = floor * float(10.0 ** rng.uniform(1.0, 1.4))
+                env = np.full(n, floor)
+                start = int(rng.uniform(0.35, 0.45) * wave_rate)
+                start += 7 if start % 50 == 0 else 0
+                if p["keys"] == 1:
+                    spans = [(start, start + int(rng.uniform(1.0, 1.5) * wave_rate))]
+                else:
+                    on1, gap, on2 = int(rng.uniform(0.45, 0.6) * wave_rate), int(rng.uniform(0.15, 0.25) * wave_rate), int(rng.uniform(0.5, 0.6) * wave_rate)
+                    gap += 3 if (start + on1 + gap) % 50 == 0 else 0
+                    spans = [(start, start + on1), (start + on1 + gap, start + on1 + gap + on2)]
+                for a, b in spans:
+                    env[a:b] = level
+                f = np.full(n, p["sent"] if p["what"] != "switch" else p["target"], np.float64)
+                quiet = 1.0
+                carrier = 0.0
+                if p["what"] == "none":
+                    # no sub-tone.  A detector window that holds the start of a transmission holds a decaying offset (the AGC's / the DC block's settling, ~200 samples), and
+                    # under a target at the bottom of its banks that reads as the tone.  So these channels carry a steady audio tone next to the OTHER end of the banks
+                    # (its leakage into the nearest bank bin outweighs the offset's into the target's), next to no noise, and -- NFM -- a carrier a quarter of the wave rate
+                    # off, where the discriminator's mean is the value its DC block starts from (0.5)
+                    f[:] = 301.3 if p["target"] < 250.0 else 21.3
+                    quiet, carrier = 0.002, np.pi / 2
+                if p["what"] == "switch":
+                    f[start + int(0.17 * wave_rate):] = p["sent"]
+                arg = 2 * np.pi * np.cumsum(f) / wave_rate
+                if nfm:
+                    beta = float(rng.uniform(1.5, 3.0))
+                    ph = np.cumsum(rng.normal(0.0, 0.02 * quiet, n)) + beta * np.sin(arg) + carrier * np.arange(n)
+                    z = env * np.exp(1j * ph) + 0.3 * quiet * floor * (rng.standard_normal(n) + 1j * rng.standard_normal(n))
+                    re, im = z.real.astype(np.float32), z.imag.astype(np.float32)
+                    iq[k, 0::2], iq[k, 1::2] = re, im
+                    wave[k] = np.sqrt(re * re + im * im)  # float32 throughout: what stage 1 hands over (src/rtl_airband.cpp:484-487)
+                else:
+                    depth = float(rng.uniform(0.3, 0.5))
+                    wave[k] = np.abs(env * (1.0 + depth * np.sin(arg)) * (1.0 + 0.03 * quiet * rng.standard_normal(n))).astype(np.float32)
+            devices.append(dict(channels=chans))
+            streams.append((wave, iq))
+            metas.append(part)
+        _ctcss_sweep_cache[key] = (devices, B, n_batches, streams, metas)
+    out = _ctcss_sweep_cache[key]
+    return out if meta else out[:4]
+
+
+def ctcss_bank_shape(pkg, target, wave_rate):
+    """(n_tones_fast, n_tones_slow) of a channel with this CTCSS target, from the library's own host code (params.cpp::build_plan)."""
+    c = dict(frequency=sg.CENTERFREQ + 48000, modulation=0, afc=0, squelch_threshold_dbfs=0, squelch_snr_threshold_db=-1.0, notch_freq=0.0, notch_q=0.0, ctcss_freq=target,
+             bandwidth_hz=0, ampfactor=1.0, tau_us=-1, has_iq_outputs=0)
+    v = pkg.derive_constants([dict(channels=[c])], 0, wave_rate=wave_rate)
+    return int(v[11]), int(v[12])

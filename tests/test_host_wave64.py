@@ -154,9 +154,10 @@ def _fuzz_streams_ct(rng, chans, wave_rate, B, n_batches, dense=False):
     return wave, iq
 
 
-def random_scenario(seed, max_dev=9):
+def random_scenario(seed, max_dev=9, tones=(67.0, 100.0, 123.0, 254.1)):
     """(devices, wave_rate, fm_demod, B, n_batches, streams): a random plan over EVERY kind and made-up stage-1 output for it -- shared with the GPU twin
-    (tests/test_gpu_parity.py::test_random_plans_on_the_gpu), so a seed means the same scenario on the emulated and on the real wavefront."""
+    (tests/test_gpu_parity.py::test_random_plans_on_the_gpu), so a seed means the same scenario on the emulated and on the real wavefront.  tones: what the CTCSS targets are drawn from (the default's scenarios are those
+    of the recorded GPU campaign and stay what they are; tests/test_gpu_ctcss.py draws from the whole sweep list)."""
     rng = np.random.default_rng(5000 + seed)
     nfm_build = bool(seed % 4)
     wave_rate = 16000 if nfm_build else 8000
@@ -174,7 +175,7 @@ def random_scenario(seed, max_dev=9):
             if rng.random() < 0.3:
                 c["bandwidth_hz"] = int(rng.choice([5000, 6250, 12500, 25000]))  # on an AM channel too: raw I/Q on an AM lane (generic kind)
             if rng.random() < 0.4:
-                c["ctcss_freq"] = float(rng.choice([67.0, 100.0, 123.0, 254.1]))
+                c["ctcss_freq"] = float(rng.choice(list(tones)))
             mode = rng.random()
             if mode < 0.3:
                 c["squelch_threshold_dbfs"] = int(rng.integers(-60, -10))
