@@ -86,6 +86,17 @@ extern "C" {
                                                wavefronts are resident at once on a full chip (about 24 000 to   \
                                                50 000 dongles of eight channels on an MI355X), off otherwise.   */
 #define AIRBAND_HIP_FLAG_NO_REGROUP 0x40u   /* never regroup (slot order), whatever the handle's size          */
+#define AIRBAND_HIP_FLAG_WIDE_HOPS 0x80u    /* the matrix-core channelizer also takes u8 / s8 / CS16 handles   \
+                                               whose hop (sample_rate / WAVE_RATE samples) is longer than 1 024  \
+                                               bytes (CS16: 1 280) -- devices above ~4 MS/s, which otherwise run \
+                                               on the wavefront FFT.  It stages the window of every hop and      \
+                                               skips the bytes between windows (csrc/channelizer_dft_wide.hip).  \
+                                               Inside those limits, and on CF32 handles, the flag changes        \
+                                               nothing: same kernel, same launch, same bits.  Geometry           \
+                                               (airband_hip_get_geometry) and the alignment rule of              \
+                                               airband_hip_process_device() do not depend on it.                 \
+                                               AIRBAND_HIP_FLAG_FORCE_FFT wins.  Opt-in; see                     \
+                                               airband_hip_channelizer_reason().                                 */
 
 /* Per-channel configuration: the values a multichannel-mode `channels` entry carries after
  * parse_channels() (reference: src/config.cpp:306-726).  The library derives bin index, derotation
@@ -445,7 +456,8 @@ int airband_hip_derive_constants(const airband_hip_config* cfg, int32_t channel_
 /* Host-only check of the matrix-core channelizer's coefficient tables for `cfg` (needs no GPU): the value the kernel's integer digit
  * sums recombine to, on `windows` pseudo-random raw windows per (dongle, group of 8 channels), against the defining sum
  * X[bin] = sum_n lev[b_n] w[n] exp(-2 pi i bin n / N) (reference: src/rtl_airband.cpp:316-351,402-489) evaluated in double.
- * *max_rel_err = largest error / RMS of the exact values.  AIRBAND_HIP_EBADSIZE when `cfg` would run on the wavefront-FFT channelizer. */
+ * *max_rel_err = largest error / RMS of the exact values.  AIRBAND_HIP_EBADSIZE when `cfg` would run on the wavefront-FFT channelizer
+ * (cfg->flags is honoured: with AIRBAND_HIP_FLAG_WIDE_HOPS a wide-hop configuration is checked, without it it is refused). */
 int airband_hip_dft_selftest(const airband_hip_config* cfg, int32_t windows, double* max_rel_err);
 
 /* Milliseconds the GPU spent on the last finished batch (HIP events on the streams the kernels run on):
@@ -466,6 +478,16 @@ int airband_hip_regrouped(const airband_hip_handle* h);
 
 /* Name of the channelizer variant the handle selected ("fft_wave64" / "dft_mfma_i8"). */
 const char* airband_hip_channelizer_name(const airband_hip_handle* h);
+
+/* One line saying WHY the handle has the channelizer it has: "" when it is on a matrix-core kernel by the ordinary rule, else e.g.
+ * "hop 5000 bytes > 1280: AIRBAND_HIP_FLAG_WIDE_HOPS not set", "FORCE_FFT", "coefficient tables past their byte budget",
+ * "wide hops: fft 4096 staging does not fit LDS (... bytes > 163840)".  Valid as long as the handle is. */
+const char* airband_hip_channelizer_reason(const airband_hip_handle* h);
+
+/* Bytes of LDS per workgroup the wide-hop staging (AIRBAND_HIP_FLAG_WIDE_HOPS) needs for this shape -- two buffers of 16 rows of one window each plus the
+ * exchange area of the window pieces; it does not depend on the hop -- or -1 where the shape is not a wide one (hop inside the ordinary limits, an odd number of
+ * bytes, not whole CS16 samples; CF32).  Needs no GPU.  A handle takes the wide-hop kernel when this is at most 163 840 (a CU's 160 KiB). */
+int64_t airband_hip_wide_hop_lds_bytes(int32_t fft_size, int32_t hop_bytes, int32_t sample_format);
 
 /* Uploads the transmitter table of the synthetic dongles: carriers [n_carriers][12] int64 rows
  * (rtlsdr-airband_amd/siggen.py::Carrier.as_row), the Q8 noise multiplier and the 4096-entry int16 sine table. */

@@ -190,6 +190,11 @@ static bool same_class(const input_t* a, const input_t* b) {
            round((double)a->sample_rate / (double)WAVE_RATE) == round((double)b->sample_rate / (double)WAVE_RATE);
 }
 
+// Weak: a host that forwards only part of the interface to a library it loads at run time (the test harness of the drop-in) links without these two,
+// and the notice below is skipped there.  Linked against libairband_hip.so they are always present.
+extern "C" const char* airband_hip_channelizer_name(const airband_hip_handle* h) __attribute__((weak));
+extern "C" const char* airband_hip_channelizer_reason(const airband_hip_handle* h) __attribute__((weak));
+
 static void prepare_part(hip_part& k) {
     const int n = (int)k.devs.size();
     std::vector<std::vector<airband_hip_channel_cfg> > ch(n);
@@ -211,6 +216,7 @@ static void prepare_part(hip_part& k) {
     cfg.abi_version = AIRBAND_HIP_ABI_VERSION;
     cfg.fft_size_log = (int32_t)fft_size_log;
     cfg.wave_rate = WAVE_RATE;
+    cfg.flags = AIRBAND_HIP_FLAG_WIDE_HOPS;  // devices above ~4 MS/s (hops beyond 1 KiB) on the matrix-core channelizer as well; changes nothing for the others
 #ifdef NFM
     cfg.fm_demod = fm_demod == FM_QUADRI_DEMOD ? AIRBAND_FM_QUADRI_DEMOD : AIRBAND_FM_FAST_ATAN2;
 #endif
@@ -251,6 +257,11 @@ static void prepare_part(hip_part& k) {
         default:
             log(LOG_CRIT, "airband_hip: %s\n", airband_hip_last_error(NULL));
             error();
+    }
+    if (airband_hip_channelizer_name && airband_hip_channelizer_reason && strcmp(airband_hip_channelizer_name(k.h), "fft_wave64") == 0) {  // the slow path: say once why this handle is on it
+        static bool said = false;
+        if (!said) log(LOG_NOTICE, "airband_hip: GPU %d runs the wavefront-FFT channelizer: %s\n", k.gpu, airband_hip_channelizer_reason(k.h));
+        said = true;
     }
     airband_hip_get_geometry(k.h, &k.g);
     k.wave.resize((size_t)k.g.total_channels * k.g.wave_batch);

@@ -34,6 +34,7 @@ EXPORTS = [
     "airband_hip_comm_group_begin", "airband_hip_comm_group_end", "airband_hip_allreduce_mixers", "airband_hip_add_mixers", "airband_hip_comm_destroy", "airband_hip_clear_mixers", "airband_hip_set_signal_plan_shift", "airband_hip_regrouped",
     "airband_hip_prepare_scan", "airband_hip_set_freq_index", "airband_hip_freq_stats",
     "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
+    "airband_hip_channelizer_reason", "airband_hip_wide_hop_lds_bytes",
 ]
 
 _lib = None
@@ -112,6 +113,10 @@ def load_library() -> C.CDLL:
     L.airband_hip_last_timings.argtypes = [vp, C.POINTER(C.c_float)]
     L.airband_hip_channelizer_name.argtypes = [vp]
     L.airband_hip_channelizer_name.restype = C.c_char_p
+    L.airband_hip_channelizer_reason.argtypes = [vp]
+    L.airband_hip_channelizer_reason.restype = C.c_char_p
+    L.airband_hip_wide_hop_lds_bytes.argtypes = [i32, i32, i32]
+    L.airband_hip_wide_hop_lds_bytes.restype = i64
     L.airband_hip_set_signal_plan.argtypes = [vp, vp, i32, i32, vp]
     L.airband_hip_generate_iq.argtypes = [vp, vp, sz, u64, sz, u64, i32, vp]
     L.airband_hip_set_signal_plan_shift.argtypes = [vp, i32, C.c_uint32]
@@ -153,15 +158,21 @@ def derive_constants(devices: Sequence[dict], channel_index: int, *, wave_rate: 
     return list(v)
 
 
-def dft_selftest(devices: Sequence[dict], *, wave_rate: int, fft_log: int = 9, windows: int = 2) -> float:
-    """Largest relative error of the matrix-core channelizer's coefficient tables for this configuration (host arithmetic, no GPU)."""
+def dft_selftest(devices: Sequence[dict], *, wave_rate: int, fft_log: int = 9, windows: int = 2, flags: int = 0) -> float:
+    """Largest relative error of the matrix-core channelizer's coefficient tables for this configuration (host arithmetic, no GPU).
+    flags: capi.FLAG_WIDE_HOPS admits hops beyond the ordinary limits, as it does for a handle."""
     L = load_library()
-    cfg, keep = make_config(devices, wave_rate=wave_rate, fft_log=fft_log)
+    cfg, keep = make_config(devices, wave_rate=wave_rate, fft_log=fft_log, flags=flags)
     err = C.c_double(0.0)
     rc = L.airband_hip_dft_selftest(C.byref(cfg), windows, C.byref(err))
     if rc != 0:
         raise AirbandError(rc, (L.airband_hip_last_error(None) or b"").decode())
     return float(err.value)
+
+
+def wide_hop_lds_bytes(fft_size: int, hop_bytes: int, sfmt: int) -> int:
+    """LDS per workgroup of the wide-hop staging (capi.FLAG_WIDE_HOPS) for this shape, -1 where the shape is not a wide one (no GPU needed)."""
+    return int(load_library().airband_hip_wide_hop_lds_bytes(fft_size, hop_bytes, sfmt))
 
 
 def make_scan(scan: Optional[dict]):
@@ -371,6 +382,10 @@ class AirbandHip:
 
     def channelizer_name(self) -> str:
         return self.L.airband_hip_channelizer_name(self.h).decode()
+
+    def channelizer_reason(self) -> str:
+        """Why the handle has the channelizer it has; "" on a matrix-core kernel by the ordinary rule."""
+        return (self.L.airband_hip_channelizer_reason(self.h) or b"").decode()
 
     def build_info(self) -> str:
         return self.L.airband_hip_build_info().decode()

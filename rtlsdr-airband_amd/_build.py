@@ -34,6 +34,7 @@ DEVICE_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 HIP_SOURCES = {
     "channelizer_fft.hip": ["-O3"],
     "channelizer_dft.hip": ["-O3"],
+    "channelizer_dft_wide.hip": ["-O3"],  # the same contraction for hops beyond the contiguous staging (AIRBAND_HIP_FLAG_WIDE_HOPS)
     "channelizer_f32.hip": ["-O3"],
     "misc_kernels.hip": ["-O3", "-ffp-contract=off"],  # mixer sums: the reference's multiply-then-add, no FMA
     "demod.hip": ["-O3", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],

@@ -246,9 +246,15 @@ DftArgs dft_args(const airband_hip_handle* h, const void* d_iq, size_t stride_by
     const int np_total = p.fft_size > 512 ? p.fft_size / 512 : 1, np = np_total > 8 ? 8 : np_total;
     const int win_bytes = 2 * p.fft_size * p.dev[0].bytes_per_sample / np_total * np;
     a.partial = reinterpret_cast<float4*>(h->d_dft_partial.p);
-    a.lds_per_buf = dft_lds_per_buf((int)h->hop_bytes, win_bytes, np);
-    a.nbuf = dft_nbuf((int)h->hop_bytes, win_bytes, np);
-    a.sub = dft_sub((int)h->hop_bytes, win_bytes, np);
+    if (h->use_wide) { /* channelizer_dft_wide.hip: a staging step is one tile of 16 rows, two buffers */
+        a.lds_per_buf = dft_wide_lds_per_buf(win_bytes);
+        a.nbuf = 2;
+        a.sub = 1;
+    } else {
+        a.lds_per_buf = dft_lds_per_buf((int)h->hop_bytes, win_bytes, np);
+        a.nbuf = dft_nbuf((int)h->hop_bytes, win_bytes, np);
+        a.sub = dft_sub((int)h->hop_bytes, win_bytes, np);
+    }
     /* Pipelined handles (stage 1 of this batch runs beside stage 2 of the batch before): eight channelizer wavefronts of ~250 registers ARE a CU's register file, and
      * stage-2 wavefronts then only get onto a CU when one of them retires.  Held to FIVE per CU (it loses ~5 % alone: 7 and 6 per CU cost nothing, 4 cost 12 %,
      * profiles/r06_occupancy/) the channelizer leaves three SIMDs a wavefront's worth of registers each: configs[2] 14.05 ms sequential, 13.77 pipelined as before,
@@ -796,16 +802,40 @@ int prep_channelizer(airband_hip_handle* h) {
     const Plan& p = h->plan;
     /* AFC moves bins at run time and needs the full spectrum of each batch's last hop: that is the FFT kernel's job */
     if (h->any_afc) HIP_TRY(PREPARING, h->d_spectrum.alloc((size_t)p.n_dev * p.fft_size * 2), AIRBAND_HIP_ENOMEM);
-    h->use_dft = !(h->flags & AIRBAND_HIP_FLAG_FORCE_FFT) && dft_supported(p.fft_size, (int)h->hop_bytes, p.dev[0].sfmt, p.max_ch);
+    const bool force_fft = (h->flags & AIRBAND_HIP_FLAG_FORCE_FFT) != 0;
+    const int sfmt = p.dev[0].sfmt, hop_b = (int)h->hop_bytes;
+    h->use_dft = !force_fft && dft_supported(p.fft_size, hop_b, sfmt, p.max_ch);
+    h->use_wide = false;
+    h->chan_reason = force_fft ? "FORCE_FFT" : "";
+    /* Hops beyond the contiguous staging of channelizer_dft.hip (u8 / s8 above 1 024 bytes, CS16 above 1 280): the row staging of channelizer_dft_wide.hip,
+     * for handles that ask for it and wherever its two buffers fit a CU's LDS (which depends on the window alone) -- else the wavefront FFT, and the handle says why */
+    const int wide_lds = force_fft || h->use_dft ? -1 : dft_wide_lds(p.fft_size, hop_b, sfmt);
+    if (wide_lds >= 0) {
+        const int limit = sfmt == AIRBAND_SFMT_S16 ? 1280 : 1024;
+        if (!(h->flags & AIRBAND_HIP_FLAG_WIDE_HOPS))
+            h->chan_reason = "hop " + std::to_string(hop_b) + " bytes > " + std::to_string(limit) + ": AIRBAND_HIP_FLAG_WIDE_HOPS not set";
+        else if (wide_lds > AB_DFT_WIDE_LDS_MAX)
+            h->chan_reason = "wide hops: fft " + std::to_string(p.fft_size) + " staging does not fit LDS (" + std::to_string(wide_lds) + " bytes > " + std::to_string(AB_DFT_WIDE_LDS_MAX) + ")";
+        else
+            h->use_dft = h->use_wide = true;
+    }
     if (h->use_dft) {
         const int rc = prep_dft_tables(h);
         if (rc != AIRBAND_HIP_OK) return rc;
+        if (!h->use_dft) { /* cleared: the tables are past their budget */
+            h->use_wide = false;
+            h->chan_reason = "coefficient tables past their byte budget";
+        }
     }
-    h->use_f32 = !h->use_dft && !(h->flags & AIRBAND_HIP_FLAG_FORCE_FFT) && f32_supported(p.fft_size, p.dev[0].hop_samples, p.dev[0].sfmt);
+    h->use_f32 = !h->use_dft && !force_fft && f32_supported(p.fft_size, p.dev[0].hop_samples, sfmt);
     if (h->use_f32) {
         const int rc = prep_f32_tables(h);
         if (rc != AIRBAND_HIP_OK) return rc;
+        if (!h->use_f32) h->chan_reason = "coefficient tables past their byte budget";
     }
+    if (!h->use_dft && !h->use_f32 && h->chan_reason.empty()) /* no matrix-core kernel takes the shape at all */
+        h->chan_reason = sfmt == AIRBAND_SFMT_F32 ? "CF32 shape outside the float matrix-core channelizer's limits"
+                                                  : "hop " + std::to_string(hop_b) + " bytes, fft " + std::to_string(p.fft_size) + ": outside the matrix-core channelizer's shapes";
     if (!h->use_dft && !h->use_f32) {
         const size_t lds = fft_lds_bytes(p.fft_log, p.dev[0].hop_samples, p.dev[0].bytes_per_sample);
         if (lds > 160 * 1024) /* e.g. F32 at 20 MS/s: a 16-hop tile of raw samples does not fit a CU's LDS */
@@ -872,7 +902,9 @@ int airband_hip_dft_selftest(const airband_hip_config* cfg, int32_t windows, dou
         *max_rel_err = f32_table_selftest(plan, windows < 1 ? 1 : windows);
         return AIRBAND_HIP_OK;
     }
-    if (!plan.uniform_hop || !dft_supported(plan.fft_size, hop_bytes, plan.dev[0].sfmt, plan.max_ch))
+    const int wide_lds = (cfg->flags & AIRBAND_HIP_FLAG_WIDE_HOPS) ? dft_wide_lds(plan.fft_size, hop_bytes, plan.dev[0].sfmt) : -1; /* the tables do not depend on the hop */
+    const bool wide = wide_lds >= 0 && wide_lds <= AB_DFT_WIDE_LDS_MAX;
+    if (!plan.uniform_hop || !(wide || dft_supported(plan.fft_size, hop_bytes, plan.dev[0].sfmt, plan.max_ch)))
         return fail(nullptr, AIRBAND_HIP_EBADSIZE, "configuration does not take the matrix-core channelizer");
     build_dft_tables(plan);
     *max_rel_err = dft_table_selftest(plan, windows < 1 ? 1 : windows);
@@ -1126,6 +1158,7 @@ static int launch_front(airband_hip_handle* h, const void* d_iq, size_t stride_b
     }
     (void)hipEventRecord(ev[0], s);
     if (h->use_f32) launch_channelizer_f32(f32_args(h, d_iq, stride_bytes, r), s);
+    else if (h->use_wide) launch_channelizer_dft_wide(dft_args(h, d_iq, stride_bytes, r), s);
     else if (h->use_dft) launch_channelizer_dft(dft_args(h, d_iq, stride_bytes, r), s);
     else launch_channelizer_fft(fft_args(h, d_iq, stride_bytes, h->row0_front, r, 0), s);
     const hipError_t launch_err = hipGetLastError(); /* right behind the launch: the event record below would mask it (or be blamed for it) */
@@ -1562,6 +1595,10 @@ int airband_hip_regrouped(const airband_hip_handle* h) { return (h && h->regroup
 const char* airband_hip_channelizer_name(const airband_hip_handle* h) {
     return (h && h->use_dft) ? "dft_mfma_i8" : (h && h->use_f32) ? "dft_mfma_f32" : "fft_wave64";
 }
+
+const char* airband_hip_channelizer_reason(const airband_hip_handle* h) { return h ? h->chan_reason.c_str() : ""; }
+
+int64_t airband_hip_wide_hop_lds_bytes(int32_t fft_size, int32_t hop_bytes, int32_t sample_format) { return dft_wide_lds(fft_size, hop_bytes, sample_format); }
 
 int airband_hip_set_signal_plan(airband_hip_handle* h, const int64_t* carriers, int32_t n_carriers, int32_t noise_q8, const int16_t* sin_table4096) {
     if (!h || !carriers || !sin_table4096 || n_carriers < 1 || n_carriers > 16) return fail(h, AIRBAND_HIP_EINVAL, "bad signal plan (1..16 carriers)");

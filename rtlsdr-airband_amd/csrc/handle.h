@@ -179,6 +179,8 @@ struct airband_hip_handle {
     bool use_f32 = false;          /* CF32 dongles on the float32 matrix pipe (channelizer_f32.hip) */
     airband::DevBuf<float> d_ftab;
     bool use_dft = false;
+    bool use_wide = false;         /* use_dft, staged by channelizer_dft_wide.hip (AIRBAND_HIP_FLAG_WIDE_HOPS and a hop beyond dft_supported()'s limits) */
+    std::string chan_reason;       /* airband_hip_channelizer_reason(): set on every branch of prep_channelizer() */
     airband::DevBuf<int> d_item_dev, d_item_group, d_item_bset, d_item_private, d_item_home; /* d_item_bset: what stage 1 reads (the re-tune kernel switches AFC groups between their home and private tables) */
     airband::DevBuf<int8_t> d_bfrag;
     airband::DevBuf<double> d_bcorr;

@@ -179,6 +179,18 @@ int dft_sub(int hop_bytes, int win_bytes, int np);
 int dft_nbuf(int hop_bytes, int win_bytes, int np);
 int dft_partial_tiles(int n_hops_max); /* 16-hop tiles a work item may touch in one launch (sizes DftArgs::partial) */
 void launch_channelizer_dft(const DftArgs& a, hipStream_t stream);
+/* wide hops (channelizer_dft_wide.hip, AIRBAND_HIP_FLAG_WIDE_HOPS): a tile is staged as 16 rows of one window each.  The geometry, shared by the kernel (as
+ * constant expressions) and the host: win_all = bytes of a whole window, np = its pieces of 512 samples.  Row pitch = window + 16 (an odd number of 16-byte
+ * bank columns, and room for the up-to-15 bytes in front of an unaligned row), a buffer = 16 rows in whole 1 KiB transfers, two buffers + the exchange area of
+ * the window pieces' partial sums. */
+constexpr int dft_wide_pitch(int win_all) { return win_all + 16; }
+constexpr int dft_wide_lds_per_buf(int win_all) { return (16 * dft_wide_pitch(win_all) + 1023) / 1024 * 1024; }
+constexpr int dft_wide_lds_bytes(int win_all, int np) { return 2 * dft_wide_lds_per_buf(win_all) + (np > 1 ? 2 * (np - 1) * 64 * 16 : 0); }
+/* dynamic LDS of the wide-hop kernel for this shape, or -1 where the shape is not its business (hops inside dft_supported()'s limits, odd hops, CF32);
+ * the handle takes the kernel when this is at most AB_DFT_WIDE_LDS_MAX */
+#define AB_DFT_WIDE_LDS_MAX (160 * 1024)
+int dft_wide_lds(int fft_size, int hop_bytes, int sfmt);
+void launch_channelizer_dft_wide(const DftArgs& a, hipStream_t stream);
 /* side: 3 extra streams, ev: 4 events (fork + 3 joins); both may be null -> everything on `stream`, one kind after the other */
 void launch_demod(const DemodArgs& a, const int* kind_first_block, const int* kind_n_blocks, hipStream_t stream, hipStream_t* side, hipEvent_t* ev);
 /* waves per workgroup = pieces the contraction index (2 fft_size values) is cut into: four up to fft_size 512 (64 / 32 resident B registers per wave), eight for 1024 and 2048
