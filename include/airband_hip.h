@@ -68,6 +68,9 @@ extern "C" {
                                                HBM-bound, the demod kernels are not).  Results lag one batch: \
                                                the first call produces none, airband_hip_flush() drains the   \
                                                last.  Same values, bit for bit, as the sequential mode.       \
+                                               Since NULL-stream batches run ahead by default (see             \
+                                               airband_hip_process_device) the flag adds nothing on the GPU:   \
+                                               it moves the enqueueing of stage 2 into the next call.          \
                                                Ignored when a channel has AFC (stage 1 of the next batch needs \
                                                stage 2's verdict, src/rtl_airband.cpp:222-251).               */
 #define AIRBAND_HIP_FLAG_REGROUP 0x20u      /* stage 2 re-sorts its channels at every batch boundary so that   \
@@ -334,7 +337,15 @@ int airband_hip_batch_ready(airband_hip_handle* h);
  * 600 -> 8; 2.0 MS/s: 250 bytes -> 2, i.e. whole I/Q samples) -- batch offsets, being multiples of the hop, keep that alignment -- and the
  * channelizer then stages aligned pieces from the aligned byte at or in front of the span, i.e. it may READ up to 15 bytes in front of d_iq + d*stride_bytes
  * (bytes of the same allocation: the tail of the previous batch, or of the previous dongle's row).  AIRBAND_HIP_EINVAL otherwise.
- * `stream` is a hipStream_t (NULL = the handle's own stream). */
+ * `stream` is a hipStream_t (NULL = the handle's own stream).
+ * Schedule.  With a caller's stream the whole batch is enqueued on it, stage 1 then stage 2.  With NULL, on a handle without AFC channels and scan lists (and without
+ * AIRBAND_HIP_FLAG_PIPELINE), stage 1 runs on a stream of its own and stage 2 of the SAME batch on the handle's stream behind it, both enqueued by this call: the
+ * batch's results are complete in the handle's stream order as ever (airband_hip_collect, airband_hip_synchronize, airband_hip_stream_wait_results are unchanged), and
+ * a caller that enqueues the next batch without waiting for this one gets its stage 1 beside this batch's stage 2 -- stage 1 waits only for the stage 1 before it and
+ * for stage 2 of the batch two back, whose ring rows it overwrites.  The input of such a batch must be ready when the call is made, or be produced by work the
+ * handle itself enqueued (airband_hip_generate_iq with a NULL stream): stage 1 does not wait for a caller's other streams.  Such handles hold rings two batches deep
+ * (one more batch of stage-1 output: 12 bytes x channels x WAVE_BATCH) and keep the channelizer to five wavefronts per CU.  AIRBAND_HIP_RUN_AHEAD=0 in the
+ * environment at prepare time gives the single-stream schedule with one-batch rings instead (A/B measurements); see airband_hip_schedule_info(). */
 int airband_hip_process_device(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, void* stream);
 
 /* Waits for the oldest un-collected batch and copies its results to HOST memory.  Any pointer may be
@@ -475,6 +486,13 @@ const char* airband_hip_build_info(void);
 
 /* 1 if stage 2 of this handle re-sorts its channels at batch boundaries (AIRBAND_HIP_FLAG_REGROUP, AIRBAND_HIP_REGROUP=1 in the environment, or the library's own choice by residency), else 0. */
 int airband_hip_regrouped(const airband_hip_handle* h);
+
+/* How the handle schedules a batch.  *run_ahead: 1 if NULL-stream airband_hip_process_device() batches put stage 1 on a stream of its own (the default where
+ * the handle qualifies; 0 with AFC channels, scan lists, AIRBAND_HIP_FLAG_PIPELINE, or AIRBAND_HIP_RUN_AHEAD=0 in the environment at prepare time).  *ring_batches:
+ * depth of the stage-1 rings in batches (2 on run-ahead and pipelined handles, else 1).  *channelizer_waves_per_cu: 5 where the matrix-core channelizer is held to
+ * five wavefronts per CU to leave stage 2 register room beside it, 0 where it is not held.  *batches_run_ahead: how many batches so far took the run-ahead path
+ * (a caller's stream, airband_hip_process and airband_hip_process_bins do not).  Any out-pointer may be NULL. */
+int airband_hip_schedule_info(const airband_hip_handle* h, int32_t* run_ahead, int32_t* ring_batches, int32_t* channelizer_waves_per_cu, int64_t* batches_run_ahead);
 
 /* Name of the channelizer variant the handle selected ("fft_wave64" / "dft_mfma_i8"). */
 const char* airband_hip_channelizer_name(const airband_hip_handle* h);

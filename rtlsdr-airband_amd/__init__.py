@@ -34,7 +34,7 @@ EXPORTS = [
     "airband_hip_comm_group_begin", "airband_hip_comm_group_end", "airband_hip_allreduce_mixers", "airband_hip_add_mixers", "airband_hip_comm_destroy", "airband_hip_clear_mixers", "airband_hip_set_signal_plan_shift", "airband_hip_regrouped",
     "airband_hip_prepare_scan", "airband_hip_set_freq_index", "airband_hip_freq_stats",
     "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
-    "airband_hip_channelizer_reason", "airband_hip_wide_hop_lds_bytes",
+    "airband_hip_channelizer_reason", "airband_hip_wide_hop_lds_bytes", "airband_hip_schedule_info",
 ]
 
 _lib = None
@@ -121,6 +121,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_generate_iq.argtypes = [vp, vp, sz, u64, sz, u64, i32, vp]
     L.airband_hip_set_signal_plan_shift.argtypes = [vp, i32, C.c_uint32]
     L.airband_hip_regrouped.argtypes = [vp]
+    L.airband_hip_schedule_info.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
     L.airband_hip_dft_selftest.argtypes = [C.POINTER(capi.Config), i32, C.POINTER(C.c_double)]
     L.airband_hip_build_info.argtypes = []
     L.airband_hip_build_info.restype = C.c_char_p
@@ -386,6 +387,13 @@ class AirbandHip:
     def channelizer_reason(self) -> str:
         """Why the handle has the channelizer it has; "" on a matrix-core kernel by the ordinary rule."""
         return (self.L.airband_hip_channelizer_reason(self.h) or b"").decode()
+
+    def schedule_info(self) -> dict:
+        """run_ahead (NULL-stream process_device batches put stage 1 on its own stream), ring_batches (depth of the stage-1 rings), channelizer_waves_per_cu (5 where
+        the channelizer is held, 0 where not), batches_run_ahead (how many batches took that path so far): airband_hip_schedule_info."""
+        a, b, c, n = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        self._check(self.L.airband_hip_schedule_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
+        return dict(run_ahead=bool(a.value), ring_batches=int(b.value), channelizer_waves_per_cu=int(c.value), batches_run_ahead=int(n.value))
 
     def build_info(self) -> str:
         return self.L.airband_hip_build_info().decode()

@@ -157,6 +157,9 @@ struct FrontRows {
     int first_row, n_hops;
 };
 
+/* stage 1 of the next batch may be written while stage 2 still reads this one: rings two batches deep, a front stream, the channelizer held to five wavefronts per CU */
+bool deep_rings(const airband_hip_handle* h) { return h->pipeline || h->run_ahead; }
+
 /* the first batch also produces the AGC_EXTRA lead-in hops (waveend starts at 0, src/config.cpp:805) */
 FrontRows front_rows(const airband_hip_handle* h) {
     const bool first = h->front_batches == 0;
@@ -255,12 +258,12 @@ DftArgs dft_args(const airband_hip_handle* h, const void* d_iq, size_t stride_by
         a.nbuf = dft_nbuf((int)h->hop_bytes, win_bytes, np);
         a.sub = dft_sub((int)h->hop_bytes, win_bytes, np);
     }
-    /* Pipelined handles (stage 1 of this batch runs beside stage 2 of the batch before): eight channelizer wavefronts of ~250 registers ARE a CU's register file, and
+    /* Pipelined and run-ahead handles (stage 1 of this batch runs beside stage 2 of the batch before): eight channelizer wavefronts of ~250 registers ARE a CU's register file, and
      * stage-2 wavefronts then only get onto a CU when one of them retires.  Held to FIVE per CU (it loses ~5 % alone: 7 and 6 per CU cost nothing, 4 cost 12 %,
      * profiles/r06_occupancy/) the channelizer leaves three SIMDs a wavefront's worth of registers each: configs[2] 14.05 ms sequential, 13.77 pipelined as before,
      * 13.05 like this (13.5 / 14.0 at 4 / 6 per CU; profiles/r06_pipelined/).  The LDS it asks for and never touches is what holds it there. */
     a.extra_lds = 0;
-    if (h->pipeline && np_total == 1) {
+    if (deep_rings(h) && np_total == 1) {
         const int used = a.nbuf * a.lds_per_buf, want = 28 * 1024; /* 160 KiB / 28 KiB = 5 */
         if (used < want) a.extra_lds = want - used;
     }
@@ -475,6 +478,8 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
     if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
     /* rotate the rings: this batch's last AGC_EXTRA rows become the next batch's carry */
     h->row0 = (h->row0 + h->B) % h->R;
+    /* run-ahead: everything of this batch that reads the rings (the raw-I/Q emit and the mixer sums included) lies in front of this mark */
+    if (h->run_ahead && s == h->stream) (void)hipEventRecord(h->back_done[h->batches_done & 1], s);
     h->batches_done++;
     if (h->results_ready) h->overruns++; /* like dev->output_overrun_count (src/rtl_airband.cpp:649-654) */
     h->results_ready = true;
@@ -501,11 +506,13 @@ int prep_streams(airband_hip_handle* h) {
     HIP_TRY(PREPARING, hipStreamCreateWithPriority(&h->stream.v, hipStreamNonBlocking, prio_hi), AIRBAND_HIP_ENODEV);
     for (auto& set : h->evp)
         for (auto& e : set) HIP_TRY(PREPARING, hipEventCreate(&e.v), AIRBAND_HIP_ENODEV);
-    if (h->pipeline) {
+    if (deep_rings(h)) {
         HIP_TRY(PREPARING, hipStreamCreateWithFlags(&h->front.v, hipStreamNonBlocking), AIRBAND_HIP_ENODEV);
         HIP_TRY(PREPARING, h->ev_in.ensure(), AIRBAND_HIP_ENODEV);
         HIP_TRY(PREPARING, h->ev_back.ensure(), AIRBAND_HIP_ENODEV);
         for (auto& e : h->front_done) HIP_TRY(PREPARING, e.ensure(), AIRBAND_HIP_ENODEV);
+        if (h->run_ahead)
+            for (auto& e : h->back_done) HIP_TRY(PREPARING, e.ensure(), AIRBAND_HIP_ENODEV);
     }
     for (auto& e : h->fork_ev) HIP_TRY(PREPARING, e.ensure(), AIRBAND_HIP_ENODEV);
     for (auto& st : h->side) HIP_TRY(PREPARING, hipStreamCreateWithPriority(&st.v, hipStreamNonBlocking, prio_lo), AIRBAND_HIP_ENODEV);
@@ -590,7 +597,7 @@ void prep_geometry(airband_hip_handle* h) {
     h->B = p.wave_batch;
     /* ring rows, whole 16-row tiles: one batch plus its AGC_EXTRA carry -- or two batches deep when stage 1 of the next batch
      * is written while stage 2 still reads this one */
-    h->R = ((h->pipeline ? 2 : 1) * p.wave_batch + AB_AGC_EXTRA + 15) / 16 * 16; /* whole 16-hop MFMA tiles (a multiple of AB_TILE_ROWS too) */
+    h->R = ((deep_rings(h) ? 2 : 1) * p.wave_batch + AB_AGC_EXTRA + 15) / 16 * 16; /* whole 16-hop MFMA tiles (a multiple of AB_TILE_ROWS too) */
     h->N = p.fft_size;
     h->hop_bytes = 2LL * p.dev[0].bytes_per_sample * p.dev[0].hop_samples;
     h->first_batch_bytes = h->hop_bytes * (h->B + AB_AGC_EXTRA);
@@ -934,6 +941,11 @@ int airband_hip_prepare_scan(const airband_hip_config* cfg, const airband_hip_sc
     /* AFC needs stage 2's verdict on batch k before stage 1 of batch k+1 picks its bins (src/rtl_airband.cpp:222-251):
      * such handles stay sequential */
     h->pipeline = (cfg->flags & AIRBAND_HIP_FLAG_PIPELINE) && !h->any_afc;
+    /* The same GPU schedule without the lag, for batches on the handle's own stream (airband_hip_process_device).  Not with AFC, for the reason above; not with scan
+     * lists, whose exchange in front of the demod kernels is ordered against stage 1 by the one stream.  AIRBAND_HIP_RUN_AHEAD=0 in the environment: off (A/B
+     * measurements; the handle then has the one-batch rings and the unheld channelizer of the sequential schedule). */
+    const char* run_ahead_env = getenv("AIRBAND_HIP_RUN_AHEAD");
+    h->run_ahead = !(cfg->flags & AIRBAND_HIP_FLAG_PIPELINE) && !h->any_afc && p.scan.empty() && !(run_ahead_env && *run_ahead_env == '0');
     rc = prep_streams(h);
     if (rc != AIRBAND_HIP_OK) return rc;
     std::vector<ChanState> cs_slots;
@@ -1169,7 +1181,8 @@ static int launch_front(airband_hip_handle* h, const void* d_iq, size_t stride_b
     return AIRBAND_HIP_OK;
 }
 
-int airband_hip_process_device(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, void* stream) {
+/* airband_hip_process_device(); run_ahead_ok = false keeps a run-ahead handle's batch on the one stream (the host-ring path, whose staging buffers are ordered there) */
+static int process_batch(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, void* stream, bool run_ahead_ok) {
     if (!h || !d_iq) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
     HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
     /* hops of whole 16-byte pieces: the channelizer's transfers address the span directly, so it must start on one.  Any other hop (300, 250 bytes ...):
@@ -1187,9 +1200,37 @@ int airband_hip_process_device(airband_hip_handle* h, const void* d_iq, size_t s
     if (h->use_dft && ((((uintptr_t)d_iq) | (uintptr_t)stride_bytes) & need))
         return fail(h, AIRBAND_HIP_EINVAL, (h->hop_bytes % 16) == 0 ? "d_iq and stride_bytes must be multiples of 16 (the channelizer fetches 16 bytes per lane)"
                                                                     : "d_iq and stride_bytes must be multiples of the largest power of two (up to 16) that divides the hop's bytes");
+    if (h->run_ahead && !stream && run_ahead_ok) {
+        /* Run-ahead: stage 1 of this batch (k) on the front stream, stage 2 (k) on the handle's stream behind it, both enqueued now -- the batch's results are complete
+         * in the handle's stream order exactly as on the sequential path, so collect / read_* / synchronize / stream_wait_results know nothing of it.  What the front
+         * stream waits for is what stage 1 (k) really depends on, and stage 2 (k-1) is not among it: stage 1 (k-1) by stream order (the scratch the two share), and
+         * the back half of batch k-2, whose ring rows it overwrites (back_done).  A caller that enqueues batches back to back therefore gets stage 1 (k+1) beside
+         * stage 2 (k).  Anything else a stage 1 may depend on -- its input written by a kernel on the handle's stream, a batch that ran on another path -- has set
+         * serialise_next, and the front waits for the whole of the handle's stream, once. */
+        const uint64_t k = h->front_batches;
+        if (h->ev_last_pending) order_behind_last_batch(h); /* an exchange or a clear on a caller's stream: this batch's sums come behind it */
+        if (h->serialise_next) {
+            HIP_TRY(h, hipEventRecord(h->ev_in, h->stream), AIRBAND_HIP_ERUNTIME);
+            HIP_TRY(h, hipStreamWaitEvent(h->front, h->ev_in, 0), AIRBAND_HIP_ERUNTIME);
+        } else if (k >= 2) {
+            HIP_TRY(h, hipStreamWaitEvent(h->front, h->back_done[k & 1], 0), AIRBAND_HIP_ERUNTIME);
+        }
+        h->serialise_next = false;
+        h->last_stream = h->stream;
+        const int rc_front = launch_front(h, d_iq, stride_bytes, h->front);
+        if (rc_front != AIRBAND_HIP_OK) return rc_front;
+        HIP_TRY(h, hipEventRecord(h->front_done[k & 1], h->front), AIRBAND_HIP_ERUNTIME);
+        HIP_TRY(h, hipStreamWaitEvent(h->stream, h->front_done[k & 1], 0), AIRBAND_HIP_ERUNTIME);
+        const int rc = run_back_half(h, h->stream);
+        h->ev_last_pending = false;
+        h->ahead_batches++;
+        return rc;
+    }
     if (!h->pipeline) {
         hipStream_t s = stream ? (hipStream_t)stream : h->stream;
         h->last_stream = s;
+        /* a run-ahead handle on its sequential path (a caller's stream; the host ring): stage 1 of the next run-ahead batch must not start beside this batch's */
+        if (h->run_ahead) h->serialise_next = true;
         const int rc_front = launch_front(h, d_iq, stride_bytes, s);
         if (rc_front != AIRBAND_HIP_OK) return rc_front;
         const int rc = run_back_half(h, s);
@@ -1222,6 +1263,8 @@ int airband_hip_process_device(airband_hip_handle* h, const void* d_iq, size_t s
     HIP_TRY(h, hipStreamWaitEvent(h->stream, h->front_done[(k - 1) & 1], 0), AIRBAND_HIP_ERUNTIME);
     return run_back_half(h, h->stream);
 }
+
+int airband_hip_process_device(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, void* stream) { return process_batch(h, d_iq, stride_bytes, stream, true); }
 
 int airband_hip_stream_wait_results(airband_hip_handle* h, void* stream) {
     if (!h || !stream) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
@@ -1338,7 +1381,7 @@ int airband_hip_process(airband_hip_handle* h) {
     if (h->pipeline) HIP_TRY(h, hipStreamWaitEvent(h->front, h->ev_h2d[b], 0), AIRBAND_HIP_ERUNTIME);
     h->ring_rd += (uint64_t)consume;
     h->host_batches++;
-    const int rc = airband_hip_process_device(h, h->d_stage2[b].p, (size_t)h->stage_stride, nullptr);
+    const int rc = process_batch(h, h->d_stage2[b].p, (size_t)h->stage_stride, nullptr, false); /* stays on the handle's stream: the DMA is what bounds this path */
     /* stage 1 of this batch (the only reader of the staging buffer) is enqueued: mark the point after which the buffer is free again */
     (void)hipEventRecord(h->ev_stage_read[b], h->pipeline ? h->front : h->stream);
     return rc;
@@ -1352,6 +1395,12 @@ int airband_hip_process_bins(airband_hip_handle* h, const float* wavein, const f
     HIP_TRY(h, h->d_tmp_wavein.reserve(n), AIRBAND_HIP_ENOMEM);
     HIP_TRY(h, h->d_tmp_iqin.reserve(2 * n), AIRBAND_HIP_ENOMEM);
     hipStream_t s = h->stream;
+    if (h->run_ahead) {
+        /* the rings are written from the handle's stream here: behind the front stream's last stage 1 (the handle's stream is already, through that batch's back
+         * half; said again where it matters), and the next stage 1 on the front stream behind this batch */
+        if (h->ahead_batches > 0) HIP_TRY(h, hipStreamWaitEvent(s, h->front_done[(h->front_batches - 1) & 1], 0), AIRBAND_HIP_ERUNTIME);
+        h->serialise_next = true;
+    }
     HIP_TRY(h, hipMemcpyAsync(h->d_tmp_wavein.p, wavein, n * sizeof(float), hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipMemcpyAsync(h->d_tmp_iqin.p, iq_in, 2 * n * sizeof(float), hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
     const Event* ev = event_set(h, h->front_batches, 0);
@@ -1592,6 +1641,16 @@ const char* airband_hip_build_info(void) { return AB_BUILD_DEFINES; }
 
 int airband_hip_regrouped(const airband_hip_handle* h) { return (h && h->regroup) ? 1 : 0; }
 
+int airband_hip_schedule_info(const airband_hip_handle* h, int32_t* run_ahead, int32_t* ring_batches, int32_t* channelizer_waves_per_cu, int64_t* batches_run_ahead) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (run_ahead) *run_ahead = h->run_ahead ? 1 : 0;
+    if (ring_batches) *ring_batches = (h->R - AB_AGC_EXTRA) / h->B;
+    if (channelizer_waves_per_cu) /* the hold is LDS the launch asks for beyond its own (dft_args) */
+        *channelizer_waves_per_cu = (h->use_dft && dft_args(h, nullptr, 0, FrontRows{AB_AGC_EXTRA, h->B}).extra_lds > 0) ? 5 : 0;
+    if (batches_run_ahead) *batches_run_ahead = (int64_t)h->ahead_batches;
+    return AIRBAND_HIP_OK;
+}
+
 const char* airband_hip_channelizer_name(const airband_hip_handle* h) {
     return (h && h->use_dft) ? "dft_mfma_i8" : (h && h->use_f32) ? "dft_mfma_f32" : "fft_wave64";
 }
@@ -1641,6 +1700,7 @@ int airband_hip_generate_iq(airband_hip_handle* h, void* d_iq, size_t stride_byt
     a.n_plans = h->sig_n_plans;
     a.plan_shift_step = h->sig_shift_step;
     launch_siggen(a, stream ? (hipStream_t)stream : h->stream);
+    if (!stream && h->run_ahead) h->serialise_next = true; /* the bytes may be the next batch's input: its stage 1, on the front stream, waits for this kernel */
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("siggen launch: ") + hipGetErrorString(e));
     return AIRBAND_HIP_OK;

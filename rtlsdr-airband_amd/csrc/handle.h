@@ -118,8 +118,15 @@ struct airband_hip_handle {
     airband::Event fork_ev[4];
     /* AIRBAND_HIP_FLAG_PIPELINE: stage 1 of batch k runs on `front` while stage 2 of batch k-1 runs on `stream` */
     bool pipeline = false;
+    /* The default schedule of airband_hip_process_device(h, ..., NULL) on a handle without AFC channels and scan lists (and without FLAG_PIPELINE): stage 1 of batch k
+     * on `front`, stage 2 of batch k on `stream` behind it IN THE SAME CALL.  Batches enqueued back to back then run stage 1 (k+1) beside stage 2 (k) -- the GPU
+     * schedule of the pipelined mode with no lag on the host.  AIRBAND_HIP_RUN_AHEAD=0 at prepare: off (one-batch rings, everything on one stream). */
+    bool run_ahead = false;
+    bool serialise_next = false;   /* something the next batch's stage 1 depends on was enqueued on `stream` (or a batch ran elsewhere): its front waits for the stream's tail, once */
+    uint64_t ahead_batches = 0;    /* batches that took the run-ahead path (airband_hip_schedule_info) */
     airband::Stream front;
     airband::Event ev_in, ev_back, ev_wait, front_done[2];
+    airband::Event back_done[2];   /* run-ahead: recorded on `stream` behind the back half of batch k, at [k & 1] -- stage 1 of batch k+2 overwrites the ring rows it read */
     hipStream_t last_stream = nullptr; /* stream the last sequential batch ran on (the caller's or ours; not owned) */
     airband::Event ev_spec[2]; /* AFC on the matrix-core channelizer: the last hop's spectrum runs on a side stream beside stage 1 (fork, done) */
     airband::Event ev_last;    /* recorded behind every batch that ran on a CALLER's stream: collect / read_* / synchronize / release
