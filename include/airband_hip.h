@@ -499,13 +499,20 @@ const char* airband_hip_channelizer_name(const airband_hip_handle* h);
 
 /* One line saying WHY the handle has the channelizer it has: "" when it is on a matrix-core kernel by the ordinary rule, else e.g.
  * "hop 5000 bytes > 1280: AIRBAND_HIP_FLAG_WIDE_HOPS not set", "FORCE_FFT", "coefficient tables past their byte budget",
- * "wide hops: fft 4096 staging does not fit LDS (... bytes > 163840)".  Valid as long as the handle is. */
+ * "wide hops: fft 8192 staging does not fit LDS (... bytes > 163840)".  Valid as long as the handle is. */
 const char* airband_hip_channelizer_reason(const airband_hip_handle* h);
 
 /* Bytes of LDS per workgroup the wide-hop staging (AIRBAND_HIP_FLAG_WIDE_HOPS) needs for this shape -- two buffers of 16 rows of one window each plus the
  * exchange area of the window pieces; it does not depend on the hop -- or -1 where the shape is not a wide one (hop inside the ordinary limits, an odd number of
- * bytes, not whole CS16 samples; CF32).  Needs no GPU.  A handle takes the wide-hop kernel when this is at most 163 840 (a CU's 160 KiB). */
+ * bytes, not whole CS16 samples; CF32).  Needs no GPU.  The rule a handle follows is airband_hip_wide_hop_plan(): windows this figure puts past a CU's 160 KiB are staged in segments. */
 int64_t airband_hip_wide_hop_lds_bytes(int32_t fft_size, int32_t hop_bytes, int32_t sample_format);
+
+/* The staging plan of an AIRBAND_HIP_FLAG_WIDE_HOPS handle for this shape (needs no GPU): *segments = k-segments per window piece, the smallest of 1 / 2 / 4 whose two
+ * staging buffers and exchange area fit 163 840 bytes -- 1 wherever whole windows fit (u8 / s8 up to fft 2048, CS16 up to 1024), 2 for CS16 fft 2048 and u8 / s8 fft 4096,
+ * 4 for CS16 fft 4096 -- and *lds_bytes = the LDS per workgroup of that plan (= airband_hip_wide_hop_lds_bytes() at one segment).  Either out-pointer may be NULL.
+ * AIRBAND_HIP_EBADSIZE where the handle stays on the wavefront FFT (fft 8192; u8 / s8 fft 4096 at hops of an odd number of samples, whose kernel variant would spill
+ * registers) or the shape is not a wide one. */
+int airband_hip_wide_hop_plan(int32_t fft_size, int32_t hop_bytes, int32_t sample_format, int32_t* segments, int64_t* lds_bytes);
 
 /* Uploads the transmitter table of the synthetic dongles: carriers [n_carriers][12] int64 rows
  * (rtlsdr-airband_amd/siggen.py::Carrier.as_row), the Q8 noise multiplier and the 4096-entry int16 sine table. */

@@ -34,7 +34,7 @@ EXPORTS = [
     "airband_hip_comm_group_begin", "airband_hip_comm_group_end", "airband_hip_allreduce_mixers", "airband_hip_add_mixers", "airband_hip_comm_destroy", "airband_hip_clear_mixers", "airband_hip_set_signal_plan_shift", "airband_hip_regrouped",
     "airband_hip_prepare_scan", "airband_hip_set_freq_index", "airband_hip_freq_stats",
     "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
-    "airband_hip_channelizer_reason", "airband_hip_wide_hop_lds_bytes", "airband_hip_schedule_info",
+    "airband_hip_channelizer_reason", "airband_hip_wide_hop_lds_bytes", "airband_hip_schedule_info", "airband_hip_wide_hop_plan",
 ]
 
 _lib = None
@@ -117,6 +117,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_channelizer_reason.restype = C.c_char_p
     L.airband_hip_wide_hop_lds_bytes.argtypes = [i32, i32, i32]
     L.airband_hip_wide_hop_lds_bytes.restype = i64
+    L.airband_hip_wide_hop_plan.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i64)]
     L.airband_hip_set_signal_plan.argtypes = [vp, vp, i32, i32, vp]
     L.airband_hip_generate_iq.argtypes = [vp, vp, sz, u64, sz, u64, i32, vp]
     L.airband_hip_set_signal_plan_shift.argtypes = [vp, i32, C.c_uint32]
@@ -174,6 +175,16 @@ def dft_selftest(devices: Sequence[dict], *, wave_rate: int, fft_log: int = 9, w
 def wide_hop_lds_bytes(fft_size: int, hop_bytes: int, sfmt: int) -> int:
     """LDS per workgroup of the wide-hop staging (capi.FLAG_WIDE_HOPS) for this shape, -1 where the shape is not a wide one (no GPU needed)."""
     return int(load_library().airband_hip_wide_hop_lds_bytes(fft_size, hop_bytes, sfmt))
+
+
+def wide_hop_plan(fft_size: int, hop_bytes: int, sfmt: int):
+    """(segments, lds_bytes): the staging plan a capi.FLAG_WIDE_HOPS handle uses for this shape (no GPU needed).  AirbandError(EBADSIZE) where such a handle stays on
+    the wavefront FFT or the shape is not a wide one."""
+    seg, lds = C.c_int32(0), C.c_int64(0)
+    rc = load_library().airband_hip_wide_hop_plan(fft_size, hop_bytes, sfmt, C.byref(seg), C.byref(lds))
+    if rc != 0:
+        raise AirbandError(rc, "no wide-hop plan for fft %d, hops of %d bytes, sample format %d" % (fft_size, hop_bytes, sfmt))
+    return int(seg.value), int(lds.value)
 
 
 def make_scan(scan: Optional[dict]):

@@ -250,7 +250,8 @@ DftArgs dft_args(const airband_hip_handle* h, const void* d_iq, size_t stride_by
     const int win_bytes = 2 * p.fft_size * p.dev[0].bytes_per_sample / np_total * np;
     a.partial = reinterpret_cast<float4*>(h->d_dft_partial.p);
     if (h->use_wide) { /* channelizer_dft_wide.hip: a staging step is one tile of 16 rows, two buffers */
-        a.lds_per_buf = dft_wide_lds_per_buf(win_bytes);
+        const int wb = win_bytes / np;
+        a.lds_per_buf = wide_image_bytes(wb, np, dft_wide_plan(p.fft_size, (int)h->hop_bytes, p.dev[0].sfmt, nullptr, nullptr));
         a.nbuf = 2;
         a.sub = 1;
     } else {
@@ -815,14 +816,18 @@ int prep_channelizer(airband_hip_handle* h) {
     h->use_wide = false;
     h->chan_reason = force_fft ? "FORCE_FFT" : "";
     /* Hops beyond the contiguous staging of channelizer_dft.hip (u8 / s8 above 1 024 bytes, CS16 above 1 280): the row staging of channelizer_dft_wide.hip,
-     * for handles that ask for it and wherever its two buffers fit a CU's LDS (which depends on the window alone) -- else the wavefront FFT, and the handle says why */
-    const int wide_lds = force_fft || h->use_dft ? -1 : dft_wide_lds(p.fft_size, hop_b, sfmt);
-    if (wide_lds >= 0) {
+     * for handles that ask for it and wherever dft_wide_plan() finds it a staging plan (whole windows, or windows in 2 / 4 k-segments: it depends on the window and, for
+     * the reader of odd hops, on the hop's alignment) -- else the wavefront FFT, and the handle says why */
+    bool wide_spills = false;
+    const int wide_seg = force_fft || h->use_dft ? -1 : dft_wide_plan(p.fft_size, hop_b, sfmt, nullptr, &wide_spills);
+    if (wide_seg >= 0) {
         const int limit = sfmt == AIRBAND_SFMT_S16 ? 1280 : 1024;
         if (!(h->flags & AIRBAND_HIP_FLAG_WIDE_HOPS))
             h->chan_reason = "hop " + std::to_string(hop_b) + " bytes > " + std::to_string(limit) + ": AIRBAND_HIP_FLAG_WIDE_HOPS not set";
-        else if (wide_lds > AB_DFT_WIDE_LDS_MAX)
-            h->chan_reason = "wide hops: fft " + std::to_string(p.fft_size) + " staging does not fit LDS (" + std::to_string(wide_lds) + " bytes > " + std::to_string(AB_DFT_WIDE_LDS_MAX) + ")";
+        else if (wide_spills)
+            h->chan_reason = "wide hops: fft " + std::to_string(p.fft_size) + " at hops of an odd number of samples: the segmented kernel spills registers and is not built";
+        else if (wide_seg == 0)
+            h->chan_reason = "wide hops: fft " + std::to_string(p.fft_size) + " staging does not fit LDS (" + std::to_string(dft_wide_lds(p.fft_size, hop_b, sfmt)) + " bytes > " + std::to_string(AB_DFT_WIDE_LDS_MAX) + ")";
         else
             h->use_dft = h->use_wide = true;
     }
@@ -909,8 +914,8 @@ int airband_hip_dft_selftest(const airband_hip_config* cfg, int32_t windows, dou
         *max_rel_err = f32_table_selftest(plan, windows < 1 ? 1 : windows);
         return AIRBAND_HIP_OK;
     }
-    const int wide_lds = (cfg->flags & AIRBAND_HIP_FLAG_WIDE_HOPS) ? dft_wide_lds(plan.fft_size, hop_bytes, plan.dev[0].sfmt) : -1; /* the tables do not depend on the hop */
-    const bool wide = wide_lds >= 0 && wide_lds <= AB_DFT_WIDE_LDS_MAX;
+    /* the tables do not depend on the hop; whether a flagged handle takes the wide-hop kernel is prep_channelizer()'s rule, dft_wide_plan() */
+    const bool wide = (cfg->flags & AIRBAND_HIP_FLAG_WIDE_HOPS) && dft_wide_plan(plan.fft_size, hop_bytes, plan.dev[0].sfmt, nullptr, nullptr) > 0;
     if (!plan.uniform_hop || !(wide || dft_supported(plan.fft_size, hop_bytes, plan.dev[0].sfmt, plan.max_ch)))
         return fail(nullptr, AIRBAND_HIP_EBADSIZE, "configuration does not take the matrix-core channelizer");
     build_dft_tables(plan);
@@ -1658,6 +1663,15 @@ const char* airband_hip_channelizer_name(const airband_hip_handle* h) {
 const char* airband_hip_channelizer_reason(const airband_hip_handle* h) { return h ? h->chan_reason.c_str() : ""; }
 
 int64_t airband_hip_wide_hop_lds_bytes(int32_t fft_size, int32_t hop_bytes, int32_t sample_format) { return dft_wide_lds(fft_size, hop_bytes, sample_format); }
+
+int airband_hip_wide_hop_plan(int32_t fft_size, int32_t hop_bytes, int32_t sample_format, int32_t* segments, int64_t* lds_bytes) {
+    int lds = 0;
+    const int seg = dft_wide_plan(fft_size, hop_bytes, sample_format, &lds, nullptr);
+    if (seg <= 0) return AIRBAND_HIP_EBADSIZE;
+    if (segments) *segments = seg;
+    if (lds_bytes) *lds_bytes = lds;
+    return AIRBAND_HIP_OK;
+}
 
 int airband_hip_set_signal_plan(airband_hip_handle* h, const int64_t* carriers, int32_t n_carriers, int32_t noise_q8, const int16_t* sin_table4096) {
     if (!h || !carriers || !sin_table4096 || n_carriers < 1 || n_carriers > 16) return fail(h, AIRBAND_HIP_EINVAL, "bad signal plan (1..16 carriers)");

@@ -26,9 +26,20 @@
  *
  * Buffers: two tile images, one tile ahead, the wait counts of channelizer_dft.hip's two-buffer path (everything younger than a tile's transfer = the output
  * stores issued since).  Window pieces (fft_size 1024 ...): wave 0 issues the transfers, one barrier hands a tile over, a second orders the partial sums.
- * LDS: 2 x roundup(16 PITCH, 1 KiB) + the exchange area -- independent of the hop (kernels.h, dft_wide_lds_bytes). */
+ * LDS: 2 x roundup(16 PITCH, 1 KiB) + the exchange area -- independent of the hop (kernels.h, dft_wide_lds_bytes).
+ *
+ * Segments (SEG = 2, 4: CS16 fft 2048, u8 / s8 fft 4096, CS16 fft 4096 -- windows of 4 - 16 KiB, whose two whole images would be 258 - 514 KiB).  Every wave reads
+ * only its own piece of a row, so every piece is cut into SEG equal segments along k and an image holds, for the 16 hops and all NP pieces, ONE segment of
+ * S = WIN_BYTES / SEG bytes: 16 x NP sub-rows of S + 16 bytes, piece-major, so that the 16 hops of a piece stay one odd pitch apart (dft_wide_map.h: the layout,
+ * and both directions of the address map as functions the host can run -- this file computes no image address of its own).  The two buffers alternate per
+ * SEGMENT: while the waves run the MFMAs of segment s of tile t, wave 0 streams in segment s + 1, or segment 0 of tile t + 1; the sums (TileAcc) live across a
+ * tile's segments; recombination, the exchange and the stores happen once per tile.  The hand-over is the same wait + one barrier, the proof that a transfer has
+ * landed the same count of stores since.  A segment starts a multiple of 16 bytes into its row: delta is the row's, unchanged.  LDS: 136 KiB (CS16 fft 2048), 146 KiB
+ * (fft 4096), one workgroup per CU.  SEG = 1 is the kernel above: the same arithmetic, LDS and register counts (the compiled code differs in register numbering and two address instructions).  Not built: SEG > 1 with the AL = 2 reader (u8 / s8 fft 4096 at hops of
+ * an odd number of samples) -- with the sums live across the staging loop it spills 29 registers; dft_wide_plan() keeps that shape on the wavefront FFT. */
 #include <hip/hip_runtime.h>
 #include <atomic>
+#include <utility>
 
 #include "common.h"
 #include "kernels.h"
@@ -41,17 +52,25 @@ namespace {
 /* s_waitcnt vmcnt(n), n wave-uniform, for this kernel's counts: the output stores since a transfer was issued (0 - 6 in the steady state) */
 __device__ __forceinline__ void wait_stores(int n) { wait_vmcnt_lo(n); }
 
-template <bool EDGE_HI_ZERO, int FFT_N, bool S16, int AL, int NP>
+/* f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): the segments of a tile, each with its own compile-time slice of the B fragments */
+template <int... I, class F>
+__device__ __forceinline__ void each_segment(std::integer_sequence<int, I...>, F&& f) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
+
+template <bool EDGE_HI_ZERO, int FFT_N, bool S16, int AL, int NP, int SEG>
 __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_wide_kernel(DftArgs a) {
     constexpr int BPS = S16 ? 2 : 1;
     constexpr int WIN_BYTES = 2 * FFT_N * BPS; /* bytes per window piece */
     constexpr int WIN_ALL = WIN_BYTES * NP;    /* bytes per window       */
-    constexpr int PITCH = dft_wide_pitch(WIN_ALL);
-    constexpr int BUF = dft_wide_lds_per_buf(WIN_ALL);
-    constexpr int N_DMA = BUF / 1024;
+    typedef WideMap<WIN_BYTES, NP, SEG> Map;   /* dft_wide_map.h: the image's layout and both directions of its address map */
+    constexpr int BUF = Map::IMAGE;
+    constexpr int N_DMA = Map::N_DMA;
     constexpr int KSTEPS = 2 * FFT_N / 64;
+    constexpr int KSEG = KSTEPS / SEG;         /* k-steps per segment */
     static_assert(KSTEPS == 16 || KSTEPS == 8, "fft_size 256 or 512 per window piece");
     static_assert(NP == 1 || FFT_N == 512, "window pieces are 512 samples long");
+    static_assert(SEG == 1 || (NP > 1 && KSEG >= 4 && KSEG * SEG == KSTEPS), "segments: windows in pieces only, at least four k-steps each");
     constexpr int EDGE = KSTEPS / 8;
     extern __shared__ __attribute__((aligned(16))) uint8_t lds_all[];
 
@@ -83,7 +102,7 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_wide
     if (t_begin >= t_end) return;
     /* bytes of the batch span that may be read, from `src`, in whole 16-byte pieces: the last hop's window and not a byte more (geometry.lookahead_bytes
      * includes the round-up) */
-    const long span_end = ((long)(a.n_hops - 1) * hop_bytes + WIN_ALL + mis + 15) & ~15L;
+    const long span_end = wide_span_end(a.n_hops, hop_bytes, WIN_ALL, mis);
 
     /* ---- B fragments, resident for the whole wave ---- */
     const int bset = a.item_bset[item] * NP + piece;
@@ -109,29 +128,21 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_wide
 
     typedef __attribute__((address_space(1))) const void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
-    /* tile t -> image `buf`: lane l of instruction i fills image byte o = 1024 i + 16 l = byte o % PITCH of row o / PITCH.  Addresses past the batch span
-     * re-read its last 16 bytes, addresses in front of it its first: they feed hops outside [0, n_hops), which are never stored, and the padding */
-    auto stage = [&](int t, uint8_t* buf) {
+    /* segment `seg` of tile t -> image `buf`: lane l of instruction i fills image byte o = 1024 i + 16 l = byte o % PITCH of sub-row o / PITCH (Map::src: which
+     * stream bytes those are, and what stands in for addresses outside the batch span) */
+    auto stage = [&](int t, int seg, uint8_t* buf) {
         const long hop0 = (long)t * TILE_HOPS - shift;
-#pragma unroll 1 /* (unrolled, the 33 - 65 per-lane addresses of a tile are all computed up front and spill the B fragments) */
+#pragma unroll 1 /* (unrolled, the 33 - 66 per-lane addresses of an image are all computed up front and spill the B fragments) */
         for (int i = 0; i < N_DMA; i++) {
-            const unsigned o = (unsigned)(i * 1024 + lane * 16);
-            unsigned r = o / (unsigned)PITCH, off = o - r * (unsigned)PITCH;
-            if (r > TILE_HOPS - 1) { /* behind the 16th row, up to the image's whole KiB: nobody reads it */
-                r = TILE_HOPS - 1;
-                off = PITCH - 16;
-            }
-            long so = (((hop0 + (long)r) * hop_bytes + mis) & ~15L) + (long)off;
-            if (so + 16 > span_end) so = span_end - 16;
-            if (so < 0) so = 0;
-            __builtin_amdgcn_global_load_lds((gptr_t)(src + so), (lptr_t)(uintptr_t)(buf + i * 1024), 16, 0, 0);
+            const long so = Map::src((unsigned)(i * WIDE_DMA_BYTES + lane * 16), hop0, hop_bytes, mis, seg, span_end);
+            __builtin_amdgcn_global_load_lds((gptr_t)(src + so), (lptr_t)(uintptr_t)(buf + i * WIDE_DMA_BYTES), 16, 0, 0);
         }
     };
     float4* exch = reinterpret_cast<float4*>(lds_all + 2 * BUF); /* partial sums of pieces 1 .. NP-1 on their way to wave 0: [tile parity][piece - 1][lane] */
     /* `stores`: output store instructions issued so far (whole tiles only: fewer than the truth is safe); mark*: what it stood at when the transfer into the
      * buffer was issued -- vector-memory operations complete in issue order, so "at most stores - mark outstanding" proves that transfer has landed */
     int stores = 0, mark0 = 0, mark1 = 0;
-    if (piece == 0) stage(t_begin, lds_all);
+    if (piece == 0) stage(t_begin, 0, lds_all);
 
     const int row_l = lane & 15, grp = lane >> 4;
     const int k_tile = ((__ballot(!(col & 1) && ch_valid && want_mag) != 0ull) ? 1 : 0) + ((__ballot(!(col & 1) && ch_valid && want_iq) != 0ull) ? 2 : 0);
@@ -145,40 +156,44 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_wide
     struct TileAcc {
         v4i a0, a1, a2, h0, h1, h2;
     };
-    /* LDS -> MFMA for the 16 hops of tile t: the lane's row, delta_r bytes in */
-    auto tile_mfma = [&](const uint8_t* buf, int t, TileAcc& A) {
-        const int delta = AL >= 16 ? 0 : (int)((((long)t * TILE_HOPS - shift + row_l) * hop_bytes + mis) & 15L);
-        const uint8_t* arow = buf + row_l * PITCH + delta + grp * (S16 ? 32 : 16) + piece * WIN_BYTES;
-        A.a0 = (v4i){0, 0, 0, 0}; A.a1 = (v4i){0, 0, 0, 0}; A.a2 = (v4i){0, 0, 0, 0};
+    /* LDS -> MFMA for the 16 hops of tile t, k-steps [SG x KSEG, (SG + 1) x KSEG) of the wave's piece out of the image of segment SG: the lane's row, delta_r
+     * bytes in.  The first segment starts the sums, the others add to them */
+    auto seg_mfma = [&](const uint8_t* buf, int t, TileAcc& A, auto seg_c) {
+        constexpr int SG = decltype(seg_c)::value, K0 = SG * KSEG;
+        const int delta = AL >= 16 ? 0 : wide_delta((long)t * TILE_HOPS - shift + row_l, hop_bytes, mis);
+        const uint8_t* arow = buf + Map::frag(row_l, piece, SG, SG * Map::S) + delta + grp * (S16 ? 32 : 16);
+        if (SG == 0) { A.a0 = (v4i){0, 0, 0, 0}; A.a1 = (v4i){0, 0, 0, 0}; A.a2 = (v4i){0, 0, 0, 0}; }
         if (!S16) {
-            v4i av[KSTEPS];
+            v4i av[KSEG];
             av[0] = lds_read16<AL>(arow); av[1] = lds_read16<AL>(arow + 64); av[2] = lds_read16<AL>(arow + 128); av[3] = lds_read16<AL>(arow + 192);
 #pragma unroll
-            for (int s = 0; s < KSTEPS; s++) {
-                if ((s & 1) == 0 && s + 4 < KSTEPS) { /* fetched four k-steps ahead of the MFMAs that consume them */
-                    av[s + 4] = lds_read16<AL>(arow + (s + 4) * 64);
-                    av[s + 5] = lds_read16<AL>(arow + (s + 5) * 64);
+            for (int i = 0; i < KSEG; i++) {
+                const int s = K0 + i; /* the k-step of the piece (compile-time once unrolled): which B fragment, which edge */
+                if ((i & 1) == 0 && i + 4 < KSEG) { /* fetched four k-steps ahead of the MFMAs that consume them */
+                    av[i + 4] = lds_read16<AL>(arow + (i + 4) * 64);
+                    av[i + 5] = lds_read16<AL>(arow + (i + 5) * 64);
                 }
-                v4i x = av[s];
+                v4i x = av[i];
                 x.x ^= flipmask; x.y ^= flipmask; x.z ^= flipmask; x.w ^= flipmask; /* u8 -> b - 128 as int8; s8 is int8 already */
                 A.a0 = ab_mfma(x, b0[s], A.a0);
                 A.a1 = ab_mfma(x, b1[s], A.a1);
                 if (!(EDGE_HI_ZERO && (s < EDGE || s >= KSTEPS - EDGE))) A.a2 = ab_mfma(x, b2[s], A.a2);
-                if (s & 1) __builtin_amdgcn_sched_barrier(0);
+                if (i & 1) __builtin_amdgcn_sched_barrier(0);
             }
         } else {
             /* CS16: plane k-step s of the lane = 16 plane bytes = 8 samples x (I, Q) = 32 raw bytes [Ilo Ihi Qlo Qhi] x 8, pulled apart with v_perm_b32 */
-            A.h0 = (v4i){0, 0, 0, 0}; A.h1 = (v4i){0, 0, 0, 0}; A.h2 = (v4i){0, 0, 0, 0};
+            if (SG == 0) { A.h0 = (v4i){0, 0, 0, 0}; A.h1 = (v4i){0, 0, 0, 0}; A.h2 = (v4i){0, 0, 0, 0}; }
             v4i ra[2], rb[2];
             ra[0] = lds_read16<AL>(arow);
             rb[0] = lds_read16<AL>(arow + 16);
 #pragma unroll
-            for (int s = 0; s < KSTEPS; s++) {
-                if (s + 1 < KSTEPS) {
-                    ra[(s + 1) & 1] = lds_read16<AL>(arow + (s + 1) * 128);
-                    rb[(s + 1) & 1] = lds_read16<AL>(arow + (s + 1) * 128 + 16);
+            for (int i = 0; i < KSEG; i++) {
+                const int s = K0 + i;
+                if (i + 1 < KSEG) {
+                    ra[(i + 1) & 1] = lds_read16<AL>(arow + (i + 1) * 128);
+                    rb[(i + 1) & 1] = lds_read16<AL>(arow + (i + 1) * 128 + 16);
                 }
-                const v4i p = ra[s & 1], q = rb[s & 1];
+                const v4i p = ra[i & 1], q = rb[i & 1];
                 v4i lo, hi;
                 lo.x = (int)__builtin_amdgcn_perm((unsigned)p.y, (unsigned)p.x, 0x06040200u); hi.x = (int)__builtin_amdgcn_perm((unsigned)p.y, (unsigned)p.x, 0x07050301u);
                 lo.y = (int)__builtin_amdgcn_perm((unsigned)p.w, (unsigned)p.z, 0x06040200u); hi.y = (int)__builtin_amdgcn_perm((unsigned)p.w, (unsigned)p.z, 0x07050301u);
@@ -260,18 +275,22 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_wide
 
     int cur = 0;
     for (int t = t_begin; t < t_end; t++) {
-        uint8_t* buf = lds_all + cur * BUF;
-        /* NP > 1: wave 0 runs the transfers and the waits; the barrier hands tile t to the other waves and tells wave 0 that they are done with the buffer the
-         * next transfer overwrites (they read it in tile t - 1) */
-        if (piece == 0) wait_stores(stores - (cur ? mark1 : mark0)); /* tile t's bytes have landed: younger than its transfer are only the stores since */
-        if (NP > 1) __syncthreads();
-        if (piece == 0 && t + 1 < t_end) { /* the next tile streams in under this tile's MFMAs */
-            stage(t + 1, lds_all + (cur ^ 1) * BUF);
-            if (cur) mark0 = stores;
-            else mark1 = stores;
-        }
-        TileAcc now;
-        tile_mfma(buf, t, now);
+        TileAcc now; /* lives across the segments of the tile */
+        each_segment(std::make_integer_sequence<int, SEG>{}, [&](auto seg_c) {
+            constexpr int SG = decltype(seg_c)::value;
+            uint8_t* buf = lds_all + cur * BUF;
+            /* NP > 1: wave 0 runs the transfers and the waits; the barrier hands the image (segment SG of tile t) to the other waves and tells wave 0 that they are
+             * done with the buffer the next transfer overwrites (they read it one image ago) */
+            if (piece == 0) wait_stores(stores - (cur ? mark1 : mark0)); /* the image's bytes have landed: younger than its transfer are only the stores since */
+            if (NP > 1) __syncthreads();
+            if (piece == 0 && (SG + 1 < SEG || t + 1 < t_end)) { /* the next image -- the tile's next segment, or the next tile's first -- streams in under these MFMAs */
+                stage(SG + 1 < SEG ? t : t + 1, SG + 1 < SEG ? SG + 1 : 0, lds_all + (cur ^ 1) * BUF);
+                if (cur) mark0 = stores;
+                else mark1 = stores;
+            }
+            seg_mfma(buf, t, now, seg_c);
+            cur ^= 1;
+        });
         float val[4];
 #pragma unroll
         for (int r = 0; r < 4; r++) val[r] = tile_value(now, r);
@@ -290,14 +309,14 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_wide
         } else {
             tile_store(t, val);
         }
-        cur ^= 1;
     }
 }
 
-template <int FFT_N, bool S16, int AL, int NP>
+template <int FFT_N, bool S16, int AL, int NP, int SEG>
 void launch_al(const DftArgs& a, hipStream_t stream) {
+    static_assert(SEG > 0 && wide_lds_total(2 * FFT_N * (S16 ? 2 : 1), NP, SEG) <= WIDE_LDS_MAX, "a shape without a plan has no kernel");
     const long groups = (long)a.n_items * a.splits;
-    const size_t lds = (size_t)dft_wide_lds_bytes(2 * FFT_N * (S16 ? 2 : 1) * NP, NP) + (size_t)(a.extra_lds > 0 ? a.extra_lds : 0);
+    const size_t lds = (size_t)wide_lds_total(2 * FFT_N * (S16 ? 2 : 1), NP, SEG) + (size_t)(a.extra_lds > 0 ? a.extra_lds : 0);
     /* more than the default 64 KiB of dynamic LDS: opt in to the CU's 160 KiB, once per kernel variant and device (as channelizer_dft.hip, launch_al) */
     static std::atomic<bool> big_lds_dev[64][2];
     int cur_dev = 0;
@@ -306,30 +325,35 @@ void launch_al(const DftArgs& a, hipStream_t stream) {
     std::atomic<bool>* big_lds = big_lds_dev[tracked ? cur_dev : 0];
     const int e = a.edge_hi_zero ? 1 : 0;
     if (lds > 64 * 1024 && (!tracked || !big_lds[e].load(std::memory_order_acquire))) {
-        const void* fn = e ? reinterpret_cast<const void*>(&channelizer_dft_wide_kernel<true, FFT_N, S16, AL, NP>)
-                           : reinterpret_cast<const void*>(&channelizer_dft_wide_kernel<false, FFT_N, S16, AL, NP>);
+        const void* fn = e ? reinterpret_cast<const void*>(&channelizer_dft_wide_kernel<true, FFT_N, S16, AL, NP, SEG>)
+                           : reinterpret_cast<const void*>(&channelizer_dft_wide_kernel<false, FFT_N, S16, AL, NP, SEG>);
         if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess && tracked) big_lds[e].store(true, std::memory_order_release);
     }
     if (e)
-        hipLaunchKernelGGL((channelizer_dft_wide_kernel<true, FFT_N, S16, AL, NP>), dim3((unsigned)groups), dim3(64 * NP), lds, stream, a);
+        hipLaunchKernelGGL((channelizer_dft_wide_kernel<true, FFT_N, S16, AL, NP, SEG>), dim3((unsigned)groups), dim3(64 * NP), lds, stream, a);
     else
-        hipLaunchKernelGGL((channelizer_dft_wide_kernel<false, FFT_N, S16, AL, NP>), dim3((unsigned)groups), dim3(64 * NP), lds, stream, a);
+        hipLaunchKernelGGL((channelizer_dft_wide_kernel<false, FFT_N, S16, AL, NP, SEG>), dim3((unsigned)groups), dim3(64 * NP), lds, stream, a);
 }
 
+/* the shape's segments are the plan's (dft_wide_map.h), at compile time: the kernel a handle launches cannot disagree with the LDS dft_wide_plan() promised it */
 template <int FFT_N, bool S16, int NP>
 void launch_generic(const DftArgs& a, hipStream_t stream) {
-    if ((a.hop_bytes & 15) == 0) return launch_al<FFT_N, S16, 16, NP>(a, stream);
-    if ((a.hop_bytes & 7) == 0) return launch_al<FFT_N, S16, 8, NP>(a, stream);
-    if ((a.hop_bytes & 3) == 0) return launch_al<FFT_N, S16, 4, NP>(a, stream);
-    if constexpr (!S16) launch_al<FFT_N, false, 2, NP>(a, stream); /* u8 / s8 hops of an odd number of samples */
+    constexpr int SEG = wide_plan_segments(2 * FFT_N * (S16 ? 2 : 1), NP);
+    if ((a.hop_bytes & 15) == 0) return launch_al<FFT_N, S16, 16, NP, SEG>(a, stream);
+    if ((a.hop_bytes & 7) == 0) return launch_al<FFT_N, S16, 8, NP, SEG>(a, stream);
+    if ((a.hop_bytes & 3) == 0) return launch_al<FFT_N, S16, 4, NP, SEG>(a, stream);
+    /* u8 / s8 hops of an odd number of samples -- whole windows only: with segments, whose sums live across the staging, this reader's five dwords per fragment
+     * spill 29 registers (fft 4096), and a spilling variant is not shipped: dft_wide_plan() keeps that shape off this kernel */
+    if constexpr (!S16 && SEG == 1) launch_al<FFT_N, false, 2, NP, SEG>(a, stream);
 }
 
 }  // namespace
 
-/* Which hops take this file's kernel (AIRBAND_HIP_FLAG_WIDE_HOPS handles): exactly those dft_supported() refuses for their LENGTH -- u8 / s8 above 1 024 bytes,
- * CS16 above 1 280 -- at any even length (CS16: whole samples, multiples of 4 bytes), as long as two tile images and the exchange area fit a CU's 160 KiB.
- * An image is 16 x (window + 16) bytes whatever the hop: u8 / s8 up to fft_size 2048 and CS16 up to 1024 fit (two buffers of 65 KiB), nothing larger does.
- * Layout rule for 1 024 < hop < window (CS16 hops of 1 500 bytes at fft 512, everything at fft 1024): rows as well.  A contiguous image would be
+/* Which hops are this file's business (AIRBAND_HIP_FLAG_WIDE_HOPS handles): exactly those dft_supported() refuses for their LENGTH -- u8 / s8 above 1 024 bytes,
+ * CS16 above 1 280 -- at any even length (CS16: whole samples, multiples of 4 bytes).  dft_wide_lds(): the LDS of two WHOLE tile images and the exchange area,
+ * 16 x (window + 16) bytes per image whatever the hop: u8 / s8 up to fft_size 2048 and CS16 up to 1024 fit a CU's 160 KiB (two buffers of 65 KiB), nothing larger
+ * does -- dft_wide_plan() below then cuts the pieces into segments.
+ * Layout rule for 1 024 < hop < window (CS16 hops of 1 500 bytes at fft 512, everything from fft 1024 up): rows as well.  A contiguous image would be
  * 15 hop + window bytes there, less than the rows' 16 x (window + 16) -- 24.5 against 32.3 KiB at CS16 hops of 1 500 bytes -- but it is a second staging path for
  * one kernel and its LDS grows with the hop; the rows' LDS does not depend on the hop, so ONE bound serves every rate, and what neighbouring rows fetch twice
  * comes out of L2, not out of memory. */
@@ -344,6 +368,20 @@ int dft_wide_lds(int fft_size, int hop_bytes, int sfmt) {
     return dft_wide_lds_bytes((int)win_all, np);
 }
 
+int dft_wide_plan(int fft_size, int hop_bytes, int sfmt, int* lds_bytes, bool* spills) {
+    if (spills) *spills = false;
+    if (dft_wide_lds(fft_size, hop_bytes, sfmt) < 0) return -1;
+    const int np = fft_size > 512 ? fft_size / 512 : 1;
+    const int win_bytes = 2 * (fft_size > 512 ? 512 : fft_size) * (sfmt == AIRBAND_SFMT_S16 ? 2 : 1);
+    int seg = wide_plan_segments(win_bytes, np);
+    if (seg > 1 && (hop_bytes & 3) != 0) { /* no segmented kernel for u8 / s8 hops of an odd number of samples (launch_generic) */
+        seg = 0;
+        if (spills) *spills = true;
+    }
+    if (seg > 0 && lds_bytes) *lds_bytes = wide_lds_total(win_bytes, np, seg);
+    return seg;
+}
+
 void launch_channelizer_dft_wide(const DftArgs& a0, hipStream_t stream) {
     DftArgs a = a0;
     const bool s16 = a.sfmt == AIRBAND_SFMT_S16;
@@ -354,8 +392,9 @@ void launch_channelizer_dft_wide(const DftArgs& a0, hipStream_t stream) {
     case 256: return s16 ? launch_generic<256, true, 1>(a, stream) : launch_generic<256, false, 1>(a, stream);
     case 512: return s16 ? launch_generic<512, true, 1>(a, stream) : launch_generic<512, false, 1>(a, stream);
     case 1024: return s16 ? launch_generic<512, true, 2>(a, stream) : launch_generic<512, false, 2>(a, stream);
-    case 2048: if (!s16) launch_generic<512, false, 4>(a, stream); return; /* (CS16: 16 rows of 8 KiB, twice, do not fit -- prep_channelizer() never sends it here) */
-    default: return;
+    case 2048: return s16 ? launch_generic<512, true, 4>(a, stream) : launch_generic<512, false, 4>(a, stream);
+    case 4096: return s16 ? launch_generic<512, true, 8>(a, stream) : launch_generic<512, false, 8>(a, stream);
+    default: return; /* (fft_size 8192 has no plan: prep_channelizer() never sends it here) */
     }
 }
 

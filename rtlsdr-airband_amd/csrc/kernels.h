@@ -7,6 +7,7 @@
 
 #include "../../include/airband_hip.h"
 #include "common.h"
+#include "dft_wide_map.h"
 
 namespace airband {
 
@@ -182,14 +183,20 @@ void launch_channelizer_dft(const DftArgs& a, hipStream_t stream);
 /* wide hops (channelizer_dft_wide.hip, AIRBAND_HIP_FLAG_WIDE_HOPS): a tile is staged as 16 rows of one window each.  The geometry, shared by the kernel (as
  * constant expressions) and the host: win_all = bytes of a whole window, np = its pieces of 512 samples.  Row pitch = window + 16 (an odd number of 16-byte
  * bank columns, and room for the up-to-15 bytes in front of an unaligned row), a buffer = 16 rows in whole 1 KiB transfers, two buffers + the exchange area of
- * the window pieces' partial sums. */
-constexpr int dft_wide_pitch(int win_all) { return win_all + 16; }
-constexpr int dft_wide_lds_per_buf(int win_all) { return (16 * dft_wide_pitch(win_all) + 1023) / 1024 * 1024; }
-constexpr int dft_wide_lds_bytes(int win_all, int np) { return 2 * dft_wide_lds_per_buf(win_all) + (np > 1 ? 2 * (np - 1) * 64 * 16 : 0); }
-/* dynamic LDS of the wide-hop kernel for this shape, or -1 where the shape is not its business (hops inside dft_supported()'s limits, odd hops, CF32);
- * the handle takes the kernel when this is at most AB_DFT_WIDE_LDS_MAX */
-#define AB_DFT_WIDE_LDS_MAX (160 * 1024)
+ * the window pieces' partial sums.  Windows whose two images do not fit are staged a k-segment at a time (dft_wide_map.h holds the geometry of both and the
+ * address map; the three functions below are its one-segment case under the names the host code uses). */
+constexpr int dft_wide_pitch(int win_all) { return wide_sub_pitch(win_all, 1, 1); }
+constexpr int dft_wide_lds_per_buf(int win_all) { return wide_image_bytes(win_all, 1, 1); }
+constexpr int dft_wide_lds_bytes(int win_all, int np) { return wide_lds_total(win_all / np, np, 1); }
+/* dynamic LDS of the wide-hop kernel for this shape with whole windows staged (one segment), or -1 where the shape is not its business (hops inside
+ * dft_supported()'s limits, odd hops, CF32) */
+#define AB_DFT_WIDE_LDS_MAX airband::WIDE_LDS_MAX
 int dft_wide_lds(int fft_size, int hop_bytes, int sfmt);
+/* THE rule by which a flagged handle takes the wide-hop kernel: the smallest number of k-segments per window piece, 1 / 2 / 4, whose two images and exchange area
+ * are at most AB_DFT_WIDE_LDS_MAX (dft_wide_map.h); *lds_bytes (may be null) = that plan's dynamic LDS.  0: no plan fits (fft_size 8192 is not tried: more than
+ * eight pieces need the two-pass partial sums of channelizer_dft.hip; *spills (may be null) = true where a plan fits but its kernel variant is not built because it
+ * spills registers: segments at u8 / s8 hops of an odd number of samples); -1: not a wide shape (as dft_wide_lds()). */
+int dft_wide_plan(int fft_size, int hop_bytes, int sfmt, int* lds_bytes, bool* spills);
 void launch_channelizer_dft_wide(const DftArgs& a, hipStream_t stream);
 /* side: 3 extra streams, ev: 4 events (fork + 3 joins); both may be null -> everything on `stream`, one kind after the other */
 void launch_demod(const DemodArgs& a, const int* kind_first_block, const int* kind_n_blocks, hipStream_t stream, hipStream_t* side, hipEvent_t* ev);

@@ -1,7 +1,8 @@
 """What AIRBAND_HIP_FLAG_WIDE_HOPS buys: the SAME handle built with the flag (int8 matrix-core channelizer, csrc/channelizer_dft_wide.hip) and without it (the
 wavefront FFT), through airband_hip_process_device on HBM-resident I/Q, interleaved in one run.
 
-Per shape -- CS16 10 MS/s in both builds, CS16 6 MS/s and s8 10 MS/s in the WAVE_RATE 8000 build -- the largest power-of-two dongle count whose resident I/Q (two
+Per shape -- at fft 512: CS16 10 MS/s in both builds, CS16 6 MS/s and s8 10 MS/s in the WAVE_RATE 8000 build; on the k-segmented staging: CS16 10 MS/s at fft 2048 in
+both builds, s8 and CS16 10 MS/s at fft 4096 -- the largest power-of-two dongle count whose resident I/Q (two
 batches) fits a quarter of the GPU's memory; eight distinct dongle streams of the test plan (helpers.format_case) repeated over the fleet; REPS interleaved
 repetitions of BATCHES timed batches per side; the channelizer's HIP-event time from airband_hip_timing_totals; the bytes the reference consumes per launch (the
 windows only where hop >= window, else every byte once) over that time as a fraction of 8 TB/s; and, after the timed region, sampled dongles of the flagged
@@ -20,19 +21,21 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "oracle"), os.path.join(ROOT, "tests")]
 
-SHAPES = [("SFMT_S16", 10_000_000, 8000), ("SFMT_S16", 10_000_000, 16000), ("SFMT_S16", 6_000_000, 8000), ("SFMT_S8", 10_000_000, 8000)]
+# (sample format, sample rate, WAVE_RATE, fft_log); --shapes takes indices into this list
+SHAPES = [("SFMT_S16", 10_000_000, 8000, 9), ("SFMT_S16", 10_000_000, 16000, 9), ("SFMT_S16", 6_000_000, 8000, 9), ("SFMT_S8", 10_000_000, 8000, 9),
+          ("SFMT_S16", 10_000_000, 8000, 11), ("SFMT_S16", 10_000_000, 16000, 11), ("SFMT_S8", 10_000_000, 8000, 12), ("SFMT_S16", 10_000_000, 8000, 12)]
 DISTINCT = 8
 HBM_BYTES_PER_S = 8e12
 
 
-def run_shape(pkg, torch, sfmt_name, sample_rate, wave_rate, a):
+def run_shape(pkg, torch, sfmt_name, sample_rate, wave_rate, fft_log, a):
     import helpers
     import pyverify
 
     capi = pkg.capi
     sfmt = getattr(capi, sfmt_name)
-    devs8, iq8 = helpers.format_case(pkg, sfmt, 9, sample_rate, wave_rate, DISTINCT, 2)
-    with pkg.AirbandHip(devs8[:1], wave_rate=wave_rate, flags=capi.FLAG_FORCE_FFT) as probe:
+    devs8, iq8 = helpers.format_case(pkg, sfmt, fft_log, sample_rate, wave_rate, DISTINCT, 2)
+    with pkg.AirbandHip(devs8[:1], wave_rate=wave_rate, fft_log=fft_log, flags=capi.FLAG_FORCE_FFT) as probe:
         g = probe.geometry
         first, batch, look = int(g.first_batch_bytes), int(g.batch_bytes), int(g.lookahead_bytes)
     span = first + batch + look
@@ -49,14 +52,14 @@ def run_shape(pkg, torch, sfmt_name, sample_rate, wave_rate, a):
     torch.cuda.synchronize()
     devices = [devs8[d % DISTINCT] for d in range(n_dev)]
     hop_bytes = 2 * round(sample_rate / wave_rate) * capi.BYTES_PER_SAMPLE[sfmt]
-    win_bytes = 2 * 512 * capi.BYTES_PER_SAMPLE[sfmt]
+    win_bytes = 2 * (1 << fft_log) * capi.BYTES_PER_SAMPLE[sfmt]
     n_hops = batch // hop_bytes
     consumed = n_dev * (n_hops * win_bytes if hop_bytes >= win_bytes else n_hops * hop_bytes + win_bytes - hop_bytes)
     dongles = pyverify.sample_dongles(n_dev, 12)
     host = {d: iq8[d % DISTINCT].view(np.uint8) for d in dongles}
-    wide = pkg.AirbandHip(devices, wave_rate=wave_rate, flags=capi.FLAG_WIDE_HOPS | capi.FLAG_TRACE_SQUELCH)
-    base = pkg.AirbandHip(devices, wave_rate=wave_rate, flags=capi.FLAG_TRACE_SQUELCH)
-    spot = pyverify.SpotCheck(lambda d: devices[d], dongles, wave_rate=wave_rate)
+    wide = pkg.AirbandHip(devices, wave_rate=wave_rate, fft_log=fft_log, flags=capi.FLAG_WIDE_HOPS | capi.FLAG_TRACE_SQUELCH)
+    base = pkg.AirbandHip(devices, wave_rate=wave_rate, fft_log=fft_log, flags=capi.FLAG_TRACE_SQUELCH)
+    spot = pyverify.SpotCheck(lambda d: devices[d], dongles, wave_rate=wave_rate, fft_log=fft_log)
     try:
         assert wide.channelizer_name() == "dft_mfma_i8" and base.channelizer_name() == "fft_wave64", (wide.channelizer_reason(), base.channelizer_reason())
 
@@ -77,7 +80,7 @@ def run_shape(pkg, torch, sfmt_name, sample_rate, wave_rate, a):
                 t = hip.timing_totals(reset=True)
                 assert t["batches"] == a.batches
                 ms[name].append(t["channelizer_ms"] / a.batches)
-        worst = spot.compare(wide, trace=True, what="%s %d S/s WAVE_RATE %d, %d dongles" % (sfmt_name, sample_rate, wave_rate, n_dev))
+        worst = spot.compare(wide, trace=True, what="%s %d S/s WAVE_RATE %d fft %d, %d dongles" % (sfmt_name, sample_rate, wave_rate, 1 << fft_log, n_dev))
         opened = sum(int((r["axc"] == ord("*")).sum()) for r in spot.last)
     finally:
         spot.close()
@@ -87,9 +90,9 @@ def run_shape(pkg, torch, sfmt_name, sample_rate, wave_rate, a):
         torch.cuda.empty_cache()
     w, b = np.array(ms["wide"]), np.array(ms["base"])
     spread = float(max(w.max() - w.min(), b.max() - b.min()))
-    rec = dict(sfmt=sfmt_name, sample_rate=sample_rate, wave_rate=wave_rate, fft_size=512, hop_bytes=hop_bytes, window_bytes=win_bytes, dongles=n_dev, hops_per_batch=n_hops,
+    rec = dict(sfmt=sfmt_name, sample_rate=sample_rate, wave_rate=wave_rate, fft_size=1 << fft_log, segments=pkg.wide_hop_plan(1 << fft_log, hop_bytes, sfmt)[0], hop_bytes=hop_bytes, window_bytes=win_bytes, dongles=n_dev, hops_per_batch=n_hops,
                reps=a.reps, batches_per_rep=a.batches, wide_ms=[float(x) for x in w], fft_wave64_ms=[float(x) for x in b], wide_ms_median=float(np.median(w)),
-               fft_wave64_ms_median=float(np.median(b)), spread_ms=spread, speedup=float(np.median(b) / np.median(w)), faster_by_more_than_spread=bool(b.min() - w.max() > spread),
+               fft_wave64_ms_median=float(np.median(b)), spread_ms=spread, speedup=float(np.median(b) / np.median(w)), faster_by_more_than_spread=bool(b.min() - w.max() > spread), every_wide_rep_beats_every_fft_rep=bool(w.max() < b.min()),
                consumed_bytes_per_launch=int(consumed), stream_bytes_per_launch=int(n_dev * batch), roofline_fraction_wide=float(consumed / (np.median(w) * 1e-3) / HBM_BYTES_PER_S),
                roofline_fraction_fft_wave64=float(consumed / (np.median(b) * 1e-3) / HBM_BYTES_PER_S), spot_check=dict(dongles=len(dongles), batches=spot.batches, open_channels_last_batch=opened,
                                                                                                                  worst_audio_rms=float(worst["audio_rms"])))
