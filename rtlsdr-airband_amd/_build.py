@@ -36,6 +36,7 @@ HIP_SOURCES = {
     "channelizer_dft.hip": ["-O3"],
     "channelizer_dft_wide.hip": ["-O3"],  # the same contraction for hops beyond the contiguous staging (AIRBAND_HIP_FLAG_WIDE_HOPS)
     "channelizer_f32.hip": ["-O3"],
+    "channelizer_f32_wide.hip": ["-O3"],  # CF32 hops beyond channelizer_f32.hip's contiguous staging (AIRBAND_HIP_FLAG_WIDE_HOPS)
     "misc_kernels.hip": ["-O3", "-ffp-contract=off"],  # mixer sums: the reference's multiply-then-add, no FMA
     "demod.hip": ["-O3", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "gate.hip": ["-O3"],  # signal-gated collect: integer passes and a row copy

@@ -10,7 +10,7 @@ MOD_AM, MOD_NFM = 0, 1
 FM_FAST_ATAN2, FM_QUADRI_DEMOD = 0, 1
 AGC_EXTRA = 100
 FLAG_TRACE_SQUELCH, FLAG_RESERVED_2, FLAG_FORCE_FFT, FLAG_SERIAL_DEMOD, FLAG_PIPELINE, FLAG_REGROUP, FLAG_NO_REGROUP = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
-FLAG_WIDE_HOPS = 0x80  # the matrix-core channelizer also takes hops beyond 1 024 bytes (CS16: 1 280): devices above ~4 MS/s
+FLAG_WIDE_HOPS = 0x80  # the matrix-core channelizers also take hops beyond 1 024 bytes (CS16: 1 280; CF32: beyond the float kernel's tile, ~3 MS/s at WAVE_RATE 8000): devices above ~4 MS/s
 GATE_NEVER, GATE_SIGNAL, GATE_ALWAYS = 0, 1, 2  # airband_hip_set_output_gate
 
 BYTES_PER_SAMPLE = {SFMT_U8: 1, SFMT_S8: 1, SFMT_S16: 2, SFMT_F32: 4}

@@ -798,7 +798,7 @@ int prep_f32_tables(airband_hip_handle* h) {
             HIP_TRY(PREPARING, upload(h->d_ftab, p.ftab), AIRBAND_HIP_ENOMEM);
         }
         /* fft_size 4096 / 8192: partial sums between the launches of the window's segments (channelizer_f32.hip) */
-        if (f32_n_seg(p.fft_size) > 1) HIP_TRY(PREPARING, h->d_dft_partial.alloc((size_t)p.item_dev.size() * f32_partial_tiles(h->B + AB_AGC_EXTRA) * 64 * 4), AIRBAND_HIP_ENOMEM);
+        if (f32_n_seg(p.fft_size) > 1 || (h->use_f32_wide && f32_wide_plan(p.fft_size, p.dev[0].hop_samples, nullptr, nullptr) > 1)) HIP_TRY(PREPARING, h->d_dft_partial.alloc((size_t)p.item_dev.size() * f32_partial_tiles(h->B + AB_AGC_EXTRA) * 64 * 4), AIRBAND_HIP_ENOMEM);
     }
     h->plan.bfrag.clear(); h->plan.bfrag.shrink_to_fit();
     h->plan.ftab.clear(); h->plan.ftab.shrink_to_fit();
@@ -845,6 +845,26 @@ int prep_channelizer(airband_hip_handle* h) {
         if (rc != AIRBAND_HIP_OK) return rc;
         if (!h->use_f32) h->chan_reason = "coefficient tables past their byte budget";
     }
+    /* CF32 hops beyond the contiguous staging of channelizer_f32.hip (a tile of 15 hops + a window no longer fits its registers or LDS: above ~3 MS/s at WAVE_RATE
+     * 8000): the row staging of channelizer_f32_wide.hip for handles that ask for it -- same tables, same contraction, whatever the hop.  Inside f32_supported()'s
+     * limits f32_wide_plan() returns -1 and the flag changes nothing. */
+    h->use_f32_wide = false;
+    if (!h->use_dft && !h->use_f32 && !force_fft && sfmt == AIRBAND_SFMT_F32 && h->chan_reason.empty()) {
+        const int wide_seg = f32_wide_plan(p.fft_size, p.dev[0].hop_samples, nullptr, nullptr);
+        if (wide_seg >= 0 && !(h->flags & AIRBAND_HIP_FLAG_WIDE_HOPS)) {
+            h->chan_reason = "hop " + std::to_string(hop_b) + " bytes: beyond the float channelizer's tile; AIRBAND_HIP_FLAG_WIDE_HOPS not set";
+        } else if (wide_seg == 0) {
+            h->chan_reason = "wide hops: CF32 fft " + std::to_string(p.fft_size) + " has no staging plan";
+        } else if (wide_seg > 0) {
+            h->use_f32 = h->use_f32_wide = true;
+            const int rc = prep_f32_tables(h);
+            if (rc != AIRBAND_HIP_OK) return rc;
+            if (!h->use_f32) {
+                h->use_f32_wide = false;
+                h->chan_reason = "coefficient tables past their byte budget";
+            }
+        }
+    }
     if (!h->use_dft && !h->use_f32 && h->chan_reason.empty()) /* no matrix-core kernel takes the shape at all */
         h->chan_reason = sfmt == AIRBAND_SFMT_F32 ? "CF32 shape outside the float matrix-core channelizer's limits"
                                                   : "hop " + std::to_string(hop_b) + " bytes, fft " + std::to_string(p.fft_size) + ": outside the matrix-core channelizer's shapes";
@@ -852,7 +872,9 @@ int prep_channelizer(airband_hip_handle* h) {
         const size_t lds = fft_lds_bytes(p.fft_log, p.dev[0].hop_samples, p.dev[0].bytes_per_sample);
         if (lds > 160 * 1024) /* e.g. F32 at 20 MS/s: a 16-hop tile of raw samples does not fit a CU's LDS */
             return fail(PREPARING, AIRBAND_HIP_EBADSIZE,
-                        "sample_rate x bytes_per_sample too large for the FFT channelizer's LDS tile (" + std::to_string(lds) + " > 163840 bytes)");
+                        "sample_rate x bytes_per_sample too large for the FFT channelizer's LDS tile (" + std::to_string(lds) + " > 163840 bytes)" +
+                            (sfmt == AIRBAND_SFMT_F32 && !force_fft && !(h->flags & AIRBAND_HIP_FLAG_WIDE_HOPS) && f32_wide_plan(p.fft_size, p.dev[0].hop_samples, nullptr, nullptr) > 0
+                                 ? "; AIRBAND_HIP_FLAG_WIDE_HOPS not set (with it the float matrix-core channelizer takes this shape)" : ""));
     }
     return AIRBAND_HIP_OK;
 }
@@ -912,6 +934,14 @@ int airband_hip_dft_selftest(const airband_hip_config* cfg, int32_t windows, dou
         build_dft_tables(plan);
         build_f32_tables(plan);
         *max_rel_err = f32_table_selftest(plan, windows < 1 ? 1 : windows);
+        return AIRBAND_HIP_OK;
+    }
+    /* CF32 beyond those limits, flagged: the same tables in the order channelizer_f32_wide.hip contracts them (prep_channelizer()'s rule, f32_wide_plan()) */
+    if (plan.uniform_hop && plan.dev[0].sfmt == AIRBAND_SFMT_F32 && (cfg->flags & AIRBAND_HIP_FLAG_WIDE_HOPS) &&
+        f32_wide_plan(plan.fft_size, plan.dev[0].hop_samples, nullptr, nullptr) > 0) {
+        build_dft_tables(plan);
+        build_f32_tables(plan);
+        *max_rel_err = f32_table_selftest(plan, windows < 1 ? 1 : windows, f32_wide_seg_size(plan.fft_size));
         return AIRBAND_HIP_OK;
     }
     /* the tables do not depend on the hop; whether a flagged handle takes the wide-hop kernel is prep_channelizer()'s rule, dft_wide_plan() */
@@ -1174,7 +1204,8 @@ static int launch_front(airband_hip_handle* h, const void* d_iq, size_t stride_b
         }
     }
     (void)hipEventRecord(ev[0], s);
-    if (h->use_f32) launch_channelizer_f32(f32_args(h, d_iq, stride_bytes, r), s);
+    if (h->use_f32_wide) launch_channelizer_f32_wide(f32_args(h, d_iq, stride_bytes, r), s);
+    else if (h->use_f32) launch_channelizer_f32(f32_args(h, d_iq, stride_bytes, r), s);
     else if (h->use_wide) launch_channelizer_dft_wide(dft_args(h, d_iq, stride_bytes, r), s);
     else if (h->use_dft) launch_channelizer_dft(dft_args(h, d_iq, stride_bytes, r), s);
     else launch_channelizer_fft(fft_args(h, d_iq, stride_bytes, h->row0_front, r, 0), s);
@@ -1200,9 +1231,9 @@ static int process_batch(airband_hip_handle* h, const void* d_iq, size_t stride_
     while (al > 2 && (h->hop_bytes % (int64_t)al) != 0) al >>= 1;
     if (al < (uintptr_t)(2 * h->plan.dev[0].bytes_per_sample)) al = (uintptr_t)(2 * h->plan.dev[0].bytes_per_sample);
     const uintptr_t need = al - 1;
-    if (h->use_f32 && ((((uintptr_t)d_iq) | (uintptr_t)stride_bytes) & 15))
+    if (h->use_f32 && !h->use_f32_wide && ((((uintptr_t)d_iq) | (uintptr_t)stride_bytes) & 15))
         return fail(h, AIRBAND_HIP_EINVAL, "d_iq and stride_bytes must be multiples of 16 (the channelizer fetches 16 bytes per lane)");
-    if (h->use_dft && ((((uintptr_t)d_iq) | (uintptr_t)stride_bytes) & need))
+    if ((h->use_dft || h->use_f32_wide) && ((((uintptr_t)d_iq) | (uintptr_t)stride_bytes) & need)) /* (CF32 wide hops: 16, or 8 at hops of an odd number of samples) */
         return fail(h, AIRBAND_HIP_EINVAL, (h->hop_bytes % 16) == 0 ? "d_iq and stride_bytes must be multiples of 16 (the channelizer fetches 16 bytes per lane)"
                                                                     : "d_iq and stride_bytes must be multiples of the largest power of two (up to 16) that divides the hop's bytes");
     if (h->run_ahead && !stream && run_ahead_ok) {
@@ -1663,6 +1694,14 @@ const char* airband_hip_channelizer_name(const airband_hip_handle* h) {
 const char* airband_hip_channelizer_reason(const airband_hip_handle* h) { return h ? h->chan_reason.c_str() : ""; }
 
 int64_t airband_hip_wide_hop_lds_bytes(int32_t fft_size, int32_t hop_bytes, int32_t sample_format) { return dft_wide_lds(fft_size, hop_bytes, sample_format); }
+
+int airband_hip_wide_hop_plan_f32(int32_t fft_size, int32_t hop_samples, int32_t* segments, int64_t* lds_bytes) {
+    int seg = 0, lds = 0;
+    if (f32_wide_plan(fft_size, hop_samples, &seg, &lds) <= 0) return AIRBAND_HIP_EBADSIZE; /* inside the ordinary kernel's limits, or no plan */
+    if (segments) *segments = seg;
+    if (lds_bytes) *lds_bytes = lds;
+    return AIRBAND_HIP_OK;
+}
 
 int airband_hip_wide_hop_plan(int32_t fft_size, int32_t hop_bytes, int32_t sample_format, int32_t* segments, int64_t* lds_bytes) {
     int lds = 0;

@@ -559,7 +559,9 @@ void launch_one(const ChannelizerArgs& a, hipStream_t stream) {
     /* a spectrum-only launch (ONE hop and one wavefront per dongle, on a side stream beside the matrix-core channelizer: airband_hip.cpp,
      * launch_last_hop_spectrum) stays on the shuffle kernel at every size: it needs no exchange buffer, so its 6 KiB workgroups fit beside the channelizer's
      * 144 KiB per CU, and one transform per dongle and batch is no time either way */
-    const size_t lds = a.spectrum_only ? (size_t)fft_raw_bytes(a.fft_log, a.hop_samples, a.bytes_per_sample) : fft_lds_bytes(a.fft_log, a.hop_samples, a.bytes_per_sample);
+    /* (sized for the ONE window it stages, not for a tile of 16 hops: on wide-hop handles -- CF32 at 20 MS/s: 300 KiB a tile -- the tile would not fit a CU) */
+    const size_t lds = a.spectrum_only ? (size_t)(((((long)((a.n_hops < HOPS_PER_TILE ? a.n_hops : HOPS_PER_TILE) - 1) * a.hop_samples + (1L << a.fft_log)) * 2 * a.bytes_per_sample + 32) + 15) & ~15L)
+                                       : fft_lds_bytes(a.fft_log, a.hop_samples, a.bytes_per_sample);
     const long blocks = (long)tiles * a.n_dev;
     /* wide formats at high sample rates: opt in to the CU's full 160 KiB (prepare() has checked the upper bound) */
     /* (should the runtime refuse, the launch below fails with hipErrorInvalidValue and the batch driver reports it: airband_hip.cpp checks hipGetLastError) */

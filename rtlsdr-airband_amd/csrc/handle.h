@@ -184,6 +184,7 @@ struct airband_hip_handle {
     int ct_stride = 0;
     /* matrix-core channelizer */
     bool use_f32 = false;          /* CF32 dongles on the float32 matrix pipe (channelizer_f32.hip) */
+    bool use_f32_wide = false;     /* use_f32, staged by channelizer_f32_wide.hip (AIRBAND_HIP_FLAG_WIDE_HOPS and a hop beyond f32_supported()'s limits) */
     airband::DevBuf<float> d_ftab;
     bool use_dft = false;
     bool use_wide = false;         /* use_dft, staged by channelizer_dft_wide.hip (AIRBAND_HIP_FLAG_WIDE_HOPS and a hop beyond dft_supported()'s limits) */

@@ -81,7 +81,7 @@ struct F32Args {
     int n_items, splits, fft_size;
     int hop_bytes, pad, lds_per_buf; /* bytes per hop (8 x hop_samples), padding per hop in the staged image, bytes per staging buffer */
     int row0, ring_rows, first_row, n_hops;
-    int seg, n_seg;         /* fft_size 4096 / 8192: window segment of this launch / segments per window (set by launch_channelizer_f32) */
+    int seg, n_seg;         /* fft_size 4096 / 8192 (wide hops: 2048 and up): window segment of this launch / segments per window (set by launch_channelizer_f32[_wide]) */
     float4* partial;        /* those sizes only: [n_items][f32_partial_tiles() tiles][64] partial sums between the segments' launches */
 };
 
@@ -221,6 +221,14 @@ bool f32_supported(int fft_size, int hop_samples, int sfmt);
 int f32_pad_bytes(int hop_samples);
 int f32_lds_per_buf(int fft_size, int hop_samples);
 void launch_channelizer_f32(const F32Args& a, hipStream_t stream);
+/* CF32 wide hops (channelizer_f32_wide.hip, AIRBAND_HIP_FLAG_WIDE_HOPS): a tile is staged as 16 rows of one window segment each (f32_wide_map.h: geometry and address
+ * map), one image in LDS and the next tile in registers.  THE rule by which a flagged CF32 handle takes it: the smallest power-of-two number of equal window segments
+ * whose image and exchange area fit a CU's 163 840 bytes -- 1 up to fft 1024, then segments of 1 024 samples, one launch each through F32Args::partial.  Returns that
+ * number (*segments the same, *lds_bytes the dynamic LDS of a launch; both may be null); 0: no plan; -1: not a wide shape (inside f32_supported()'s limits, or no fft
+ * size of the float kernels). */
+int f32_wide_plan(int fft_size, int hop_samples, int* segments, int* lds_bytes);
+int f32_wide_seg_size(int fft_size); /* window samples per segment of that plan */
+void launch_channelizer_f32_wide(const F32Args& a, hipStream_t stream);
 void launch_emit_iq(const EmitArgs& a, hipStream_t stream);
 void launch_axc(const ChanConst* cc, const ChanState* cs, const int* slot_to_ext, uint8_t* out_axc, int n_slots, hipStream_t stream);
 void launch_mix(const MixArgs& a, hipStream_t stream);

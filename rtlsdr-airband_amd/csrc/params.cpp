@@ -492,8 +492,10 @@ void build_dft_tables(Plan& p, bool host_private) {
 /* host-only: the float tables of channelizer_f32.hip contracted the way the kernel contracts them -- per wave (piece) 64 (32) instructions of K = 4, lane
  * l supplying stream value 16 (s / 4) + 4 (l >> 4) + s % 4 of its piece against table entry [piece][s][l], partial sums of a piece in float, the four pieces
  * added in float -- against the double-precision sum, on pseudo-random windows; largest error relative to the RMS of the exact values */
-double f32_table_selftest(const Plan& p, int windows) {
-    const int N = p.fft_size, SEG = N < 2048 ? N : 2048, NSEG = N / SEG, NW = N <= 512 ? 4 : 8, VPP = 2 * SEG / NW, KW = VPP / 4;
+/* wide_seg > 0: the order of channelizer_f32_wide.hip -- segments of wide_seg samples (kernels.h f32_wide_seg_size), four waves up to 512 samples, eight beyond.  The
+ * table is the same: linear in the contraction index, whatever the cut into segments and pieces */
+double f32_table_selftest(const Plan& p, int windows, int wide_seg) {
+    const int N = p.fft_size, SEG = wide_seg > 0 ? wide_seg : N < 2048 ? N : 2048, NSEG = N / SEG, NW = (wide_seg > 0 ? SEG : N) <= 512 ? 4 : 8, VPP = 2 * SEG / NW, KW = VPP / 4;
     uint64_t rng = 0x9E3779B97F4A7C15ull;
     auto next = [&]() {
         rng ^= rng << 13; rng ^= rng >> 7; rng ^= rng << 17;

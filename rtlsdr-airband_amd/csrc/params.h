@@ -80,7 +80,7 @@ float div_const_reciprocal(float g);
 void channel_constants(const Plan& plan, int ext_index, double* out16);
 /* host-only: largest error (relative to the RMS of the exact values) of the matrix-core coefficient tables on `windows` pseudo-random windows per work item */
 double dft_table_selftest(const Plan& plan, int windows);
-double f32_table_selftest(const Plan& plan, int windows);
+double f32_table_selftest(const Plan& plan, int windows, int wide_seg = 0); /* wide_seg > 0: in the order of channelizer_f32_wide.hip, segments of that many samples */
 
 }  // namespace airband
 #endif
