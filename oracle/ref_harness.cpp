@@ -590,6 +590,12 @@ int refh_run_device(int d, const unsigned char* iq, size_t nbytes, int max_batch
         /* feed at most one hop-batch at a time so that at most one output batch can complete */
         size_t room = in->buf_size - 1 - refh_available(in);
         size_t n = std::min(nbytes - off, std::min(room, bps * (size_t)WAVE_BATCH / 4));
+        /* The reference refreshes the copy of the ring's head behind buf_size -- what a window that crosses the ring's end reads -- only from the append that
+         * wraps, and only with the bytes THAT append brings past the wrap (src/input-helpers.cpp:48-51).  A chunk that ends less than a window behind the wrap
+         * leaves the rest of the copy as it was a lap ago (zeros on the first lap): at windows of 16 KiB (CS16 fft 4096) the quarter-batch chunks of this loop did
+         * end there.  Such a chunk stops at the wrap; the next one starts at bufe == 0 and brings the whole window. */
+        const size_t to_end = in->buf_size - in->bufe, win = 2 * (size_t)in->bytes_per_sample * fft_size;
+        if (n > to_end && n - to_end < win) n = to_end;
         if (n == 0) break;
         circbuffer_append(in, const_cast<unsigned char*>(iq) + off, n);
         off += n;

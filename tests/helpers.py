@@ -70,6 +70,22 @@ def convert_format(iq_u8, sfmt, capi, s16_gain=200.0):
     return (x / 127.5).astype(np.float32)
 
 
+def _format_plan(capi, sfmt, sample_rate, wave_rate, n_dev):
+    """format_case's channels (the BASELINE plan scaled into the dongle's passband) and its per-dongle CS16 gains."""
+    chans, _ = sg.baseline_plan(mixed=wave_rate == 16000)
+    scale = sample_rate / 2_560_000
+    for c in chans:  # keep every channel inside the dongle's (possibly narrower) passband
+        c["frequency"] = 120_000_000 + int((c["frequency"] - 120_000_000) * scale * 0.8)
+    gains = [200.0 if d % 2 == 0 else 50.0 for d in range(n_dev)] if sfmt == capi.SFMT_S16 else [1.0] * n_dev
+    return chans, gains
+
+
+def _format_devices(capi, sfmt, sample_rate, wave_rate, n_dev):
+    chans, gains = _format_plan(capi, sfmt, sample_rate, wave_rate, n_dev)
+    return [dict(channels=[dict(c) for c in chans], sample_rate=sample_rate, sfmt=sfmt, fullscale=0.0 if sfmt != capi.SFMT_S16 else 127.5 * gains[d])
+            for d in range(n_dev)]
+
+
 def format_case(pkg, sfmt, fft_log, sample_rate, wave_rate, n_dev, n_batches, first_dongle=0):
     """n_dev dongles of the BASELINE channel plan re-expressed for another sample format / fft size / sample rate: channels scaled
     into the dongle's passband, every transmitter placed where the reference LOOKS -- its bin formula divides by the integer
@@ -78,11 +94,7 @@ def format_case(pkg, sfmt, fft_log, sample_rate, wave_rate, n_dev, n_batches, fi
     the same signal at a quarter of the amplitude and say so in input->fullscale (src/rtl_airband.cpp:403).
     Returns (devices, iq list in the format's dtype)."""
     capi = pkg.capi
-    mixed = wave_rate == 16000
-    chans, _ = sg.baseline_plan(mixed=mixed)
-    scale = sample_rate / 2_560_000
-    for c in chans:  # keep every channel inside the dongle's (possibly narrower) passband
-        c["frequency"] = 120_000_000 + int((c["frequency"] - 120_000_000) * scale * 0.8)
+    chans, gains = _format_plan(capi, sfmt, sample_rate, wave_rate, n_dev)
     carriers = []
     probe = [dict(channels=[dict(c) for c in chans], sample_rate=sample_rate)]
     n_fft = 1 << fft_log
@@ -90,13 +102,120 @@ def format_case(pkg, sfmt, fft_log, sample_rate, wave_rate, n_dev, n_batches, fi
         b = int(pkg.derive_constants(probe, k, wave_rate=wave_rate, fft_log=fft_log)[0])
         off = (b if b < n_fft // 2 else b - n_fft) * sample_rate / n_fft
         carriers.append(sg.make_carrier(off, sample_rate, kind=c["modulation"], ctcss_hz=c["ctcss_freq"], key_slot=k, key_period_s=0.5, key_on_s=0.3, key_slot_s=0.04))
-    gains = [200.0 if d % 2 == 0 else 50.0 for d in range(n_dev)] if sfmt == capi.SFMT_S16 else [1.0] * n_dev
-    devices = [dict(channels=[dict(c) for c in chans], sample_rate=sample_rate, sfmt=sfmt, fullscale=0.0 if sfmt != capi.SFMT_S16 else 127.5 * gains[d])
-               for d in range(n_dev)]
+    devices = _format_devices(capi, sfmt, sample_rate, wave_rate, n_dev)
     hop = round(sample_rate / wave_rate)
     n_samples = (n_batches * (wave_rate // 8) + 100) * hop + n_fft + 8  # + 8: hops of 300 / 600 bytes are staged in whole 16-byte pieces
     iq = [convert_format(sg.generate_u8(first_dongle + d, 0, n_samples, carriers), sfmt, capi, gains[d]) for d in range(n_dev)]
     return devices, iq
+
+
+# ---- wide hops at every kernel variant (tests/test_wide_variants.py, tests/test_gpu_wide_variants.py) ------------------------------------------------
+# Dongle 1 of a sweep case: channel offsets as fractions of the sample rate.  Five lie below the centre frequency (bins in the upper half of the spectrum), channels
+# 4 and 5 share a frequency and so a bin, eleven channels are two column sets of the coefficient tables with the second holding three (a partly filled group).
+WIDE_PLAN_B = [-0.41, -0.33, -0.21, -0.12, 0.07, 0.07, 0.16, 0.24, 0.31, 0.38, -0.05]
+WIDE_PLAN_B_IQ_CHANNEL = 2   # an AM channel with has_iq_outputs: magnitude and raw I/Q stored from one lane
+# Tone amplitude (u8 counts) and noise deviation of dongle 1: ten tones of amplitude a at unrelated frequencies and phases (the eleventh is a weak one, below) add
+# up to a deviation of sqrt(10 a^2 / 2 + s^2) = 49.5 per rail, and the rails (+-127.5) are 2.57 of those away: about 1 % of the samples of either rail clip
+WIDE_TONE_B, WIDE_NOISE_B = 21.7, 10.0
+WIDE_TONE_A, WIDE_NOISE_A = 8.0, 6.0   # dongle 0: eight tones, 23.4 per rail -- 5.4 deviations inside the rails
+# An AM channel that stores raw I/Q has its magnitudes REWRITTEN IN PLACE by stage 2 while its squelch sees a signal (|I/Q of 100 hops earlier|: src/rtl_airband.cpp,
+# the oracle's stage2_channel; the library does the same in its rings), so what read_bins() returns for it is stage 1's output only while the squelch stays shut.
+# Such a channel therefore gets a manual squelch level (-1 dBFS = 0.696 sqrt(fft size) in |bin| units, whatever the format) and a tone that stays at half of it:
+# a tone of a u8 counts reads 0.00216 x fft size x a, so a = 161 / sqrt(fft size); the noise in a bin is a twentieth of the level at these deviations.
+WIDE_SHUT_DBFS = -1
+
+
+def shut_squelch_tone(n_fft):
+    return 161.0 / float(np.sqrt(n_fft))
+
+
+def wide_channel(frequency, modulation=0, has_iq_outputs=0):
+    """(an AM channel with raw-I/Q outputs gets the manual squelch level of WIDE_SHUT_DBFS: see there)"""
+    return dict(frequency=int(frequency), modulation=modulation, afc=0, squelch_threshold_dbfs=WIDE_SHUT_DBFS if has_iq_outputs and modulation == 0 else 0,
+                squelch_snr_threshold_db=-1.0, notch_freq=0.0, notch_q=0.0, ctcss_freq=0.0, bandwidth_hz=0, ampfactor=1.0, tau_us=-1, has_iq_outputs=has_iq_outputs)
+
+
+def tone_stream(pkg, device, fft_log, wave_rate, n_samples, rng, *, noise, levels, gain=1.0):
+    """One dongle's I/Q in its sample format: Gaussian noise plus a steady tone per channel within 0.3 bins of the bin the reference LOOKS at (the library's own
+    constants: src/config.cpp:666-667), levels[k] u8 counts high, rounded and clipped to the u8 rails and then re-expressed (convert_format).  Returns (iq, the
+    fraction of u8 values on a rail)."""
+    n_fft = 1 << fft_log
+    t = np.arange(n_samples, dtype=np.float64)
+    z = rng.normal(0.0, noise, (n_samples, 2)) @ np.array([1.0, 1j])
+    for k in range(len(device["channels"])):
+        b = int(pkg.derive_constants([device], k, wave_rate=wave_rate, fft_log=fft_log)[0])
+        f = ((b if b < n_fft // 2 else b - n_fft) + float(rng.uniform(-0.3, 0.3))) / n_fft
+        z += levels[k] * np.exp(2j * np.pi * (f * t + rng.random()))
+    u8 = np.empty(2 * n_samples, np.uint8)
+    u8[0::2] = np.clip(np.round(z.real + 127.5), 0, 255)
+    u8[1::2] = np.clip(np.round(z.imag + 127.5), 0, 255)
+    railed = float(np.mean((u8 == 0) | (u8 == 255)))
+    return convert_format(u8, device["sfmt"], pkg.capi, gain), railed
+
+
+def wide_devices(capi, sfmt, sample_rate, wave_rate, n_dev):
+    """The dongles of wide_case(), without streams."""
+    devices = _format_devices(capi, sfmt, sample_rate, wave_rate, n_dev)
+    for d in range(1, n_dev, 2):
+        devices[d]["channels"] = [wide_channel(120_000_000 + int(f * sample_rate), modulation=1 if wave_rate == 16000 and k % 2 == 1 else 0,
+                                               has_iq_outputs=1 if k == WIDE_PLAN_B_IQ_CHANNEL else 0) for k, f in enumerate(WIDE_PLAN_B)]
+    return devices
+
+
+def wide_case(pkg, sfmt, fft_log, sample_rate, wave_rate, n_dev, n_batches, first_dongle=0, only=None, info=None):
+    """A wide-hop configuration with more than one plan shape on the handle.  Even dongles: format_case's plan (the eight BASELINE channels scaled into the passband).
+    Odd dongles: the eleven channels of WIDE_PLAN_B -- two column sets, the second partly filled; bins in the upper half; two channels on one bin; one AM channel with
+    raw-I/Q outputs (its squelch held shut: WIDE_SHUT_DBFS); WAVE_RATE 16000: odd channels NFM (raw I/Q stored, no magnitude).  CS16: odd dongles at a quarter of the full scale, as format_case.
+    Input: tone_stream() -- even dongles well inside the rails, odd dongles driven into them on about 1 % of the samples (info["railed"][d] = the fraction).
+    only: the dongles to make streams for (the others get None).  Returns (devices, iq list in the format's dtype)."""
+    capi = pkg.capi
+    devices = wide_devices(capi, sfmt, sample_rate, wave_rate, n_dev)
+    hop, n_fft = round(sample_rate / wave_rate), 1 << fft_log
+    n_samples = (n_batches * (wave_rate // 8) + 100) * hop + n_fft + 8
+    iq, railed = [], []
+    for d in range(n_dev):
+        if only is not None and d not in only:
+            iq.append(None)
+            railed.append(None)
+            continue
+        rng = np.random.default_rng([7100, first_dongle + d, int(sfmt), fft_log, sample_rate, wave_rate])
+        tone, noise = (WIDE_TONE_B, WIDE_NOISE_B) if d % 2 else (WIDE_TONE_A, WIDE_NOISE_A)
+        gain = devices[d]["fullscale"] / 127.5 if sfmt == capi.SFMT_S16 else 1.0
+        levels = [shut_squelch_tone(n_fft) if c["squelch_threshold_dbfs"] == WIDE_SHUT_DBFS else tone for c in devices[d]["channels"]]
+        x, r = tone_stream(pkg, devices[d], fft_log, wave_rate, n_samples, rng, noise=noise, levels=levels, gain=gain)
+        iq.append(x)
+        railed.append(r)
+    if info is not None:
+        info["railed"] = railed
+    return devices, iq
+
+
+def feed_zero_copy(hip, iq, n_batches, misalign):
+    """The construction of tests/test_gpu_wide_hops.py::test_zero_copy_spans_sized_to_the_byte for any alignment: every batch through process_device from one
+    allocation in which dongle 0's span starts on the first byte, dongle d's d x misalign bytes (mod 16) behind a 16-byte boundary, and the last dongle's span ends
+    where the allocation ends -- batch_bytes + lookahead_bytes and not a byte more, so a read past a span is a read past the allocation.
+    Yields dict(waveout, axc, w, q) per batch."""
+    import torch
+
+    g = hip.geometry
+    n_dev, pos = len(iq), 0
+    for b in range(n_batches):
+        nb = int(g.first_batch_bytes if b == 0 else g.batch_bytes)
+        span = nb + int(g.lookahead_bytes)
+        stride = (span + 15) // 16 * 16 + misalign
+        buf = torch.empty(((n_dev - 1) * stride + span,), dtype=torch.uint8, device="cuda")
+        assert buf.data_ptr() % 16 == 0 and stride % 16 == misalign % 16
+        for d in range(n_dev):
+            raw = iq[d].view(np.uint8)[pos:pos + span]
+            assert len(raw) == span
+            buf[d * stride:d * stride + span] = torch.from_numpy(raw.copy()).cuda()
+        torch.cuda.synchronize()
+        hip.process_device(buf.data_ptr(), stride)
+        out = hip.collect()
+        w, q = hip.read_bins()
+        yield dict(waveout=out["waveout"].copy(), axc=out["axc"].copy(), w=w.copy(), q=q.copy())
+        pos += nb
+        del buf
 
 
 def wait_for_gpu_memory(nbytes: int, timeout_s: float = 60.0) -> None:

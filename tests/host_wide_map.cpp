@@ -8,7 +8,9 @@ using namespace airband;
 
 namespace {
 
-// (bytes per window piece, pieces, segments): CS16 fft 2048, u8 / s8 fft 4096, CS16 fft 4096, and CS16 fft 512 as the one-segment control
+// (bytes per window piece, pieces, segments): CS16 fft 2048, u8 / s8 fft 4096, CS16 fft 4096, and CS16 fft 512 as the one-segment control; then every other shape
+// launch_channelizer_dft_wide() can select -- u8 / s8 fft 256, u8 / s8 fft 512, CS16 fft 256 (the same map, walked with CS16 hops), u8 / s8 fft 1024, CS16 fft 1024,
+// u8 / s8 fft 2048
 template <class F>
 int with_shape(int shape, F&& f) {
     switch (shape) {
@@ -16,6 +18,12 @@ int with_shape(int shape, F&& f) {
     case 1: return f(WideMap<1024, 8, 2>{});
     case 2: return f(WideMap<2048, 8, 4>{});
     case 3: return f(WideMap<2048, 1, 1>{});
+    case 4: return f(WideMap<512, 1, 1>{});
+    case 5: return f(WideMap<1024, 1, 1>{});
+    case 6: return f(WideMap<1024, 1, 1>{});
+    case 7: return f(WideMap<1024, 2, 1>{});
+    case 8: return f(WideMap<2048, 2, 1>{});
+    case 9: return f(WideMap<1024, 4, 1>{});
     default: return -1;
     }
 }

@@ -16,6 +16,7 @@ import pytest
 import helpers
 import pyoracle
 import pyref
+import test_wide_variants
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
@@ -122,8 +123,10 @@ def test_map_geometry(pkg, built, wm):
         assert pkg.wide_hop_plan_f32(fft, 2000) == (seg, total)   # the kernel's header and the library's plan are one
 
 
-# the GPU shapes, one even and one odd hop more per fft size (the first refused hops among them), and the segmented sizes
-MAP_SHAPES = sorted(set([(1 << f, h) for (f, _, _, _), h in zip(GPU_CASES, HOPS)] + [(256, 393), (256, 700), (512, 376), (512, 625), (1024, 751), (1024, 1250), (2048, 625), (4096, 1250)]))
+# the GPU shapes, one even and one odd hop more per fft size (the first refused hops among them), the segmented sizes, and every CF32 shape of the variant sweep
+# (tests/test_wide_variants.py: the first wide hop of each parity at every fft size, 8192 and its eight segment launches included)
+MAP_SHAPES = sorted(set([(1 << f, h) for (f, _, _, _), h in zip(GPU_CASES, HOPS)] + [(256, 393), (256, 700), (512, 376), (512, 625), (1024, 751), (1024, 1250), (2048, 625), (4096, 1250)]
+                        + [(1 << n, r // w) for f, n, r, w in test_wide_variants.SWEEP_CASES if f == "SFMT_F32"]))
 
 
 @pytest.mark.parametrize("fft,hop", MAP_SHAPES)

@@ -135,6 +135,15 @@ def test_tables_selftest_follows_the_plan(pkg, built):
 
 # shape id of tests/host_wide_map.cpp -> (bytes per window piece, pieces, segments, the alignment-class hops of the format: AL = 16 / 8 / 4 [/ 2])
 MAP_SHAPES = {0: (2048, 4, 2, (4000, 5000, 2500)), 1: (1024, 8, 2, (2000, 1500, 1250)), 2: (2048, 8, 4, (4000, 5000, 2500)), 3: (2048, 1, 1, (4000, 5000, 2500))}
+# ... and the one-segment shapes of every other (format, fft size) launch_channelizer_dft_wide() selects, each at the FIRST wide hop of every alignment class
+# (tests/test_wide_variants.py: the edge of the selection) -- u8 / s8: 1 040 / 1 032 / 1 028 / 1 026 bytes (AL = 16 / 8 / 4 / 2), CS16: 1 296 / 1 288 / 1 284
+WIDE_HOPS_8BIT, WIDE_HOPS_CS16 = (1040, 1032, 1028, 1026), (1296, 1288, 1284)
+MAP_SHAPES.update({4: (512, 1, 1, WIDE_HOPS_8BIT),      # u8 / s8 fft 256
+                   5: (1024, 1, 1, WIDE_HOPS_8BIT),     # u8 / s8 fft 512
+                   6: (1024, 1, 1, WIDE_HOPS_CS16),     # CS16 fft 256
+                   7: (1024, 2, 1, WIDE_HOPS_8BIT),     # u8 / s8 fft 1024
+                   8: (2048, 2, 1, WIDE_HOPS_CS16),     # CS16 fft 1024
+                   9: (1024, 4, 1, WIDE_HOPS_8BIT)})    # u8 / s8 fft 2048
 
 
 @pytest.fixture(scope="module")
