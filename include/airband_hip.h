@@ -427,6 +427,40 @@ int airband_hip_collect_active(airband_hip_handle* h, int64_t* n_active, int32_t
  * [max_rows][wave_batch], d_iq_rows [max_rows][2*wave_batch] or NULL on a handle without raw-I/Q outputs.  Any out-pointer may be NULL. */
 int airband_hip_device_active(airband_hip_handle* h, int32_t** d_index, int32_t** d_count, float** d_rows, float** d_iq_rows);
 
+/* ---- band scope -------------------------------------------------------------------------------------------------------------------
+ * The channelizer keeps the few bins of every transform that carry a configured channel.  A handle with a band scope also keeps, per selected dongle and batch,
+ * the POWER SPECTRUM OF THE WHOLE BAND over a handful of the batch's FFT windows: what the band looks like, where to put channels, an overloaded or deaf
+ * front end, a carrier no channel is configured for.  (The reference has no counterpart: its TUI "waterfall" shows the configured channels' levels only.)
+ * Which windows.  With K = windows_per_batch, window j in [0, K) of a batch is the FFT window of that batch's NEW hop number (j * WAVE_BATCH) / K (integer
+ * division): hop 0 is the first row airband_hip_read_bins() returns for the batch; the first batch's AGC_EXTRA lead-in hops are never selected.
+ * Which values.  Bin k of a window is re^2 + im^2 of the transform the channelizer defines (reference: src/rtl_airband.cpp:316-351,402-460): the dongle's
+ * sample-to-float conversion and `fullscale`, the reference's window, unnormalised, natural bin order -- the indexing of airband_hip_channel_stats.bin, so the
+ * value in a channel's bin for the window of hop t is the square of the `wavein` row airband_hip_read_bins() returns at t (to float rounding).  AFC moves bins,
+ * not the transform: it does not move the scope.  MEAN is the arithmetic mean over the K windows, PEAK their maximum.  The summation order is fixed and no
+ * atomics are involved: two runs of one input give identical bits.
+ * Rows.  The selected dongles get dense rows in ascending dongle order.  A dongle switched off with airband_hip_device_enable() is skipped: its rows keep the
+ * values of the last batch it took part in.  The scope belongs to the batch whose results airband_hip_collect() would return -- on an AIRBAND_HIP_FLAG_PIPELINE
+ * handle it lags with them -- and is complete where they are (airband_hip_collect, airband_hip_synchronize, airband_hip_stream_wait_results cover it).
+ * airband_hip_process_bins() has no input to look at and leaves the scope as it is.  A handle without a scope allocates nothing for this, launches nothing and
+ * creates no stream or event. */
+#define AIRBAND_SCOPE_MEAN 0x1u   /* mean over the batch's selected windows of re^2 + im^2 */
+#define AIRBAND_SCOPE_PEAK 0x2u   /* maximum over the same windows */
+
+/* dev_mask [device_count]: non-zero = the dongle gets a row; NULL = every dongle.  windows_per_batch in 1 .. WAVE_BATCH.  traces: AIRBAND_SCOPE_* bits.  Before the
+ * first batch only (calling it again before then replaces the setting).  Validated before the device is touched: AIRBAND_HIP_EINVAL for a NULL handle,
+ * windows_per_batch out of range, traces that are 0 or hold an unknown bit, a mask that selects no dongle, a batch already enqueued; AIRBAND_HIP_ENOMEM when the
+ * buffers cannot be had -- the handle then runs on as it was. */
+int airband_hip_set_band_scope(airband_hip_handle* h, const uint8_t* dev_mask, int32_t windows_per_batch, uint32_t traces);
+
+/* The scope of the batch airband_hip_collect() would return, for dongles [first_dev, first_dev + n_dev) (dongle indices, not rows): mean and peak are HOST
+ * arrays [n_dev][fft_size]; either may be NULL.  Zeros for a dongle the mask did not select, and for a trace the scope does not keep.  Does not mark the batch
+ * as collected (like airband_hip_collect_channels).  AIRBAND_HIP_EAGAIN before any batch, AIRBAND_HIP_EINVAL on a handle without a scope. */
+int airband_hip_collect_band_scope(airband_hip_handle* h, int32_t first_dev, int32_t n_dev, float* mean, float* peak);
+
+/* Device-side views of the same (valid until the next process call) for consumers that stay on the GPU: d_mean, d_peak [rows][fft_size] (NULL for a trace the
+ * scope does not keep), d_row_of_dev [device_count]: a dongle's row, or -1.  Any out-pointer may be NULL. */
+int airband_hip_device_band_scope(airband_hip_handle* h, float** d_mean, float** d_peak, int32_t** d_row_of_dev);
+
 /* Makes `stream` (a hipStream_t of a GPU-side consumer, e.g. the stream an RCCL all-reduce of the mixer sums is issued on)
  * wait for the results of the batch the last process call completed -- no host synchronisation.  The consumer hands its
  * stream to the next airband_hip_process_device() call, which then orders the overwrite of the result buffers behind it. */

@@ -34,6 +34,7 @@ EXPORTS = [
     "airband_hip_comm_group_begin", "airband_hip_comm_group_end", "airband_hip_allreduce_mixers", "airband_hip_add_mixers", "airband_hip_comm_destroy", "airband_hip_clear_mixers", "airband_hip_set_signal_plan_shift", "airband_hip_regrouped",
     "airband_hip_prepare_scan", "airband_hip_set_freq_index", "airband_hip_freq_stats",
     "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
+    "airband_hip_set_band_scope", "airband_hip_collect_band_scope", "airband_hip_device_band_scope",
     "airband_hip_channelizer_reason", "airband_hip_wide_hop_lds_bytes", "airband_hip_schedule_info", "airband_hip_wide_hop_plan",
 ]
 # Exported entries whose names carry digits.  Kept apart from EXPORTS, which tests/test_abi.py compares with the header's names through a pattern of letters and
@@ -105,6 +106,9 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
+    for name, argtypes in capi.BAND_SCOPE_PROTOTYPES.items():
+        if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
+            getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
     L.airband_hip_device_results.argtypes = [vp] + [C.POINTER(vp)] * 6
     L.airband_hip_synchronize.argtypes = [vp]
@@ -348,6 +352,39 @@ class AirbandHip:
         ptrs = [C.c_void_p() for _ in range(4)]
         self._check(self.L.airband_hip_device_active(self.h, *[C.byref(p) for p in ptrs]))
         return {k: (p.value or 0) for k, p in zip(["index", "count", "rows", "iq_rows"], ptrs)}
+
+    def set_band_scope(self, mask=None, windows: int = 8, mean: bool = True, peak: bool = False):
+        """Band scope (airband_hip_set_band_scope): per batch and selected dongle, the power spectrum of the whole band over `windows` of the batch's FFT windows.
+        mask: one byte per dongle (None = every dongle).  Before the first batch."""
+        m = None
+        if mask is not None:
+            m = np.ascontiguousarray(mask, np.uint8)
+            if m.shape != (self.geometry.device_count,):
+                raise ValueError("mask needs one byte per dongle (%d), got shape %r" % (self.geometry.device_count, m.shape))
+        traces = (capi.SCOPE_MEAN if mean else 0) | (capi.SCOPE_PEAK if peak else 0)
+        self._check(self.L.airband_hip_set_band_scope(self.h, m.ctypes.data if m is not None else None, int(windows), traces))
+        self.scope_traces = traces
+
+    def collect_band_scope(self, first_dev: int = 0, n_dev: Optional[int] = None) -> dict:
+        """The scope of the batch collect() would return, for dongles [first_dev, first_dev + n_dev): dict(mean=[n_dev][fft_size], peak=...) with the traces
+        the scope keeps; zeros for dongles the mask did not select.  Repeatable: does not mark the batch as collected."""
+        n = self.geometry.device_count - first_dev if n_dev is None else int(n_dev)
+        traces = getattr(self, "scope_traces", capi.SCOPE_MEAN | capi.SCOPE_PEAK)
+        out = {}
+        if traces & capi.SCOPE_MEAN:
+            out["mean"] = np.empty((n, self.geometry.fft_size), np.float32)
+        if traces & capi.SCOPE_PEAK:
+            out["peak"] = np.empty((n, self.geometry.fft_size), np.float32)
+        self._check(self.L.airband_hip_collect_band_scope(self.h, int(first_dev), n, out["mean"].ctypes.data if "mean" in out else None,
+                                                          out["peak"].ctypes.data if "peak" in out else None))
+        return out
+
+    def device_band_scope(self) -> dict:
+        """Device pointers of the current scope (valid until the next process call): mean, peak [rows][fft_size] float32 (0 for a trace the scope does not keep),
+        row_of_dev [device_count] int32."""
+        ptrs = [C.c_void_p() for _ in range(3)]
+        self._check(self.L.airband_hip_device_band_scope(self.h, *[C.byref(p) for p in ptrs]))
+        return {k: (p.value or 0) for k, p in zip(["mean", "peak", "row_of_dev"], ptrs)}
 
     def set_freq_index(self, dev: int, freq_idx: int):
         """Entry freq_idx of dongle dev's scan list is in force for every batch enqueued from now on (latched per batch)."""

@@ -12,6 +12,7 @@ AGC_EXTRA = 100
 FLAG_TRACE_SQUELCH, FLAG_RESERVED_2, FLAG_FORCE_FFT, FLAG_SERIAL_DEMOD, FLAG_PIPELINE, FLAG_REGROUP, FLAG_NO_REGROUP = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20, 0x40
 FLAG_WIDE_HOPS = 0x80  # the matrix-core channelizers also take hops beyond 1 024 bytes (CS16: 1 280; CF32: beyond the float kernel's tile, ~3 MS/s at WAVE_RATE 8000): devices above ~4 MS/s
 GATE_NEVER, GATE_SIGNAL, GATE_ALWAYS = 0, 1, 2  # airband_hip_set_output_gate
+SCOPE_MEAN, SCOPE_PEAK = 0x1, 0x2  # airband_hip_set_band_scope: traces
 
 BYTES_PER_SAMPLE = {SFMT_U8: 1, SFMT_S8: 1, SFMT_S16: 2, SFMT_F32: 4}
 
@@ -64,3 +65,17 @@ def device_cfg(channels, sample_rate=2_560_000, centerfreq=120_000_000, sfmt=SFM
     arr = (ChannelCfg * len(chs))(*chs)
     dev = DeviceCfg(int(sample_rate), int(centerfreq), int(sfmt), float(fullscale), int(tau_us), len(chs), C.cast(arr, C.POINTER(ChannelCfg)))
     return dev, arr
+
+
+# the band scope's entry points (include/airband_hip.h): argument types by symbol, applied by load_library()
+_vp, _i32, _u32 = C.c_void_p, C.c_int32, C.c_uint32
+BAND_SCOPE_PROTOTYPES = {
+    "airband_hip_set_band_scope": [_vp, _vp, _i32, _u32],
+    "airband_hip_collect_band_scope": [_vp, _i32, _i32, _vp, _vp],
+    "airband_hip_device_band_scope": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
+}
+
+
+def scope_window_hops(windows: int, wave_batch: int):
+    """The batch's new hops whose FFT windows a band scope of `windows` windows per batch looks at: (j * WAVE_BATCH) / K, j = 0 .. K-1."""
+    return [(j * wave_batch) // windows for j in range(windows)]

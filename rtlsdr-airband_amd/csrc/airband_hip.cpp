@@ -70,6 +70,7 @@ void destroy(airband_hip_handle* h) {
         if (st) (void)hipStreamSynchronize(st);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     if (h->h2d) (void)hipStreamSynchronize(h->h2d);
+    if (h->scope.stream) (void)hipStreamSynchronize(h->scope.stream);
     delete h;
 }
 
@@ -291,6 +292,79 @@ int launch_last_hop_spectrum(airband_hip_handle* h, hipStream_t s) {
     return AIRBAND_HIP_OK;
 }
 
+/* The band scope of the batch whose stage 1 goes on stream s (airband_hip_set_band_scope): it depends on the batch's input only, like AFC's one-hop spectrum
+ * above.  scope_fork() in front of stage 1: the kernel runs on the scope's own stream beside it.  scope_join() behind stage 1: s waits for it, so that EVERY point
+ * that declares the batch's input consumed by recording an event on s behind stage 1 -- ev_stage_read of the host ring, front_done of pipelined and run-ahead
+ * handles, the stream order a run-ahead batch's next stage 1 relies on -- is behind the scope's reads too, and the batch's results, which wait for stage 1, are
+ * complete only once the scope is.  On a CALLER's stream there is no fork: the kernel goes on that stream behind stage 1. */
+bool scope_on_side(const airband_hip_handle* h, hipStream_t s) { return s == h->stream || s == h->front; }
+
+ScopeArgs scope_args(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, FrontRows r) {
+    BandScope& sc = h->scope;
+    const Plan& p = h->plan;
+    const int set = (int)(sc.launches % (uint64_t)sc.n_sets);
+    ScopeArgs a;
+    a.iq = (const uint8_t*)d_iq;
+    a.iq_stride = (long)stride_bytes;
+    a.dev = h->d_dev.p;
+    a.dev_of_row = sc.d_dev_of_row.p;
+    a.window = h->d_window.p;
+    a.twiddle = reinterpret_cast<const float2*>(h->d_twiddle.p);
+    a.mean = sc.d_mean[set].p;
+    a.peak = sc.d_peak[set].p;
+    a.prev_mean = sc.n_sets > 1 ? sc.d_mean[set ^ 1].p : nullptr;
+    a.prev_peak = sc.n_sets > 1 ? sc.d_peak[set ^ 1].p : nullptr;
+    a.n_rows = sc.n_rows;
+    a.fft_log = p.fft_log;
+    a.hop_samples = p.dev[0].hop_samples;
+    a.bytes_per_sample = p.dev[0].bytes_per_sample;
+    a.sfmt = p.dev[0].sfmt;
+    a.first_hop = r.n_hops - h->B; /* the first batch's AGC_EXTRA lead-in hops are never selected */
+    a.span_hops = r.n_hops;
+    a.wave_batch = h->B;
+    a.n_windows = sc.windows;
+    a.region_bytes = 0;
+    return a;
+}
+
+/* front batch front_batches has its scope in set (launches % n_sets); the set becomes the current one with the batch's back half (run_back_half) */
+void scope_launched(airband_hip_handle* h) {
+    BandScope& sc = h->scope;
+    sc.set_of_front[h->front_batches & 1] = (int)(sc.launches % (uint64_t)sc.n_sets);
+    sc.launches++;
+}
+
+int scope_fork(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, FrontRows r, hipStream_t s) {
+    BandScope& sc = h->scope;
+    if (sc.windows <= 0 || !scope_on_side(h, s)) return AIRBAND_HIP_OK;
+    HIP_TRY(h, hipEventRecord(sc.ev_fork, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamWaitEvent(sc.stream, sc.ev_fork, 0), AIRBAND_HIP_ERUNTIME);
+    if (h->ev_last && h->ev_last_pending) HIP_TRY(h, hipStreamWaitEvent(sc.stream, h->ev_last, 0), AIRBAND_HIP_ERUNTIME); /* a batch (and its scope) on a caller's stream */
+    launch_band_scope(scope_args(h, d_iq, stride_bytes, r), sc.stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("band scope launch: ") + hipGetErrorString(e));
+    HIP_TRY(h, hipEventRecord(sc.ev_done, sc.stream), AIRBAND_HIP_ERUNTIME);
+    scope_launched(h);
+    return AIRBAND_HIP_OK;
+}
+
+int scope_join(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, FrontRows r, hipStream_t s) {
+    BandScope& sc = h->scope;
+    if (sc.windows <= 0) return AIRBAND_HIP_OK;
+    if (scope_on_side(h, s)) {
+        HIP_TRY(h, hipStreamWaitEvent(s, sc.ev_done, 0), AIRBAND_HIP_ERUNTIME);
+        return AIRBAND_HIP_OK;
+    }
+    /* the caller's stream, behind stage 1 -- and behind the scope launch before this one, whose rows a switched-off dongle's are carried over from */
+    if (sc.launches > 0) HIP_TRY(h, hipStreamWaitEvent(s, sc.ev_done, 0), AIRBAND_HIP_ERUNTIME);
+    launch_band_scope(scope_args(h, d_iq, stride_bytes, r), s);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("band scope launch: ") + hipGetErrorString(e));
+    HIP_TRY(h, hipEventRecord(sc.ev_done, s), AIRBAND_HIP_ERUNTIME);
+    scope_launched(h);
+    return AIRBAND_HIP_OK;
+}
+
 ScanExchangeArgs scan_args(airband_hip_handle* h) {
     ScanExchangeArgs a;
     a.cc = h->d_cc.p;
@@ -411,6 +485,8 @@ GateArgs gate_args(const airband_hip_handle* h) {
 /* stage 2 + emit (+ mixers, + the output gate) of the batch whose stage-1 rows are already in the rings */
 int run_back_half(airband_hip_handle* h, hipStream_t s) {
     const Event* ev = event_set(h, h->batches_done, 1);
+    /* the band scope of this batch (computed beside its stage 1, which s is behind) is the current one from here on; a batch without input leaves it alone */
+    if (h->scope.windows > 0 && h->scope.set_of_front[h->batches_done & 1] >= 0) h->scope.cur = h->scope.set_of_front[h->batches_done & 1];
     (void)hipEventRecord(ev[2], s);
     DemodArgs da;
     da.cc = h->d_cc.p;
@@ -1203,6 +1279,8 @@ static int launch_front(airband_hip_handle* h, const void* d_iq, size_t stride_b
             if (rc != AIRBAND_HIP_OK) return rc;
         }
     }
+    const int rc_scope = scope_fork(h, d_iq, stride_bytes, r, s);
+    if (rc_scope != AIRBAND_HIP_OK) return rc_scope;
     (void)hipEventRecord(ev[0], s);
     if (h->use_f32_wide) launch_channelizer_f32_wide(f32_args(h, d_iq, stride_bytes, r), s);
     else if (h->use_f32) launch_channelizer_f32(f32_args(h, d_iq, stride_bytes, r), s);
@@ -1213,6 +1291,8 @@ static int launch_front(airband_hip_handle* h, const void* d_iq, size_t stride_b
     (void)hipEventRecord(ev[1], s);
     /* a refused launch (an LDS opt-in that failed, a bad grid) is this call's error, not a puzzle for whoever synchronises next */
     if (launch_err != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("channelizer launch: ") + hipGetErrorString(launch_err));
+    const int rc_join = scope_join(h, d_iq, stride_bytes, r, s);
+    if (rc_join != AIRBAND_HIP_OK) return rc_join;
     front_enqueued(h, r.first_row, r.n_hops);
     return AIRBAND_HIP_OK;
 }
@@ -1444,6 +1524,7 @@ int airband_hip_process_bins(airband_hip_handle* h, const float* wavein, const f
     h->afc_spectrum_valid = false;
     launch_scatter_bins(h->d_tmp_wavein.p, h->d_tmp_iqin.p, h->d_slot_to_ext.p, h->d_cc.p, h->d_mag.p, h->d_iq.p, h->n_slots, h->B, h->row0, h->R, s);
     (void)hipEventRecord(ev[1], s);
+    h->scope.set_of_front[h->front_batches & 1] = -1; /* no input to look at: the band scope stays as it is */
     front_enqueued(h, AB_AGC_EXTRA, h->B); /* the caller's rows are the batch's new ones; the carry is what the rings hold */
     return run_back_half(h, s);
 }
@@ -1529,6 +1610,86 @@ int airband_hip_set_output_gate(airband_hip_handle* h, const uint8_t* gate, int6
     }
     g.max_rows = (int)max_rows;
     h->gate = std::move(g);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_set_band_scope(airband_hip_handle* h, const uint8_t* dev_mask, int32_t windows_per_batch, uint32_t traces) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const Plan& p = h->plan;
+    if (windows_per_batch < 1 || windows_per_batch > h->B) return fail(h, AIRBAND_HIP_EINVAL, "windows_per_batch must lie in 1 .. WAVE_BATCH");
+    if (traces == 0 || (traces & ~(uint32_t)(AIRBAND_SCOPE_MEAN | AIRBAND_SCOPE_PEAK))) return fail(h, AIRBAND_HIP_EINVAL, "traces must be a non-empty set of AIRBAND_SCOPE_* bits");
+    BandScope sc;
+    sc.row_of_dev.assign((size_t)p.n_dev, -1);
+    std::vector<int> dev_of_row;
+    for (int d = 0; d < p.n_dev; d++)
+        if (!dev_mask || dev_mask[d]) {
+            sc.row_of_dev[d] = (int)dev_of_row.size();
+            dev_of_row.push_back(d);
+        }
+    if (dev_of_row.empty()) return fail(h, AIRBAND_HIP_EINVAL, "the mask selects no dongle");
+    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the band scope is set before the first batch");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* built beside the handle and moved in whole: a failed allocation leaves the handle as it was */
+    sc.windows = windows_per_batch;
+    sc.traces = traces;
+    sc.n_rows = (int)dev_of_row.size();
+    sc.n_sets = deep_rings(h) ? 2 : 1; /* where the next stage 1 may run before this batch's results are collected (the validity rule of the result buffers) */
+    const size_t n = (size_t)sc.n_rows * (size_t)h->N;
+    hipError_t e = upload(sc.d_row_of_dev, sc.row_of_dev);
+    if (e == hipSuccess) e = upload(sc.d_dev_of_row, dev_of_row);
+    for (int q = 0; q < sc.n_sets; q++) {
+        if (e == hipSuccess && (traces & AIRBAND_SCOPE_MEAN)) e = sc.d_mean[q].alloc_zeroed(n);
+        if (e == hipSuccess && (traces & AIRBAND_SCOPE_PEAK)) e = sc.d_peak[q].alloc_zeroed(n);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize(); /* the zeros are in place before a kernel on another stream writes the rows */
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&sc.stream.v, hipStreamNonBlocking);
+    if (e == hipSuccess) e = sc.ev_fork.ensure();
+    if (e == hipSuccess) e = sc.ev_done.ensure();
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); /* this call's error, reported here: not the next launch's */
+        return fail(h, AIRBAND_HIP_ENOMEM, std::string("band scope buffers: ") + hipGetErrorString(e));
+    }
+    h->scope = std::move(sc);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_band_scope(airband_hip_handle* h, int32_t first_dev, int32_t n_dev, float* mean, float* peak) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const BandScope& sc = h->scope;
+    if (sc.windows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band scope (airband_hip_set_band_scope)");
+    if (first_dev < 0 || n_dev < 0 || (int64_t)first_dev + n_dev > h->plan.n_dev) return fail(h, AIRBAND_HIP_EINVAL, "device range out of bounds");
+    if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    const size_t N = (size_t)h->N;
+    float* const out[2] = {mean, peak};
+    const float* const src[2] = {sc.d_mean[sc.cur].p, sc.d_peak[sc.cur].p};
+    for (int t = 0; t < 2; t++) {
+        if (!out[t]) continue;
+        for (int i = 0; i < n_dev;) { /* runs of selected dongles are runs of rows: one copy each */
+            const int row = src[t] ? sc.row_of_dev[first_dev + i] : -1;
+            int j = i + 1;
+            if (row < 0) { /* not selected (or a trace the scope does not keep): zeros */
+                std::memset(out[t] + (size_t)i * N, 0, N * sizeof(float));
+            } else {
+                while (j < n_dev && sc.row_of_dev[first_dev + j] >= 0) j++;
+                HIP_TRY(h, hipMemcpyAsync(out[t] + (size_t)i * N, src[t] + (size_t)row * N, (size_t)(j - i) * N * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+            }
+            i = j;
+        }
+    }
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_device_band_scope(airband_hip_handle* h, float** d_mean, float** d_peak, int32_t** d_row_of_dev) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const BandScope& sc = h->scope;
+    if (sc.windows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band scope (airband_hip_set_band_scope)");
+    if (d_mean) *d_mean = sc.d_mean[sc.cur].p;
+    if (d_peak) *d_peak = sc.d_peak[sc.cur].p;
+    if (d_row_of_dev) *d_row_of_dev = sc.d_row_of_dev.p;
     return AIRBAND_HIP_OK;
 }
 

@@ -35,43 +35,14 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "wave_fft8.h"
+#include "wave_lds.h"
 
 namespace airband {
 
 namespace {
 
-/* the workgroup's dynamic LDS (tests/hostshim_wave64 gives the host build a static array instead) */
-#if !defined(AB_DYNAMIC_LDS_BYTES)
-#define AB_DYNAMIC_LDS_BYTES(name) extern __shared__ __attribute__((aligned(16))) uint8_t name[]
-#endif
-
-/* Lanes of ONE wavefront exchange data through LDS: a wavefront's LDS operations execute in order, so what is NEEDED is that the compiler keeps them in
- * program order across the exchange (the two wavefront-scope fences around the wave barrier: no instruction).  tests/hostshim_wave64 makes the lanes, which it
- * runs as fibers, meet here. */
-#if !defined(AB_WAVE_SYNC)
-/* Round 5: every exchange also WAITS until the wavefront's own LDS operations have completed (s_waitcnt lgkmcnt(0)) before any lane reads what another lane wrote.
- * In-order execution of one wavefront's LDS instructions already orders them; the wait takes the kernel off that assumption, at 0 (u8, fft 512) to 2.3 % (CF32, fft 4096) of
- * its time (profiles/r05_misc/fft_*.json, f32_4096_*.json).  It is NOT a fix for round 4's rare wrong transforms: round 5 reproduced those at will -- they need a SECOND PROCESS
- * running this library's long int8 launches on the same GPU, they happen with this wait and with one wavefront per workgroup, they spare the shuffle kernel, and the same kind of
- * fault then hits the main path's CTCSS chain (profiles/r05_event_hunt.md).  One process per GPU: never seen.  What failed turned out to be packed-f32 instructions (lanes 48 - 63 of a
- * result); the library is built without them (_build.py, DEVICE_FLAGS) and the events are gone.  -DAB_WAVE_SYNC_NO_WAIT builds the kernel without the wait. */
-#if defined(AB_WAVE_SYNC_NO_WAIT)
-#define AB_WAVE_SYNC_EXTRA() (void)0
-#else
-#define AB_WAVE_SYNC_EXTRA() __builtin_amdgcn_s_waitcnt(0xc07f) /* vmcnt(63) expcnt(7) lgkmcnt(0) */
-#endif
-#define AB_WAVE_SYNC()                                           \
-    do {                                                         \
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   \
-        AB_WAVE_SYNC_EXTRA();                                    \
-        __builtin_amdgcn_wave_barrier();                         \
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   \
-    } while (0)
-#endif
-
 constexpr int HOPS_PER_TILE = 16;
-constexpr int XS = 72;                    /* complex values per row of a wavefront's exchange buffer: 64 + 8, so that two rows land in different banks */
-constexpr int XBUF_BYTES = 8 * XS * 8;    /* eight rows */
 
 /* bytes of a tile's raw samples in LDS (+ alignment slack), a multiple of 16 */
 __host__ __device__ inline long fft_raw_bytes(int fft_log, int hop_samples, int bytes_per_sample) {
@@ -84,9 +55,6 @@ inline bool fft_uses_exchange(int fft_log, int hop_samples, int bytes_per_sample
     static const bool shuffle_only = std::getenv("AIRBAND_HIP_FFT_SHUFFLE") != nullptr;
     return !shuffle_only && fft_raw_bytes(fft_log, hop_samples, bytes_per_sample) + 4 * XBUF_BYTES <= 160 * 1024;
 }
-constexpr float kPi = 3.14159265358979323846f;
-
-__device__ __forceinline__ int bitrev(int v, int bits) { return (int)(__brev((unsigned)v) >> (32 - bits)); }
 
 template <int LOGP>
 __global__ __launch_bounds__(256) void channelizer_fft_kernel(ChannelizerArgs a) {
@@ -280,36 +248,6 @@ __global__ __launch_bounds__(256) void channelizer_fft_kernel(ChannelizerArgs a)
     }
 }
 
-typedef float v2f __attribute__((ext_vector_type(2))); /* (re, im).  Until round 5 arithmetic on these became v_pk_*_f32; the library is now built WITHOUT packed-f32 instructions
-                                                         (_build.py, DEVICE_FLAGS: beside another process's long launches they leave lanes 48 - 63 wrong now and then), so a pair is two scalar operations */
-
-/* x * w with the twiddle as the pair w = (c, s), wr = i w = (-s, c): (x.re, x.re) * w + (x.im, x.im) * wr -- two multiplies and two FMAs (one packed
- * multiply and one packed FMA in a build with packed-f32 instructions; left to itself the compiler spends five instructions on a complex product: it does not negate one half of a packed operand) */
-__device__ __forceinline__ v2f cmul(const v2f x, const v2f w, const v2f wr) { return __builtin_elementwise_fma(x.xx, w, x.yy * wr); }
-__device__ __forceinline__ v2f rot_i(const v2f w) { return v2f{-w.y, w.x}; }
-
-/* P-point radix-2 decimation-in-frequency FFT in registers, constant twiddles; output in bit-reversed register order */
-template <int P>
-__device__ __forceinline__ void fft_dif(v2f (&x)[P]) {
-#pragma unroll
-    for (int half = P / 2; half >= 1; half >>= 1) {
-#pragma unroll
-        for (int base = 0; base < P; base += 2 * half) {
-#pragma unroll
-            for (int j = 0; j < half; j++) {
-                const int i0 = base + j, i1 = i0 + half;
-                const v2f u = x[i0], v = x[i1];
-                x[i0] = u + v;
-                const v2f d = u - v;
-                const float ang = -kPi * (float)j / (float)half; /* W_(2 half)^j: a compile-time constant after unrolling */
-                const float wc = __builtin_cosf(ang), ws = __builtin_sinf(ang);
-                if (j == 0) x[i1] = d;
-                else if (2 * j == half) x[i1] = d.yx * v2f{1.0f, -1.0f}; /* -i: (im, -re), a packed multiply that contracts into the next butterfly's add */
-                else x[i1] = cmul(d, v2f{wc, ws}, v2f{-ws, wc});
-            }
-        }
-    }
-}
 
 /* LOGM > 0: fft_size = M x 512 (1024 ... 8192).  With n = M n1 + n2 the transform is M transforms of 512 points over the DECIMATED samples,
  *      X[k] = sum over n2 of  W_N^(n2 k) * F_n2[k mod 512],      F_n2[kk] = sum over n1 of x[M n1 + n2] w[M n1 + n2] W_512^(n1 kk),

@@ -107,6 +107,23 @@ struct OutputGate {
     DevBuf<float> d_rows, d_iq_rows;
 };
 
+/* what airband_hip_set_band_scope() set up: replaced as a whole, one without windows is a handle without a scope (nothing allocated, nothing launched, no
+ * stream, no event).  Handles whose next stage 1 may run before the last batch's results are collected (pipelined, run-ahead) keep TWO sets of rows: the
+ * scope of front batch k goes to a set of its own and becomes the current one when the batch's back half is enqueued, as the batch's results do. */
+struct BandScope {
+    int windows = 0;           /* windows per batch; 0 = no scope */
+    uint32_t traces = 0;       /* AIRBAND_SCOPE_* */
+    int n_rows = 0, n_sets = 1;
+    std::vector<int> row_of_dev;
+    DevBuf<int> d_row_of_dev, d_dev_of_row;
+    DevBuf<float> d_mean[2], d_peak[2];
+    Stream stream;             /* beside stage 1, forked where it starts and joined behind it */
+    Event ev_fork, ev_done;
+    uint64_t launches = 0;     /* scope launches so far: launch n writes set n % n_sets */
+    int set_of_front[2] = {-1, -1}; /* by front batch k & 1: the set its scope went to, -1 for a batch without input (airband_hip_process_bins) */
+    int cur = 0;               /* the set of the batch whose results are current */
+};
+
 }  // namespace airband
 
 struct airband_hip_handle {
@@ -222,6 +239,7 @@ struct airband_hip_handle {
 
     airband::MixerWiring mix;
     airband::OutputGate gate;
+    airband::BandScope scope;
 
     /* the mixer exchange (airband_hip_comm_*): this handle's rank in an RCCL communicator over the GPUs that hold the other dongles */
     ncclComm_t comm = nullptr;

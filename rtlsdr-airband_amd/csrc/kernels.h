@@ -307,5 +307,28 @@ struct GateArgs {
 int gate_blocks(int n_ch);
 void launch_gate(const GateArgs& a, hipStream_t stream);
 
+/* band scope (band_scope.hip): mean and peak of |X[k]|^2 over n_windows windows of the batch's input span, one workgroup per selected dongle */
+struct ScopeArgs {
+    const uint8_t* iq;        /* device: dongle d's span starts at iq + d * iq_stride (the batch's stage-1 input) */
+    long iq_stride;           /* bytes */
+    const DevConst* dev;
+    const int* dev_of_row;    /* [n_rows] the selected dongles, ascending */
+    const float* window;      /* fft_size: the channelizer's window (params.cpp) */
+    const float2* twiddle;    /* fft_size: exp(-2 pi i k / fft_size) */
+    float* mean;              /* [n_rows][fft_size], or null */
+    float* peak;              /* [n_rows][fft_size], or null */
+    const float* prev_mean;   /* handles with two sets of rows: the set of the batch before, from which a switched-off dongle's rows are carried over; else null */
+    const float* prev_peak;
+    int n_rows, fft_log;
+    int hop_samples, bytes_per_sample, sfmt;
+    int first_hop;            /* hops of the span in front of the batch's new ones (the first batch's AGC_EXTRA lead-in, else 0) */
+    int span_hops;            /* hops the span holds: first_hop + wave_batch */
+    int wave_batch, n_windows;/* window j of n_windows = new hop (j * wave_batch) / n_windows */
+    int region_bytes;         /* LDS per wavefront (set by launch_band_scope) */
+};
+long scope_region_bytes(int fft_log, int bytes_per_sample);
+int scope_waves(int fft_log, int bytes_per_sample); /* wavefronts per workgroup: four where four regions fit a CU's 160 KiB, else two, else one */
+void launch_band_scope(const ScopeArgs& a, hipStream_t stream);
+
 }  // namespace airband
 #endif
