@@ -24,6 +24,8 @@
  *     hops overlap, so every HBM byte is fetched once (16 B/lane coalesced) and re-used N/hop times from LDS.
  *   B (64 x 16 per MFMA, 3 digits x 16 steps, all-zero edge digits dropped: 44 fragments): 176 VGPRs, loaded once per wave from a per-bin-set table.
  *   D: lane l holds column (l&15) = (channel, re|im) of hops (l>>4)*4 + {0..3}; |bin| needs the neighbour lane.
+ *
+ * From mfma_front.h: work_item(), tile_range(), split_share(), opt_in_big_lds(); from dft_common.h: TileAcc, recombine(), digit_value(), piece_sum(), the wait-count ladders, ab_mfma(), lds_read16().
  */
 #include <hip/hip_runtime.h>
 #include <atomic>
@@ -116,16 +118,8 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_kern
     /* wave p of the workgroup: window piece p -- the same number on every lane of the wave; told so, the compiler keeps everything that is
      * decided per piece (who runs the transfers, the store accounting of the waits) in scalar registers and scalar branches */
     const int piece = NP > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-    /* XCD-aware placement: workgroup b runs on XCD b % 8 (observed dispatch order; speed only).  16 consecutive
-     * dongles write neighbouring slots of the same 128-byte lines, so they are given to the SAME XCD and meet in
-     * one L2: inside every group of 128 dongles, workgroup i*8 + x takes dongle x*16 + i. */
-    const int wave_global = blockIdx.x;
-    /* a work item = (dongle, group of 8 channels): dongles with more than 8 channels appear once per group, side by side, so the
-     * groups of a dongle stream the same bytes at the same time through the same L2 */
-    const int i_lin = wave_global % a.n_items;
-    const int g128 = i_lin & ~127, in128 = i_lin & 127;
-    const int item = ((a.n_items - g128) >= 128) ? g128 + (in128 & 7) * 16 + (in128 >> 3) : i_lin;
-    const int split = wave_global / a.n_items;
+    const WorkItem w = work_item((int)blockIdx.x, a.n_items); /* which (dongle, group of 8 channels), placed by XCD (mfma_front.h) */
+    const int item = w.item, split = w.split;
     if (split >= a.splits) return;
     const int d = a.item_dev[item], ch0 = a.item_group[item] * 8;
     if (a.dev[d].disabled) return; /* a failed / disabled dongle (airband_hip_device_enable): workgroup-uniform, in front of every barrier */
@@ -138,9 +132,8 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_kern
     const int buf_bytes = (step_hops - 1) * hop_bytes + WIN_ALL + (AL >= 16 ? 0 : 16);
     uint8_t* lds = lds_all;                               /* two buffers of lds_per_buf bytes */
 
-    /* MFMA tiles are aligned to the 16-row tiles of the output rings: tile t covers hops [16 t - shift, 16 t - shift + 16);
-     * hops < 0 (first tile) and >= n_hops (last tile) are computed on whatever bytes are there and never stored */
-    const int shift = (a.row0 + a.first_row) & 15;
+    const TileRange g = tile_range(a.row0, a.first_row, a.ring_rows, a.n_hops);
+    const int shift = g.shift, tiles_total = g.tiles_total, ring_tiles = g.ring_tiles, ring_tiles16 = g.ring_tiles16, ptile0 = g.ptile0;
     /* hops that are not multiples of 16 bytes: a step's first byte sits `delta` bytes into its (16-byte aligned) LDS image; a step
      * advances by 16 hops, so delta is the same for every step of the wave */
     const uint8_t* src = a.iq + (long)d * a.iq_stride + (long)a.piece0 * WIN_BYTES;    /* first byte this pass reads of the batch's first hop */
@@ -150,14 +143,9 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_kern
     const int mis = AL >= 16 ? 0 : (int)(reinterpret_cast<uintptr_t>(src) & 15u);
     src -= mis;
     const int delta = AL >= 16 ? 0 : (int)((-(long)shift * (HOPB ? HOPB : a.hop_bytes) + mis) & 15);
-    const int ring_tiles = a.ring_rows / AB_TILE_ROWS;
-    const int ring_tiles16 = a.ring_rows / TILE_HOPS; /* the ring length is a whole number of 16-hop MFMA tiles */
-    const int ptile0 = (a.row0 + a.first_row) >> 4;
-    const int tiles_total = (shift + a.n_hops + TILE_HOPS - 1) / TILE_HOPS;
     const int steps_total = (tiles_total + sub - 1) / sub;
-    const int steps_per_split = (steps_total + a.splits - 1) / a.splits;
-    const int st_begin = split * steps_per_split;
-    const int st_end = min(steps_total, st_begin + steps_per_split);
+    const Share sh = split_share(steps_total, a.splits, split);
+    const int st_begin = sh.begin, st_end = sh.end;
     if (st_begin >= st_end) return;
 
 
@@ -265,17 +253,7 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_kern
         mark1 = b == 1 ? v : mark1;
         mark2 = b == 2 ? v : mark2;
     };
-    /* ---- round 6: the hop-specialised variants stage through ONE ring without the window overlap (below, "staging ring") ---- */
-#ifndef AB_RING
-#define AB_RING 0 /* 1: experiment builds (-DAB_RING=1).  Measured, parity-green and NOT adopted (profiles/r06_ring/, profiles/r06_experiments.md J): 8 % fewer L1 -> L2 read
-                   * requests, 18 % fewer L2 hits, the same bytes fetched -- and the same launch time, 8.31 / 8.42 / 8.95 against 8.34 / 8.42 / 8.43 ms (hops of 640 bytes:
-                   * 7.37 / 7.36 / 7.40 against 7.35 / 7.35 / 7.41): the kernel waits for HBM, not for its requests.  The product stays on round 5's three buffers. */
-#endif
-#ifndef AB_RING_640
-#define AB_RING_640 1 /* hops of 640 bytes (WAVE_RATE 8000): three slots of 10 KiB = 31 KiB per wave, five waves per CU (round 5: two buffers of 11 KiB, seven) */
-#endif
-    constexpr bool RING = AB_RING != 0 && HOPB != 0 && (HOPB != 640 || AB_RING_640 != 0) && NP == 1 && !S16 && AL >= 16 && (TILE_HOPS * (HOPB ? HOPB : 64)) % 1024 == 0;
-    if (!RING && piece == 0) {
+    if (piece == 0) {
         stage(st_begin, lds);
         if (nbuf == 3 && st_begin + 1 < st_end) stage(st_begin + 1, lds + lds_per_buf);
     }
@@ -292,15 +270,9 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_kern
      * tests/test_gpu_parity.py, stage-1 bar 1e-5 relative RMS).  Round 2 recombined in float64: 36 half- and quarter-rate
      * instructions per tile against 12 full-rate ones. */
     /* (the scale factors are the same number on every lane -- a.unscale, and for CS16 the wave's own dongle's 1 / fullscale: scalar registers) */
-    const int flipmask = a.sfmt == AIRBAND_SFMT_S8 ? 0 : (int)0x80808080;
-    auto uni = [](double v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)v))); };
-    const float u0 = uni(unscale), u1 = uni(unscale * 256.0), u2 = uni(unscale * 65536.0);
-    const float cu = a.sfmt == AIRBAND_SFMT_S8 ? 0.0f : (float)(corr * unscale); /* s8 samples are i / 128: nothing to restore */
-    const float w0 = u1, w1 = u2, w2 = uni(unscale * 16777216.0); /* CS16 high-byte plane */
+    const Recombine rc = recombine(unscale, corr, a.sfmt);
+    const int flipmask = rc.flipmask;
 
-    struct TileAcc {
-        v4i a0, a1, a2, h0, h1, h2; /* h*: CS16 high-byte plane */
-    };
     /* LDS -> MFMA for the 16 hops of tile (step buffer `buf`, sub-tile sb): leaves the integer digit sums in A */
     /* u8 / s8: the lane's row of the staged stream, and the first four k-steps' A fragments -- split off so that the pipelined loop can
      * issue them for tile t + 1 before it recombines and stores tile t */
@@ -390,17 +362,7 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_kern
     };
     /* digit sums -> the lane's four values (hops grp * 4 .. + 3 of column col): recombine, restore the -127.5 offset of the reference's
      * LUT (u8) / the + 128 of the low byte (CS16), undo the fixed-point scale */
-    auto tile_value = [&](const TileAcc& A, int r) {
-        float y = __builtin_fmaf((float)A.a0[r], u0, cu);
-        y = __builtin_fmaf((float)A.a1[r], u1, y);
-        y = __builtin_fmaf((float)A.a2[r], u2, y);
-        if (S16) {
-            y = __builtin_fmaf((float)A.h0[r], w0, y);
-            y = __builtin_fmaf((float)A.h1[r], w1, y);
-            y = __builtin_fmaf((float)A.h2[r], w2, y);
-        }
-        return y;
-    };
+    auto tile_value = [&](const TileAcc& A, int r) { return digit_value<S16>(A, rc, r); };
     /* the neighbour lane's value: a DPP move inside the quad (quad_perm [1, 0, 3, 2]), no LDS round trip */
     auto pair_swap = [&](float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true)); };
     /* values of tile t -> rings.  Lane pairs (2ch, 2ch+1) hold (re, im) of the same hop; even lanes write 4 consecutive rows of their slot */
@@ -466,96 +428,6 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_kern
      * t - 1) -> the buffer tile t read is free: the transfer of step t + 3 goes out (three steps in flight, was two) -> wait for step
      * t + 1's bytes, issue tile t + 1's first A fragments -> recombine and store tile t while those LDS reads fly.  The wave no longer
      * stalls on LDS latency at the top of every tile, nor on the matrix pipe's drain with nothing else to issue. */
-    /* ---- staging ring (round 6; review item 3 ii): the stream of a wave lives ONCE in LDS.  Three slots of one 16-hop step each (5 KiB at hops of 320 bytes) form a
-     * ring; a step's transfer brings only its NEW bytes, and a tile reads its window tail in place -- the first 704 bytes of the NEXT slot (the ring's first KiB is kept a
-     * second time behind its end, so a row never wraps).  Against the three buffers of round 5: five transfers per step instead of six (the sixth re-read the previous
-     * step's last KiB out of L2: a sixth of this kernel's requests), none of them read twice, so EVERY piece may go out non-temporal (section A of
-     * profiles/r06_experiments.md: nt on every piece cost 13 % while two pieces in six were re-read), 16 KiB of LDS per wave instead of 18.  What it costs: tile st needs
-     * the head (first KiB) of step st + 1, so that transfer is waited for one tile earlier than its step used to be.  (Result: see AB_RING above -- no gain.)
-     * Order inside a step's transfer: piece 0, its replica (slot 0 only), pieces 1 ...: "the head of step v has landed" = at most tail(v) + everything younger outstanding. */
-    if constexpr (RING) {
-        constexpr int RS = TILE_HOPS * (HOPB ? HOPB : 64); /* bytes per step = per slot */
-        constexpr int RNP = RS / 1024;                     /* transfers per step */
-        constexpr int RING_BYTES = 3 * RS;                 /* + 1 KiB replica of the ring's first KiB behind it */
-        static_assert(RNP >= 2 && RNP <= 12, "pieces at immediate offsets below 12 KiB");
-#ifndef AB_RING_AUX
-#define AB_RING_AUX 2 /* nt: every piece of the ring is read once */
-#endif
-#ifndef AB_RING_HEAD_AUX
-#define AB_RING_HEAD_AUX 0 /* piece 0 of a slot-0 step is requested twice in a row (the ring and its replica) */
-#endif
-        const uint8_t* const rp_lane = src - (long)shift * HOPB + lane * 16; /* (16-byte aligned hops: mis = delta = 0) */
-        const int r_in_lo = shift > 0 ? 1 : 0;
-        const long room_n = span_end - (long)RNP * 1024, room_1 = span_end - 1024;
-        const int r_in_hi_n = __builtin_amdgcn_readfirstlane(room_n < 0 ? -1 : (int)((room_n / HOPB + shift) / TILE_HOPS));
-        const int r_in_hi_1 = __builtin_amdgcn_readfirstlane(room_1 < 0 ? -1 : (int)((room_1 / HOPB + shift) / TILE_HOPS));
-        /* step v (st_begin ... st_end: the one past the last tile's brings its head only) into ring slot `slot` */
-        auto ring_stage = [&](int v, int slot) {
-            const bool whole = v < st_end;
-            uint8_t* dst = lds + slot * RS;
-            if (v >= r_in_lo && v <= (whole ? r_in_hi_n : r_in_hi_1)) { /* wave-uniform: no lane's address needs clamping */
-                const uint8_t* p = rp_lane + (unsigned long long)(unsigned)v * (unsigned)RS;
-                if (slot == 0) {
-                    AB_DMA((gptr_t)p, (lptr_t)(uintptr_t)dst, 0, AB_RING_HEAD_AUX);
-                    AB_DMA((gptr_t)p, (lptr_t)(uintptr_t)(lds + RING_BYTES), 0, AB_RING_HEAD_AUX);
-                } else {
-                    AB_DMA((gptr_t)p, (lptr_t)(uintptr_t)dst, 0, AB_RING_AUX);
-                }
-                if (whole) {
-#define AB_RPIECE(K, BASE, OFF) \
-    if (RNP > (K)) AB_DMA((gptr_t)(p + (BASE)), (lptr_t)(uintptr_t)(dst + (BASE)), (OFF), AB_RING_AUX)
-                    AB_RPIECE(1, 0, 1024); AB_RPIECE(2, 0, 2048); AB_RPIECE(3, 0, 3072);
-                    AB_RPIECE(4, 4096, 0); AB_RPIECE(5, 4096, 1024); AB_RPIECE(6, 4096, 2048); AB_RPIECE(7, 4096, 3072);
-                    AB_RPIECE(8, 8192, 0); AB_RPIECE(9, 8192, 1024); AB_RPIECE(10, 8192, 2048); AB_RPIECE(11, 8192, 3072);
-#undef AB_RPIECE
-                }
-                return;
-            }
-            const long base = ((long)v * TILE_HOPS - shift) * HOPB;
-            const int np = whole ? RNP : 1;
-            for (int i = 0; i < np; i++) {
-                long so = base + i * 1024 + lane * 16;
-                if (so + 16 > span_end) so = span_end - 16;
-                if (so < 0) so = 0;
-                AB_DMA((gptr_t)(src + so), (lptr_t)(uintptr_t)(dst + i * 1024), 0, 0);
-                if (i == 0 && slot == 0) AB_DMA((gptr_t)(src + so), (lptr_t)(uintptr_t)(lds + RING_BYTES), 0, 0);
-            }
-        };
-        const int nst = st_end - st_begin;
-        ring_stage(st_begin, 0);
-        ring_stage(st_begin + 1, 1);
-        if (nst >= 2) ring_stage(st_begin + 2, 2);
-        /* step st_begin whole + the head of the next: younger are that step's tail and the third transfer */
-        wait_vmcnt((nst >= 2 ? RNP - 1 : 0) + (nst >= 3 ? RNP : nst == 2 ? 1 : 0));
-        v4i pre[4];
-        a_head(a_row(lds, 0), pre);
-        int mark2 = 0; /* `stores` when the transfer of step st + 2 was issued */
-        int slot = 0;
-        for (int st = st_begin; st < st_end; st++) {
-            TileAcc now;
-            tile_body(a_row(lds + slot * RS, 0), pre, now, no_mid);
-            const bool has3 = st + 3 <= st_end;
-            if (has3) ring_stage(st + 3, slot); /* every LDS read of this slot has returned (the MFMAs consumed them; the tile before read its first 704 bytes): it takes the step three ahead */
-            const int mark3 = stores;
-            const int slot1 = slot == 2 ? 0 : slot + 1;
-            if (st + 1 < st_end) {
-                /* tile st + 1 needs step st + 1 whole and the head of step st + 2 (transfers land in issue order): younger than that head are its step's tail, the
-                 * transfer just issued and the stores since step st + 2 went out */
-                const int tail2 = st + 2 < st_end ? RNP - 1 : 0;
-                const int cnt3 = has3 ? (st + 3 < st_end ? RNP : 1) + (slot == 0 ? 1 : 0) : 0;
-                wait_vmcnt(tail2 + cnt3 + (stores - mark2));
-                a_head(a_row(lds + slot1 * RS, 0), pre);
-            }
-            mark2 = mark3;
-            float val[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) val[r] = tile_value(now, r);
-            tile_store(st, val);
-            slot = slot1;
-        }
-        return;
-    }
-
     if (NP == 1 && !S16 && nbuf == 3 && sub == 1) {
         /* steps whose transfer lies wholly inside the batch span (no lane's address needs clamping), as a range worked out once: the per-step
          * test is two scalar compares and the source address one multiply-add */
@@ -616,12 +488,7 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_kern
     int pend_t = 0;
     bool have_pend = false;
     auto finish_tile = [&](int t, float* val) {
-        const float4* ex = exch + (t & 1) * (NP - 1) * 64;
-#pragma unroll
-        for (int q = 0; q < NP - 1; q++) {
-            const float4 o = ex[q * 64 + lane];
-            val[0] += o.x; val[1] += o.y; val[2] += o.z; val[3] += o.w;
-        }
+        piece_sum<NP>(exch, t, lane, val);
         if (a.partial) { /* fft_size 8192: the first pass parks its sums (whole-wave 1 KiB rows), the second adds them to its own */
             /* (row base through scalar registers: left to itself the compiler keeps a per-lane 64-bit base alive across the whole loop) */
             const unsigned long long rb = (unsigned long long)(a.partial + ((long)item * tiles_total + t) * 64);
@@ -736,21 +603,11 @@ static void launch_al(const DftArgs& a, hipStream_t stream) {
         const char* e = getenv("AIRBAND_HIP_DFT_EXTRA_LDS");
         return e ? (size_t)atol(e) : (size_t)0;
     }();
-    constexpr bool ring = AB_RING != 0 && HOPB != 0 && (HOPB != 640 || AB_RING_640 != 0) && NP == 1 && !S16 && AL >= 16 && (TILE_HOPS * (HOPB ? HOPB : 64)) % 1024 == 0; /* (the kernel's RING) */
-    const size_t lds = (ring ? (size_t)3 * TILE_HOPS * HOPB + 1024 : (size_t)a.nbuf * a.lds_per_buf + (NP > 1 ? 2 * (NP - 1) * 64 * sizeof(float4) : 0)) + extra_lds + (size_t)(a.extra_lds > 0 ? a.extra_lds : 0);
-    /* more than the default 64 KiB of dynamic LDS (eight-piece windows): opt in to the CU's 160 KiB, once per kernel variant */
-    /* (once per kernel variant AND device: the attribute belongs to the function as loaded on the current device, and a process may drive several GPUs) */
-    static std::atomic<bool> big_lds_dev[64][2]; /* (zero-initialised; one launching thread per GPU in the shim: setting it twice is harmless) */
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    const bool tracked = cur_dev >= 0 && cur_dev < 64; /* devices beyond the table opt in on every launch */
-    std::atomic<bool>* big_lds = big_lds_dev[tracked ? cur_dev : 0];
-    if (lds > 64 * 1024 && (!tracked || !big_lds[a.edge_hi_zero ? 1 : 0].load(std::memory_order_acquire))) {
-        const void* fn = a.edge_hi_zero ? reinterpret_cast<const void*>(&channelizer_dft_kernel<FFT_N, true, HOPB, S16, AL, NP>)
-                                        : reinterpret_cast<const void*>(&channelizer_dft_kernel<FFT_N, false, HOPB, S16, AL, NP>);
-        /* the CU's whole 160 KiB, not this launch's size: the flag is per variant, and a later handle of the same process may need more (runtime hop lengths) */
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess && tracked) big_lds[a.edge_hi_zero ? 1 : 0].store(true, std::memory_order_release);
-    }
+    const size_t lds = (size_t)a.nbuf * a.lds_per_buf + (NP > 1 ? 2 * (NP - 1) * 64 * sizeof(float4) : 0) + extra_lds + (size_t)(a.extra_lds > 0 ? a.extra_lds : 0);
+    static std::atomic<bool> big_lds[2][BIG_LDS_DEVICES]; /* (eight-piece windows; per kernel variant: this instantiation x EDGE_HI_ZERO) */
+    const void* fn = a.edge_hi_zero ? reinterpret_cast<const void*>(&channelizer_dft_kernel<FFT_N, true, HOPB, S16, AL, NP>)
+                                    : reinterpret_cast<const void*>(&channelizer_dft_kernel<FFT_N, false, HOPB, S16, AL, NP>);
+    opt_in_big_lds(fn, lds, big_lds[a.edge_hi_zero ? 1 : 0]);
     if (a.edge_hi_zero)
         hipLaunchKernelGGL((channelizer_dft_kernel<FFT_N, true, HOPB, S16, AL, NP>), dim3((unsigned)groups), dim3(64 * NP), lds, stream, a);
     else

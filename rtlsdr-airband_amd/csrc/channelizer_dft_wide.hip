@@ -36,7 +36,9 @@
  * tile's segments; recombination, the exchange and the stores happen once per tile.  The hand-over is the same wait + one barrier, the proof that a transfer has
  * landed the same count of stores since.  A segment starts a multiple of 16 bytes into its row: delta is the row's, unchanged.  LDS: 136 KiB (CS16 fft 2048), 146 KiB
  * (fft 4096), one workgroup per CU.  SEG = 1 is the kernel above: the same arithmetic, LDS and register counts (the compiled code differs in register numbering and two address instructions).  Not built: SEG > 1 with the AL = 2 reader (u8 / s8 fft 4096 at hops of
- * an odd number of samples) -- with the sums live across the staging loop it spills 29 registers; dft_wide_plan() keeps that shape on the wavefront FFT. */
+ * an odd number of samples) -- with the sums live across the staging loop it spills 29 registers; dft_wide_plan() keeps that shape on the wavefront FFT.
+ *
+ * From mfma_front.h: work_item(), tile_range(), split_share(), opt_in_big_lds(); from dft_common.h: TileAcc, recombine(), digit_value(), piece_sum(), wait_vmcnt_lo(), ab_mfma(), lds_read16(). */
 #include <hip/hip_runtime.h>
 #include <atomic>
 #include <utility>
@@ -76,29 +78,21 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_wide
 
     const int lane = NP > 1 ? (int)(threadIdx.x & 63) : (int)threadIdx.x;
     const int piece = NP > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;
-    /* work items and their placement on the XCDs: as channelizer_dft.hip */
-    const int wave_global = blockIdx.x;
-    const int i_lin = wave_global % a.n_items;
-    const int g128 = i_lin & ~127, in128 = i_lin & 127;
-    const int item = ((a.n_items - g128) >= 128) ? g128 + (in128 & 7) * 16 + (in128 >> 3) : i_lin;
-    const int split = wave_global / a.n_items;
+    const WorkItem w = work_item((int)blockIdx.x, a.n_items); /* which (dongle, group of 8 channels), placed by XCD (mfma_front.h) */
+    const int item = w.item, split = w.split;
     if (split >= a.splits) return;
     const int d = a.item_dev[item], ch0 = a.item_group[item] * 8;
     if (a.dev[d].disabled) return; /* workgroup-uniform, in front of every barrier */
     const long hop_bytes = a.hop_bytes;
 
-    const int shift = (a.row0 + a.first_row) & 15;
+    const TileRange g = tile_range(a.row0, a.first_row, a.ring_rows, a.n_hops);
+    const int shift = g.shift, tiles_total = g.tiles_total, ring_tiles = g.ring_tiles, ring_tiles16 = g.ring_tiles16, ptile0 = g.ptile0;
     const uint8_t* src = a.iq + (long)d * a.iq_stride;
     /* the transfers move aligned 16-byte pieces: the stream is addressed from the aligned byte at or in front of the span's first one */
     const int mis = (int)(reinterpret_cast<uintptr_t>(src) & 15u);
     src -= mis;
-    const int ring_tiles = a.ring_rows / AB_TILE_ROWS;
-    const int ring_tiles16 = a.ring_rows / TILE_HOPS;
-    const int ptile0 = (a.row0 + a.first_row) >> 4;
-    const int tiles_total = (shift + a.n_hops + TILE_HOPS - 1) / TILE_HOPS;
-    const int tiles_per_split = (tiles_total + a.splits - 1) / a.splits;
-    const int t_begin = split * tiles_per_split;
-    const int t_end = min(tiles_total, t_begin + tiles_per_split);
+    const Share sh = split_share(tiles_total, a.splits, split);
+    const int t_begin = sh.begin, t_end = sh.end;
     if (t_begin >= t_end) return;
     /* bytes of the batch span that may be read, from `src`, in whole 16-byte pieces: the last hop's window and not a byte more (geometry.lookahead_bytes
      * includes the round-up) */
@@ -147,15 +141,9 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_wide
     const int row_l = lane & 15, grp = lane >> 4;
     const int k_tile = ((__ballot(!(col & 1) && ch_valid && want_mag) != 0ull) ? 1 : 0) + ((__ballot(!(col & 1) && ch_valid && want_iq) != 0ull) ? 2 : 0);
 
-    const int flipmask = a.sfmt == AIRBAND_SFMT_S8 ? 0 : (int)0x80808080;
-    auto uni = [](double v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)v))); };
-    const float u0 = uni(unscale), u1 = uni(unscale * 256.0), u2 = uni(unscale * 65536.0);
-    const float cu = a.sfmt == AIRBAND_SFMT_S8 ? 0.0f : (float)(corr * unscale);
-    const float w0 = u1, w1 = u2, w2 = uni(unscale * 16777216.0); /* CS16 high-byte plane */
+    const Recombine rc = recombine(unscale, corr, a.sfmt);
+    const int flipmask = rc.flipmask;
 
-    struct TileAcc {
-        v4i a0, a1, a2, h0, h1, h2;
-    };
     /* LDS -> MFMA for the 16 hops of tile t, k-steps [SG x KSEG, (SG + 1) x KSEG) of the wave's piece out of the image of segment SG: the lane's row, delta_r
      * bytes in.  The first segment starts the sums, the others add to them */
     auto seg_mfma = [&](const uint8_t* buf, int t, TileAcc& A, auto seg_c) {
@@ -213,17 +201,7 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_wide
         }
     };
     /* digit sums -> the lane's four values (hops grp * 4 .. + 3 of column col), in single precision: every accumulator is an exact integer below 2^24 */
-    auto tile_value = [&](const TileAcc& A, int r) {
-        float y = __builtin_fmaf((float)A.a0[r], u0, cu);
-        y = __builtin_fmaf((float)A.a1[r], u1, y);
-        y = __builtin_fmaf((float)A.a2[r], u2, y);
-        if (S16) {
-            y = __builtin_fmaf((float)A.h0[r], w0, y);
-            y = __builtin_fmaf((float)A.h1[r], w1, y);
-            y = __builtin_fmaf((float)A.h2[r], w2, y);
-        }
-        return y;
-    };
+    auto tile_value = [&](const TileAcc& A, int r) { return digit_value<S16>(A, rc, r); };
     auto pair_swap = [&](float v) { return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), 0xB1, 0xF, 0xF, true)); };
     typedef float v4f __attribute__((ext_vector_type(4)));
     const bool store_lane = !(col & 1) && ch_valid;
@@ -298,12 +276,7 @@ __global__ __launch_bounds__(64 * NP, NP <= 4 ? 2 : 1) void channelizer_dft_wide
             if (piece > 0) exch[((t & 1) * (NP - 1) + (piece - 1)) * 64 + lane] = make_float4(val[0], val[1], val[2], val[3]);
             __syncthreads();
             if (piece == 0) {
-                const float4* ex = exch + (t & 1) * (NP - 1) * 64;
-#pragma unroll
-                for (int q = 0; q < NP - 1; q++) {
-                    const float4 o = ex[q * 64 + lane];
-                    val[0] += o.x; val[1] += o.y; val[2] += o.z; val[3] += o.w;
-                }
+                piece_sum<NP>(exch, t, lane, val);
                 tile_store(t, val);
             }
         } else {
@@ -317,18 +290,12 @@ void launch_al(const DftArgs& a, hipStream_t stream) {
     static_assert(SEG > 0 && wide_lds_total(2 * FFT_N * (S16 ? 2 : 1), NP, SEG) <= WIDE_LDS_MAX, "a shape without a plan has no kernel");
     const long groups = (long)a.n_items * a.splits;
     const size_t lds = (size_t)wide_lds_total(2 * FFT_N * (S16 ? 2 : 1), NP, SEG) + (size_t)(a.extra_lds > 0 ? a.extra_lds : 0);
-    /* more than the default 64 KiB of dynamic LDS: opt in to the CU's 160 KiB, once per kernel variant and device (as channelizer_dft.hip, launch_al) */
-    static std::atomic<bool> big_lds_dev[64][2];
-    int cur_dev = 0;
-    (void)hipGetDevice(&cur_dev);
-    const bool tracked = cur_dev >= 0 && cur_dev < 64;
-    std::atomic<bool>* big_lds = big_lds_dev[tracked ? cur_dev : 0];
+    static_assert(WIDE_LDS_MAX == CU_LDS_BYTES, "the plans are cut to the LDS that opt_in_big_lds() asks for");
+    static std::atomic<bool> big_lds[2][BIG_LDS_DEVICES]; /* (per kernel variant: this instantiation x EDGE_HI_ZERO) */
     const int e = a.edge_hi_zero ? 1 : 0;
-    if (lds > 64 * 1024 && (!tracked || !big_lds[e].load(std::memory_order_acquire))) {
-        const void* fn = e ? reinterpret_cast<const void*>(&channelizer_dft_wide_kernel<true, FFT_N, S16, AL, NP, SEG>)
-                           : reinterpret_cast<const void*>(&channelizer_dft_wide_kernel<false, FFT_N, S16, AL, NP, SEG>);
-        if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess && tracked) big_lds[e].store(true, std::memory_order_release);
-    }
+    const void* fn = e ? reinterpret_cast<const void*>(&channelizer_dft_wide_kernel<true, FFT_N, S16, AL, NP, SEG>)
+                       : reinterpret_cast<const void*>(&channelizer_dft_wide_kernel<false, FFT_N, S16, AL, NP, SEG>);
+    opt_in_big_lds(fn, lds, big_lds[e]);
     if (e)
         hipLaunchKernelGGL((channelizer_dft_wide_kernel<true, FFT_N, S16, AL, NP, SEG>), dim3((unsigned)groups), dim3(64 * NP), lds, stream, a);
     else

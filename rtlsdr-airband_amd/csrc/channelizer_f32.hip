@@ -22,21 +22,20 @@
  * wherever the hop's own length in 16-byte units is even (row pitch = an odd number of 16-byte units: the 16 rows of a read fall in 16 different
  * bank groups).  A window crosses hop boundaries, so a byte's LDS address is  o + pad * floor(o / hop_bytes); for a lane the second term differs
  * from its row number by a constant per fragment read -- sixteen per-lane offsets, computed once.
+ * From mfma_front.h: work_item(), tile_range(), split_share(), opt_in_big_lds().
  */
 #include <hip/hip_runtime.h>
 #include <atomic>
 
 #include "common.h"
 #include "kernels.h"
+#include "mfma_front.h"
 
 namespace airband {
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 typedef unsigned v4u __attribute__((ext_vector_type(4))); /* (not HIP's uint4: an array of that class type ends up in scratch memory) */
-
-constexpr int TILE_HOPS = 16;
 
 /* (hops of an odd number of samples -- 8 mod 16 bytes -- need no padding: their rows do not start in the same bank to begin with) */
 __host__ __device__ constexpr int f32_pad(int hop_bytes) { return (hop_bytes & 8) ? 0 : ((hop_bytes / 16) & 1) ? 0 : 16; }
@@ -64,27 +63,19 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (MAX_LD <= 6 ? 3 : 1) : 2) void 
 
     const int lane = (int)(threadIdx.x & 63);
     const int piece = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    /* XCD-aware placement, as channelizer_dft.hip: 16 neighbouring work items (their output lines interleave) on one XCD */
     const int wg = blockIdx.x;
-    const int i_lin = wg % a.n_items;
-    const int g128 = i_lin & ~127, in128 = i_lin & 127;
-    const int item = ((a.n_items - g128) >= 128) ? g128 + (in128 & 7) * 16 + (in128 >> 3) : i_lin;
-    const int split = wg / a.n_items;
+    const WorkItem w = work_item(wg, a.n_items); /* which (dongle, group of 8 channels), placed by XCD */
+    const int item = w.item, split = w.split;
     if (split >= a.splits) return;
     const int d = a.item_dev[item], ch0 = a.item_group[item] * 8;
     const DevConst dev = a.dev[d];
     if (dev.disabled) return; /* workgroup-uniform, in front of every barrier */
     const int hop_bytes = a.hop_bytes, pad = a.pad;
 
-    /* MFMA tiles are aligned to the 16-row tiles of the output rings: tile t covers hops [16 t - shift, 16 t - shift + 16) */
-    const int shift = (a.row0 + a.first_row) & 15;
-    const int ring_tiles = a.ring_rows / AB_TILE_ROWS;
-    const int ring_tiles16 = a.ring_rows / TILE_HOPS;
-    const int ptile0 = (a.row0 + a.first_row) >> 4;
-    const int tiles_total = (shift + a.n_hops + TILE_HOPS - 1) / TILE_HOPS;
-    const int tiles_per_split = (tiles_total + a.splits - 1) / a.splits;
-    const int t_begin = split * tiles_per_split;
-    const int t_end = min(tiles_total, t_begin + tiles_per_split);
+    const TileRange g = tile_range(a.row0, a.first_row, a.ring_rows, a.n_hops);
+    const int shift = g.shift, tiles_total = g.tiles_total, ring_tiles = g.ring_tiles, ring_tiles16 = g.ring_tiles16, ptile0 = g.ptile0;
+    const Share sh = split_share(tiles_total, a.splits, split);
+    const int t_begin = sh.begin, t_end = sh.end;
     if (t_begin >= t_end) return;
 
     /* fft_size 4096 / 8192 (round 6): the window in SEGMENTS of 2 048 samples, one launch each -- segment a.seg contracts window samples [2048 seg, 2048 seg + 2048)
@@ -206,6 +197,7 @@ __global__ __launch_bounds__(64 * NW, NW == 4 ? (MAX_LD <= 6 ? 3 : 1) : 2) void 
             __builtin_amdgcn_sched_barrier(0);
         }
         acc += acc1;
+        /* (its own copy of mfma_front.h's f32_exchange_put() / f32_exchange_sum(): measured in this file: with the helpers the eight MAX_LD = 12, NW = 4 variants invert two branches -- s_cbranch_vccz 0 -> 2, s_cbranch_vccnz 21 -> 19) */
         /* the other pieces' partial sums reach wave 0 through LDS; two areas alternate so that a wave a tile ahead never overwrites what wave 0 still adds up */
         float4* ex = exch + (t & 1) * (NW - 1) * 64;
         if (piece != fin) ex[((piece - fin - 1) & (NW - 1)) * 64 + lane] = make_float4(acc[0], acc[1], acc[2], acc[3]);
@@ -298,15 +290,8 @@ template <int FFT_N, int MAX_LD, int NW, int AL8>
 static void launch_f32_al(const F32Args& a, hipStream_t stream) {
     const long groups = (long)a.n_items * a.splits;
     const size_t lds = (size_t)2 * a.lds_per_buf + 2 * (NW - 1) * 64 * sizeof(float4);
-    /* more than the default 64 KiB of dynamic LDS: opt in to the CU's 160 KiB, once per kernel variant AND device (the attribute belongs to the function as loaded
-     * on the current device; a process may drive several GPUs) */
-    static std::atomic<bool> big_lds[64]; /* (per instantiation; zero-initialised; the shim launches from one thread per GPU: set twice is harmless, torn is not possible) */
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (lds > 64 * 1024 && (dev >= 64 || !big_lds[dev].load(std::memory_order_acquire))) {
-        /* (the CU's whole 160 KiB, not this launch's size: a later handle of the same process may have longer hops) */
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&channelizer_f32_kernel<FFT_N, MAX_LD, NW, AL8>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess && dev < 64) big_lds[dev].store(true, std::memory_order_release);
-    }
+    static std::atomic<bool> big_lds[BIG_LDS_DEVICES]; /* (per kernel variant) */
+    opt_in_big_lds(reinterpret_cast<const void*>(&channelizer_f32_kernel<FFT_N, MAX_LD, NW, AL8>), lds, big_lds);
     hipLaunchKernelGGL((channelizer_f32_kernel<FFT_N, MAX_LD, NW, AL8>), dim3((unsigned)groups), dim3(64 * NW), lds, stream, a);
 }
 

@@ -4,7 +4,7 @@
  * The contraction is channelizer_f32.hip's, unchanged: v_mfma_f32_16x16x4_f32, float32 products and sums, the contraction index split over the workgroup's waves
  * (wave p owns window samples [S p / NW, S (p + 1) / NW)), resident B fragments read from the SAME tables in the same order (params.cpp, build_f32_tables: the table
  * is linear in the contraction index, so it serves any cut into segments and pieces), two accumulators, the finishing wave that rotates with the workgroup, the
- * ring stores and the XCD-aware work-item order.  A flagged handle inside f32_supported()'s limits never comes here.
+ * ring stores and the XCD-aware work-item order.  From mfma_front.h: work_item(), tile_range(), split_share(), f32_exchange_put(), f32_exchange_sum(), opt_in_big_lds().  A flagged handle inside f32_supported()'s limits never comes here.
  *
  * What differs is the staging.  The ordinary kernel stages the 16 hops of a tile as ONE contiguous piece of the stream, 15 hops + a window long: at these hops
  * that is mostly bytes between windows, and it is what overflows LDS.  Here a tile is staged as 16 ROWS, row r = the S window samples of hop r that this launch
@@ -30,17 +30,17 @@
 #include "common.h"
 #include "f32_wide_map.h"
 #include "kernels.h"
+#include "mfma_front.h"
 
 namespace airband {
 
 namespace {
 
-typedef float v4f __attribute__((ext_vector_type(4)));
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef unsigned v4u __attribute__((ext_vector_type(4))); /* (not HIP's uint4: an array of that class type ends up in scratch memory) */
 typedef unsigned v2u __attribute__((ext_vector_type(2)));
 
-constexpr int TILE_HOPS = F32W_TILE_HOPS;
+static_assert(TILE_HOPS == F32W_TILE_HOPS, "f32_wide_map.h plans for the tiles of mfma_front.h");
 
 /* S: window samples staged per launch (256, 512, 1024); NW = f32w_nw(S) waves; AL8: hops of an odd number of samples */
 template <int S, int NW, bool AL8>
@@ -59,26 +59,19 @@ __global__ __launch_bounds__(64 * NW, S == 256 ? 3 : 2) void channelizer_f32_wid
     const int tid = (int)threadIdx.x;
     const int lane = tid & 63;
     const int piece = __builtin_amdgcn_readfirstlane(tid >> 6);
-    /* XCD-aware placement, as channelizer_f32.hip */
     const int wg = blockIdx.x;
-    const int i_lin = wg % a.n_items;
-    const int g128 = i_lin & ~127, in128 = i_lin & 127;
-    const int item = ((a.n_items - g128) >= 128) ? g128 + (in128 & 7) * 16 + (in128 >> 3) : i_lin;
-    const int split = wg / a.n_items;
+    const WorkItem w = work_item(wg, a.n_items); /* which (dongle, group of 8 channels), placed by XCD */
+    const int item = w.item, split = w.split;
     if (split >= a.splits) return;
     const int d = a.item_dev[item], ch0 = a.item_group[item] * 8;
     const DevConst dev = a.dev[d];
     if (dev.disabled) return; /* workgroup-uniform, in front of every barrier */
     const long hop_bytes = a.hop_bytes;
 
-    const int shift = (a.row0 + a.first_row) & 15;
-    const int ring_tiles = a.ring_rows / AB_TILE_ROWS;
-    const int ring_tiles16 = a.ring_rows / TILE_HOPS;
-    const int ptile0 = (a.row0 + a.first_row) >> 4;
-    const int tiles_total = (shift + a.n_hops + TILE_HOPS - 1) / TILE_HOPS;
-    const int tiles_per_split = (tiles_total + a.splits - 1) / a.splits;
-    const int t_begin = split * tiles_per_split;
-    const int t_end = min(tiles_total, t_begin + tiles_per_split);
+    const TileRange g = tile_range(a.row0, a.first_row, a.ring_rows, a.n_hops);
+    const int shift = g.shift, tiles_total = g.tiles_total, ring_tiles = g.ring_tiles, ring_tiles16 = g.ring_tiles16, ptile0 = g.ptile0;
+    const Share sh = split_share(tiles_total, a.splits, split);
+    const int t_begin = sh.begin, t_end = sh.end;
     if (t_begin >= t_end) return;
 
     /* the span of this dongle, from the aligned origin at or in front of its first byte, moved on to the window segment of this launch */
@@ -173,18 +166,12 @@ __global__ __launch_bounds__(64 * NW, S == 256 ? 3 : 2) void channelizer_f32_wid
             __builtin_amdgcn_sched_barrier(0);
         }
         acc += acc1;
-        /* two exchange areas alternate: a wave a tile ahead never overwrites what the finishing wave still adds up */
-        float4* ex = exch + (t & 1) * (NW - 1) * 64;
-        if (piece != fin) ex[((piece - fin - 1) & (NW - 1)) * 64 + lane] = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        float4* ex = f32_exchange_put<NW>(exch, t, piece, fin, lane, acc);
         __syncthreads(); /* every wave has read the image; the partial sums are in place */
         if (t + 1 < t_end) park_tile();
         if (piece != fin) continue;
         float val[4] = {acc[0], acc[1], acc[2], acc[3]};
-#pragma unroll
-        for (int q = 0; q < NW - 1; q++) {
-            const float4 o = ex[q * 64 + lane];
-            val[0] += o.x; val[1] += o.y; val[2] += o.z; val[3] += o.w;
-        }
+        f32_exchange_sum<NW>(ex, lane, val);
         if (a.n_seg > 1) { /* (launch-uniform) window segments: whole-wave 1 KiB rows of partial sums, one per (work item, tile) */
             float4* row = a.partial + ((long)item * tiles_total + t) * 64 + lane;
             if (a.seg > 0) {
@@ -242,14 +229,9 @@ template <int S, int NW, bool AL8>
 void launch_one(const F32Args& a, hipStream_t stream) {
     const long groups = (long)a.n_items * a.splits;
     const size_t lds = (size_t)f32w_lds_total(S, NW);
-    /* more than the default 64 KiB of dynamic LDS: opt in, once per kernel variant and device (channelizer_f32.hip, launch_f32_al) */
-    static std::atomic<bool> big_lds[64];
-    int dev = 0;
-    (void)hipGetDevice(&dev);
-    if (lds > 64 * 1024 && (dev >= 64 || !big_lds[dev].load(std::memory_order_acquire))) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&channelizer_f32_wide_kernel<S, NW, AL8>), hipFuncAttributeMaxDynamicSharedMemorySize, F32W_LDS_MAX) == hipSuccess && dev < 64)
-            big_lds[dev].store(true, std::memory_order_release);
-    }
+    static_assert(F32W_LDS_MAX == CU_LDS_BYTES, "the plans are cut to the LDS that opt_in_big_lds() asks for");
+    static std::atomic<bool> big_lds[BIG_LDS_DEVICES]; /* (per kernel variant) */
+    opt_in_big_lds(reinterpret_cast<const void*>(&channelizer_f32_wide_kernel<S, NW, AL8>), lds, big_lds);
     hipLaunchKernelGGL((channelizer_f32_wide_kernel<S, NW, AL8>), dim3((unsigned)groups), dim3(64 * NW), lds, stream, a);
 }
 

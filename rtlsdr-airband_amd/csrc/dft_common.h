@@ -1,18 +1,22 @@
 /* csrc/dft_common.h -- what the staging variants of the int8 matrix-core channelizer share (channelizer_dft.hip: one contiguous image of 16 hops;
- * channelizer_dft_wide.hip: one row per hop): the wait-count ladders, the MFMA wrapper of the ablation builds and the A-fragment readers. */
+ * channelizer_dft_wide.hip: one row per hop): the wait-count ladders, the MFMA wrapper of the ablation builds and the A-fragment readers; through mfma_front.h, the host's opt-in to more than 64 KiB of LDS.
+ *
+ * Ablation switches (experiment builds only, AIRBAND_EXTRA_DEFINES; the results are WRONG by construction, only the launch time is of interest): AB_ABL_NO_DMA,
+ * AB_ABL_NO_MFMA, AB_ABL_NO_STORE and AB_ABL_NO_LDS take the HBM reads, the matrix pipe, the output stores or the A-fragment reads out of the int8 kernel.  They are how
+ * its cost is taken apart (profiles/r04_experiments.md) and they stay; experiments that were measured and not adopted do not -- docs/KERNEL_HISTORY.md keeps those. */
 #ifndef AIRBAND_CSRC_DFT_COMMON_H
 #define AIRBAND_CSRC_DFT_COMMON_H
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mfma_front.h"
+
 namespace airband {
 
 namespace {
 
 typedef int v4i __attribute__((ext_vector_type(4)));
-
-constexpr int TILE_HOPS = 16;
 
 /* s_waitcnt vmcnt(n) for a run-time (wave-uniform) n: the instruction takes an immediate.  Waiting for FEWER operations than n to be
  * outstanding is always safe (it waits longer), so this is a ladder of compares, not a switch: the compiler lowers a 25-way switch to a
@@ -49,6 +53,53 @@ __device__ __forceinline__ v4i ab_mfma(v4i x, v4i b, v4i acc) {
 #else
     return __builtin_amdgcn_mfma_i32_16x16x64_i8(x, b, acc, 0, 0, 0);
 #endif
+}
+
+/* the integer digit sums of a tile: three balanced base-256 digits of the coefficient table; h*: the CS16 high-byte plane */
+struct TileAcc {
+    v4i a0, a1, a2, h0, h1, h2;
+};
+/* Recombination of the digit sums in single precision: every accumulator is an exact integer below 2^24 (exact as a float), and
+ *     value = ((acc2 * 2^16 + acc1 * 2^8 + acc0) + corr) * unscale          [+ 2^8 * the same of the high-byte plane for CS16]
+ * is three fused multiply-adds with the constants folded -- rounding at 2^-24 of partial sums that are never larger than the result's own full scale, the same error
+ * class as the final conversion to float (tests/test_gpu_parity.py, stage-1 bar 1e-5 relative RMS).  The scale factors are the same number on every lane -- scalar
+ * registers.  flipmask: u8 -> b - 128 as int8 in front of the MFMAs; s8 is int8 already, and has no offset to restore (cu = 0). */
+struct Recombine {
+    int flipmask;
+    float u0, u1, u2, cu, w0, w1, w2; /* w*: CS16 high-byte plane */
+};
+__device__ __forceinline__ float uni_f(double v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)v))); }
+__device__ __forceinline__ Recombine recombine(double unscale, double corr, int sfmt) {
+    Recombine k;
+    k.flipmask = sfmt == AIRBAND_SFMT_S8 ? 0 : (int)0x80808080;
+    k.u0 = uni_f(unscale); k.u1 = uni_f(unscale * 256.0); k.u2 = uni_f(unscale * 65536.0);
+    k.cu = sfmt == AIRBAND_SFMT_S8 ? 0.0f : (float)(corr * unscale);
+    k.w0 = k.u1; k.w1 = k.u2; k.w2 = uni_f(unscale * 16777216.0);
+    return k;
+}
+/* digit sums -> value r of the lane's four (hops grp * 4 .. + 3 of its column) */
+template <bool S16>
+__device__ __forceinline__ float digit_value(const TileAcc& A, Recombine k, int r) {
+    float y = __builtin_fmaf((float)A.a0[r], k.u0, k.cu);
+    y = __builtin_fmaf((float)A.a1[r], k.u1, y);
+    y = __builtin_fmaf((float)A.a2[r], k.u2, y);
+    if (S16) {
+        y = __builtin_fmaf((float)A.h0[r], k.w0, y);
+        y = __builtin_fmaf((float)A.h1[r], k.w1, y);
+        y = __builtin_fmaf((float)A.h2[r], k.w2, y);
+    }
+    return y;
+}
+
+/* Window pieces: the partial sums of pieces 1 .. NP-1 reach wave 0 through LDS, exch = [tile parity][piece - 1][lane] x 4 floats; wave 0 adds them to its own */
+template <int NP>
+__device__ __forceinline__ void piece_sum(const float4* exch, int t, int lane, float* val) {
+    const float4* ex = exch + (t & 1) * (NP - 1) * 64;
+#pragma unroll
+    for (int q = 0; q < NP - 1; q++) {
+        const float4 o = ex[q * 64 + lane];
+        val[0] += o.x; val[1] += o.y; val[2] += o.z; val[3] += o.w;
+    }
 }
 
 template <int AL>

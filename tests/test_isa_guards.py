@@ -304,3 +304,24 @@ def test_cf32_layouts_with_immediate_offsets_do_not_spill(f32_asm):
         assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, name
         assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)) == 0, name
     assert seen == 24  # 4 fft sizes x 2 tile sizes x 3 layouts
+
+
+def test_wide_hop_channelizers_do_not_spill(tmp_path):
+    """channelizer_dft_wide.hip promises that "a spilling variant is not shipped" (its segmented AL = 2 shape, which would spill 29 registers, is not built:
+    dft_wide_plan() keeps it on the wavefront FFT), and channelizer_f32_wide.hip's launch bounds hold two or three workgroups per CU without scratch.  Every kernel of
+    the two files, compiled with the product flags, keeps its vector registers out of scratch memory; the counts pin that every variant was looked at."""
+    if not (os.path.exists(HIPCC) or shutil.which("hipcc")):
+        pytest.skip("no hipcc")
+    for name, kernel, expected in (("channelizer_dft_wide.hip", "channelizer_dft_wide_kernel", 68), ("channelizer_f32_wide.hip", "channelizer_f32_wide_kernel", 6)):
+        out = str(tmp_path / (name + ".s"))
+        cmd = [HIPCC, "--offload-arch=gfx950", "-std=c++17"] + _product_flags(name) + ["-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only", "-o", out,
+                                                                                          os.path.join(ROOT, "rtlsdr-airband_amd", "csrc", name)]
+        subprocess.run(cmd, check=True, stderr=subprocess.DEVNULL, timeout=900)
+        seen = 0
+        for blk in open(out).read().split("  - .agpr_count")[1:]:
+            sym = re.search(r"\.name:\s+(\S+)", blk).group(1)
+            if kernel not in sym:
+                continue
+            seen += 1
+            assert int(re.search(r"\.vgpr_spill_count:\s+(\d+)", blk).group(1)) == 0, sym
+        assert seen == expected, (name, seen)
