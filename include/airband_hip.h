@@ -461,6 +461,56 @@ int airband_hip_collect_band_scope(airband_hip_handle* h, int32_t first_dev, int
  * scope does not keep), d_row_of_dev [device_count]: a dongle's row, or -1.  Any out-pointer may be NULL. */
 int airband_hip_device_band_scope(airband_hip_handle* h, float** d_mean, float** d_peak, int32_t** d_row_of_dev);
 
+/* ---- band survey ------------------------------------------------------------------------------------------------------------------
+ * A scope row answers questions -- where is the noise floor, is the front end overloaded or deaf, is there a carrier no channel is configured for -- whose
+ * answers are a handful of numbers, while the row is fft_size floats per dongle and batch.  A handle with a band scope may also carry a BAND SURVEY: the
+ * answers, worked out on the GPU behind the scope's kernel, so that a host copies 32 bytes and a few peaks per dongle instead of the rows.
+ * Definition.  For every selected dongle and batch take P[0 .. N), the dongle's row of ONE scope trace (N = fft_size, natural bin order: exactly the floats
+ * airband_hip_collect_band_scope() returns).  Every value is compared BY ITS BIT PATTERN as an unsigned 32-bit integer: for the non-negative floats the scope
+ * produces that is the float order; for any other bits (a NaN out of CF32 input) it is still a total order, and it indexes nothing.
+ *   floor       the value of rank r = min(N - 1, (N * floor_permille) / 1000) in ascending order (integer division, 0-based rank; 500: the upper median)
+ *   threshold   floor * threshold_ratio, one float32 multiplication
+ *   max_power, max_bin   the largest value and its bin, the lowest bin among equals
+ *   n_over      the number of bins with P[k] > threshold
+ *   peak        bin k with P[k] > threshold, P[k] >= P[(k - 1) mod N] and P[k] > P[(k + 1) mod N] (the band is circular; a plateau counts once, at its last
+ *               bin) that is not COVERED: k is covered when guard_bins >= 0 and min(|k - b|, N - |k - b|) <= guard_bins for the bin b of any channel
+ *               configured on that dongle
+ *   n_peaks     the number of peaks (may exceed max_peaks)
+ *   peaks[0 .. min(n_peaks, max_peaks))   the peaks by power descending, equal powers by ascending bin; entries behind them are {-1, 0.0f}
+ * b is the channel's PREPARE-TIME bin, slot [0] of airband_hip_channel_constants(); a scan device has the one bin of its channel.  AFC moves a channel's bin by
+ * a few bins while it tracks; the survey does not follow it: size guard_bins for the movement AFC is allowed.
+ * Lifetime.  The survey follows the scope's rows everywhere: it belongs to the batch airband_hip_collect() would return (on an AIRBAND_HIP_FLAG_PIPELINE handle
+ * it lags with it), is complete where the rows are (airband_hip_collect, airband_hip_synchronize, airband_hip_stream_wait_results), is left as it is by
+ * airband_hip_process_bins(), and a dongle that is switched off keeps the survey of its last batch.  Integer comparisons and no atomics on global memory: two
+ * runs of one input give identical bytes.  A handle without a survey allocates nothing for this, launches nothing and creates no stream or event. */
+typedef struct airband_hip_band_peak {
+    int32_t bin;    /* -1: no peak in this entry */
+    float power;
+} airband_hip_band_peak; /* 8 bytes */
+
+typedef struct airband_hip_band_summary {
+    float floor, threshold, max_power;
+    int32_t max_bin, n_over, n_peaks;
+    int32_t reserved[2]; /* 0 */
+} airband_hip_band_summary; /* 32 bytes */
+
+/* After airband_hip_set_band_scope() and before the first batch (calling it again before then replaces the survey; airband_hip_set_band_scope() called again
+ * drops it).  trace: the ONE AIRBAND_SCOPE_* bit whose rows are surveyed.  Validated before the device is touched: AIRBAND_HIP_EINVAL for a NULL handle, a
+ * handle without a scope, a trace that is not exactly one bit the scope keeps, max_peaks outside 1 .. 64, floor_permille outside 0 .. 1000, a threshold_ratio
+ * that is not finite and > 0, guard_bins outside -1 .. fft_size / 2 (-1: no bin is covered), a batch already enqueued; AIRBAND_HIP_ENOMEM when the buffers
+ * cannot be had -- the handle then runs on as it was, scope included. */
+int airband_hip_set_band_survey(airband_hip_handle* h, uint32_t trace, int32_t max_peaks, int32_t floor_permille, float threshold_ratio, int32_t guard_bins);
+
+/* The survey of the batch airband_hip_collect() would return, for dongles [first_dev, first_dev + n_dev) (dongle indices, not rows): summary is a HOST array
+ * [n_dev], peaks a HOST array [n_dev][max_peaks]; either may be NULL.  A dongle the scope's mask did not select gets a summary of zeros and peaks that are all
+ * {-1, 0.0f}.  One device-to-host copy per array, whatever the mask.  Does not mark the batch as collected.  AIRBAND_HIP_EAGAIN before any batch,
+ * AIRBAND_HIP_EINVAL on a handle without a survey or for a range outside the handle's dongles. */
+int airband_hip_collect_band_survey(airband_hip_handle* h, int32_t first_dev, int32_t n_dev, airband_hip_band_summary* summary, airband_hip_band_peak* peaks);
+
+/* Device-side views of the same (valid until the next process call), indexed BY SCOPE ROW (d_row_of_dev of airband_hip_device_band_scope()): d_summary [rows],
+ * d_peaks [rows][max_peaks].  Either out-pointer may be NULL. */
+int airband_hip_device_band_survey(airband_hip_handle* h, airband_hip_band_summary** d_summary, airband_hip_band_peak** d_peaks);
+
 /* Makes `stream` (a hipStream_t of a GPU-side consumer, e.g. the stream an RCCL all-reduce of the mixer sums is issued on)
  * wait for the results of the batch the last process call completed -- no host synchronisation.  The consumer hands its
  * stream to the next airband_hip_process_device() call, which then orders the overwrite of the result buffers behind it. */

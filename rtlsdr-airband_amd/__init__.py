@@ -35,6 +35,7 @@ EXPORTS = [
     "airband_hip_prepare_scan", "airband_hip_set_freq_index", "airband_hip_freq_stats",
     "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
     "airband_hip_set_band_scope", "airband_hip_collect_band_scope", "airband_hip_device_band_scope",
+    "airband_hip_set_band_survey", "airband_hip_collect_band_survey", "airband_hip_device_band_survey",
     "airband_hip_channelizer_reason", "airband_hip_wide_hop_lds_bytes", "airband_hip_schedule_info", "airband_hip_wide_hop_plan",
 ]
 # Exported entries whose names carry digits.  Kept apart from EXPORTS, which tests/test_abi.py compares with the header's names through a pattern of letters and
@@ -106,7 +107,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
-    for name, argtypes in capi.BAND_SCOPE_PROTOTYPES.items():
+    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()):
         if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
             getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
@@ -364,6 +365,7 @@ class AirbandHip:
         traces = (capi.SCOPE_MEAN if mean else 0) | (capi.SCOPE_PEAK if peak else 0)
         self._check(self.L.airband_hip_set_band_scope(self.h, m.ctypes.data if m is not None else None, int(windows), traces))
         self.scope_traces = traces
+        self.survey_peaks = 0  # a new scope drops the survey
 
     def collect_band_scope(self, first_dev: int = 0, n_dev: Optional[int] = None) -> dict:
         """The scope of the batch collect() would return, for dongles [first_dev, first_dev + n_dev): dict(mean=[n_dev][fft_size], peak=...) with the traces
@@ -385,6 +387,31 @@ class AirbandHip:
         ptrs = [C.c_void_p() for _ in range(3)]
         self._check(self.L.airband_hip_device_band_scope(self.h, *[C.byref(p) for p in ptrs]))
         return {k: (p.value or 0) for k, p in zip(["mean", "peak", "row_of_dev"], ptrs)}
+
+    def set_band_survey(self, trace: str = "mean", max_peaks: int = 8, floor_permille: int = 500, threshold_db: float = 10.0, guard_bins: int = 8):
+        """Band survey (airband_hip_set_band_survey): per batch and scope row of `trace` ("mean" or "peak"), the noise floor (the value of rank floor_permille / 1000),
+        the strongest bin and the peaks more than threshold_db above the floor that lie further than guard_bins from every configured channel (guard_bins = -1:
+        every peak).  After set_band_scope(), before the first batch."""
+        bit = {"mean": capi.SCOPE_MEAN, "peak": capi.SCOPE_PEAK}[trace]
+        ratio = np.float32(10.0 ** (float(threshold_db) / 10.0))
+        self._check(self.L.airband_hip_set_band_survey(self.h, bit, int(max_peaks), int(floor_permille), float(ratio), int(guard_bins)))
+        self.survey_peaks = int(max_peaks)
+
+    def collect_band_survey(self, first_dev: int = 0, n_dev: Optional[int] = None) -> dict:
+        """The survey of the batch collect() would return, for dongles [first_dev, first_dev + n_dev): dict(summary=[n_dev] of capi.SUMMARY_DTYPE,
+        peaks=[n_dev][max_peaks] of capi.PEAK_DTYPE); a zero summary and {-1, 0} peaks for dongles the scope's mask did not select.  Repeatable."""
+        n = self.geometry.device_count - first_dev if n_dev is None else int(n_dev)
+        summary = np.empty((n,), capi.SUMMARY_DTYPE)
+        peaks = np.empty((n, max(getattr(self, "survey_peaks", 0), 1)), capi.PEAK_DTYPE)
+        self._check(self.L.airband_hip_collect_band_survey(self.h, int(first_dev), n, summary.ctypes.data, peaks.ctypes.data))
+        return dict(summary=summary, peaks=peaks)
+
+    def device_band_survey(self) -> dict:
+        """Device pointers of the current survey (valid until the next process call), indexed by scope row: summary [rows] of 32 bytes, peaks [rows][max_peaks]
+        of 8 bytes."""
+        ptrs = [C.c_void_p() for _ in range(2)]
+        self._check(self.L.airband_hip_device_band_survey(self.h, *[C.byref(p) for p in ptrs]))
+        return {k: (p.value or 0) for k, p in zip(["summary", "peaks"], ptrs)}
 
     def set_freq_index(self, dev: int, freq_idx: int):
         """Entry freq_idx of dongle dev's scan list is in force for every batch enqueued from now on (latched per batch)."""

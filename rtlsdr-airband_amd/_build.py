@@ -41,6 +41,7 @@ HIP_SOURCES = {
     "demod.hip": ["-O3", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "gate.hip": ["-O3"],  # signal-gated collect: integer passes and a row copy
     "band_scope.hip": ["-O3"],  # band scope: a wavefront FFT of a few windows per batch and dongle, mean and peak power per bin
+    "band_survey.hip": ["-O3"],  # band survey: rank select, threshold and peak list of every scope row, integer passes over LDS
     "airband_hip.cpp": ["-O2", "-x", "hip"],
 }
 HOST_SOURCES = {"params.cpp": ["-O2", "-ffp-contract=off", "-fno-fast-math"]}

@@ -53,6 +53,15 @@ class ChannelStats(C.Structure):
                 ("active_counter", C.c_uint64), ("bin", C.c_int32), ("squelch_state", C.c_int32), ("signal_outside_filter", C.c_int32), ("reserved", C.c_int32)]
 
 
+class BandPeak(C.Structure):
+    _fields_ = [("bin", C.c_int32), ("power", C.c_float)]
+
+
+class BandSummary(C.Structure):
+    _fields_ = [("floor", C.c_float), ("threshold", C.c_float), ("max_power", C.c_float), ("max_bin", C.c_int32), ("n_over", C.c_int32), ("n_peaks", C.c_int32),
+                ("reserved", C.c_int32 * 2)]
+
+
 def channel_cfg(frequency, modulation=MOD_AM, afc=0, squelch_threshold_dbfs=0, squelch_snr_threshold_db=-1.0, notch_freq=0.0, notch_q=0.0, ctcss_freq=0.0,
                 bandwidth_hz=0, ampfactor=1.0, tau_us=-1, has_iq_outputs=0) -> ChannelCfg:
     return ChannelCfg(int(frequency), int(modulation), int(afc), int(squelch_threshold_dbfs), float(squelch_snr_threshold_db), float(notch_freq),
@@ -74,6 +83,51 @@ BAND_SCOPE_PROTOTYPES = {
     "airband_hip_collect_band_scope": [_vp, _i32, _i32, _vp, _vp],
     "airband_hip_device_band_scope": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
 }
+
+# the band survey's (same header)
+_f32 = C.c_float
+BAND_SURVEY_PROTOTYPES = {
+    "airband_hip_set_band_survey": [_vp, _u32, _i32, _i32, _f32, _i32],
+    "airband_hip_collect_band_survey": [_vp, _i32, _i32, _vp, _vp],
+    "airband_hip_device_band_survey": [_vp, C.POINTER(_vp), C.POINTER(_vp)],
+}
+# numpy views of airband_hip_band_peak / airband_hip_band_summary
+PEAK_DTYPE = [("bin", "<i4"), ("power", "<f4")]
+SUMMARY_DTYPE = [("floor", "<f4"), ("threshold", "<f4"), ("max_power", "<f4"), ("max_bin", "<i4"), ("n_over", "<i4"), ("n_peaks", "<i4"), ("reserved", "<i4", (2,))]
+
+
+def band_survey_reference(row, bins, max_peaks, floor_permille, ratio, guard_bins):
+    """The band survey's definition (include/airband_hip.h) on one scope row, in numpy: what airband_hip_collect_band_survey() returns for the dongle whose row of
+    the surveyed trace is `row` and whose channels sit on the prepare-time bins `bins`.  Every comparison is on the values' bit patterns as unsigned integers;
+    the threshold is the one float32 multiplication.  Returns dict(floor, threshold, max_power: float32; max_bin, n_over, n_peaks: int;
+    peaks: [max_peaks] array of PEAK_DTYPE, {-1, 0} behind the listed ones)."""
+    import numpy as np
+
+    row = np.ascontiguousarray(row, np.float32)
+    u = row.view(np.uint32)
+    n = len(u)
+    order = np.sort(u)
+    floor = order[min(n - 1, (n * int(floor_permille)) // 1000)]
+    with np.errstate(all="ignore"):
+        threshold = np.array([floor], np.uint32).view(np.float32)[0] * np.float32(ratio)
+    t = np.array([threshold], np.float32).view(np.uint32)[0]
+    max_bin = int(np.argmax(u))  # the first among equals
+    over = u > t
+    is_peak = over & (u >= np.roll(u, 1)) & (u > np.roll(u, -1))
+    if guard_bins >= 0:
+        k = np.arange(n)
+        for b in bins:
+            d = np.abs(k - int(b))
+            is_peak &= ~(np.minimum(d, n - d) <= guard_bins)
+    at = np.flatnonzero(is_peak)
+    at = at[np.lexsort((at, -u[at].astype(np.int64)))]  # power descending, then bin ascending
+    peaks = np.zeros(int(max_peaks), PEAK_DTYPE)
+    peaks["bin"] = -1
+    m = min(len(at), int(max_peaks))
+    peaks["bin"][:m] = at[:m]
+    peaks["power"][:m] = row[at[:m]]
+    return dict(floor=np.array([floor], np.uint32).view(np.float32)[0], threshold=np.float32(threshold), max_power=row[max_bin], max_bin=max_bin,
+                n_over=int(over.sum()), n_peaks=int(len(at)), peaks=peaks)
 
 
 def scope_window_hops(windows: int, wave_batch: int):

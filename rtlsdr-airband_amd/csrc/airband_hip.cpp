@@ -8,7 +8,9 @@
 #include <hip/hip_runtime.h>
 #include <dlfcn.h>
 
+#include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -327,6 +329,55 @@ ScopeArgs scope_args(airband_hip_handle* h, const void* d_iq, size_t stride_byte
     return a;
 }
 
+/* The band survey of the same batch (airband_hip_set_band_survey): directly behind the scope's kernel on whatever stream that went to, so that stream order alone
+ * makes the rows complete, a switched-off dongle's carried-over row included.  Its results go to the set the scope's rows went to. */
+void launch_survey_behind_scope(airband_hip_handle* h, const ScopeArgs& sa, hipStream_t s) {
+    BandScope& sc = h->scope;
+    BandSurvey& sv = sc.survey;
+    if (sv.max_peaks <= 0) return;
+    const int set = (int)(sc.launches % (uint64_t)sc.n_sets);
+    SurveyArgs a;
+    a.rows = sv.trace == AIRBAND_SCOPE_MEAN ? sa.mean : sa.peak;
+    a.bin_first = sv.d_bin_first.p;
+    a.bins = sv.d_bins.p;
+    a.summary = sv.d_summary[set].p;
+    a.peaks = sv.d_peaks[set].p;
+    a.n_rows = sc.n_rows;
+    a.fft_log = sa.fft_log;
+    a.max_peaks = sv.max_peaks;
+    a.rank = sv.rank;
+    a.guard_bins = sv.guard_bins;
+    a.ratio = sv.ratio;
+    launch_band_survey(a, s);
+}
+
+/* rows [r0, r0 + n) of a survey array of `per_row` elements a row -> the entries of the selected dongles among [first_dev, first_dev + n_dev): ONE copy, straight into
+ * the caller's array where every dongle of the range is selected, through a host vector otherwise.  Entries of the other dongles are set to `blank`. */
+template <class T>
+int collect_survey_rows(airband_hip_handle* h, const T* d_src, size_t per_row, int first_dev, int n_dev, T* out, const T& blank, hipStream_t s) {
+    const BandScope& sc = h->scope;
+    int r0 = -1, n = 0;
+    for (int i = 0; i < n_dev; i++)
+        if (sc.row_of_dev[first_dev + i] >= 0) {
+            if (r0 < 0) r0 = sc.row_of_dev[first_dev + i];
+            n++; /* rows are dense in ascending dongle order: the range's rows are r0 .. r0 + n - 1 */
+        }
+    if (n == n_dev) {
+        if (n) HIP_TRY(h, hipMemcpyAsync(out, d_src + (size_t)r0 * per_row, (size_t)n * per_row * sizeof(T), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+        HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+        return AIRBAND_HIP_OK;
+    }
+    std::vector<T> tmp((size_t)n * per_row);
+    if (n) HIP_TRY(h, hipMemcpyAsync(tmp.data(), d_src + (size_t)r0 * per_row, tmp.size() * sizeof(T), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    for (int i = 0; i < n_dev; i++) {
+        const int row = sc.row_of_dev[first_dev + i];
+        if (row < 0) std::fill(out + (size_t)i * per_row, out + (size_t)(i + 1) * per_row, blank);
+        else std::copy(tmp.begin() + (size_t)(row - r0) * per_row, tmp.begin() + (size_t)(row - r0 + 1) * per_row, out + (size_t)i * per_row);
+    }
+    return AIRBAND_HIP_OK;
+}
+
 /* front batch front_batches has its scope in set (launches % n_sets); the set becomes the current one with the batch's back half (run_back_half) */
 void scope_launched(airband_hip_handle* h) {
     BandScope& sc = h->scope;
@@ -340,7 +391,9 @@ int scope_fork(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, Fro
     HIP_TRY(h, hipEventRecord(sc.ev_fork, s), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipStreamWaitEvent(sc.stream, sc.ev_fork, 0), AIRBAND_HIP_ERUNTIME);
     if (h->ev_last && h->ev_last_pending) HIP_TRY(h, hipStreamWaitEvent(sc.stream, h->ev_last, 0), AIRBAND_HIP_ERUNTIME); /* a batch (and its scope) on a caller's stream */
-    launch_band_scope(scope_args(h, d_iq, stride_bytes, r), sc.stream);
+    const ScopeArgs sa = scope_args(h, d_iq, stride_bytes, r);
+    launch_band_scope(sa, sc.stream);
+    launch_survey_behind_scope(h, sa, sc.stream);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("band scope launch: ") + hipGetErrorString(e));
     HIP_TRY(h, hipEventRecord(sc.ev_done, sc.stream), AIRBAND_HIP_ERUNTIME);
@@ -357,7 +410,9 @@ int scope_join(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, Fro
     }
     /* the caller's stream, behind stage 1 -- and behind the scope launch before this one, whose rows a switched-off dongle's are carried over from */
     if (sc.launches > 0) HIP_TRY(h, hipStreamWaitEvent(s, sc.ev_done, 0), AIRBAND_HIP_ERUNTIME);
-    launch_band_scope(scope_args(h, d_iq, stride_bytes, r), s);
+    const ScopeArgs sa = scope_args(h, d_iq, stride_bytes, r);
+    launch_band_scope(sa, s);
+    launch_survey_behind_scope(h, sa, s);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("band scope launch: ") + hipGetErrorString(e));
     HIP_TRY(h, hipEventRecord(sc.ev_done, s), AIRBAND_HIP_ERUNTIME);
@@ -1690,6 +1745,79 @@ int airband_hip_device_band_scope(airband_hip_handle* h, float** d_mean, float**
     if (d_mean) *d_mean = sc.d_mean[sc.cur].p;
     if (d_peak) *d_peak = sc.d_peak[sc.cur].p;
     if (d_row_of_dev) *d_row_of_dev = sc.d_row_of_dev.p;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_set_band_survey(airband_hip_handle* h, uint32_t trace, int32_t max_peaks, int32_t floor_permille, float threshold_ratio, int32_t guard_bins) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const Plan& p = h->plan;
+    BandScope& sc = h->scope;
+    if (sc.windows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band scope (airband_hip_set_band_scope)");
+    if ((trace != AIRBAND_SCOPE_MEAN && trace != AIRBAND_SCOPE_PEAK) || !(sc.traces & trace))
+        return fail(h, AIRBAND_HIP_EINVAL, "trace must be exactly one AIRBAND_SCOPE_* bit the scope keeps");
+    if (max_peaks < 1 || max_peaks > 64) return fail(h, AIRBAND_HIP_EINVAL, "max_peaks must lie in 1 .. 64");
+    if (floor_permille < 0 || floor_permille > 1000) return fail(h, AIRBAND_HIP_EINVAL, "floor_permille must lie in 0 .. 1000");
+    if (!std::isfinite(threshold_ratio) || !(threshold_ratio > 0.0f)) return fail(h, AIRBAND_HIP_EINVAL, "threshold_ratio must be finite and above 0");
+    if (guard_bins < -1 || guard_bins > h->N / 2) return fail(h, AIRBAND_HIP_EINVAL, "guard_bins must lie in -1 .. fft_size / 2");
+    if (p.fft_log < 8 || p.fft_log > 13) return fail(h, AIRBAND_HIP_EINVAL, "the band survey takes fft sizes 256 .. 8192");
+    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the band survey is set before the first batch");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* built beside the handle and moved in whole: a failed allocation leaves the handle, its scope and an earlier survey as they were */
+    BandSurvey sv;
+    sv.trace = trace;
+    sv.rank = (int)std::min<int64_t>((int64_t)h->N - 1, (int64_t)h->N * floor_permille / 1000);
+    sv.guard_bins = guard_bins;
+    sv.ratio = threshold_ratio;
+    std::vector<int> bin_first(1, 0), bins;
+    for (int d = 0; d < p.n_dev; d++) {
+        if (sc.row_of_dev[d] < 0) continue;
+        for (int j = 0; j < p.dev[d].n_ch; j++) bins.push_back(p.cc[p.chan_base[d] + j].base_bin); /* the prepare-time bin: slot [0] of airband_hip_channel_constants() */
+        bin_first.push_back((int)bins.size());
+    }
+    const std::vector<airband_hip_band_peak> none((size_t)sc.n_rows * (size_t)max_peaks, airband_hip_band_peak{-1, 0.0f});
+    hipError_t e = upload(sv.d_bin_first, bin_first);
+    if (e == hipSuccess) e = upload(sv.d_bins, bins);
+    for (int q = 0; q < sc.n_sets; q++) {
+        if (e == hipSuccess) e = sv.d_summary[q].alloc_zeroed((size_t)sc.n_rows);
+        if (e == hipSuccess) e = upload(sv.d_peaks[q], none);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize(); /* the initial values are in place before a kernel on another stream writes the rows */
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); /* this call's error, reported here: not the next launch's */
+        return fail(h, AIRBAND_HIP_ENOMEM, std::string("band survey buffers: ") + hipGetErrorString(e));
+    }
+    sv.max_peaks = max_peaks;
+    sc.survey = std::move(sv);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_band_survey(airband_hip_handle* h, int32_t first_dev, int32_t n_dev, airband_hip_band_summary* summary, airband_hip_band_peak* peaks) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const BandScope& sc = h->scope;
+    const BandSurvey& sv = sc.survey;
+    if (sc.windows <= 0 || sv.max_peaks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band survey (airband_hip_set_band_survey)");
+    if (first_dev < 0 || n_dev < 0 || (int64_t)first_dev + n_dev > h->plan.n_dev) return fail(h, AIRBAND_HIP_EINVAL, "device range out of bounds");
+    if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    if (summary) {
+        const int rc = collect_survey_rows(h, sv.d_summary[sc.cur].p, 1, first_dev, n_dev, summary, airband_hip_band_summary{}, s);
+        if (rc != AIRBAND_HIP_OK) return rc;
+    }
+    if (peaks) {
+        const int rc = collect_survey_rows(h, sv.d_peaks[sc.cur].p, (size_t)sv.max_peaks, first_dev, n_dev, peaks, airband_hip_band_peak{-1, 0.0f}, s);
+        if (rc != AIRBAND_HIP_OK) return rc;
+    }
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_device_band_survey(airband_hip_handle* h, airband_hip_band_summary** d_summary, airband_hip_band_peak** d_peaks) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const BandScope& sc = h->scope;
+    if (sc.windows <= 0 || sc.survey.max_peaks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band survey (airband_hip_set_band_survey)");
+    if (d_summary) *d_summary = sc.survey.d_summary[sc.cur].p;
+    if (d_peaks) *d_peaks = sc.survey.d_peaks[sc.cur].p;
     return AIRBAND_HIP_OK;
 }
 

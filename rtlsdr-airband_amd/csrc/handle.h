@@ -110,8 +110,21 @@ struct OutputGate {
 /* what airband_hip_set_band_scope() set up: replaced as a whole, one without windows is a handle without a scope (nothing allocated, nothing launched, no
  * stream, no event).  Handles whose next stage 1 may run before the last batch's results are collected (pipelined, run-ahead) keep TWO sets of rows: the
  * scope of front batch k goes to a set of its own and becomes the current one when the batch's back half is enqueued, as the batch's results do. */
+/* what airband_hip_set_band_survey() set up, a part of the scope it reads: replaced as a whole, gone with the scope, one without max_peaks is a scope without
+ * a survey (nothing allocated, nothing launched).  Its results follow the scope's rows: the same sets, the same `cur`. */
+struct BandSurvey {
+    int max_peaks = 0;         /* 0 = no survey */
+    uint32_t trace = 0;        /* the one AIRBAND_SCOPE_* bit whose rows are surveyed */
+    int rank = 0, guard_bins = 0;
+    float ratio = 0.0f;
+    DevBuf<int> d_bin_first, d_bins; /* by scope row: the prepare-time bins of the dongle's channels */
+    DevBuf<airband_hip_band_summary> d_summary[2];
+    DevBuf<airband_hip_band_peak> d_peaks[2];
+};
+
 struct BandScope {
     int windows = 0;           /* windows per batch; 0 = no scope */
+    BandSurvey survey;
     uint32_t traces = 0;       /* AIRBAND_SCOPE_* */
     int n_rows = 0, n_sets = 1;
     std::vector<int> row_of_dev;

@@ -330,5 +330,22 @@ long scope_region_bytes(int fft_log, int bytes_per_sample);
 int scope_waves(int fft_log, int bytes_per_sample); /* wavefronts per workgroup: four where four regions fit a CU's 160 KiB, else two, else one */
 void launch_band_scope(const ScopeArgs& a, hipStream_t stream);
 
+/* band survey (band_survey.hip): noise floor, strongest bin and the unconfigured carriers of every row of one scope trace, one workgroup per row; launched
+ * directly behind launch_band_scope() on the same stream */
+struct SurveyArgs {
+    const float* rows;        /* [n_rows][fft_size]: the scope trace's rows of this batch (ScopeArgs::mean or ::peak) */
+    const int* bin_first;     /* [n_rows + 1] a row's channel bins are bins[bin_first[row] .. bin_first[row + 1]): at most AB_MAX_CH_PER_DEV */
+    const int* bins;          /* prepare-time bins (ChanConst::base_bin) of the row's dongle */
+    airband_hip_band_summary* summary; /* [n_rows] */
+    airband_hip_band_peak* peaks;      /* [n_rows][max_peaks] */
+    int n_rows, fft_log;
+    int max_peaks;            /* 1 .. 64 */
+    int rank;                 /* min(fft_size - 1, fft_size * floor_permille / 1000) */
+    int guard_bins;           /* -1: no bin is covered */
+    float ratio;              /* threshold = floor * ratio */
+};
+size_t survey_lds_bytes(int fft_log); /* dynamic LDS per workgroup: the row and 1.5 KiB */
+void launch_band_survey(const SurveyArgs& a, hipStream_t stream);
+
 }  // namespace airband
 #endif
