@@ -511,6 +511,89 @@ int airband_hip_collect_band_survey(airband_hip_handle* h, int32_t first_dev, in
  * d_peaks [rows][max_peaks].  Either out-pointer may be NULL. */
 int airband_hip_device_band_survey(airband_hip_handle* h, airband_hip_band_summary** d_summary, airband_hip_band_peak** d_peaks);
 
+/* ---- band watch -------------------------------------------------------------------------------------------------------------------
+ * The survey of batch k knows nothing of batch k - 1.  A handle with a survey may also carry a BAND WATCH: a small table of carrier TRACKS per scope row,
+ * advanced once per batch on the GPU behind the survey's kernel, and one fleet-wide packed list of the batch's EVENTS -- a carrier confirmed, a carrier gone --
+ * so that a host copies a count and a few 16-byte records instead of every dongle's survey.  Defined on integers and on the survey's own output:
+ * capi.band_watch_reference() (rtlsdr-airband_amd/capi.py) is this text in plain Python, and the GPU's bytes equal its bytes.
+ * Parameters.  max_tracks T in 1 .. 64, match_bins M in 0 .. fft_size / 2, confirm_hits C in 1 .. 255, release_misses R in 1 .. 255, max_events E in
+ * 1 .. rows * (T + max_peaks).
+ * State per scope row.  T track slots; a slot is FREE, TENTATIVE or CONFIRMED.
+ * One batch of one row.  The watch batch number k counts the batches the watch has been advanced for on this handle, from 0.  The input is the survey's list
+ * of that row and batch, peaks[0 .. min(n_peaks, max_peaks)), in the survey's order (power descending, equal powers by ascending bin).
+ *   1. FOR EVERY PEAK {b, p} IN LIST ORDER consider the tracks that were live at the start of the batch and have not been matched in this batch.  Take the one
+ *      with the smallest circular distance min(|b - t|, N - |b - t|) (t: the track's bin, N = fft_size) that is <= M; among equals the lowest slot.
+ *        - there is one: bin = b (the track follows drift), power = p, max_power = the larger of the two BY BIT PATTERN as unsigned, misses = 0,
+ *          hits = min(hits + 1, 65535), last_batch = k; a tentative track with hits >= C becomes confirmed and an APPEAR event is emitted.
+ *        - there is none: take the lowest slot that was free at the start of the batch and has not been taken in this batch and fill it: tentative, bin = b,
+ *          hits = 1, misses = 0, first_batch = last_batch = k, power = max_power = p; with C == 1 it is confirmed at once and an APPEAR event is emitted.
+ *          No such slot: the row's `dropped` counter is incremented and nothing else happens.
+ *   2. FOR EVERY TRACK THAT WAS LIVE AT THE START OF THE BATCH AND WAS NOT MATCHED, in slot order: misses = min(misses + 1, 255); a tentative track is freed
+ *      at once (its sightings must be consecutive); a confirmed track with misses >= R emits a VANISH event and is freed.  A slot freed here is not reused
+ *      in the same batch.
+ * The row's events are those of step 1 in peak order, then those of step 2 in slot order: at most max_peaks + T.
+ * The fleet's event list.  All rows' events in ascending row order (ascending dongle order); n_events is the total, the first min(n_events, E) are kept.
+ * n_events > E is the caller's cue to read the track tables for this batch.
+ * Lifetime.  The watch follows the survey everywhere, as the survey follows the scope: it belongs to the batch airband_hip_collect() would return (on an
+ * AIRBAND_HIP_FLAG_PIPELINE handle it lags with it), is complete where the survey is, and airband_hip_process_bins() leaves it as it is.  ONE DIFFERENCE: a
+ * dongle that is switched off is NOT advanced -- its tracks are frozen, it has no events, its misses do not count, and it carries on when it is switched on
+ * again (the survey repeats the stale row of such a dongle; the watch does not turn that into hits).  k is one number per handle: it advances with every
+ * batch the watch's kernel runs for.  No floating-point operation, no atomics on global memory: equal input, equal bytes.  A handle without a watch
+ * allocates nothing for this and launches nothing. */
+#define AIRBAND_WATCH_FREE 0
+#define AIRBAND_WATCH_TENTATIVE 1
+#define AIRBAND_WATCH_CONFIRMED 2
+#define AIRBAND_WATCH_APPEAR 1
+#define AIRBAND_WATCH_VANISH 2
+
+typedef struct airband_hip_band_track {
+    int32_t bin;          /* -1: free slot (every other field 0) */
+    float power;          /* the matched peak's power in the last batch it was seen */
+    float max_power;      /* largest power ever matched, compared by bit pattern as unsigned */
+    uint32_t first_batch; /* watch batch number of the first sighting */
+    uint32_t last_batch;  /* ... of the last sighting */
+    uint16_t hits;        /* consecutive sightings while tentative, total sightings once confirmed, saturating at 65535 */
+    uint8_t misses;       /* consecutive batches without a match */
+    uint8_t state;        /* AIRBAND_WATCH_FREE / _TENTATIVE / _CONFIRMED */
+} airband_hip_band_track; /* 24 bytes */
+
+typedef struct airband_hip_band_event {
+    int32_t dev;      /* dongle index */
+    int32_t bin;      /* APPEAR: the peak's bin; VANISH: the track's last bin */
+    float power;      /* APPEAR: the peak's power; VANISH: the track's max_power */
+    uint8_t kind;     /* AIRBAND_WATCH_APPEAR / _VANISH */
+    uint8_t track;    /* slot */
+    uint16_t batches; /* APPEAR: hits; VANISH: min(65535, last_batch - first_batch + 1) */
+} airband_hip_band_event; /* 16 bytes */
+
+typedef struct airband_hip_band_watch_row {
+    int32_t n_live, n_confirmed; /* slots that are not free / that are confirmed, after the batch */
+    int32_t n_events;            /* the row's events of this batch */
+    int32_t dropped;             /* peaks that found neither a track nor a free slot: cumulative */
+} airband_hip_band_watch_row; /* 16 bytes */
+
+/* After airband_hip_set_band_survey() and before the first batch (calling it again before then replaces the watch; airband_hip_set_band_scope() and
+ * airband_hip_set_band_survey() called again drop it).  Validated before the device is touched: AIRBAND_HIP_EINVAL for a NULL handle, a handle without a
+ * survey, max_tracks outside 1 .. 64, match_bins outside 0 .. fft_size / 2, confirm_hits or release_misses outside 1 .. 255, max_events outside
+ * 1 .. rows * (max_tracks + max_peaks), a batch already enqueued; AIRBAND_HIP_ENOMEM when the buffers cannot be had -- the handle then runs on as it was,
+ * survey included. */
+int airband_hip_set_band_watch(airband_hip_handle* h, int32_t max_tracks, int32_t match_bins, int32_t confirm_hits, int32_t release_misses, int64_t max_events);
+
+/* The events of the batch airband_hip_collect() would return: *n_events is the fleet's total, events a HOST array sized for max_events records of which
+ * min(n_events, max_events) are written -- nothing past them.  Either pointer may be NULL.  Two small copies: the count, then exactly those records.  Does not
+ * mark the batch as collected.  AIRBAND_HIP_EAGAIN before any batch, AIRBAND_HIP_EINVAL on a handle without a watch. */
+int airband_hip_collect_band_events(airband_hip_handle* h, int64_t* n_events, airband_hip_band_event* events);
+
+/* The track tables of the same batch for dongles [first_dev, first_dev + n_dev) (dongle indices, not rows): rows is a HOST array [n_dev], tracks a HOST array
+ * [n_dev][max_tracks]; either may be NULL.  A dongle the scope's mask did not select gets a row of zeros and free slots (bin = -1, everything else 0).  One
+ * device-to-host copy per array.  Does not mark the batch as collected.  AIRBAND_HIP_EAGAIN before any batch, AIRBAND_HIP_EINVAL on a handle without a watch
+ * or for a range outside the handle's dongles. */
+int airband_hip_collect_band_tracks(airband_hip_handle* h, int32_t first_dev, int32_t n_dev, airband_hip_band_watch_row* rows, airband_hip_band_track* tracks);
+
+/* Device-side views of the same (valid until the next process call): d_n_events [1], d_events [max_events]; d_rows [rows], d_tracks [rows][max_tracks] indexed
+ * BY SCOPE ROW (d_row_of_dev of airband_hip_device_band_scope()).  Any out-pointer may be NULL. */
+int airband_hip_device_band_watch(airband_hip_handle* h, int32_t** d_n_events, airband_hip_band_event** d_events, airband_hip_band_watch_row** d_rows, airband_hip_band_track** d_tracks);
+
 /* Makes `stream` (a hipStream_t of a GPU-side consumer, e.g. the stream an RCCL all-reduce of the mixer sums is issued on)
  * wait for the results of the batch the last process call completed -- no host synchronisation.  The consumer hands its
  * stream to the next airband_hip_process_device() call, which then orders the overwrite of the result buffers behind it. */

@@ -36,6 +36,7 @@ EXPORTS = [
     "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
     "airband_hip_set_band_scope", "airband_hip_collect_band_scope", "airband_hip_device_band_scope",
     "airband_hip_set_band_survey", "airband_hip_collect_band_survey", "airband_hip_device_band_survey",
+    "airband_hip_set_band_watch", "airband_hip_collect_band_events", "airband_hip_collect_band_tracks", "airband_hip_device_band_watch",
     "airband_hip_channelizer_reason", "airband_hip_wide_hop_lds_bytes", "airband_hip_schedule_info", "airband_hip_wide_hop_plan",
 ]
 # Exported entries whose names carry digits.  Kept apart from EXPORTS, which tests/test_abi.py compares with the header's names through a pattern of letters and
@@ -107,7 +108,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
-    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()):
+    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()):
         if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
             getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
@@ -365,7 +366,9 @@ class AirbandHip:
         traces = (capi.SCOPE_MEAN if mean else 0) | (capi.SCOPE_PEAK if peak else 0)
         self._check(self.L.airband_hip_set_band_scope(self.h, m.ctypes.data if m is not None else None, int(windows), traces))
         self.scope_traces = traces
+        self.scope_rows = int(np.count_nonzero(m)) if m is not None else self.geometry.device_count
         self.survey_peaks = 0  # a new scope drops the survey
+        self.watch_tracks = self.watch_events = 0  # and the watch
 
     def collect_band_scope(self, first_dev: int = 0, n_dev: Optional[int] = None) -> dict:
         """The scope of the batch collect() would return, for dongles [first_dev, first_dev + n_dev): dict(mean=[n_dev][fft_size], peak=...) with the traces
@@ -396,6 +399,7 @@ class AirbandHip:
         ratio = np.float32(10.0 ** (float(threshold_db) / 10.0))
         self._check(self.L.airband_hip_set_band_survey(self.h, bit, int(max_peaks), int(floor_permille), float(ratio), int(guard_bins)))
         self.survey_peaks = int(max_peaks)
+        self.watch_tracks = self.watch_events = 0  # a new survey drops the watch
 
     def collect_band_survey(self, first_dev: int = 0, n_dev: Optional[int] = None) -> dict:
         """The survey of the batch collect() would return, for dongles [first_dev, first_dev + n_dev): dict(summary=[n_dev] of capi.SUMMARY_DTYPE,
@@ -412,6 +416,40 @@ class AirbandHip:
         ptrs = [C.c_void_p() for _ in range(2)]
         self._check(self.L.airband_hip_device_band_survey(self.h, *[C.byref(p) for p in ptrs]))
         return {k: (p.value or 0) for k, p in zip(["summary", "peaks"], ptrs)}
+
+    def set_band_watch(self, max_tracks: int = 8, match_bins: int = 2, confirm_hits: int = 2, release_misses: int = 4, max_events: Optional[int] = None):
+        """Band watch (airband_hip_set_band_watch): per scope row a table of max_tracks carrier tracks advanced by each batch's survey -- a peak within match_bins
+        of a track continues it, confirm_hits consecutive sightings confirm it (an APPEAR event), release_misses batches without it release it (a VANISH event) --
+        and one list of the fleet's events per batch, max_events records (None: 4 x rows, clipped to the range).  After set_band_survey(), before the first batch."""
+        if max_events is None:
+            rows = getattr(self, "scope_rows", 0)
+            max_events = max(1, min(4 * rows, rows * (int(max_tracks) + getattr(self, "survey_peaks", 0))))
+        self._check(self.L.airband_hip_set_band_watch(self.h, int(max_tracks), int(match_bins), int(confirm_hits), int(release_misses), int(max_events)))
+        self.watch_tracks, self.watch_events = int(max_tracks), int(max_events)
+
+    def collect_band_events(self) -> dict:
+        """The fleet's events of the batch collect() would return: dict(n_events = the total, events = the first min(n_events, max_events) of capi.EVENT_DTYPE, in
+        ascending dongle order).  Two small copies.  Repeatable."""
+        n = C.c_int64(0)
+        events = np.zeros((max(getattr(self, "watch_events", 0), 1),), capi.EVENT_DTYPE)
+        self._check(self.L.airband_hip_collect_band_events(self.h, C.byref(n), events.ctypes.data))
+        return dict(n_events=int(n.value), events=events[:min(int(n.value), len(events))])
+
+    def collect_band_tracks(self, first_dev: int = 0, n_dev: Optional[int] = None) -> dict:
+        """The track tables of the same batch for dongles [first_dev, first_dev + n_dev): dict(rows=[n_dev] of capi.WATCH_ROW_DTYPE, tracks=[n_dev][max_tracks] of
+        capi.TRACK_DTYPE); zero rows and free slots for dongles the scope's mask did not select.  Repeatable."""
+        n = self.geometry.device_count - first_dev if n_dev is None else int(n_dev)
+        rows = np.empty((n,), capi.WATCH_ROW_DTYPE)
+        tracks = np.empty((n, max(getattr(self, "watch_tracks", 0), 1)), capi.TRACK_DTYPE)
+        self._check(self.L.airband_hip_collect_band_tracks(self.h, int(first_dev), n, rows.ctypes.data, tracks.ctypes.data))
+        return dict(rows=rows, tracks=tracks)
+
+    def device_band_watch(self) -> dict:
+        """Device pointers of the current watch (valid until the next process call): n_events [1] int32, events [max_events] of 16 bytes; rows [rows] of 16 bytes
+        and tracks [rows][max_tracks] of 24 bytes, indexed by scope row."""
+        ptrs = [C.c_void_p() for _ in range(4)]
+        self._check(self.L.airband_hip_device_band_watch(self.h, *[C.byref(p) for p in ptrs]))
+        return {k: (p.value or 0) for k, p in zip(["n_events", "events", "rows", "tracks"], ptrs)}
 
     def set_freq_index(self, dev: int, freq_idx: int):
         """Entry freq_idx of dongle dev's scan list is in force for every batch enqueued from now on (latched per batch)."""

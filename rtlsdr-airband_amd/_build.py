@@ -42,6 +42,7 @@ HIP_SOURCES = {
     "gate.hip": ["-O3"],  # signal-gated collect: integer passes and a row copy
     "band_scope.hip": ["-O3"],  # band scope: a wavefront FFT of a few windows per batch and dongle, mean and peak power per bin
     "band_survey.hip": ["-O3"],  # band survey: rank select, threshold and peak list of every scope row, integer passes over LDS
+    "band_watch.hip": ["-O3"],  # band watch: carrier tracks per scope row advanced by the survey's list, the fleet's events packed in row order; integers only
     "airband_hip.cpp": ["-O2", "-x", "hip"],
 }
 HOST_SOURCES = {"params.cpp": ["-O2", "-ffp-contract=off", "-fno-fast-math"]}

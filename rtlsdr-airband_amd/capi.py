@@ -62,6 +62,19 @@ class BandSummary(C.Structure):
                 ("reserved", C.c_int32 * 2)]
 
 
+class BandTrack(C.Structure):
+    _fields_ = [("bin", C.c_int32), ("power", C.c_float), ("max_power", C.c_float), ("first_batch", C.c_uint32), ("last_batch", C.c_uint32), ("hits", C.c_uint16),
+                ("misses", C.c_uint8), ("state", C.c_uint8)]
+
+
+class BandEvent(C.Structure):
+    _fields_ = [("dev", C.c_int32), ("bin", C.c_int32), ("power", C.c_float), ("kind", C.c_uint8), ("track", C.c_uint8), ("batches", C.c_uint16)]
+
+
+class BandWatchRow(C.Structure):
+    _fields_ = [("n_live", C.c_int32), ("n_confirmed", C.c_int32), ("n_events", C.c_int32), ("dropped", C.c_int32)]
+
+
 def channel_cfg(frequency, modulation=MOD_AM, afc=0, squelch_threshold_dbfs=0, squelch_snr_threshold_db=-1.0, notch_freq=0.0, notch_q=0.0, ctcss_freq=0.0,
                 bandwidth_hz=0, ampfactor=1.0, tau_us=-1, has_iq_outputs=0) -> ChannelCfg:
     return ChannelCfg(int(frequency), int(modulation), int(afc), int(squelch_threshold_dbfs), float(squelch_snr_threshold_db), float(notch_freq),
@@ -128,6 +141,113 @@ def band_survey_reference(row, bins, max_peaks, floor_permille, ratio, guard_bin
     peaks["power"][:m] = row[at[:m]]
     return dict(floor=np.array([floor], np.uint32).view(np.float32)[0], threshold=np.float32(threshold), max_power=row[max_bin], max_bin=max_bin,
                 n_over=int(over.sum()), n_peaks=int(len(at)), peaks=peaks)
+
+
+# the band watch's (same header)
+_i64 = C.c_int64
+BAND_WATCH_PROTOTYPES = {
+    "airband_hip_set_band_watch": [_vp, _i32, _i32, _i32, _i32, _i64],
+    "airband_hip_collect_band_events": [_vp, C.POINTER(_i64), _vp],
+    "airband_hip_collect_band_tracks": [_vp, _i32, _i32, _vp, _vp],
+    "airband_hip_device_band_watch": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
+}
+WATCH_FREE, WATCH_TENTATIVE, WATCH_CONFIRMED = 0, 1, 2
+WATCH_APPEAR, WATCH_VANISH = 1, 2
+# numpy views of airband_hip_band_track / airband_hip_band_event / airband_hip_band_watch_row
+TRACK_DTYPE = [("bin", "<i4"), ("power", "<f4"), ("max_power", "<f4"), ("first_batch", "<u4"), ("last_batch", "<u4"), ("hits", "<u2"), ("misses", "u1"), ("state", "u1")]
+EVENT_DTYPE = [("dev", "<i4"), ("bin", "<i4"), ("power", "<f4"), ("kind", "u1"), ("track", "u1"), ("batches", "<u2")]
+WATCH_ROW_DTYPE = [("n_live", "<i4"), ("n_confirmed", "<i4"), ("n_events", "<i4"), ("dropped", "<i4")]
+
+
+def band_watch_blank(max_tracks):
+    """The state a watch starts from: (tracks [max_tracks] of TRACK_DTYPE, every slot free; row of WATCH_ROW_DTYPE, zeros)."""
+    import numpy as np
+
+    tracks = np.zeros(int(max_tracks), TRACK_DTYPE)
+    tracks["bin"] = -1
+    return tracks, np.zeros((), WATCH_ROW_DTYPE)
+
+
+def band_watch_reference(tracks, row, peaks, n_peaks, batch, max_tracks, match_bins, confirm_hits, release_misses, n_fft, dev=0):
+    """The band watch's definition (include/airband_hip.h) for one batch of one scope row, in plain Python: the row's table `tracks` ([max_tracks] of TRACK_DTYPE)
+    and record `row` (WATCH_ROW_DTYPE) as the batch before left them, the row's survey of this batch (`peaks` of PEAK_DTYPE as collect_band_survey() returns
+    them, `n_peaks` the summary's count), the watch batch number `batch`.  Returns (tracks, row, events): new arrays, events of EVENT_DTYPE with `dev` in their
+    first field.  A switched-off dongle is not advanced: do not call this for it.  Powers are moved and compared as bit patterns; nothing here is a float
+    operation."""
+    import numpy as np
+
+    T, M, Cn, R, N, k = int(max_tracks), int(match_bins), int(confirm_hits), int(release_misses), int(n_fft), int(batch) & 0xFFFFFFFF
+    tracks = np.array(tracks, TRACK_DTYPE).reshape(T).copy()
+    row = np.array(row, WATCH_ROW_DTYPE).copy()
+    peaks = np.ascontiguousarray(peaks, PEAK_DTYPE)
+    bits = peaks["power"].view(np.uint32)
+
+    def as_float(u):
+        return np.array([u], np.uint32).view(np.float32)[0]
+
+    def free(s):
+        tracks[s] = np.zeros((), TRACK_DTYPE)
+        tracks[s]["bin"] = -1
+
+    events = []
+    live0 = [int(tracks[s]["state"]) != WATCH_FREE for s in range(T)]  # at the start of the batch
+    matched, taken, dropped = [False] * T, [False] * T, 0
+    # 1. every peak in list order
+    for i in range(min(max(int(n_peaks), 0), len(peaks))):
+        b, p = int(peaks["bin"][i]), int(bits[i])
+        best = None
+        for s in range(T):
+            if live0[s] and not matched[s]:
+                d = abs(b - int(tracks[s]["bin"]))
+                d = min(d, N - d)
+                if d <= M and (best is None or d < best[0]):  # among equals the lowest slot
+                    best = (d, s)
+        if best is not None:
+            s = best[1]
+            t = tracks[s]
+            t["bin"] = b
+            t["power"] = as_float(p)
+            t["max_power"] = as_float(max(p, int(t["max_power"].view(np.uint32))))
+            t["misses"] = 0
+            t["hits"] = min(int(t["hits"]) + 1, 65535)
+            t["last_batch"] = k
+            matched[s] = True
+            if int(t["state"]) == WATCH_TENTATIVE and int(t["hits"]) >= Cn:
+                t["state"] = WATCH_CONFIRMED
+                events.append((dev, b, as_float(p), WATCH_APPEAR, s, int(t["hits"])))
+            continue
+        slot = next((s for s in range(T) if not live0[s] and not taken[s]), None)
+        if slot is None:
+            dropped += 1
+            continue
+        taken[slot] = True
+        t = tracks[slot]
+        t["bin"], t["power"], t["max_power"] = b, as_float(p), as_float(p)
+        t["first_batch"] = t["last_batch"] = k
+        t["hits"], t["misses"], t["state"] = 1, 0, WATCH_TENTATIVE
+        if Cn <= 1:
+            t["state"] = WATCH_CONFIRMED
+            events.append((dev, b, as_float(p), WATCH_APPEAR, slot, 1))
+    # 2. the tracks nothing matched, in slot order
+    for s in range(T):
+        if not live0[s] or matched[s]:
+            continue
+        t = tracks[s]
+        t["misses"] = min(int(t["misses"]) + 1, 255)
+        if int(t["state"]) == WATCH_TENTATIVE:
+            free(s)
+        elif int(t["misses"]) >= R:
+            span = (int(t["last_batch"]) - int(t["first_batch"]) + 1) & 0xFFFFFFFF
+            events.append((dev, int(t["bin"]), t["max_power"], WATCH_VANISH, s, min(65535, span)))
+            free(s)
+    row["n_live"] = int((tracks["state"] != WATCH_FREE).sum())
+    row["n_confirmed"] = int((tracks["state"] == WATCH_CONFIRMED).sum())
+    row["n_events"] = len(events)
+    row["dropped"] = int(row["dropped"]) + dropped
+    out = np.zeros(len(events), EVENT_DTYPE)
+    for j, e in enumerate(events):
+        out[j] = e
+    return tracks, row, out
 
 
 def scope_window_hops(windows: int, wave_batch: int):

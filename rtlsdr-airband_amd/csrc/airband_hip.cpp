@@ -349,6 +349,32 @@ void launch_survey_behind_scope(airband_hip_handle* h, const ScopeArgs& sa, hipS
     a.guard_bins = sv.guard_bins;
     a.ratio = sv.ratio;
     launch_band_survey(a, s);
+    /* the band watch of the same batch (airband_hip_set_band_watch), behind the survey it reads: the tables of the launch before are in the other set */
+    BandWatch& w = sv.watch;
+    if (w.max_tracks <= 0) return;
+    const int prev = sc.n_sets > 1 ? set ^ 1 : set;
+    WatchArgs wa;
+    wa.dev = h->d_dev.p;
+    wa.dev_of_row = sc.d_dev_of_row.p;
+    wa.summary = a.summary;
+    wa.peaks = a.peaks;
+    wa.tracks_in = w.d_tracks[prev].p;
+    wa.rows_in = w.d_rows[prev].p;
+    wa.tracks_out = w.d_tracks[set].p;
+    wa.rows_out = w.d_rows[set].p;
+    wa.stage = w.d_stage.p;
+    wa.events = w.d_events[set].p;
+    wa.n_events = w.d_count[set].p;
+    wa.n_rows = sc.n_rows;
+    wa.fft_log = sa.fft_log;
+    wa.max_peaks = sv.max_peaks;
+    wa.max_tracks = w.max_tracks;
+    wa.match_bins = w.match_bins;
+    wa.confirm_hits = w.confirm_hits;
+    wa.release_misses = w.release_misses;
+    wa.max_events = w.max_events;
+    wa.batch = w.batch++;
+    launch_band_watch(wa, s);
 }
 
 /* rows [r0, r0 + n) of a survey array of `per_row` elements a row -> the entries of the selected dongles among [first_dev, first_dev + n_dev): ONE copy, straight into
@@ -1818,6 +1844,105 @@ int airband_hip_device_band_survey(airband_hip_handle* h, airband_hip_band_summa
     if (sc.windows <= 0 || sc.survey.max_peaks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band survey (airband_hip_set_band_survey)");
     if (d_summary) *d_summary = sc.survey.d_summary[sc.cur].p;
     if (d_peaks) *d_peaks = sc.survey.d_peaks[sc.cur].p;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_set_band_watch(airband_hip_handle* h, int32_t max_tracks, int32_t match_bins, int32_t confirm_hits, int32_t release_misses, int64_t max_events) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    BandScope& sc = h->scope;
+    BandSurvey& sv = sc.survey;
+    if (sc.windows <= 0 || sv.max_peaks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band survey (airband_hip_set_band_survey)");
+    if (max_tracks < 1 || max_tracks > 64) return fail(h, AIRBAND_HIP_EINVAL, "max_tracks must lie in 1 .. 64");
+    if (match_bins < 0 || match_bins > h->N / 2) return fail(h, AIRBAND_HIP_EINVAL, "match_bins must lie in 0 .. fft_size / 2");
+    if (confirm_hits < 1 || confirm_hits > 255) return fail(h, AIRBAND_HIP_EINVAL, "confirm_hits must lie in 1 .. 255");
+    if (release_misses < 1 || release_misses > 255) return fail(h, AIRBAND_HIP_EINVAL, "release_misses must lie in 1 .. 255");
+    const int64_t per_row = (int64_t)max_tracks + sv.max_peaks, most = (int64_t)sc.n_rows * per_row;
+    if (max_events < 1 || max_events > most || max_events > INT32_MAX) return fail(h, AIRBAND_HIP_EINVAL, "max_events must lie in 1 .. rows * (max_tracks + max_peaks)");
+    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the band watch is set before the first batch");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* built beside the handle and moved in whole: a failed allocation leaves the handle, its survey and an earlier watch as they were */
+    BandWatch w;
+    w.match_bins = match_bins;
+    w.confirm_hits = confirm_hits;
+    w.release_misses = release_misses;
+    w.max_events = (int)max_events;
+    airband_hip_band_track none;
+    std::memset(&none, 0, sizeof(none));
+    none.bin = -1;
+    const std::vector<airband_hip_band_track> free_slots((size_t)sc.n_rows * (size_t)max_tracks, none);
+    hipError_t e = w.d_stage.alloc((size_t)most);
+    for (int q = 0; q < sc.n_sets; q++) {
+        if (e == hipSuccess) e = upload(w.d_tracks[q], free_slots);
+        if (e == hipSuccess) e = w.d_rows[q].alloc_zeroed((size_t)sc.n_rows);
+        if (e == hipSuccess) e = w.d_events[q].alloc_zeroed((size_t)max_events);
+        if (e == hipSuccess) e = w.d_count[q].alloc_zeroed(1);
+    }
+    if (e == hipSuccess) e = hipDeviceSynchronize(); /* the initial values are in place before a kernel on another stream reads the tables */
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); /* this call's error, reported here: not the next launch's */
+        return fail(h, AIRBAND_HIP_ENOMEM, std::string("band watch buffers: ") + hipGetErrorString(e));
+    }
+    w.max_tracks = max_tracks;
+    sv.watch = std::move(w);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_band_events(airband_hip_handle* h, int64_t* n_events, airband_hip_band_event* events) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const BandScope& sc = h->scope;
+    const BandWatch& w = sc.survey.watch;
+    if (sc.windows <= 0 || sc.survey.max_peaks <= 0 || w.max_tracks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band watch (airband_hip_set_band_watch)");
+    if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    /* how many events there are is on the device: the count first, then exactly those records */
+    int count = 0;
+    HIP_TRY(h, hipMemcpyAsync(&count, w.d_count[sc.cur].p, sizeof(int), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (count < 0 || (int64_t)count > (int64_t)sc.n_rows * (w.max_tracks + sc.survey.max_peaks)) return fail(h, AIRBAND_HIP_ERUNTIME, "event count out of range: " + std::to_string(count));
+    if (n_events) *n_events = count;
+    const size_t n = (size_t)(count < w.max_events ? count : w.max_events);
+    if (events && n) {
+        HIP_TRY(h, hipMemcpyAsync(events, w.d_events[sc.cur].p, n * sizeof(airband_hip_band_event), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+        HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    }
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_band_tracks(airband_hip_handle* h, int32_t first_dev, int32_t n_dev, airband_hip_band_watch_row* rows, airband_hip_band_track* tracks) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const BandScope& sc = h->scope;
+    const BandWatch& w = sc.survey.watch;
+    if (sc.windows <= 0 || sc.survey.max_peaks <= 0 || w.max_tracks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band watch (airband_hip_set_band_watch)");
+    if (first_dev < 0 || n_dev < 0 || (int64_t)first_dev + n_dev > h->plan.n_dev) return fail(h, AIRBAND_HIP_EINVAL, "device range out of bounds");
+    if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    if (rows) {
+        const int rc = collect_survey_rows(h, w.d_rows[sc.cur].p, 1, first_dev, n_dev, rows, airband_hip_band_watch_row{}, s);
+        if (rc != AIRBAND_HIP_OK) return rc;
+    }
+    if (tracks) {
+        airband_hip_band_track none;
+        std::memset(&none, 0, sizeof(none));
+        none.bin = -1;
+        const int rc = collect_survey_rows(h, w.d_tracks[sc.cur].p, (size_t)w.max_tracks, first_dev, n_dev, tracks, none, s);
+        if (rc != AIRBAND_HIP_OK) return rc;
+    }
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_device_band_watch(airband_hip_handle* h, int32_t** d_n_events, airband_hip_band_event** d_events, airband_hip_band_watch_row** d_rows, airband_hip_band_track** d_tracks) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const BandScope& sc = h->scope;
+    const BandWatch& w = sc.survey.watch;
+    if (sc.windows <= 0 || sc.survey.max_peaks <= 0 || w.max_tracks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band watch (airband_hip_set_band_watch)");
+    if (d_n_events) *d_n_events = w.d_count[sc.cur].p;
+    if (d_events) *d_events = w.d_events[sc.cur].p;
+    if (d_rows) *d_rows = w.d_rows[sc.cur].p;
+    if (d_tracks) *d_tracks = w.d_tracks[sc.cur].p;
     return AIRBAND_HIP_OK;
 }
 

@@ -112,8 +112,22 @@ struct OutputGate {
  * scope of front batch k goes to a set of its own and becomes the current one when the batch's back half is enqueued, as the batch's results do. */
 /* what airband_hip_set_band_survey() set up, a part of the scope it reads: replaced as a whole, gone with the scope, one without max_peaks is a scope without
  * a survey (nothing allocated, nothing launched).  Its results follow the scope's rows: the same sets, the same `cur`. */
+/* what airband_hip_set_band_watch() set up, a part of the survey it reads: replaced as a whole, gone with the survey, one without max_tracks is a survey
+ * without a watch (nothing allocated, nothing launched).  Its results follow the survey's: the same sets, the same `cur`; the tables a batch starts from are
+ * the other set's where there are two. */
+struct BandWatch {
+    int max_tracks = 0;        /* 0 = no watch */
+    int match_bins = 0, confirm_hits = 0, release_misses = 0, max_events = 0;
+    uint32_t batch = 0;        /* the watch batch number of the next launch */
+    DevBuf<airband_hip_band_track> d_tracks[2];
+    DevBuf<airband_hip_band_watch_row> d_rows[2];
+    DevBuf<airband_hip_band_event> d_events[2], d_stage; /* d_stage: the rows' events between the two kernels of one launch */
+    DevBuf<int> d_count[2];
+};
+
 struct BandSurvey {
     int max_peaks = 0;         /* 0 = no survey */
+    BandWatch watch;
     uint32_t trace = 0;        /* the one AIRBAND_SCOPE_* bit whose rows are surveyed */
     int rank = 0, guard_bins = 0;
     float ratio = 0.0f;

@@ -347,5 +347,28 @@ struct SurveyArgs {
 size_t survey_lds_bytes(int fft_log); /* dynamic LDS per workgroup: the row and 1.5 KiB */
 void launch_band_survey(const SurveyArgs& a, hipStream_t stream);
 
+/* band watch (band_watch.hip): the carrier tracks of every scope row advanced by the row's survey, one wavefront per row, and the rows' events packed into one
+ * fleet-wide list in row order; launched directly behind launch_band_survey() on the same stream */
+struct WatchArgs {
+    const DevConst* dev;
+    const int* dev_of_row;                      /* [n_rows] the selected dongles, ascending */
+    const airband_hip_band_summary* summary;    /* [n_rows] the survey of this batch: n_peaks */
+    const airband_hip_band_peak* peaks;         /* [n_rows][max_peaks] */
+    const airband_hip_band_track* tracks_in;    /* [n_rows][max_tracks] the tables the batch starts from: the set of the batch before (== tracks_out on a handle with one set) */
+    const airband_hip_band_watch_row* rows_in;  /* [n_rows] */
+    airband_hip_band_track* tracks_out;
+    airband_hip_band_watch_row* rows_out;
+    airband_hip_band_event* stage;              /* [n_rows][max_peaks + max_tracks] a row's events of this batch, rows_out[row].n_events of them */
+    airband_hip_band_event* events;             /* [max_events] */
+    int* n_events;                              /* [1] */
+    int n_rows, fft_log;
+    int max_peaks;                              /* 1 .. 64: the survey's */
+    int max_tracks;                             /* 1 .. 64 */
+    int match_bins, confirm_hits, release_misses;
+    int max_events;
+    uint32_t batch;                             /* the watch batch number k */
+};
+void launch_band_watch(const WatchArgs& a, hipStream_t stream);
+
 }  // namespace airband
 #endif
