@@ -74,7 +74,8 @@ extern "C" {
                                                airband_hip_process_device) the flag adds nothing on the GPU:   \
                                                it moves the enqueueing of stage 2 into the next call.          \
                                                Ignored when a channel has AFC (stage 1 of the next batch needs \
-                                               stage 2's verdict, src/rtl_airband.cpp:222-251).               */
+                                               stage 2's verdict, src/rtl_airband.cpp:222-251) or is a follower \
+                                               (airband_hip_prepare_follow).                                  */
 #define AIRBAND_HIP_FLAG_REGROUP 0x20u      /* stage 2 re-sorts its channels at every batch boundary so that   \
                                                channels whose squelch is closed share wavefronts (csrc/demod.hip,\
                                                "regrouping"): same values, bit for bit; what changes is which   \
@@ -190,7 +191,7 @@ typedef struct airband_hip_channel_stats {
     uint64_t ctcss_count;
     uint64_t no_ctcss_count;
     uint64_t active_counter; /* freq_t.active_counter                                                 */
-    int32_t bin;             /* dev->bins[i] (moves only with AFC)                                    */
+    int32_t bin;             /* dev->bins[i]: the bin the NEXT batch is channelized at (moves with AFC, and on a follower with the band follow) */
     int32_t squelch_state;   /* Squelch::State after the batch                                        */
     int32_t signal_outside_filter; /* Squelch::signal_outside_filter() after the batch (src/squelch.cpp:152-154): the TUI prints '~' for it (src/rtl_airband.cpp:633) */
     int32_t reserved;
@@ -594,6 +595,93 @@ int airband_hip_collect_band_tracks(airband_hip_handle* h, int32_t first_dev, in
  * BY SCOPE ROW (d_row_of_dev of airband_hip_device_band_scope()).  Any out-pointer may be NULL. */
 int airband_hip_device_band_watch(airband_hip_handle* h, int32_t** d_n_events, airband_hip_band_event** d_events, airband_hip_band_watch_row** d_rows, airband_hip_band_track** d_tracks);
 
+/* ---- band follow ------------------------------------------------------------------------------------------------------------------
+ * The watch says "a carrier has been up on dongle 31 207, bin 143, for four batches"; a channel's bin is fixed at prepare time, so nobody can listen to it.
+ * A handle prepared with FOLLOWERS (airband_hip_prepare_follow) and carrying a watch may also carry a BAND FOLLOW: per scope row the GPU tunes the row's
+ * followers -- spare configured channels -- onto the row's confirmed tracks, moves them with the tracks' drift and sends them home when the track ends; one
+ * fleet-wide packed list holds the batch's CHANGES.  Defined on integers and on the watch's own tables: capi.band_follow_reference()
+ * (rtlsdr-airband_amd/capi.py) is this text in plain Python, and the GPU's bytes equal its bytes.
+ * Followers.  Configured channels named at prepare time by their device-major channel index; their `frequency` is their HOME.  A follower is an AM channel
+ * (modulation == AIRBAND_MOD_AM) with afc == 0, has_iq_outputs == 0 and bandwidth_hz == 0 -- only |bin| feeds such a channel, so no dm_dphi depends on a frequency
+ * nobody knows in advance -- that is not on a scan device; at most 64 per dongle.  NFM followers are out of scope.
+ * State per follower: {track = the slot it follows or -1 (idle, at home), bin = the bin it is tuned to, since_batch}.
+ * One batch of one scope row, after the watch has advanced the row, with k = the watch batch number of that batch.  The row's followers are taken in ascending
+ * channel order; tracks[] is the row's table as the watch left it.
+ *   A. FOR EVERY FOLLOWER WITH A TRACK s:  tracks[s].state != AIRBAND_WATCH_CONFIRMED: the follower goes home -- bin = home bin, track = -1, since_batch = k, a
+ *      HOME change.  Else tracks[s].bin != bin: it moves with the track -- bin = tracks[s].bin, a MOVE change.
+ *   B. FOR EVERY SLOT s, ASCENDING, THAT IS CONFIRMED AND FOLLOWED BY NO FOLLOWER AFTER STEP A:  the lowest follower that was idle AT THE START OF THE BATCH and
+ *      has not been taken in this batch takes it -- track = s, bin = tracks[s].bin, since_batch = k, a TUNE change.  There is none: the slot stays unserved.
+ * The row's record after the batch: n_following (followers with a track), n_unserved (confirmed slots nobody follows: a count of this batch, not cumulative),
+ * n_changes.  The row's changes are those of step A in follower order, then those of step B in slot order: at most followers + max_tracks.
+ * The fleet's list.  All rows' changes in ascending dongle order; n_changes is the total, the first min(n_changes, max_changes) are kept -- the contract of
+ * airband_hip_collect_band_events().
+ * Effect of a change.  The follower's bin is set on the GPU behind stage 2 of the batch, the way AFC moves a bin: it applies to stage 1 of the NEXT batch
+ * enqueued.  Squelch, AGC, filter and ring state carry on across the move exactly as across an AFC step; nothing is reset.  airband_hip_channel_stats.bin of the
+ * batch therefore shows the bin the next batch will be channelized at.  On the matrix-core channelizers a group of eight channels with a follower owns a private
+ * coefficient table, as a group with an AFC channel does; a channel whose bin has not moved keeps its home table byte for byte.  Columns built on the device may
+ * differ from host-built ones by one coefficient unit.
+ * The survey keeps judging "covered" by PREPARE-TIME bins: a followed carrier stays a peak and its track stays alive -- that is how the follower learns when to go
+ * home -- and a follower's home bin covers its guard like any channel's.
+ * Schedule.  A handle with followers schedules like a handle with AFC channels: stage 1 of batch k + 1 needs batch k's decision, so there is no run-ahead and
+ * AIRBAND_HIP_FLAG_PIPELINE is ignored (airband_hip_schedule_info() says so), whether or not airband_hip_set_band_follow() is called.
+ * Lifetime.  The follow belongs to the batch airband_hip_collect() would return and is complete where its results are.  A dongle that is switched off is frozen
+ * exactly as the watch freezes it: followers, bins and record stay, no changes.  airband_hip_process_bins() leaves everything as it is.  No floating-point
+ * operation, no atomics on global memory: equal input, equal bytes.  A handle without followers does exactly the work it did: same tables, same schedule, same
+ * bits. */
+#define AIRBAND_FOLLOW_TUNE 1
+#define AIRBAND_FOLLOW_MOVE 2
+#define AIRBAND_FOLLOW_HOME 3
+
+typedef struct airband_hip_band_follower {
+    int32_t channel;      /* device-major channel index */
+    int32_t bin;          /* the bin the channel is tuned to: its home bin while track == -1 */
+    uint32_t since_batch; /* watch batch number of the last TUNE or HOME (0 before any) */
+    int16_t track;        /* the slot it follows, -1: idle */
+    uint16_t reserved;    /* 0 */
+} airband_hip_band_follower; /* 16 bytes */
+
+typedef struct airband_hip_band_follow_change {
+    int32_t dev;       /* dongle index */
+    int32_t channel;   /* device-major channel index of the follower */
+    int32_t bin;       /* the bin it is tuned to from the next batch on (HOME: its home bin) */
+    uint8_t kind;      /* AIRBAND_FOLLOW_TUNE / _MOVE / _HOME */
+    uint8_t track;     /* the slot taken, followed or (HOME) left */
+    uint16_t reserved; /* 0 */
+} airband_hip_band_follow_change; /* 16 bytes */
+
+typedef struct airband_hip_band_follow_row {
+    int32_t n_following; /* followers with a track, after the batch */
+    int32_t n_unserved;  /* confirmed slots no follower follows, after the batch */
+    int32_t n_changes;   /* the row's changes of this batch */
+    int32_t reserved;    /* 0 */
+} airband_hip_band_follow_row; /* 16 bytes */
+
+/* airband_hip_prepare_scan() with n_follow followers: follow_channels[0 .. n_follow) are device-major channel indices, strictly ascending
+ * (follow_channels may be NULL when n_follow == 0; airband_hip_prepare_scan(cfg, scan, n, out) is exactly airband_hip_prepare_follow(cfg, scan, n, NULL, 0, out)).
+ * Validated before any device is touched: AIRBAND_HIP_EINVAL, with a text that names the offending channel, for an index out of range or not above the one
+ * before it, a follower that is not AM, has afc, has_iq_outputs or bandwidth_hz, or sits on a scan device, and more than 64 followers on one dongle. */
+int airband_hip_prepare_follow(const airband_hip_config* cfg, const airband_hip_scan_cfg* scan, int32_t n_scan, const int32_t* follow_channels, int32_t n_follow, airband_hip_handle** out);
+
+/* After airband_hip_set_band_watch() and before the first batch (calling it again before then replaces the follow; airband_hip_set_band_scope(), _survey() and
+ * _watch() called again drop it).  max_changes: capacity of the fleet's list.  Validated before the device is touched: AIRBAND_HIP_EINVAL for a NULL handle, a
+ * handle without a watch or without followers, max_changes outside 1 .. followers + rows * max_tracks, a batch already enqueued; AIRBAND_HIP_ENOMEM when the
+ * buffers cannot be had -- the handle then runs on as it was, watch included. */
+int airband_hip_set_band_follow(airband_hip_handle* h, int64_t max_changes);
+
+/* The changes of the batch airband_hip_collect() would return: *n_changes is the fleet's total, changes a HOST array sized for max_changes records of which
+ * min(n_changes, max_changes) are written -- nothing past them.  Either pointer may be NULL.  Two small copies: the count, then exactly those records.  Does not
+ * mark the batch as collected.  AIRBAND_HIP_EAGAIN before any batch, AIRBAND_HIP_EINVAL on a handle without a follow. */
+int airband_hip_collect_band_follow_changes(airband_hip_handle* h, int64_t* n_changes, airband_hip_band_follow_change* changes);
+
+/* The followers of the same batch, a HOST array [n_follow] in prepare order, and the rows' records, a HOST array [device_count] (zeros for a dongle the scope's
+ * mask did not select; its followers stay idle).  Either may be NULL.  One device-to-host copy per array.  Does not mark the batch as collected.
+ * AIRBAND_HIP_EAGAIN before any batch, AIRBAND_HIP_EINVAL on a handle without a follow. */
+int airband_hip_collect_band_followers(airband_hip_handle* h, airband_hip_band_follower* followers, airband_hip_band_follow_row* rows);
+
+/* Device-side views of the same (valid until the next process call): d_n_changes [1], d_changes [max_changes], d_followers [n_follow] in prepare order, d_rows
+ * [rows] indexed BY SCOPE ROW (d_row_of_dev of airband_hip_device_band_scope()).  Any out-pointer may be NULL. */
+int airband_hip_device_band_follow(airband_hip_handle* h, int32_t** d_n_changes, airband_hip_band_follow_change** d_changes, airband_hip_band_follower** d_followers, airband_hip_band_follow_row** d_rows);
+
 /* Makes `stream` (a hipStream_t of a GPU-side consumer, e.g. the stream an RCCL all-reduce of the mixer sums is issued on)
  * wait for the results of the batch the last process call completed -- no host synchronisation.  The consumer hands its
  * stream to the next airband_hip_process_device() call, which then orders the overwrite of the result buffers behind it. */
@@ -665,7 +753,7 @@ const char* airband_hip_build_info(void);
 int airband_hip_regrouped(const airband_hip_handle* h);
 
 /* How the handle schedules a batch.  *run_ahead: 1 if NULL-stream airband_hip_process_device() batches put stage 1 on a stream of its own (the default where
- * the handle qualifies; 0 with AFC channels, scan lists, AIRBAND_HIP_FLAG_PIPELINE, or AIRBAND_HIP_RUN_AHEAD=0 in the environment at prepare time).  *ring_batches:
+ * the handle qualifies; 0 with AFC channels, followers (airband_hip_prepare_follow), scan lists, AIRBAND_HIP_FLAG_PIPELINE, or AIRBAND_HIP_RUN_AHEAD=0 in the environment at prepare time).  *ring_batches:
  * depth of the stage-1 rings in batches (2 on run-ahead and pipelined handles, else 1).  *channelizer_waves_per_cu: 5 where the matrix-core channelizer is held to
  * five wavefronts per CU to leave stage 2 register room beside it, 0 where it is not held.  *batches_run_ahead: how many batches so far took the run-ahead path
  * (a caller's stream, airband_hip_process and airband_hip_process_bins do not).  Any out-pointer may be NULL. */

@@ -37,6 +37,7 @@ EXPORTS = [
     "airband_hip_set_band_scope", "airband_hip_collect_band_scope", "airband_hip_device_band_scope",
     "airband_hip_set_band_survey", "airband_hip_collect_band_survey", "airband_hip_device_band_survey",
     "airband_hip_set_band_watch", "airband_hip_collect_band_events", "airband_hip_collect_band_tracks", "airband_hip_device_band_watch",
+    "airband_hip_prepare_follow", "airband_hip_set_band_follow", "airband_hip_collect_band_follow_changes", "airband_hip_collect_band_followers", "airband_hip_device_band_follow",
     "airband_hip_channelizer_reason", "airband_hip_wide_hop_lds_bytes", "airband_hip_schedule_info", "airband_hip_wide_hop_plan",
 ]
 # Exported entries whose names carry digits.  Kept apart from EXPORTS, which tests/test_abi.py compares with the header's names through a pattern of letters and
@@ -108,7 +109,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
-    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()):
+    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()):
         if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
             getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
@@ -235,18 +236,40 @@ def prepare_scan_rc(devices: Sequence[dict], scan: Optional[dict], *, wave_rate:
     return rc
 
 
+def prepare_follow_rc(devices: Sequence[dict], scan: Optional[dict], follow, *, wave_rate: int, fft_log: int = 9, fm_demod: int = 0, flags: int = 0):
+    """(return code, error text) of airband_hip_prepare_follow() for this configuration (the handle, if one was made, is released at once).  Lets tests check the
+    validation of followers, which happens before any device is touched.  follow: device-major channel indices, or None for (NULL, 0)."""
+    L = load_library()
+    cfg, keep = make_config(devices, wave_rate=wave_rate, fft_log=fft_log, fm_demod=fm_demod, flags=flags)
+    sptr, n, skeep = make_scan(scan)
+    farr = (C.c_int32 * len(follow))(*[int(c) for c in follow]) if follow is not None else None
+    h = C.c_void_p()
+    rc = L.airband_hip_prepare_follow(C.byref(cfg), sptr, n, farr, len(follow) if follow is not None else 0, C.byref(h))
+    if h:
+        L.airband_hip_release(h)
+    return rc, (L.airband_hip_last_error(None) or b"").decode() if rc != 0 else ""
+
+
 class AirbandHip:
     """One handle = the dongles demodulated on one GPU (the reference's demodulate() thread for a device shard,
     src/rtl_airband.cpp:1052-1086)."""
 
     def __init__(self, devices: Sequence[dict], *, wave_rate: int, fft_log: int = 9, fm_demod: int = 0, flags: int = 0, hip_device: int = 0,
-                 scan: Optional[dict] = None):
-        """scan = {device index: [channel kwargs, ...]}: scan-mode devices (airband_hip_prepare_scan); each list's first entry must equal the device's channel."""
+                 scan: Optional[dict] = None, follow: Optional[Sequence[int]] = None):
+        """scan = {device index: [channel kwargs, ...]}: scan-mode devices (airband_hip_prepare_scan); each list's first entry must equal the device's channel.
+        follow = [device-major channel index, ...] ascending: the followers (airband_hip_prepare_follow) -- spare AM channels the band follow may tune onto the
+        carriers the band watch confirms (set_band_follow); such a handle schedules like one with AFC channels: no run-ahead, FLAG_PIPELINE ignored."""
         self.L = load_library()
         self.devices = list(devices)
+        self.follow_channels = [int(c) for c in follow] if follow else []
         cfg, self._keep = make_config(devices, wave_rate=wave_rate, fft_log=fft_log, fm_demod=fm_demod, flags=flags, hip_device=hip_device)
         h = C.c_void_p()
-        if scan:
+        if self.follow_channels:
+            sptr, n, skeep = make_scan(scan)
+            self._keep.append(skeep)
+            farr = (C.c_int32 * len(self.follow_channels))(*self.follow_channels)
+            rc = self.L.airband_hip_prepare_follow(C.byref(cfg), sptr, n, farr, len(self.follow_channels), C.byref(h))
+        elif scan:
             sptr, n, skeep = make_scan(scan)
             self._keep.append(skeep)
             rc = self.L.airband_hip_prepare_scan(C.byref(cfg), sptr, n, C.byref(h))
@@ -450,6 +473,40 @@ class AirbandHip:
         ptrs = [C.c_void_p() for _ in range(4)]
         self._check(self.L.airband_hip_device_band_watch(self.h, *[C.byref(p) for p in ptrs]))
         return {k: (p.value or 0) for k, p in zip(["n_events", "events", "rows", "tracks"], ptrs)}
+
+    def set_band_follow(self, max_changes: Optional[int] = None):
+        """Band follow (airband_hip_set_band_follow): per batch and scope row the GPU tunes the row's followers (the constructor's follow=) onto the watch's
+        confirmed tracks -- TUNE when an idle follower takes a track, MOVE when the track's bin drifts, HOME when the track ends -- and keeps one list of the
+        fleet's changes per batch, max_changes records (None: 4 x rows, clipped to the range).  A change applies to stage 1 of the next batch; squelch, AGC and
+        filter state carry on as across an AFC step.  After set_band_watch(), before the first batch."""
+        if max_changes is None:
+            rows = getattr(self, "scope_rows", 0)
+            max_changes = max(1, min(4 * rows, len(self.follow_channels) + rows * getattr(self, "watch_tracks", 0)))
+        self._check(self.L.airband_hip_set_band_follow(self.h, int(max_changes)))
+        self.follow_changes = int(max_changes)
+
+    def collect_band_follow_changes(self) -> dict:
+        """The fleet's changes of the batch collect() would return: dict(n_changes = the total, changes = the first min(n_changes, max_changes) of
+        capi.FOLLOW_CHANGE_DTYPE, in ascending dongle order).  Two small copies.  Repeatable."""
+        n = C.c_int64(0)
+        changes = np.zeros((max(getattr(self, "follow_changes", 0), 1),), capi.FOLLOW_CHANGE_DTYPE)
+        self._check(self.L.airband_hip_collect_band_follow_changes(self.h, C.byref(n), changes.ctypes.data))
+        return dict(n_changes=int(n.value), changes=changes[:min(int(n.value), len(changes))])
+
+    def collect_band_followers(self) -> dict:
+        """The followers of the same batch: dict(followers=[n_follow] of capi.FOLLOWER_DTYPE in the constructor's order, rows=[device_count] of
+        capi.FOLLOW_ROW_DTYPE, zeros for dongles the scope's mask did not select).  Repeatable."""
+        followers = np.empty((max(len(self.follow_channels), 1),), capi.FOLLOWER_DTYPE)
+        rows = np.empty((self.geometry.device_count,), capi.FOLLOW_ROW_DTYPE)
+        self._check(self.L.airband_hip_collect_band_followers(self.h, followers.ctypes.data, rows.ctypes.data))
+        return dict(followers=followers[:len(self.follow_channels)], rows=rows)
+
+    def device_band_follow(self) -> dict:
+        """Device pointers of the current follow (valid until the next process call): n_changes [1] int32, changes [max_changes] of 16 bytes, followers
+        [n_follow] of 16 bytes in the constructor's order, rows [rows] of 16 bytes indexed by scope row."""
+        ptrs = [C.c_void_p() for _ in range(4)]
+        self._check(self.L.airband_hip_device_band_follow(self.h, *[C.byref(p) for p in ptrs]))
+        return {k: (p.value or 0) for k, p in zip(["n_changes", "changes", "followers", "rows"], ptrs)}
 
     def set_freq_index(self, dev: int, freq_idx: int):
         """Entry freq_idx of dongle dev's scan list is in force for every batch enqueued from now on (latched per batch)."""

@@ -43,6 +43,7 @@ HIP_SOURCES = {
     "band_scope.hip": ["-O3"],  # band scope: a wavefront FFT of a few windows per batch and dongle, mean and peak power per bin
     "band_survey.hip": ["-O3"],  # band survey: rank select, threshold and peak list of every scope row, integer passes over LDS
     "band_watch.hip": ["-O3"],  # band watch: carrier tracks per scope row advanced by the survey's list, the fleet's events packed in row order; integers only
+    "band_follow.hip": ["-O3"],  # band follow: followers tuned onto the watch's confirmed tracks per scope row, their bins applied, the fleet's changes packed; integers only
     "airband_hip.cpp": ["-O2", "-x", "hip"],
 }
 HOST_SOURCES = {"params.cpp": ["-O2", "-ffp-contract=off", "-fno-fast-math"]}

@@ -250,6 +250,87 @@ def band_watch_reference(tracks, row, peaks, n_peaks, batch, max_tracks, match_b
     return tracks, row, out
 
 
+# the band follow's (same header)
+class BandFollower(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("bin", C.c_int32), ("since_batch", C.c_uint32), ("track", C.c_int16), ("reserved", C.c_uint16)]
+
+
+class BandFollowChange(C.Structure):
+    _fields_ = [("dev", C.c_int32), ("channel", C.c_int32), ("bin", C.c_int32), ("kind", C.c_uint8), ("track", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+class BandFollowRow(C.Structure):
+    _fields_ = [("n_following", C.c_int32), ("n_unserved", C.c_int32), ("n_changes", C.c_int32), ("reserved", C.c_int32)]
+
+
+BAND_FOLLOW_PROTOTYPES = {
+    "airband_hip_prepare_follow": [C.POINTER(Config), C.POINTER(ScanCfg), _i32, C.POINTER(_i32), _i32, C.POINTER(_vp)],
+    "airband_hip_set_band_follow": [_vp, _i64],
+    "airband_hip_collect_band_follow_changes": [_vp, C.POINTER(_i64), _vp],
+    "airband_hip_collect_band_followers": [_vp, _vp, _vp],
+    "airband_hip_device_band_follow": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
+}
+FOLLOW_TUNE, FOLLOW_MOVE, FOLLOW_HOME = 1, 2, 3
+# numpy views of airband_hip_band_follower / airband_hip_band_follow_change / airband_hip_band_follow_row
+FOLLOWER_DTYPE = [("channel", "<i4"), ("bin", "<i4"), ("since_batch", "<u4"), ("track", "<i2"), ("reserved", "<u2")]
+FOLLOW_CHANGE_DTYPE = [("dev", "<i4"), ("channel", "<i4"), ("bin", "<i4"), ("kind", "u1"), ("track", "u1"), ("reserved", "<u2")]
+FOLLOW_ROW_DTYPE = [("n_following", "<i4"), ("n_unserved", "<i4"), ("n_changes", "<i4"), ("reserved", "<i4")]
+
+
+def band_follow_blank(channels, home_bins):
+    """The state the followers start from: [len(channels)] of FOLLOWER_DTYPE, every one idle on its home bin."""
+    import numpy as np
+
+    f = np.zeros(len(channels), FOLLOWER_DTYPE)
+    f["channel"], f["bin"], f["track"] = channels, home_bins, -1
+    return f
+
+
+def band_follow_reference(followers, tracks, home_bins, batch, dev=0):
+    """The band follow's definition (include/airband_hip.h) for one batch of one scope row, in plain Python: the row's `followers` (FOLLOWER_DTYPE, ascending channel
+    order) as the batch before left them, the row's table `tracks` (TRACK_DTYPE) as the watch left it after THIS batch, the followers' `home_bins`, the watch batch
+    number `batch`.  Returns (followers, row, changes): new arrays; row of FOLLOW_ROW_DTYPE, changes of FOLLOW_CHANGE_DTYPE with `dev` in their first field.  A
+    switched-off dongle is frozen: do not call this for it (its record keeps its counts with n_changes = 0)."""
+    import numpy as np
+
+    fol = np.array(followers, FOLLOWER_DTYPE).reshape(-1).copy()
+    tracks = np.ascontiguousarray(tracks, TRACK_DTYPE).reshape(-1)
+    T, k = len(tracks), int(batch) & 0xFFFFFFFF
+    confirmed = [int(t["state"]) == WATCH_CONFIRMED for t in tracks]
+    idle0 = [not 0 <= int(f["track"]) < T for f in fol]  # at the start of the batch
+    changes = []
+    # A. the followers that have a track, in follower order
+    for i, f in enumerate(fol):
+        s = int(f["track"])
+        if idle0[i]:
+            continue
+        if not confirmed[s]:
+            f["bin"], f["track"], f["since_batch"] = int(home_bins[i]), -1, k
+            changes.append((dev, int(f["channel"]), int(f["bin"]), FOLLOW_HOME, s, 0))
+        elif int(tracks[s]["bin"]) != int(f["bin"]):
+            f["bin"] = int(tracks[s]["bin"])
+            changes.append((dev, int(f["channel"]), int(f["bin"]), FOLLOW_MOVE, s, 0))
+    # B. the confirmed slots nobody follows, in slot order
+    taken, unserved = [False] * len(fol), 0
+    for s in range(T):
+        if not confirmed[s] or any(int(f["track"]) == s for f in fol):
+            continue
+        i = next((i for i in range(len(fol)) if idle0[i] and not taken[i]), None)
+        if i is None:
+            unserved += 1
+            continue
+        taken[i] = True
+        f = fol[i]
+        f["track"], f["bin"], f["since_batch"] = s, int(tracks[s]["bin"]), k
+        changes.append((dev, int(f["channel"]), int(f["bin"]), FOLLOW_TUNE, s, 0))
+    row = np.zeros((), FOLLOW_ROW_DTYPE)
+    row["n_following"], row["n_unserved"], row["n_changes"] = int((fol["track"] >= 0).sum()), unserved, len(changes)
+    out = np.zeros(len(changes), FOLLOW_CHANGE_DTYPE)
+    for j, c in enumerate(changes):
+        out[j] = c
+    return fol, row, out
+
+
 def scope_window_hops(windows: int, wave_batch: int):
     """The batch's new hops whose FFT windows a band scope of `windows` windows per batch looks at: (j * WAVE_BATCH) / K, j = 0 .. K-1."""
     return [(j * wave_batch) // windows for j in range(windows)]

@@ -563,6 +563,41 @@ GateArgs gate_args(const airband_hip_handle* h) {
     return a;
 }
 
+/* The band follow of the batch whose back half goes on stream s (airband_hip_set_band_follow), behind its demod kernels.  It reads the track tables the batch's
+ * watch left, and the watch ran on the scope's stream: s is behind that already (scope_join() made the stage-1 stream wait for the scope, and a handle with
+ * followers runs both halves of a batch on one stream), said again here because this is the point that depends on it.  The watch batch number of this batch is
+ * the last one launched: such a handle never has a second stage 1 in flight. */
+void launch_follow_behind_demod(airband_hip_handle* h, int* moved_epoch, int epoch, hipStream_t s) {
+    BandScope& sc = h->scope;
+    BandWatch& w = sc.survey.watch;
+    BandFollow& fo = w.follow;
+    if (scope_on_side(h, s)) (void)hipStreamWaitEvent(s, sc.ev_done, 0);
+    FollowArgs a;
+    a.dev = h->d_dev.p;
+    a.dev_of_row = sc.d_dev_of_row.p;
+    a.tracks = w.d_tracks[sc.cur].p;
+    a.fol_range = fo.d_range.p;
+    a.fol_slot = fo.d_slot.p;
+    a.fol_home = fo.d_home.p;
+    a.followers = fo.d_followers.p;
+    a.rows = fo.d_rows.p;
+    a.stage = fo.d_stage.p;
+    a.changes = fo.d_changes.p;
+    a.n_changes = fo.d_count.p;
+    a.cs = h->d_cs.p;
+    a.moved_epoch = moved_epoch;
+    a.epoch = epoch;
+    a.n_rows = sc.n_rows;
+    a.n_follow = (int)h->plan.follow_ext.size();
+    a.n_slots = h->n_slots;
+    a.fft_log = h->plan.fft_log;
+    a.max_tracks = w.max_tracks;
+    a.cap = fo.cap;
+    a.max_changes = fo.max_changes;
+    a.batch = w.batch - 1u;
+    launch_band_follow(a, s);
+}
+
 /* stage 2 + emit (+ mixers, + the output gate) of the batch whose stage-1 rows are already in the rings */
 int run_back_half(airband_hip_handle* h, hipStream_t s) {
     const Event* ev = event_set(h, h->batches_done, 1);
@@ -611,13 +646,21 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
     hipStream_t side[3] = {h->side[0], h->side[1], h->side[2]};
     hipEvent_t fork_ev[4] = {h->fork_ev[0], h->fork_ev[1], h->fork_ev[2], h->fork_ev[3]};
     launch_demod(da, h->kind_first_block, h->kind_n_blocks, s, (h->flags & AIRBAND_HIP_FLAG_SERIAL_DEMOD) ? nullptr : side, fork_ev);
-    if (h->any_afc && h->afc_spectrum_valid) { /* afc.finalize(), src/rtl_airband.cpp:626-630: may turn '*' into '<' / '>' */
+    /* What moves bins between this batch and the next, behind the demod kernels (they read and write ChanState) on their stream: AFC, and the band follow of a batch
+     * that had a scope (a batch without input leaves the follow as it is).  Both stamp ONE epoch; the re-tune kernel runs once behind them. */
+    const bool afc = h->any_afc && h->afc_spectrum_valid;
+    const bool follow = h->scope.windows > 0 && h->scope.survey.watch.follow.max_changes > 0 && h->scope.set_of_front[h->batches_done & 1] >= 0;
+    if (afc || follow) {
         const bool tables = h->use_dft || h->use_f32; /* the matrix-core channelizers: a channel's bin is baked into its coefficient columns */
-        if (tables) (void)hipStreamWaitEvent(s, h->ev_spec[1], 0); /* the last hop's spectrum, computed beside stage 1 */
         const int epoch = (int)(h->batches_done % 0x7fffffff) + 1; /* never 0: that is the start-up build's */
-        launch_afc(h->d_cc.p, h->d_cs.p, h->d_spectrum.p, h->N, h->n_slots, tables ? h->d_bset_bin.p + (size_t)h->plan.n_bsets * 8 : nullptr, epoch, s);
+        int* const moved_epoch = tables ? h->d_bset_bin.p + (size_t)h->plan.n_bsets * 8 : nullptr;
+        if (afc) { /* afc.finalize(), src/rtl_airband.cpp:626-630: may turn '*' into '<' / '>' */
+            if (tables) (void)hipStreamWaitEvent(s, h->ev_spec[1], 0); /* the last hop's spectrum, computed beside stage 1 */
+            launch_afc(h->d_cc.p, h->d_cs.p, h->d_spectrum.p, h->N, h->n_slots, moved_epoch, epoch, s);
+        }
+        if (follow) launch_follow_behind_demod(h, moved_epoch, epoch, s);
         if (tables) launch_retune_tables(h, s, epoch); /* the next batch's stage 1 reads the moved channels' new columns */
-        launch_axc(h->d_cc.p, h->d_cs.p, h->d_slot_to_ext.p, h->d_out_axc.p, h->n_slots, s);
+        if (afc) launch_axc(h->d_cc.p, h->d_cs.p, h->d_slot_to_ext.p, h->d_out_axc.p, h->n_slots, s);
     }
     (void)hipEventRecord(ev[3], s);
     if (h->d_out_iq.p) { /* handles with has_iq_outputs channels: raw I/Q rows -> channel-major */
@@ -1113,6 +1156,10 @@ int airband_hip_dft_selftest(const airband_hip_config* cfg, int32_t windows, dou
 int airband_hip_prepare(const airband_hip_config* cfg, airband_hip_handle** out) { return airband_hip_prepare_scan(cfg, nullptr, 0, out); }
 
 int airband_hip_prepare_scan(const airband_hip_config* cfg, const airband_hip_scan_cfg* scan, int32_t n_scan, airband_hip_handle** out) {
+    return airband_hip_prepare_follow(cfg, scan, n_scan, nullptr, 0, out);
+}
+
+int airband_hip_prepare_follow(const airband_hip_config* cfg, const airband_hip_scan_cfg* scan, int32_t n_scan, const int32_t* follow_channels, int32_t n_follow, airband_hip_handle** out) {
     if (!out) return fail(nullptr, AIRBAND_HIP_EINVAL, "out is NULL");
     *out = nullptr;
     HandlePtr owner(new (std::nothrow) airband_hip_handle(), destroy);
@@ -1120,11 +1167,13 @@ int airband_hip_prepare_scan(const airband_hip_config* cfg, const airband_hip_sc
     if (!h) return fail(nullptr, AIRBAND_HIP_ENOMEM, "host allocation failed");
     int rc = build_plan(cfg, h->plan);
     if (rc == AIRBAND_HIP_OK) rc = build_scan(cfg, scan, n_scan, h->plan); /* before any device is touched */
+    if (rc == AIRBAND_HIP_OK) rc = build_follow(cfg, follow_channels, n_follow, h->plan);
     if (rc != AIRBAND_HIP_OK) return fail(PREPARING, rc, h->plan.error);
     const Plan& p = h->plan;
     if (!p.uniform_hop)
         return fail(PREPARING, AIRBAND_HIP_EINVAL, "all dongles of one handle must share sample format and sample_rate/WAVE_RATE hop; use one handle per class");
     for (const ChanConst& c : p.cc) h->any_afc |= c.afc != 0;
+    const bool followers = !p.follow_ext.empty(); /* the band follow decides a follower's bin behind stage 2 of batch k, stage 1 of batch k+1 reads it: sequential, as with AFC */
     h->flags = cfg->flags;
     h->hip_device = cfg->hip_device;
     int ndev = 0;
@@ -1132,12 +1181,12 @@ int airband_hip_prepare_scan(const airband_hip_config* cfg, const airband_hip_sc
         return fail(PREPARING, AIRBAND_HIP_ENODEV, "no usable HIP device (libairband_hip has no CPU fallback)");
     /* AFC needs stage 2's verdict on batch k before stage 1 of batch k+1 picks its bins (src/rtl_airband.cpp:222-251):
      * such handles stay sequential */
-    h->pipeline = (cfg->flags & AIRBAND_HIP_FLAG_PIPELINE) && !h->any_afc;
+    h->pipeline = (cfg->flags & AIRBAND_HIP_FLAG_PIPELINE) && !h->any_afc && !followers;
     /* The same GPU schedule without the lag, for batches on the handle's own stream (airband_hip_process_device).  Not with AFC, for the reason above; not with scan
      * lists, whose exchange in front of the demod kernels is ordered against stage 1 by the one stream.  AIRBAND_HIP_RUN_AHEAD=0 in the environment: off (A/B
      * measurements; the handle then has the one-batch rings and the unheld channelizer of the sequential schedule). */
     const char* run_ahead_env = getenv("AIRBAND_HIP_RUN_AHEAD");
-    h->run_ahead = !(cfg->flags & AIRBAND_HIP_FLAG_PIPELINE) && !h->any_afc && p.scan.empty() && !(run_ahead_env && *run_ahead_env == '0');
+    h->run_ahead = !(cfg->flags & AIRBAND_HIP_FLAG_PIPELINE) && !h->any_afc && !followers && p.scan.empty() && !(run_ahead_env && *run_ahead_env == '0');
     rc = prep_streams(h);
     if (rc != AIRBAND_HIP_OK) return rc;
     std::vector<ChanState> cs_slots;
@@ -1943,6 +1992,115 @@ int airband_hip_device_band_watch(airband_hip_handle* h, int32_t** d_n_events, a
     if (d_events) *d_events = w.d_events[sc.cur].p;
     if (d_rows) *d_rows = w.d_rows[sc.cur].p;
     if (d_tracks) *d_tracks = w.d_tracks[sc.cur].p;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_set_band_follow(airband_hip_handle* h, int64_t max_changes) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const Plan& p = h->plan;
+    BandScope& sc = h->scope;
+    BandWatch& w = sc.survey.watch;
+    if (sc.windows <= 0 || sc.survey.max_peaks <= 0 || w.max_tracks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band watch (airband_hip_set_band_watch)");
+    const int64_t n_follow = (int64_t)p.follow_ext.size();
+    if (n_follow == 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no followers (airband_hip_prepare_follow)");
+    const int64_t most = n_follow + (int64_t)sc.n_rows * w.max_tracks;
+    if (max_changes < 1 || max_changes > most || max_changes > INT32_MAX) return fail(h, AIRBAND_HIP_EINVAL, "max_changes must lie in 1 .. followers + rows * max_tracks");
+    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the band follow is set before the first batch");
+    if (sc.n_sets != 1) return fail(h, AIRBAND_HIP_EINVAL, "a handle with followers keeps one set of scope rows"); /* (it never runs ahead: airband_hip_prepare_follow) */
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* the followers in prepare order are in ascending dongle order, as the scope's rows are: a row's followers are one range */
+    std::vector<int> range((size_t)sc.n_rows * 2, 0), slot, home;
+    std::vector<airband_hip_band_follower> start;
+    int most_per_row = 0;
+    for (size_t i = 0; i < p.follow_ext.size(); i++) {
+        const int ext = p.follow_ext[i];
+        const ChanConst& c = p.cc[(size_t)ext];
+        const int row = sc.row_of_dev[(size_t)c.dev];
+        if (row >= 0) {
+            if (range[(size_t)row * 2 + 1]++ == 0) range[(size_t)row * 2] = (int)i;
+            most_per_row = std::max(most_per_row, range[(size_t)row * 2 + 1]);
+        }
+        slot.push_back(h->ext_to_slot[(size_t)ext]);
+        home.push_back(c.base_bin);
+        airband_hip_band_follower f;
+        std::memset(&f, 0, sizeof(f));
+        f.channel = ext;
+        f.bin = c.base_bin;
+        f.track = -1;
+        start.push_back(f);
+    }
+    /* built beside the handle and moved in whole: a failed allocation leaves the handle, its watch and an earlier follow as they were */
+    BandFollow fo;
+    fo.cap = most_per_row + w.max_tracks;
+    hipError_t e = upload(fo.d_range, range);
+    if (e == hipSuccess) e = upload(fo.d_slot, slot);
+    if (e == hipSuccess) e = upload(fo.d_home, home);
+    if (e == hipSuccess) e = upload(fo.d_followers, start);
+    if (e == hipSuccess) e = fo.d_rows.alloc_zeroed((size_t)sc.n_rows);
+    if (e == hipSuccess) e = fo.d_stage.alloc((size_t)sc.n_rows * (size_t)fo.cap);
+    if (e == hipSuccess) e = fo.d_changes.alloc_zeroed((size_t)max_changes);
+    if (e == hipSuccess) e = fo.d_count.alloc_zeroed(1);
+    if (e == hipSuccess) e = hipDeviceSynchronize(); /* the initial values are in place before a kernel on another stream reads them */
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); /* this call's error, reported here: not the next launch's */
+        return fail(h, AIRBAND_HIP_ENOMEM, std::string("band follow buffers: ") + hipGetErrorString(e));
+    }
+    fo.max_changes = (int)max_changes;
+    w.follow = std::move(fo);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_band_follow_changes(airband_hip_handle* h, int64_t* n_changes, airband_hip_band_follow_change* changes) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const BandScope& sc = h->scope;
+    const BandWatch& w = sc.survey.watch;
+    const BandFollow& fo = w.follow;
+    if (sc.windows <= 0 || sc.survey.max_peaks <= 0 || w.max_tracks <= 0 || fo.max_changes <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band follow (airband_hip_set_band_follow)");
+    if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    /* how many changes there are is on the device: the count first, then exactly those records */
+    int count = 0;
+    HIP_TRY(h, hipMemcpyAsync(&count, fo.d_count.p, sizeof(int), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (count < 0 || (int64_t)count > (int64_t)sc.n_rows * fo.cap) return fail(h, AIRBAND_HIP_ERUNTIME, "change count out of range: " + std::to_string(count));
+    if (n_changes) *n_changes = count;
+    const size_t n = (size_t)(count < fo.max_changes ? count : fo.max_changes);
+    if (changes && n) {
+        HIP_TRY(h, hipMemcpyAsync(changes, fo.d_changes.p, n * sizeof(airband_hip_band_follow_change), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+        HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    }
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_band_followers(airband_hip_handle* h, airband_hip_band_follower* followers, airband_hip_band_follow_row* rows) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const BandScope& sc = h->scope;
+    const BandWatch& w = sc.survey.watch;
+    const BandFollow& fo = w.follow;
+    if (sc.windows <= 0 || sc.survey.max_peaks <= 0 || w.max_tracks <= 0 || fo.max_changes <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band follow (airband_hip_set_band_follow)");
+    if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    if (followers) {
+        HIP_TRY(h, hipMemcpyAsync(followers, fo.d_followers.p, fo.d_followers.n * sizeof(airband_hip_band_follower), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+        HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    }
+    if (rows) return collect_survey_rows(h, fo.d_rows.p, 1, 0, h->plan.n_dev, rows, airband_hip_band_follow_row{}, s);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_device_band_follow(airband_hip_handle* h, int32_t** d_n_changes, airband_hip_band_follow_change** d_changes, airband_hip_band_follower** d_followers, airband_hip_band_follow_row** d_rows) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const BandWatch& w = h->scope.survey.watch;
+    const BandFollow& fo = w.follow;
+    if (h->scope.windows <= 0 || h->scope.survey.max_peaks <= 0 || w.max_tracks <= 0 || fo.max_changes <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band follow (airband_hip_set_band_follow)");
+    if (d_n_changes) *d_n_changes = fo.d_count.p;
+    if (d_changes) *d_changes = fo.d_changes.p;
+    if (d_followers) *d_followers = fo.d_followers.p;
+    if (d_rows) *d_rows = fo.d_rows.p;
     return AIRBAND_HIP_OK;
 }
 

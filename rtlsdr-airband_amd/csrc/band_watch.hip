@@ -24,16 +24,15 @@
  *   * the row record is written by lane 0.
  * A switched-off dongle (DevConst::disabled, as band_scope.hip recognises it) is not advanced: its table and counters are carried over unchanged -- from the
  * other set where the handle keeps two -- with n_events = 0.
- * band_watch_pack_kernel: ONE workgroup of sixteen wavefronts walks the rows in chunks of 1 024 with a carried total: an exclusive prefix sum of the rows'
- * n_events (shuffles inside a wavefront, sixteen totals through LDS in two alternating sets: one barrier a chunk), then thread t copies its row's events to
- * events[offset ..) while below max_events, 16 bytes a record.  65 536 rows are 64 chunks of a load, six shuffles and a barrier each, and a batch has events
- * on a few rows: a single workgroup is enough at that size, and the order cannot depend on which workgroup arrives first because there is only one.
+ * band_watch_pack_kernel: ONE workgroup packs the rows' events into events[] in row order by a carried prefix sum of the rows' n_events (band_pack.h, shared with
+ * the band follow's list of changes).
  * Integer arithmetic throughout (powers are handled as bit patterns), no atomics, every store by the lane that holds the value: equal input, equal bytes.
  * Every index into the staging area is below max_peaks + T by construction (at most one event per peak round, at most one per slot) and checked again where it
  * is used; n_peaks and a row's n_events are clamped to the sizes the buffers have before anything is indexed with them.
  */
 #include <hip/hip_runtime.h>
 
+#include "band_pack.h"
 #include "common.h"
 #include "kernels.h"
 
@@ -42,7 +41,6 @@ namespace airband {
 namespace {
 
 constexpr int WATCH_ROWS = 4, WATCH_THREADS = 64 * WATCH_ROWS;
-constexpr int PACK_THREADS = 1024, PACK_WAVES = PACK_THREADS / 64;
 constexpr unsigned NO_KEY = 0xffffffffu;
 
 typedef unsigned long long u64;
@@ -204,39 +202,8 @@ __global__ __launch_bounds__(WATCH_THREADS) void band_watch_kernel(WatchArgs a) 
 }
 
 __global__ __launch_bounds__(PACK_THREADS) void band_watch_pack_kernel(WatchArgs a) {
-    __shared__ int wave_total[2][PACK_WAVES];
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int cap = a.max_peaks + a.max_tracks;
-    int carry = 0; /* the events of the rows in front of the chunk: the same in every thread */
-    int chunk = 0;
-#pragma unroll 1
-    for (int r0 = 0; r0 < a.n_rows; r0 += PACK_THREADS, chunk++) {
-        const int row = r0 + tid;
-        int n = row < a.n_rows ? a.rows_out[row].n_events : 0;
-        n = n < 0 ? 0 : n;
-        n = n > cap ? cap : n;
-        int incl = n;
-#pragma unroll
-        for (int dl = 1; dl < 64; dl <<= 1) {
-            const int o = (int)__shfl_up((unsigned)incl, (unsigned)dl);
-            if (lane >= dl) incl += o;
-        }
-        int* const tot = wave_total[chunk & 1]; /* written again two chunks on: every thread has passed the barrier between */
-        if (lane == 63) tot[wave] = incl;
-        __syncthreads();
-        int before = carry, all = 0;
-        for (int w = 0; w < PACK_WAVES; w++) {
-            const int v = tot[w];
-            before += w < wave ? v : 0;
-            all += v;
-        }
-        const long off = (long)before + (incl - n);
-        const uint4* const src = reinterpret_cast<const uint4*>(a.stage + (long)row * cap);
-        uint4* const dst = reinterpret_cast<uint4*>(a.events);
-        for (int i = 0; i < n && off + i < (long)a.max_events; i++) dst[off + i] = src[i];
-        carry += all;
-    }
-    if (tid == 0) a.n_events[0] = carry;
+    pack_rows(&a.rows_out[0].n_events, (int)(sizeof(airband_hip_band_watch_row) / sizeof(int)), reinterpret_cast<const uint4*>(a.stage), a.max_peaks + a.max_tracks,
+              reinterpret_cast<uint4*>(a.events), a.max_events, a.n_events, a.n_rows);
 }
 
 void launch_band_watch(const WatchArgs& a, hipStream_t stream) {

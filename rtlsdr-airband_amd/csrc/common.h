@@ -61,7 +61,7 @@ struct ChanState {
     /* freq_t / channel_t */
     float agcavgfast, pr, pj, prev_waveout;
     uint32_t dm_phi;
-    int32_t bin; /* dev->bins[i]; moves only with AFC */
+    int32_t bin; /* dev->bins[i]; moves with AFC, and on a follower with the band follow (band_follow.hip) */
     int32_t axc; /* channel->axcindicate of the last batch */
     uint32_t active_counter;
     /* Squelch (src/squelch.h:117-158) */

@@ -115,8 +115,21 @@ struct OutputGate {
 /* what airband_hip_set_band_watch() set up, a part of the survey it reads: replaced as a whole, gone with the survey, one without max_tracks is a survey
  * without a watch (nothing allocated, nothing launched).  Its results follow the survey's: the same sets, the same `cur`; the tables a batch starts from are
  * the other set's where there are two. */
+/* what airband_hip_set_band_follow() set up, a part of the watch whose tables it reads: replaced as a whole, gone with the watch, one without max_changes is a
+ * watch without a follow (nothing allocated, nothing launched).  A handle with followers never runs ahead: the scope keeps ONE set, and so does this. */
+struct BandFollow {
+    int max_changes = 0;       /* capacity of the fleet's list; 0 = no follow */
+    int cap = 0;               /* a row's staging slice: the most followers of a row + max_tracks */
+    DevBuf<int> d_range, d_slot, d_home; /* by scope row: first follower and count; by follower (prepare order): demod slot, home bin */
+    DevBuf<airband_hip_band_follower> d_followers;
+    DevBuf<airband_hip_band_follow_row> d_rows;
+    DevBuf<airband_hip_band_follow_change> d_changes, d_stage; /* d_stage: the rows' changes between the two kernels of one launch */
+    DevBuf<int> d_count;
+};
+
 struct BandWatch {
     int max_tracks = 0;        /* 0 = no watch */
+    BandFollow follow;
     int match_bins = 0, confirm_hits = 0, release_misses = 0, max_events = 0;
     uint32_t batch = 0;        /* the watch batch number of the next launch */
     DevBuf<airband_hip_band_track> d_tracks[2];

@@ -370,5 +370,31 @@ struct WatchArgs {
 };
 void launch_band_watch(const WatchArgs& a, hipStream_t stream);
 
+/* band follow (band_follow.hip): every scope row's followers decided against the row's track table as the watch left it, one wavefront per row; a follower that
+ * changes has its ChanState::bin written and the re-tune epoch stamped there and then, and the rows' changes are packed into one fleet-wide list in row order.
+ * Launched on the batch's stage-2 stream behind the demod kernels (which own ChanState) and behind the batch's watch. */
+struct FollowArgs {
+    const DevConst* dev;
+    const int* dev_of_row;                      /* [n_rows] the selected dongles, ascending */
+    const airband_hip_band_track* tracks;       /* [n_rows][max_tracks] the watch's tables of this batch */
+    const int* fol_range;                       /* [n_rows][2] the row's followers: first (index in prepare order) and count (<= 64) */
+    const int* fol_slot;                        /* [n_follow] the follower's demod slot */
+    const int* fol_home;                        /* [n_follow] its home bin (ChanConst::base_bin) */
+    airband_hip_band_follower* followers;       /* [n_follow] prepare order, advanced in place */
+    airband_hip_band_follow_row* rows;          /* [n_rows] */
+    airband_hip_band_follow_change* stage;      /* [n_rows][cap] a row's changes of this batch, rows[row].n_changes of them */
+    airband_hip_band_follow_change* changes;    /* [max_changes] */
+    int* n_changes;                             /* [1] */
+    ChanState* cs;                              /* by slot: a changed follower's bin is written here */
+    int* moved_epoch;                           /* the re-tune kernel's stamp (RetuneArgs::moved_epoch), or null where no coefficient table follows the bins */
+    int epoch;
+    int n_rows, n_follow, n_slots, fft_log;
+    int max_tracks;                             /* 1 .. 64: the watch's */
+    int cap;                                    /* most followers of a row + max_tracks */
+    int max_changes;
+    uint32_t batch;                             /* the watch batch number k of this batch */
+};
+void launch_band_follow(const FollowArgs& a, hipStream_t stream);
+
 }  // namespace airband
 #endif

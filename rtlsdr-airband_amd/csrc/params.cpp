@@ -426,7 +426,7 @@ void build_dft_tables(Plan& p, bool host_private) {
             bool private_table = false;
             for (int j = g * 8; j < p.dev[d].n_ch && j < g * 8 + 8; j++) {
                 key.push_back(p.cc[p.chan_base[d] + j].base_bin);
-                private_table |= p.cc[p.chan_base[d] + j].afc != 0;
+                private_table |= p.cc[p.chan_base[d] + j].afc != 0 || (!p.is_follower.empty() && p.is_follower[(size_t)(p.chan_base[d] + j)]); /* the band follow moves a follower's bin as AFC moves a channel's */
             }
             int found = -1, home = -1;
             if (last_shared >= 0 && shared_keys[last_shared] == key) home = last_shared; /* fleets of identical dongles: the common case */
@@ -723,6 +723,35 @@ int build_scan(const airband_hip_config* cfg, const airband_hip_scan_cfg* scan, 
         k += (size_t)sl.n;
         p.scan.push_back(sl);
     }
+    return AIRBAND_HIP_OK;
+}
+
+int build_follow(const airband_hip_config* cfg, const int32_t* follow, int n_follow, Plan& p) {
+    p.follow_ext.clear();
+    p.is_follower.clear();
+    if (n_follow < 0 || (n_follow > 0 && !follow)) return fail(p, AIRBAND_HIP_EINVAL, "bad follower arguments");
+    if (n_follow == 0) return AIRBAND_HIP_OK;
+    std::vector<uint8_t> scan_dev((size_t)p.n_dev, 0);
+    for (const ScanList& sl : p.scan) scan_dev[(size_t)sl.dev] = 1;
+    std::vector<int> per_dev((size_t)p.n_dev, 0);
+    int d = 0;
+    for (int i = 0; i < n_follow; i++) {
+        const int ext = follow[i];
+        const std::string who = "follower " + std::to_string(i) + " (channel " + std::to_string(ext) + ")";
+        if (ext < 0 || ext >= p.total_ch) return fail(p, AIRBAND_HIP_EINVAL, who + ": channel index out of range");
+        if (i > 0 && ext <= follow[i - 1]) return fail(p, AIRBAND_HIP_EINVAL, who + ": channel indices must be strictly ascending");
+        while (d + 1 < p.n_dev && ext >= p.chan_base[d + 1]) d++; /* ascending: the dongle only moves up */
+        const airband_hip_channel_cfg& ch = cfg->devices[d].channels[ext - p.chan_base[d]];
+        if (ch.modulation != AIRBAND_MOD_AM) return fail(p, AIRBAND_HIP_EINVAL, who + ": a follower is an AM channel (NFM followers are out of scope)");
+        if (ch.afc != 0) return fail(p, AIRBAND_HIP_EINVAL, who + ": a follower has afc == 0");
+        if (ch.has_iq_outputs != 0) return fail(p, AIRBAND_HIP_EINVAL, who + ": a follower has no raw-I/Q output");
+        if (ch.bandwidth_hz != 0) return fail(p, AIRBAND_HIP_EINVAL, who + ": a follower has bandwidth_hz == 0");
+        if (scan_dev[(size_t)d]) return fail(p, AIRBAND_HIP_EINVAL, who + ": a follower is not on a scan device");
+        if (++per_dev[(size_t)d] > 64) return fail(p, AIRBAND_HIP_EINVAL, who + ": more than 64 followers on dongle " + std::to_string(d));
+    }
+    p.follow_ext.assign(follow, follow + n_follow);
+    p.is_follower.assign((size_t)p.total_ch, 0);
+    for (int ext : p.follow_ext) p.is_follower[(size_t)ext] = 1;
     return AIRBAND_HIP_OK;
 }
 

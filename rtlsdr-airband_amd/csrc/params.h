@@ -53,6 +53,9 @@ struct Plan {
     std::vector<ScanList> scan;
     std::vector<ChanConst> scan_cc;
     std::vector<ChanState> scan_cs0;
+    /* followers (airband_hip_prepare_follow): their external channel indices in prepare order (ascending), and a mark per external channel index */
+    std::vector<int> follow_ext;
+    std::vector<uint8_t> is_follower;  /* empty on a plan without followers */
     std::string error;
 };
 
@@ -64,7 +67,12 @@ int build_plan(const airband_hip_config* cfg, Plan& plan);
  * merges the channel's needs_raw_iq over the list (src/config.cpp:671-678).  No GPU needed. */
 int build_scan(const airband_hip_config* cfg, const airband_hip_scan_cfg* scan, int n_scan, Plan& plan);
 
-/* Builds the int8 coefficient tables for the matrix-core channelizer.  host_private = false: tables of groups with an AFC channel are left
+/* Adds the followers to a plan build_plan() and build_scan() made from the same cfg: validates them (AIRBAND_HIP_EINVAL with a text that names the offending
+ * channel, see airband_hip_prepare_follow) and marks their channels.  Call it before build_dft_tables(): a group of eight with a follower owns a private
+ * coefficient table.  No GPU needed. */
+int build_follow(const airband_hip_config* cfg, const int32_t* follow, int n_follow, Plan& plan);
+
+/* Builds the int8 coefficient tables for the matrix-core channelizer.  host_private = false: tables of groups with an AFC channel or a follower are left
  * to the device (retune kernel); their slots exist (item_bset, n_bsets) but plan.bfrag / bcorr hold the shared tables only. */
 void build_dft_tables(Plan& plan, bool host_private = true);
 
