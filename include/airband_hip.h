@@ -428,6 +428,69 @@ int airband_hip_collect_active(airband_hip_handle* h, int64_t* n_active, int32_t
  * [max_rows][wave_batch], d_iq_rows [max_rows][2*wave_batch] or NULL on a handle without raw-I/Q outputs.  Any out-pointer may be NULL. */
 int airband_hip_device_active(airband_hip_handle* h, int32_t** d_index, int32_t** d_count, float** d_rows, float** d_iq_rows);
 
+/* ---- encoded audio collect ------------------------------------------------------------------------------------------------------------
+ * Every row the gate delivers is float32 samples of 8 kHz or 16 kHz voice audio in +-1.0 (what the reference hands lame_encode_buffer_ieee_float, its UDP
+ * stream and pulse).  A consumer that ships int16 or G.711 (8 kHz mono is exactly RTP payload types 0, PCMU, and 8, PCMA) copies four bytes per sample over
+ * PCIe and converts on the host.  A gated handle with an output encoding converts on the GPU, behind the gate, the rows the gate selected: half the bytes for
+ * int16, a quarter for G.711, and one 16-byte record per row.  Mixer outputs and raw-I/Q rows are out of scope: they stay float.
+ * The definition (normative).  For one float32 sample x of a delivered row:
+ *   x NaN:                  q = 0, not clipped;
+ *   otherwise               v = x * 32767.0f -- ONE float32 multiplication, nothing fused with it;
+ *   |v| > 32767 (the infinities included):  q = +-32767 and the sample counts as clipped;
+ *   otherwise               q = v rounded to the nearest integer, ties to even (rintf).  q lies in -32767 .. 32767.
+ * AIRBAND_AUDIO_S16   q as little-endian int16.
+ * AIRBAND_AUDIO_ULAW  G.711 mu-law of q: p = q >> 2 (arithmetic shift); the sign mask is 0x7F if p < 0, else 0xFF; m = min(|p|, 8159) + 33; seg = how many of
+ *                     {0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF, 0x1FFF} m exceeds; seg == 8: the code is 0x7F ^ mask, otherwise
+ *                     ((seg << 4) | ((m >> (seg + 1)) & 0xF)) ^ mask.
+ * AIRBAND_AUDIO_ALAW  G.711 A-law of q: p = q >> 3; p >= 0: mask 0xD5, m = p; p < 0: mask 0x55, m = -p - 1; seg = how many of {0x1F, 0x3F, 0x7F, 0xFF, 0x1FF,
+ *                     0x3FF, 0x7FF, 0xFFF} m exceeds; seg == 8: 0x7F ^ mask; seg < 2: ((seg << 4) | ((m >> 1) & 0xF)) ^ mask; seg >= 2:
+ *                     ((seg << 4) | ((m >> seg) & 0xF)) ^ mask.
+ * Both laws are byte for byte what Python 3.10's audioop.lin2ulaw / lin2alaw make of every int16 value.  mu-law produces 255 distinct codes (never 0x7F);
+ * encode(decode(c)) == c for every A-law code and every mu-law code but 0x7F; |decode(encode(q)) - q| <= (|q| >> 5) + 8 for both laws over -32767 .. 32767.
+ * Everything behind the one multiplication is integer arithmetic: two implementations of this text agree in every byte.
+ * The record is computed on q, so it is the same whatever the format.  A closed squelch leaves zeros in a row: `first` and `end` tell a sender which part of a
+ * trailing batch carries audio.
+ * Alignment: a lane of the kernel moves four samples (16 bytes in, 8 or 4 out), so wave_batch must be a multiple of four.  It is 1000 or 2000.
+ * A handle that sets no encoding allocates nothing for this, launches nothing and returns the same bits. */
+#define AIRBAND_AUDIO_F32 0
+#define AIRBAND_AUDIO_S16 1
+#define AIRBAND_AUDIO_ULAW 2
+#define AIRBAND_AUDIO_ALAW 3
+
+typedef struct airband_hip_audio_row {
+    int32_t  channel;    /* device-major channel index: channel_index[i] */
+    uint16_t peak;       /* max |q| over the row, 0 .. 32767 */
+    uint16_t n_clipped;  /* samples that were clipped */
+    uint16_t first;      /* index of the first sample with q != 0; wave_batch if there is none */
+    uint16_t end;        /* one past the last sample with q != 0; 0 if there is none */
+    uint32_t reserved;   /* 0 */
+} airband_hip_audio_row; /* 16 bytes */
+
+/* encoding = AIRBAND_AUDIO_*.  After airband_hip_set_output_gate() and before the first batch; calling it again before then replaces the encoding,
+ * AIRBAND_AUDIO_F32 removes it, and airband_hip_set_output_gate() called again drops it with the gate it belonged to.  Validated before the device is touched:
+ * AIRBAND_HIP_EINVAL for a NULL handle, a handle without a gate, an unknown encoding, a batch already enqueued; AIRBAND_HIP_EBADSIZE where wave_batch is no
+ * multiple of four.  Buffers: [max_rows][wave_batch] bytes (G.711) or int16 (S16) and [max_rows] records; AIRBAND_HIP_ENOMEM when they cannot be had -- the
+ * handle then runs on as it was, gate included. */
+int airband_hip_set_output_encoding(airband_hip_handle* h, int32_t encoding);
+
+/* airband_hip_collect_active() with encoded rows: the same count, the same list, n = min(*n_active, max_rows), nothing past row n is written, any pointer may be
+ * NULL, the batch is marked as collected, AIRBAND_HIP_EAGAIN likewise.
+ *   audio [n][wave_batch]  int16 (S16) or bytes (G.711): row i = the encoding of channel channel_index[i]'s row of airband_hip_collect();
+ *   info  [n]              the rows' records.
+ * The count, then the list, then one contiguous copy of n encoded rows and one of n records.  AIRBAND_HIP_EINVAL on a handle without an encoding.
+ * airband_hip_collect_active(), airband_hip_collect() and airband_hip_collect_channels() keep returning what they return on a handle without an encoding: the
+ * float rows are still packed. */
+int airband_hip_collect_active_encoded(airband_hip_handle* h, int64_t* n_active, int32_t* channel_index, void* audio, airband_hip_audio_row* info, char* axc_all);
+
+/* Device-side views of the same (valid until the next process call): d_audio [max_rows][wave_batch] int16 or bytes, d_info [max_rows].  Any out-pointer may be
+ * NULL.  The list and the count are airband_hip_device_active()'s. */
+int airband_hip_device_active_encoded(airband_hip_handle* h, void** d_audio, airband_hip_audio_row** d_info);
+
+/* The same kernel on caller-provided HOST rows [n_rows][wave_batch] float32: audio [n_rows][wave_batch] int16 or bytes, info [n_rows] with info[i].channel = i
+ * (either may be NULL).  For mixer outputs or airband_hip_collect_channels() rows in the same format.  Needs no gate and touches no handle state; synchronous.
+ * AIRBAND_HIP_EINVAL for NULL rows, n_rows < 0 (or too many to index), encoding AIRBAND_AUDIO_F32 or unknown; n_rows == 0 is AIRBAND_HIP_OK. */
+int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const float* rows, int64_t n_rows, void* audio, airband_hip_audio_row* info);
+
 /* ---- band scope -------------------------------------------------------------------------------------------------------------------
  * The channelizer keeps the few bins of every transform that carry a configured channel.  A handle with a band scope also keeps, per selected dongle and batch,
  * the POWER SPECTRUM OF THE WHOLE BAND over a handful of the batch's FFT windows: what the band looks like, where to put channels, an overloaded or deaf
@@ -737,7 +800,7 @@ int airband_hip_derive_constants(const airband_hip_config* cfg, int32_t channel_
 int airband_hip_dft_selftest(const airband_hip_config* cfg, int32_t windows, double* max_rel_err);
 
 /* Milliseconds the GPU spent on the last finished batch (HIP events on the streams the kernels run on):
- * [0] channelizer kernel, [1] demod kernels (+ per-kind emit), [2] joint emit / mixers (+ the output gate's select and gather), [3] their sum.  Waits for the
+ * [0] channelizer kernel, [1] demod kernels (+ per-kind emit), [2] joint emit / mixers (+ the output gate's select and gather, + the output encoding's kernel), [3] their sum.  Waits for the
  * enqueued batches. */
 int airband_hip_last_timings(airband_hip_handle* h, float* ms4);
 

@@ -34,6 +34,7 @@ EXPORTS = [
     "airband_hip_comm_group_begin", "airband_hip_comm_group_end", "airband_hip_allreduce_mixers", "airband_hip_add_mixers", "airband_hip_comm_destroy", "airband_hip_clear_mixers", "airband_hip_set_signal_plan_shift", "airband_hip_regrouped",
     "airband_hip_prepare_scan", "airband_hip_set_freq_index", "airband_hip_freq_stats",
     "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
+    "airband_hip_set_output_encoding", "airband_hip_collect_active_encoded", "airband_hip_device_active_encoded", "airband_hip_encode_audio",
     "airband_hip_set_band_scope", "airband_hip_collect_band_scope", "airband_hip_device_band_scope",
     "airband_hip_set_band_survey", "airband_hip_collect_band_survey", "airband_hip_device_band_survey",
     "airband_hip_set_band_watch", "airband_hip_collect_band_events", "airband_hip_collect_band_tracks", "airband_hip_device_band_watch",
@@ -109,7 +110,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
-    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()):
+    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()):
         if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
             getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
@@ -354,6 +355,7 @@ class AirbandHip:
         rows = self.total_channels if max_rows is None else int(max_rows)
         self._check(self.L.airband_hip_set_output_gate(self.h, gate.ctypes.data, rows))
         self.gate_rows = rows
+        self.audio_encoding = capi.AUDIO_F32  # a new gate drops the encoding
 
     def collect_active(self, *, iq: bool = False) -> dict:
         """The batch collect() would return, packed to the channels the gate selected (airband_hip_collect_active): n_active (may exceed the capacity: only
@@ -377,6 +379,48 @@ class AirbandHip:
         ptrs = [C.c_void_p() for _ in range(4)]
         self._check(self.L.airband_hip_device_active(self.h, *[C.byref(p) for p in ptrs]))
         return {k: (p.value or 0) for k, p in zip(["index", "count", "rows", "iq_rows"], ptrs)}
+
+    def set_output_encoding(self, encoding):
+        """encoding: "s16", "ulaw", "alaw" or None (capi.AUDIO_* values are taken too): the gate's rows are also delivered as int16 or G.711 bytes with one record
+        per row (airband_hip_set_output_encoding).  After set_output_gate(), before the first batch; None removes it."""
+        enc = capi.AUDIO_F32 if encoding is None else capi.audio_encoding_value(encoding)
+        self._check(self.L.airband_hip_set_output_encoding(self.h, enc))
+        self.audio_encoding = enc
+
+    def _audio_dtype(self, enc):
+        return np.dtype("<i2") if enc == capi.AUDIO_S16 else np.dtype(np.uint8)
+
+    def collect_active_encoded(self) -> dict:
+        """collect_active() with encoded rows (airband_hip_collect_active_encoded): n_active, channels [n] ascending, audio [n][B] int16 ("s16") or uint8 (G.711),
+        info [n] of capi.AUDIO_ROW_DTYPE, axcindicate of every channel."""
+        rows, B = max(self.gate_rows, 1), self.B
+        n = C.c_int64(0)
+        idx = np.empty((rows,), np.int32)
+        audio = np.empty((rows, B), self._audio_dtype(getattr(self, "audio_encoding", capi.AUDIO_F32)))
+        info = np.empty((rows,), capi.AUDIO_ROW_DTYPE)
+        axc = np.empty((self.total_channels,), np.uint8)
+        self._check(self.L.airband_hip_collect_active_encoded(self.h, C.byref(n), idx.ctypes.data, audio.ctypes.data, info.ctypes.data, axc.ctypes.data))
+        kept = min(int(n.value), rows)
+        return dict(n_active=int(n.value), channels=idx[:kept], audio=audio[:kept], info=info[:kept], axcindicate=axc)
+
+    def device_active_encoded(self) -> dict:
+        """Device pointers of the encoded results (valid until the next process call): audio [max_rows][B] int16 or bytes, info [max_rows] of 16 bytes; the list
+        and the count are device_active()'s."""
+        ptrs = [C.c_void_p() for _ in range(2)]
+        self._check(self.L.airband_hip_device_active_encoded(self.h, *[C.byref(p) for p in ptrs]))
+        return {k: (p.value or 0) for k, p in zip(["audio", "info"], ptrs)}
+
+    def encode_audio(self, rows, encoding):
+        """The encoder on host rows [n][B] float32 (airband_hip_encode_audio): (audio [n][B] int16 or uint8, info [n] of capi.AUDIO_ROW_DTYPE, channel = row)."""
+        enc = capi.audio_encoding_value(encoding)
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2 or rows.shape[1] != self.B:
+            raise ValueError("rows must be [n][%d], got shape %r" % (self.B, rows.shape))
+        n = rows.shape[0]
+        audio = np.empty((n, self.B), self._audio_dtype(enc))
+        info = np.empty((n,), capi.AUDIO_ROW_DTYPE)
+        self._check(self.L.airband_hip_encode_audio(self.h, enc, rows.ctypes.data, n, audio.ctypes.data, info.ctypes.data))
+        return audio, info
 
     def set_band_scope(self, mask=None, windows: int = 8, mean: bool = True, peak: bool = False):
         """Band scope (airband_hip_set_band_scope): per batch and selected dongle, the power spectrum of the whole band over `windows` of the batch's FFT windows.

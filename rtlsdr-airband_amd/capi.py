@@ -331,6 +331,110 @@ def band_follow_reference(followers, tracks, home_bins, batch, dev=0):
     return fol, row, out
 
 
+# the encoded audio collect's (same header)
+AUDIO_F32, AUDIO_S16, AUDIO_ULAW, AUDIO_ALAW = 0, 1, 2, 3
+AUDIO_ENCODINGS = {"s16": AUDIO_S16, "ulaw": AUDIO_ULAW, "alaw": AUDIO_ALAW}
+
+
+class AudioRow(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("peak", C.c_uint16), ("n_clipped", C.c_uint16), ("first", C.c_uint16), ("end", C.c_uint16), ("reserved", C.c_uint32)]
+
+
+AUDIO_ENCODING_PROTOTYPES = {
+    "airband_hip_set_output_encoding": [_vp, _i32],
+    "airband_hip_collect_active_encoded": [_vp, C.POINTER(_i64), _vp, _vp, _vp, _vp],
+    "airband_hip_device_active_encoded": [_vp, C.POINTER(_vp), C.POINTER(_vp)],
+    "airband_hip_encode_audio": [_vp, _i32, _vp, _i64, _vp, _vp],
+}
+# numpy view of airband_hip_audio_row
+AUDIO_ROW_DTYPE = [("channel", "<i4"), ("peak", "<u2"), ("n_clipped", "<u2"), ("first", "<u2"), ("end", "<u2"), ("reserved", "<u4")]
+_ULAW_ENDS = (0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF, 0x1FFF)
+_ALAW_ENDS = (0x1F, 0x3F, 0x7F, 0xFF, 0x1FF, 0x3FF, 0x7FF, 0xFFF)
+
+
+def audio_encoding_value(encoding) -> int:
+    """"s16" / "ulaw" / "alaw" or an AUDIO_* value -> the AUDIO_* value"""
+    return AUDIO_ENCODINGS[encoding] if isinstance(encoding, str) else int(encoding)
+
+
+def audio_quantize_reference(rows):
+    """The float step of the encoded audio collect (include/airband_hip.h): (q int32 in -32767 .. 32767, clipped bool), of the shape of `rows`."""
+    import numpy as np
+
+    x = np.ascontiguousarray(rows, np.float32)
+    with np.errstate(all="ignore"):
+        v = x * np.float32(32767.0)  # one float32 multiplication
+        nan = np.isnan(x)
+        clipped = ~nan & (np.abs(v) > np.float32(32767.0))
+        q = np.rint(np.where(nan | clipped, np.float32(0.0), v)).astype(np.int32)  # to nearest, ties to even
+    q = np.where(clipped, np.where(v < 0, -32767, 32767), q).astype(np.int32)
+    return q, clipped
+
+
+def audio_law_reference(q, encoding):
+    """G.711 codes (uint8) of integers q in -32768 .. 32767, by the header's definition: AUDIO_ULAW or AUDIO_ALAW."""
+    import numpy as np
+
+    q = np.asarray(q, np.int32)
+    if encoding == AUDIO_ULAW:
+        p = q >> 2
+        mask = np.where(p < 0, 0x7F, 0xFF)
+        m = np.minimum(np.abs(p), 8159) + 33
+        seg = (m[..., None] > np.array(_ULAW_ENDS)).sum(-1)
+        code = np.where(seg == 8, 0x7F, (seg << 4) | ((m >> (seg + 1)) & 0xF))
+    elif encoding == AUDIO_ALAW:
+        p = q >> 3
+        mask = np.where(p >= 0, 0xD5, 0x55)
+        m = np.where(p >= 0, p, -p - 1)
+        seg = (m[..., None] > np.array(_ALAW_ENDS)).sum(-1)
+        code = np.where(seg == 8, 0x7F, (seg << 4) | ((m >> np.where(seg < 2, 1, seg)) & 0xF))
+    else:
+        raise ValueError("not a G.711 encoding: %r" % (encoding,))
+    return ((code ^ mask) & 0xFF).astype(np.uint8)
+
+
+def audio_encode_reference(rows, encoding):
+    """The encoded audio collect's definition (include/airband_hip.h) in numpy.  rows [n][B] float32, encoding "s16" / "ulaw" / "alaw" or an AUDIO_* value ->
+    (audio [n][B] int16 or uint8, info [n] of AUDIO_ROW_DTYPE with channel = the row's number)."""
+    import numpy as np
+
+    enc = audio_encoding_value(encoding)
+    rows = np.ascontiguousarray(rows, np.float32)
+    n, B = rows.shape
+    q, clipped = audio_quantize_reference(rows)
+    audio = q.astype("<i2") if enc == AUDIO_S16 else audio_law_reference(q, enc)
+    info = np.zeros(n, AUDIO_ROW_DTYPE)
+    info["channel"] = np.arange(n)
+    nz = q != 0
+    some = nz.any(axis=1)
+    info["peak"] = np.abs(q).max(axis=1) if B else 0
+    info["n_clipped"] = clipped.sum(axis=1)
+    info["first"] = np.where(some, nz.argmax(axis=1), B)
+    info["end"] = np.where(some, B - nz[:, ::-1].argmax(axis=1), 0)
+    return audio, info
+
+
+def audio_decode_reference(codes, encoding):
+    """The standard G.711 expansion (ITU-T G.711; audioop.ulaw2lin / alaw2lin) of uint8 codes to int32 linear values on the int16 scale; the identity for S16."""
+    import numpy as np
+
+    enc = audio_encoding_value(encoding)
+    if enc == AUDIO_S16:
+        return np.asarray(codes).astype(np.int32)
+    c = np.asarray(codes).astype(np.int32) & 0xFF
+    if enc == AUDIO_ULAW:
+        u = ~c & 0xFF
+        t = (((u & 0x0F) << 3) + 0x84) << ((u & 0x70) >> 4)
+        return np.where(u & 0x80, 0x84 - t, t - 0x84).astype(np.int32)
+    if enc == AUDIO_ALAW:
+        a = c ^ 0x55
+        t = (a & 0x0F) << 4
+        seg = (a & 0x70) >> 4
+        t = np.where(seg == 0, t + 8, (t + 0x108) << np.maximum(seg - 1, 0))
+        return np.where(a & 0x80, t, -t).astype(np.int32)
+    raise ValueError("unknown encoding: %r" % (encoding,))
+
+
 def scope_window_hops(windows: int, wave_batch: int):
     """The batch's new hops whose FFT windows a band scope of `windows` windows per batch looks at: (j * WAVE_BATCH) / K, j = 0 .. K-1."""
     return [(j * wave_batch) // windows for j in range(windows)]

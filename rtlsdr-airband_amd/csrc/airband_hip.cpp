@@ -563,6 +563,25 @@ GateArgs gate_args(const airband_hip_handle* h) {
     return a;
 }
 
+/* the gate's list and count, the rows the gather reads (airband_hip_set_output_encoding) */
+AudioPackArgs audio_pack_args(const airband_hip_handle* h) {
+    const OutputGate& g = h->gate;
+    AudioPackArgs a;
+    a.index = g.d_index.p;
+    a.count = g.d_count.p;
+    a.n_rows = 0;
+    a.max_rows = g.max_rows;
+    a.n_ch = h->plan.total_ch;
+    a.src = h->d_out_wave.p;
+    a.src_stride = h->wave_stride;
+    a.src_pad = AB_OUT_PAD;
+    a.audio = g.enc.d_audio.p;
+    a.info = g.enc.d_info.p;
+    a.wave_batch = h->B;
+    a.encoding = g.enc.encoding;
+    return a;
+}
+
 /* The band follow of the batch whose back half goes on stream s (airband_hip_set_band_follow), behind its demod kernels.  It reads the track tables the batch's
  * watch left, and the watch ran on the scope's stream: s is behind that already (scope_join() made the stage-1 stream wait for the scope, and a handle with
  * followers runs both halves of a batch on one stream), said again here because this is the point that depends on it.  The watch batch number of this batch is
@@ -674,6 +693,7 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
     }
     if (h->mix.n_mixers > 0) launch_mix(mix_args(h), s);
     if (h->gate.max_rows > 0) launch_gate(gate_args(h), s); /* the batch's active channels and their rows, packed (gate.hip) */
+    if (h->gate.max_rows > 0 && h->gate.enc.encoding != AIRBAND_AUDIO_F32) launch_audio_pack(audio_pack_args(h), 0, s); /* ... and encoded (audio_pack.hip) */
     (void)hipEventRecord(ev[4], s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
@@ -2141,6 +2161,109 @@ int airband_hip_device_active(airband_hip_handle* h, int32_t** d_index, int32_t*
     if (d_count) *d_count = g.d_count.p;
     if (d_rows) *d_rows = g.d_rows.p;
     if (d_iq_rows) *d_iq_rows = g.d_iq_rows.p;
+    return AIRBAND_HIP_OK;
+}
+
+static bool audio_encoding_known(int32_t e) { return e == AIRBAND_AUDIO_S16 || e == AIRBAND_AUDIO_ULAW || e == AIRBAND_AUDIO_ALAW; }
+static size_t audio_sample_bytes(int e) { return e == AIRBAND_AUDIO_S16 ? 2 : 1; }
+
+int airband_hip_set_output_encoding(airband_hip_handle* h, int32_t encoding) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    OutputGate& g = h->gate;
+    if (g.max_rows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output gate (airband_hip_set_output_gate)");
+    if (encoding != AIRBAND_AUDIO_F32 && !audio_encoding_known(encoding)) return fail(h, AIRBAND_HIP_EINVAL, "encoding is not an AIRBAND_AUDIO_* value");
+    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the output encoding is set before the first batch");
+    if (h->B % 4) return fail(h, AIRBAND_HIP_EBADSIZE, "the encoder moves four samples per lane: WAVE_BATCH must be a multiple of four");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* built beside the gate and moved in whole: a failed allocation leaves the handle as it was */
+    OutputEncoding enc;
+    if (encoding != AIRBAND_AUDIO_F32) {
+        const size_t rows = (size_t)g.max_rows;
+        hipError_t e = enc.d_audio.alloc(rows * h->B * audio_sample_bytes(encoding));
+        if (e == hipSuccess) e = enc.d_info.alloc(rows);
+        if (e != hipSuccess) {
+            (void)hipGetLastError(); /* this call's error, reported here: not the next launch's */
+            return fail(h, AIRBAND_HIP_ENOMEM, std::string("output encoding buffers: ") + hipGetErrorString(e));
+        }
+        enc.encoding = encoding;
+    }
+    g.enc = std::move(enc);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_active_encoded(airband_hip_handle* h, int64_t* n_active, int32_t* channel_index, void* audio, airband_hip_audio_row* info, char* axc_all) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const OutputGate& g = h->gate;
+    if (g.max_rows <= 0 || g.enc.encoding == AIRBAND_AUDIO_F32) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output encoding (airband_hip_set_output_encoding)");
+    if (!h->results_ready || h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    /* how many rows there are is on the device: the count first, then exactly those rows */
+    int count = 0;
+    HIP_TRY(h, hipMemcpyAsync(&count, g.d_count.p, sizeof(int), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (count < 0 || count > h->plan.total_ch) return fail(h, AIRBAND_HIP_ERUNTIME, "active count out of range: " + std::to_string(count));
+    const size_t n = (size_t)(count < g.max_rows ? count : g.max_rows), row_bytes = (size_t)h->B * audio_sample_bytes(g.enc.encoding);
+    if (channel_index && n) HIP_TRY(h, hipMemcpyAsync(channel_index, g.d_index.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (audio && n) HIP_TRY(h, hipMemcpyAsync(audio, g.enc.d_audio.p, n * row_bytes, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (info && n) HIP_TRY(h, hipMemcpyAsync(info, g.enc.d_info.p, n * sizeof(airband_hip_audio_row), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (axc_all) HIP_TRY(h, hipMemcpyAsync(axc_all, h->d_out_axc.p, (size_t)h->plan.total_ch, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (n_active) *n_active = count;
+    h->results_ready = false;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_device_active_encoded(airband_hip_handle* h, void** d_audio, airband_hip_audio_row** d_info) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const OutputGate& g = h->gate;
+    if (g.max_rows <= 0 || g.enc.encoding == AIRBAND_AUDIO_F32) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output encoding (airband_hip_set_output_encoding)");
+    if (d_audio) *d_audio = g.enc.d_audio.p;
+    if (d_info) *d_info = g.enc.d_info.p;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const float* rows, int64_t n_rows, void* audio, airband_hip_audio_row* info) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!rows) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    if (!audio_encoding_known(encoding)) return fail(h, AIRBAND_HIP_EINVAL, "encoding is not AIRBAND_AUDIO_S16, _ULAW or _ALAW");
+    if (n_rows < 0 || n_rows > 0x7fffffff / 4) return fail(h, AIRBAND_HIP_EINVAL, "n_rows out of range");
+    if (h->B % 4) return fail(h, AIRBAND_HIP_EBADSIZE, "the encoder moves four samples per lane: WAVE_BATCH must be a multiple of four");
+    if (n_rows == 0) return AIRBAND_HIP_OK;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* buffers of the call's own, on the null stream: nothing of the handle is read or written */
+    const size_t n = (size_t)n_rows, B = (size_t)h->B, row_bytes = B * audio_sample_bytes(encoding);
+    DevBuf<float> d_rows;
+    DevBuf<uint8_t> d_audio;
+    DevBuf<airband_hip_audio_row> d_info;
+    hipError_t e = d_rows.alloc(n * B);
+    if (e == hipSuccess) e = d_audio.alloc(n * row_bytes);
+    if (e == hipSuccess) e = d_info.alloc(n);
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(h, AIRBAND_HIP_ENOMEM, std::string("encode_audio buffers: ") + hipGetErrorString(e));
+    }
+    HIP_TRY(h, hipMemcpy(d_rows.p, rows, n * B * sizeof(float), hipMemcpyHostToDevice), AIRBAND_HIP_ERUNTIME);
+    AudioPackArgs a;
+    a.index = nullptr;
+    a.count = nullptr;
+    a.n_rows = (int)n_rows;
+    a.max_rows = (int)n_rows;
+    a.n_ch = (int)n_rows;
+    a.src = d_rows.p;
+    a.src_stride = (long)B;
+    a.src_pad = 0;
+    a.audio = d_audio.p;
+    a.info = d_info.p;
+    a.wave_batch = h->B;
+    a.encoding = encoding;
+    launch_audio_pack(a, 0, nullptr);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
+    if (audio) HIP_TRY(h, hipMemcpy(audio, d_audio.p, n * row_bytes, hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
+    if (info) HIP_TRY(h, hipMemcpy(info, d_info.p, n * sizeof(airband_hip_audio_row), hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(nullptr), AIRBAND_HIP_ERUNTIME); /* the buffers go with this call */
     return AIRBAND_HIP_OK;
 }
 

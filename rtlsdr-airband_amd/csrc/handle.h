@@ -97,8 +97,17 @@ struct MixerWiring {
     DevBuf<uint8_t> d_stereo, d_signal;
 };
 
+/* what airband_hip_set_output_encoding() set up, a part of the gate whose list it reads: replaced as a whole, gone with the gate, AIRBAND_AUDIO_F32 is a gate
+ * without an encoding (nothing allocated, nothing launched) */
+struct OutputEncoding {
+    int encoding = AIRBAND_AUDIO_F32;
+    DevBuf<uint8_t> d_audio; /* [max_rows][wave_batch] bytes, or int16 for S16 */
+    DevBuf<airband_hip_audio_row> d_info;
+};
+
 /* what airband_hip_set_output_gate() set up: replaced as a whole, one without max_rows is a handle without a gate (nothing allocated, nothing launched) */
 struct OutputGate {
+    OutputEncoding enc;
     int max_rows = 0;          /* capacity of the packed buffers; 0 = no gate */
     std::vector<uint8_t> gate; /* the caller's bytes (the device copy also carries AB_GATE_OFF for the channels of dongles switched off) */
     DevBuf<uint8_t> d_gate, d_prev;

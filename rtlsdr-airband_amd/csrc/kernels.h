@@ -307,6 +307,22 @@ struct GateArgs {
 int gate_blocks(int n_ch);
 void launch_gate(const GateArgs& a, hipStream_t stream);
 
+/* encoded audio collect (audio_pack.hip): rows as int16 or G.711 bytes and one record per row; one wavefront per row, workgroups stride over the rows */
+struct AudioPackArgs {
+    const int* index;         /* [max_rows] row r is channel index[r] (the gate's list); null: row r is source row r (airband_hip_encode_audio) */
+    const int* count;         /* [1] on the device: the gate's count (may exceed max_rows); null: n_rows */
+    int n_rows;
+    int max_rows, n_ch;       /* the clamps: rows written, source rows there are */
+    const float* src;         /* source row c starts at src + c * src_stride + src_pad, 16-byte aligned */
+    long src_stride;
+    int src_pad;
+    void* audio;              /* [max_rows][wave_batch] int16 (S16) or bytes (G.711) */
+    airband_hip_audio_row* info; /* [max_rows] */
+    int wave_batch;           /* a multiple of four */
+    int encoding;             /* AIRBAND_AUDIO_S16 / _ULAW / _ALAW */
+};
+void launch_audio_pack(const AudioPackArgs& a, int grid, hipStream_t stream); /* grid: workgroups, 0 = min(max_rows, one per wavefront slot of the GPU) */
+
 /* band scope (band_scope.hip): mean and peak of |X[k]|^2 over n_windows windows of the batch's input span, one workgroup per selected dongle */
 struct ScopeArgs {
     const uint8_t* iq;        /* device: dongle d's span starts at iq + d * iq_stride (the batch's stage-1 input) */
