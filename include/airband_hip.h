@@ -237,13 +237,92 @@ int airband_hip_prepare_scan(const airband_hip_config* cfg, const airband_hip_sc
 /* Makes entry freq_idx of device dev's list the one in force for every batch enqueued from now on (by airband_hip_process, _process_device or
  * _process_bins): channel->freq_idx as the controller thread sets it (src/rtl_airband.cpp:101-139).  The index is latched per batch: on an
  * AIRBAND_HIP_FLAG_PIPELINE handle stage 2 of a batch, which runs during the next call, uses the index that was in force when the batch was
- * enqueued.  AIRBAND_HIP_EINVAL for a device without a scan list or an index out of range (nothing changes then). */
+ * enqueued.  AIRBAND_HIP_EINVAL for a device without a scan list or an index out of range (nothing changes then), and while the handle's lists are under scan
+ * control (airband_hip_set_scan_control: the GPU sets the index then). */
 int airband_hip_set_freq_index(airband_hip_handle* h, int32_t dev, int32_t freq_idx);
 
 /* Squelch / AGC statistics of entry freq_idx of device dev's list as of the last completed batch -- what the stats file prints for every entry
  * (src/output.cpp:615-720).  Entries that were not active report the values they were frozen with.  Computed by the same code as the rows of
  * airband_hip_collect(), bit for bit; that row of a scan channel describes the entry that was active in the batch. */
 int airband_hip_freq_stats(airband_hip_handle* h, int32_t dev, int32_t freq_idx, airband_hip_channel_stats* out);
+
+/* ---- scan control -------------------------------------------------------------------------------------------------------------------
+ * WHEN a scan list hops is the controller thread's decision in the reference (src/rtl_airband.cpp:101-139), one thread per dongle polling axcindicate every
+ * 200 ms.  With airband_hip_set_scan_control() the GPU takes it: per scan list a small state, advanced once per batch behind stage 2 from the channel's
+ * axcindicate of that batch, the switch of the list's entry fed straight to the exchange in front of the next batch's stage 2, and one fleet-wide packed list of
+ * the batch's RECORDS -- the hops a host has to retune dongles for, and the reference's "Activity on ..." lines.  Integers only:
+ * capi.scan_control_reference() (rtlsdr-airband_amd/capi.py) is this text in plain Python, and the GPU's bytes equal its bytes.
+ * State per list: idx (the entry in force), idle (consecutive_squelch_off, saturating at idle_batches), since (batches since the last hop while saturated),
+ * last (dev->last_frequency as an index; initially 0), hold (-1: none).  Lists start at idx = 0, or at what airband_hip_set_freq_index() last set.
+ * One batch of one list, for a dongle that is enabled (a switched-off dongle is FROZEN: nothing advances, no record, no switch) and a list of freq_count >= 2
+ * (the reference's thread returns at once otherwise, :108-109), with axc = the channel's axcindicate of the batch and k = the control's batch number
+ * (0 for the first batch behind airband_hip_set_scan_control()):
+ *     if hold >= 0:
+ *         if idx != hold: prev = idx; idx = hold; a HOP record
+ *         idle = 0; since = 0
+ *     else if axc == ' ' (NO_SIGNAL):
+ *         if idle < idle_batches: idle += 1                                  (:113-114)
+ *         else: since += 1; if since >= dwell_batches: prev = idx; idx = (idx + 1) % freq_count; since = 0; a HOP record      (:116-122)
+ *     else:
+ *         if idle == idle_batches: an ACTIVITY record, flags = AIRBAND_SCAN_RETAG if idx != last; last = idx                 (:125-133)
+ *         idle = 0; since = 0                                                 (:135)
+ * A new idx is the entry stage 2 of the NEXT batch runs with, in every schedule (AIRBAND_HIP_FLAG_PIPELINE included: decision and exchange are in one stream's
+ * order).  At most one record per list and batch; the batch's records form one list in ascending dongle order, n_records is the total and the first
+ * min(n_records, max_records) are kept.  A HOP record {freq_idx = the new entry, prev_idx = the one left} is the host's cue for input_set_centerfreq() (:119-122);
+ * an ACTIVITY record {freq_idx = idx, prev_idx = last before the record} is the log line (:126-127) and, with AIRBAND_SCAN_RETAG, tag_queue_put() (:128-133).
+ * With dwell_batches = 1 and a poll per batch this is the reference's thread; idle_batches = 16 is its 10 polls of 200 ms in 125 ms batches.
+ * Every list of the handle is under control or none is.  A handle without scan control does exactly the work it did. */
+#define AIRBAND_SCAN_HOP 1
+#define AIRBAND_SCAN_ACTIVITY 2
+#define AIRBAND_SCAN_RETAG 1
+
+typedef struct airband_hip_scan_event {
+    int32_t dev;       /* dongle index */
+    int16_t freq_idx;  /* HOP: the entry in force from the next batch on; ACTIVITY: the entry that heard the signal */
+    int16_t prev_idx;  /* HOP: the entry that was left; ACTIVITY: `last` before this record */
+    uint8_t kind;      /* AIRBAND_SCAN_HOP / _ACTIVITY */
+    uint8_t flags;     /* ACTIVITY: AIRBAND_SCAN_RETAG or 0 */
+    uint16_t reserved; /* 0 */
+    uint32_t batch;    /* the control's batch number k */
+} airband_hip_scan_event; /* 16 bytes */
+
+typedef struct airband_hip_scan_state {
+    int16_t idx;      /* the entry in force for the next batch */
+    int16_t hold;     /* the entry the list is pinned to, -1: none */
+    int32_t idle;     /* 0 .. idle_batches */
+    int32_t since;
+    int16_t last;
+    int16_t has_list; /* 1; 0 for a dongle without a scan list (every other field 0 then) */
+} airband_hip_scan_state; /* 16 bytes */
+
+/* The controller thread (src/rtl_airband.cpp:101-139) for every scan list of the handle, on the GPU.  idle_batches > 0 switches it on (again: the lists keep
+ * their entries, everything else starts afresh) with dwell_batches (0 counts as 1) and a record list of max_records (<= 0, or more than there are lists: one per
+ * list).  idle_batches == 0 switches it off: the host's view of every list's index is refreshed from the device, so that airband_hip_set_freq_index() continues
+ * from where the GPU left the lists.  Waits for the batches enqueued so far.  On an AIRBAND_HIP_FLAG_PIPELINE handle a batch whose stage 1 is enqueued and whose
+ * stage 2 is not runs with the entry it was enqueued with, and the lists start from that entry: an index airband_hip_set_freq_index() named after that batch was
+ * enqueued has been latched by no batch and is dropped.  AIRBAND_HIP_EINVAL for a NULL handle, a handle without scan lists, negative idle_batches or
+ * dwell_batches, and (switching on) a list of more than 32 767 entries, whose indices the int16 fields below cannot hold; AIRBAND_HIP_ENOMEM when the buffers
+ * cannot be had -- the handle then runs on as it was. */
+int airband_hip_set_scan_control(airband_hip_handle* h, int32_t idle_batches, int32_t dwell_batches, int64_t max_records);
+
+/* Pins device dev's list to entry freq_idx (what a host does by hand instead of src/rtl_airband.cpp:116-118); -1 releases the pin.  It takes effect behind the next
+ * batch and gives a HOP record if it changes the entry.  AIRBAND_HIP_EINVAL while scan control is off, for a device without a list and for an index out of range. */
+int airband_hip_scan_hold(airband_hip_handle* h, int32_t dev, int32_t freq_idx);
+
+/* The records of the batch airband_hip_collect() would return (the log line and tag of src/rtl_airband.cpp:125-133, the retune of :119-122): *n_records is the
+ * fleet's total, records a HOST array sized for max_records of which min(n_records, max_records) are written -- nothing past them.  Either pointer may be NULL.
+ * Two small copies: the count, then exactly those records.  Does not mark the batch as collected.  AIRBAND_HIP_EAGAIN before the first batch under control,
+ * AIRBAND_HIP_EINVAL while scan control is off. */
+int airband_hip_collect_scan_events(airband_hip_handle* h, int64_t* n_records, airband_hip_scan_event* records);
+
+/* The lists' states behind the same batch (i, consecutive_squelch_off and dev->last_frequency of src/rtl_airband.cpp:101-139) for dongles
+ * [first_dev, first_dev + n_dev): state is a HOST array [n_dev], zeros for a dongle without a list.  Valid from the moment control is switched on.
+ * AIRBAND_HIP_EINVAL while scan control is off or for a range outside the handle's dongles. */
+int airband_hip_collect_scan_state(airband_hip_handle* h, int32_t first_dev, int32_t n_dev, airband_hip_scan_state* state);
+
+/* Device-side views of the same (valid until the next process call; what replaces the per-dongle polls of src/rtl_airband.cpp:110-112 for a consumer on the GPU):
+ * d_n_records [1], d_records [max_records], d_state [lists] in ascending dongle order of the dongles that have a list.  Any out-pointer may be NULL. */
+int airband_hip_device_scan_control(airband_hip_handle* h, int32_t** d_n_records, airband_hip_scan_event** d_records, airband_hip_scan_state** d_state);
 
 /* Optional: wire channels into mixers before the first batch (reference: src/config.cpp mixer outputs,
  * src/mixer.cpp:57-94).  mixer_count mixers, n_inputs connections. */

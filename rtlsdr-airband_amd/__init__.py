@@ -33,6 +33,7 @@ EXPORTS = [
     "airband_hip_batch_ready", "airband_hip_mixer_set_stereo", "airband_hip_comm_unique_id", "airband_hip_comm_init_rank", "airband_hip_comm_init_all",
     "airband_hip_comm_group_begin", "airband_hip_comm_group_end", "airband_hip_allreduce_mixers", "airband_hip_add_mixers", "airband_hip_comm_destroy", "airband_hip_clear_mixers", "airband_hip_set_signal_plan_shift", "airband_hip_regrouped",
     "airband_hip_prepare_scan", "airband_hip_set_freq_index", "airband_hip_freq_stats",
+    "airband_hip_set_scan_control", "airband_hip_scan_hold", "airband_hip_collect_scan_events", "airband_hip_collect_scan_state", "airband_hip_device_scan_control",
     "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
     "airband_hip_set_output_encoding", "airband_hip_collect_active_encoded", "airband_hip_device_active_encoded", "airband_hip_encode_audio",
     "airband_hip_set_band_scope", "airband_hip_collect_band_scope", "airband_hip_device_band_scope",
@@ -110,7 +111,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
-    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()):
+    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()):
         if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
             getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
@@ -263,6 +264,7 @@ class AirbandHip:
         self.L = load_library()
         self.devices = list(devices)
         self.follow_channels = [int(c) for c in follow] if follow else []
+        self.scan_devices = sorted(int(d) for d in scan) if scan else []
         cfg, self._keep = make_config(devices, wave_rate=wave_rate, fft_log=fft_log, fm_demod=fm_demod, flags=flags, hip_device=hip_device)
         h = C.c_void_p()
         if self.follow_channels:
@@ -555,6 +557,41 @@ class AirbandHip:
     def set_freq_index(self, dev: int, freq_idx: int):
         """Entry freq_idx of dongle dev's scan list is in force for every batch enqueued from now on (latched per batch)."""
         self._check(self.L.airband_hip_set_freq_index(self.h, dev, freq_idx))
+
+    def set_scan_control(self, idle_batches: int = 16, dwell_batches: int = 2, max_records: Optional[int] = None):
+        """Scan control (airband_hip_set_scan_control): the GPU hops every scan list of the handle -- after idle_batches batches without signal a list moves on
+        every dwell_batches batches, the squelch opening after such a spell gives an ACTIVITY record, every hop a HOP record -- and keeps one list of the fleet's
+        records per batch, max_records of them (None: one per list).  idle_batches = 0 switches it off; set_freq_index() then continues from the GPU's indices.
+        While it is on set_freq_index() is refused."""
+        self._check(self.L.airband_hip_set_scan_control(self.h, int(idle_batches), int(dwell_batches), 0 if max_records is None else int(max_records)))
+
+    def scan_hold(self, dev: int, freq_idx: int):
+        """Pins dongle dev's list to entry freq_idx from the next batch on (a HOP record if that changes the entry); -1 releases it (airband_hip_scan_hold)."""
+        self._check(self.L.airband_hip_scan_hold(self.h, int(dev), int(freq_idx)))
+
+    def collect_scan_events(self) -> dict:
+        """The fleet's scan records of the batch collect() would return: dict(n_records = the total, records = the first min(n_records, max_records) of
+        capi.SCAN_EVENT_DTYPE, in ascending dongle order).  Two small copies.  Repeatable."""
+        n = C.c_int64(0)
+        records = np.zeros((max(len(self.scan_devices), 1),), capi.SCAN_EVENT_DTYPE)  # max_records is at most one per list
+        self._check(self.L.airband_hip_collect_scan_events(self.h, C.byref(n), records.ctypes.data))
+        kept = int(np.count_nonzero(records["kind"][:max(int(n.value), 0)]))  # the library wrote a prefix; a record's kind is never 0
+        return dict(n_records=int(n.value), records=records[:kept])
+
+    def collect_scan_state(self, first_dev: int = 0, n_dev: Optional[int] = None) -> np.ndarray:
+        """The scan lists' states behind the same batch for dongles [first_dev, first_dev + n_dev): [n_dev] of capi.SCAN_STATE_DTYPE, zeros for a dongle without
+        a list.  Repeatable."""
+        n = self.geometry.device_count - first_dev if n_dev is None else int(n_dev)
+        state = np.zeros((max(n, 1),), capi.SCAN_STATE_DTYPE)
+        self._check(self.L.airband_hip_collect_scan_state(self.h, int(first_dev), n, state.ctypes.data))
+        return state[:max(n, 0)]
+
+    def device_scan_control(self) -> dict:
+        """Device pointers of scan control (valid until the next process call): n_records [1] int32, records [max_records] of 16 bytes, state [lists] of 16
+        bytes in ascending dongle order of the dongles that have a list."""
+        ptrs = [C.c_void_p() for _ in range(3)]
+        self._check(self.L.airband_hip_device_scan_control(self.h, *[C.byref(p) for p in ptrs]))
+        return {k: (p.value or 0) for k, p in zip(["n_records", "records", "state"], ptrs)}
 
     def freq_stats(self, dev: int, freq_idx: int) -> dict:
         """Statistics of entry freq_idx of dongle dev's scan list as of the last completed batch (frozen values for inactive entries)."""

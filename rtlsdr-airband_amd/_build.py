@@ -45,6 +45,7 @@ HIP_SOURCES = {
     "band_survey.hip": ["-O3"],  # band survey: rank select, threshold and peak list of every scope row, integer passes over LDS
     "band_watch.hip": ["-O3"],  # band watch: carrier tracks per scope row advanced by the survey's list, the fleet's events packed in row order; integers only
     "band_follow.hip": ["-O3"],  # band follow: followers tuned onto the watch's confirmed tracks per scope row, their bins applied, the fleet's changes packed; integers only
+    "scan_control.hip": ["-O3"],  # scan control: every scan list's hop decision per batch, the switch list the exchange kernel reads, the fleet's records packed; integers only
     "airband_hip.cpp": ["-O2", "-x", "hip"],
 }
 HOST_SOURCES = {"params.cpp": ["-O2", "-ffp-contract=off", "-fno-fast-math"]}

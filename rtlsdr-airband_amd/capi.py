@@ -331,6 +331,81 @@ def band_follow_reference(followers, tracks, home_bins, batch, dev=0):
     return fol, row, out
 
 
+# scan control's (same header)
+class ScanEvent(C.Structure):
+    _fields_ = [("dev", C.c_int32), ("freq_idx", C.c_int16), ("prev_idx", C.c_int16), ("kind", C.c_uint8), ("flags", C.c_uint8), ("reserved", C.c_uint16),
+                ("batch", C.c_uint32)]
+
+
+class ScanState(C.Structure):
+    _fields_ = [("idx", C.c_int16), ("hold", C.c_int16), ("idle", C.c_int32), ("since", C.c_int32), ("last", C.c_int16), ("has_list", C.c_int16)]
+
+
+SCAN_CONTROL_PROTOTYPES = {
+    "airband_hip_set_scan_control": [_vp, _i32, _i32, _i64],
+    "airband_hip_scan_hold": [_vp, _i32, _i32],
+    "airband_hip_collect_scan_events": [_vp, C.POINTER(_i64), _vp],
+    "airband_hip_collect_scan_state": [_vp, _i32, _i32, _vp],
+    "airband_hip_device_scan_control": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
+}
+SCAN_HOP, SCAN_ACTIVITY = 1, 2
+SCAN_RETAG = 1
+NO_SIGNAL = 0x20  # channel->axcindicate of a batch without signal: ' '
+# numpy views of airband_hip_scan_event / airband_hip_scan_state
+SCAN_EVENT_DTYPE = [("dev", "<i4"), ("freq_idx", "<i2"), ("prev_idx", "<i2"), ("kind", "u1"), ("flags", "u1"), ("reserved", "<u2"), ("batch", "<u4")]
+SCAN_STATE_DTYPE = [("idx", "<i2"), ("hold", "<i2"), ("idle", "<i4"), ("since", "<i4"), ("last", "<i2"), ("has_list", "<i2")]
+
+
+def scan_control_blank(idx=0):
+    """The state a list starts from when control is switched on: entry `idx` in force, no hold, has_list = 1 (a scalar of SCAN_STATE_DTYPE)."""
+    import numpy as np
+
+    st = np.zeros((), SCAN_STATE_DTYPE)
+    st["idx"], st["hold"], st["has_list"] = idx, -1, 1
+    return st
+
+
+def scan_control_reference(state, axc, freq_count, batch, idle_batches=16, dwell_batches=2, dev=0, enabled=True):
+    """Scan control's definition (include/airband_hip.h) for one batch of one scan list, in plain Python: the list's `state` (SCAN_STATE_DTYPE) as the batch
+    before left it, `axc` the channel's axcindicate of this batch (a byte), `freq_count` the list's length, `batch` the control's batch number.  Returns
+    (state, records): new arrays, records of SCAN_EVENT_DTYPE, none or one, with `dev` in the first field.  The entry stage 2 of the NEXT batch runs with is
+    state["idx"].  A switched-off dongle (enabled=False) and a list of fewer than two entries are frozen: the state comes back as it went in, no record."""
+    import numpy as np
+
+    st = np.array(state, SCAN_STATE_DTYPE).reshape(()).copy()
+    none = np.zeros(0, SCAN_EVENT_DTYPE)
+    n, k = int(freq_count), int(batch) & 0xFFFFFFFF
+    if not enabled or n < 2:
+        return st, none
+    idx, hold, idle, since, last = int(st["idx"]), int(st["hold"]), int(st["idle"]), int(st["since"]), int(st["last"])
+    rec = None
+    if hold >= 0:
+        if idx != hold:
+            rec = (dev, hold, idx, SCAN_HOP, 0, 0, k)
+            idx = hold
+        idle = since = 0
+    elif int(axc) == NO_SIGNAL:
+        if idle < int(idle_batches):
+            idle += 1
+        else:
+            since += 1
+            if since >= int(dwell_batches):
+                rec = (dev, (idx + 1) % n, idx, SCAN_HOP, 0, 0, k)
+                idx = (idx + 1) % n
+                since = 0
+    else:
+        if idle == int(idle_batches):
+            rec = (dev, idx, last, SCAN_ACTIVITY, SCAN_RETAG if idx != last else 0, 0, k)
+            last = idx
+        idle = since = 0
+    st["idx"], st["idle"], st["since"], st["last"] = idx, idle, since, last
+    if rec is None:
+        return st, none
+    out = np.zeros(1, SCAN_EVENT_DTYPE)
+    out[0] = rec
+    return st, out
+
+
 # the encoded audio collect's (same header)
 AUDIO_F32, AUDIO_S16, AUDIO_ULAW, AUDIO_ALAW = 0, 1, 2, 3
 AUDIO_ENCODINGS = {"s16": AUDIO_S16, "ulaw": AUDIO_ULAW, "alaw": AUDIO_ALAW}

@@ -466,7 +466,7 @@ ScanExchangeArgs scan_args(airband_hip_handle* h) {
 /* front batch k is being enqueued: the scan entries in force now are its entries (airband_hip_set_freq_index latches per batch) */
 void scan_latch(airband_hip_handle* h, uint64_t k, int first_row, int n_rows) {
     if (h->plan.scan.empty()) return;
-    h->scan_latch[k & 1] = h->scan_cur;
+    if (h->scan_ctl.idle_batches == 0) h->scan_latch[k & 1] = h->scan_cur; /* (under scan control the entries are the GPU's: scan_before_demod) */
     h->scan_first_row[k & 1] = first_row;
     h->scan_n_rows[k & 1] = n_rows;
 }
@@ -482,6 +482,17 @@ void front_enqueued(airband_hip_handle* h, int first_row, int n_rows) {
  * holds (one launch for all of them), and |bin| of the lists that mix AM and NFM */
 int scan_before_demod(airband_hip_handle* h, hipStream_t s) {
     const int b = (int)(h->batches_done & 1);
+    if (h->scan_ctl.idle_batches > 0) {
+        /* scan control: the switch list is the one the decision kernel left behind the batch before (or airband_hip_set_scan_control at the start), on this
+         * stream's order -- nothing is built, copied or waited for here.  One workgroup per list; an item with slot -1 leaves at the kernel's first test. */
+        ScanExchangeArgs a = scan_args(h);
+        a.sw = h->scan_ctl.d_sw.p;
+        a.n_switch = (int)h->scan_ctl.list_of.size();
+        launch_scan_exchange(a, s);
+        if (h->d_scan_mix_slots.n > 0)
+            launch_scan_mag(h->d_scan_mix_slots.p, (int)h->d_scan_mix_slots.n, h->d_mag.p, h->d_iq.p, h->scan_first_row[b], h->scan_n_rows[b], h->row0, h->R, s);
+        return AIRBAND_HIP_OK;
+    }
     const std::vector<int>& want = h->scan_latch[b];
     const int q = h->switch_buf;
     int* list = h->h_switch[q].get();
@@ -617,6 +628,36 @@ void launch_follow_behind_demod(airband_hip_handle* h, int* moved_epoch, int epo
     launch_band_follow(a, s);
 }
 
+ScanControlArgs scan_control_args(airband_hip_handle* h) {
+    ScanControl& c = h->scan_ctl;
+    ScanControlArgs a;
+    a.dev = h->d_dev.p;
+    a.axc = h->d_out_axc.p;
+    a.lists = c.d_lists.p;
+    a.state = c.d_state.p;
+    a.stage = c.d_stage.p;
+    a.stage_n = c.d_stage_n.p;
+    a.sw = c.d_sw.p;
+    a.events = c.d_events.p;
+    a.n_events = c.d_count.p;
+    a.n_lists = (int)c.list_of.size();
+    a.n_dev = h->plan.n_dev;
+    a.n_ch = h->plan.total_ch;
+    a.idle_batches = c.idle_batches;
+    a.dwell_batches = c.dwell_batches;
+    a.max_records = c.max_records;
+    a.batch = c.batch;
+    return a;
+}
+
+/* The scan control of the batch whose back half goes on stream s (airband_hip_set_scan_control), behind everything that writes the batch's axcindicate.  The
+ * switch list it writes is read by the exchange in front of the NEXT batch's demod kernels, which goes on the same stream (or, where a caller changes streams
+ * between batches, behind ev_last like everything else of the next batch). */
+void launch_scan_control_behind_demod(airband_hip_handle* h, hipStream_t s) {
+    launch_scan_control(scan_control_args(h), s);
+    h->scan_ctl.batch++;
+}
+
 /* stage 2 + emit (+ mixers, + the output gate) of the batch whose stage-1 rows are already in the rings */
 int run_back_half(airband_hip_handle* h, hipStream_t s) {
     const Event* ev = event_set(h, h->batches_done, 1);
@@ -694,6 +735,7 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
     if (h->mix.n_mixers > 0) launch_mix(mix_args(h), s);
     if (h->gate.max_rows > 0) launch_gate(gate_args(h), s); /* the batch's active channels and their rows, packed (gate.hip) */
     if (h->gate.max_rows > 0 && h->gate.enc.encoding != AIRBAND_AUDIO_F32) launch_audio_pack(audio_pack_args(h), 0, s); /* ... and encoded (audio_pack.hip) */
+    if (h->scan_ctl.idle_batches > 0) launch_scan_control_behind_demod(h, s); /* the lists' hops for the next batch, from this batch's axcindicate (AFC's verdict included) */
     (void)hipEventRecord(ev[4], s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
@@ -1344,6 +1386,12 @@ int airband_hip_device_enable(airband_hip_handle* h, int32_t dev, int32_t enable
         const int slot = h->ext_to_slot[c];
         ChanConst& cc = h->cc_slots[slot];
         cc.flags = on ? (cc.flags | AB_F_VALID) : (cc.flags & ~AB_F_VALID);
+        if (h->scan_ctl.idle_batches > 0 && !h->scan_of_dev.empty() && h->scan_of_dev[dev] >= 0) {
+            /* a scan slot under scan control: the per-frequency bits of the live word are those of the entry the GPU put in force, which the host copy does not
+             * follow -- only VALID is set or cleared, on the device, in stream order */
+            launch_scan_set_valid(h->d_cc.p, slot, h->n_slots, on, s);
+            continue;
+        }
         HIP_TRY(h, hipMemcpyAsync(&h->d_cc.p[slot].flags, &cc.flags, sizeof(cc.flags), hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
     }
     /* channel->axcindicate of a device that is not demodulated any more: NO_SIGNAL */
@@ -1373,7 +1421,204 @@ int airband_hip_set_freq_index(airband_hip_handle* h, int32_t dev, int32_t freq_
     if (dev < 0 || dev >= h->plan.n_dev || h->scan_of_dev.empty() || h->scan_of_dev[dev] < 0) return fail(h, AIRBAND_HIP_EINVAL, "device has no scan list");
     const int i = h->scan_of_dev[dev];
     if (freq_idx < 0 || freq_idx >= h->plan.scan[i].n) return fail(h, AIRBAND_HIP_EINVAL, "frequency index out of range");
+    if (h->scan_ctl.idle_batches > 0) return fail(h, AIRBAND_HIP_EINVAL, "the lists are under scan control (airband_hip_set_scan_control): the GPU sets the index");
     h->scan_cur[i] = freq_idx; /* latched by the next batch that is enqueued */
+    return AIRBAND_HIP_OK;
+}
+
+/* Scan control: where list i (index in plan.scan) stands once everything enqueued on the handle has run -- *idx the entry in force for the next batch, *held the
+ * entry its slot holds now (they differ between a hop's decision and the exchange in front of the next batch).  Two small copies and a synchronize. */
+static int scan_ctl_where(airband_hip_handle* h, int i, int* idx, int* held) {
+    const ScanControl& c = h->scan_ctl;
+    const int k = c.ctl_of[(size_t)i];
+    const ScanList& sl = h->plan.scan[(size_t)i];
+    hipStream_t s = h->stream;
+    airband_hip_scan_state st;
+    int sw[3];
+    HIP_TRY(h, hipMemcpyAsync(&st, c.d_state.p + k, sizeof(st), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipMemcpyAsync(sw, c.d_sw.p + 3 * (size_t)k, sizeof(sw), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (st.idx < 0 || st.idx >= sl.n) return fail(h, AIRBAND_HIP_ERUNTIME, "scan control: index out of range: " + std::to_string(st.idx));
+    *idx = st.idx;
+    *held = st.idx;
+    if (sw[0] >= 0) {
+        const int old = sw[1] - sl.first_entry;
+        if (old < 0 || old >= sl.n) return fail(h, AIRBAND_HIP_ERUNTIME, "scan control: switch item out of range: " + std::to_string(sw[1]));
+        *held = old;
+    }
+    return AIRBAND_HIP_OK;
+}
+
+/* Switching scan control off: the host's mirrors take over where the GPU left every list.  The stream is idle (the caller has synchronized). */
+static int scan_ctl_refresh_host(airband_hip_handle* h) {
+    const ScanControl& c = h->scan_ctl;
+    const size_t nl = c.list_of.size();
+    std::vector<airband_hip_scan_state> st(nl);
+    std::vector<int> sw(nl * 3);
+    HIP_TRY(h, hipMemcpy(st.data(), c.d_state.p, nl * sizeof(st[0]), hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipMemcpy(sw.data(), c.d_sw.p, nl * 3 * sizeof(int), hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
+    for (size_t k = 0; k < nl; k++) {
+        const int i = c.list_of[k];
+        const ScanList& sl = h->plan.scan[(size_t)i];
+        int idx = st[k].idx, held = sw[3 * k] >= 0 ? sw[3 * k + 1] - sl.first_entry : idx;
+        if (idx < 0 || idx >= sl.n || held < 0 || held >= sl.n) return fail(h, AIRBAND_HIP_ERUNTIME, "scan control: a list's index is out of range");
+        h->scan_cur[(size_t)i] = h->scan_latch[0][(size_t)i] = h->scan_latch[1][(size_t)i] = idx;
+        h->scan_held[(size_t)i] = held;
+        ChanConst& hc = h->cc_slots[(size_t)h->ext_to_slot[(size_t)sl.ext]];
+        hc.flags = (hc.flags & ~AB_SCAN_FREQ_FLAGS) | (h->plan.scan_cc[(size_t)(sl.first_entry + held)].flags & AB_SCAN_FREQ_FLAGS);
+    }
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_set_scan_control(airband_hip_handle* h, int32_t idle_batches, int32_t dwell_batches, int64_t max_records) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const Plan& p = h->plan;
+    if (p.scan.empty()) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no scan lists (airband_hip_prepare_scan)");
+    if (idle_batches < 0 || dwell_batches < 0) return fail(h, AIRBAND_HIP_EINVAL, "idle_batches and dwell_batches must not be negative");
+    for (const ScanList& sl : p.scan) /* idx, hold and last of airband_hip_scan_state and the records' indices are int16 */
+        if (idle_batches > 0 && sl.n > 32767) return fail(h, AIRBAND_HIP_EINVAL, "scan control takes lists of at most 32 767 entries (device " + std::to_string(sl.dev) + " has " + std::to_string(sl.n) + ")");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    order_behind_last_batch(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME); /* the decisions and exchanges enqueued so far have run */
+    if (h->scan_ctl.idle_batches > 0) { /* on -> off, and on -> on through off: the lists keep their entries */
+        const int rc = scan_ctl_refresh_host(h);
+        if (rc != AIRBAND_HIP_OK) return rc;
+        if (idle_batches == 0) {
+            h->scan_ctl = ScanControl();
+            return AIRBAND_HIP_OK;
+        }
+    } else if (idle_batches == 0) {
+        return AIRBAND_HIP_OK;
+    }
+    const size_t nl = p.scan.size();
+    ScanControl c; /* built beside the handle and moved in whole: a failed allocation leaves the handle as it was (an earlier control is off then, its lists the host's) */
+    c.list_of.resize(nl);
+    for (size_t i = 0; i < nl; i++) c.list_of[i] = (int)i;
+    std::sort(c.list_of.begin(), c.list_of.end(), [&](int x, int y) { return p.scan[(size_t)x].dev < p.scan[(size_t)y].dev; });
+    c.ctl_of.resize(nl);
+    std::vector<ScanCtlList> lists(nl);
+    std::vector<airband_hip_scan_state> start(nl);
+    std::vector<int> sw(nl * 3, 0);
+    /* a pipelined handle may have a batch whose stage 1 is enqueued and whose stage 2 is not: that batch runs with the entry it was enqueued with (scan_latch), and
+     * the lists start from there -- an index airband_hip_set_freq_index() named after that batch was enqueued has not been latched by any batch and is dropped */
+    const bool pending = h->front_batches > h->batches_done;
+    for (size_t k = 0; k < nl; k++) {
+        const int i = c.list_of[k];
+        const ScanList& sl = p.scan[(size_t)i];
+        c.ctl_of[(size_t)i] = (int)k;
+        ScanCtlList& l = lists[k];
+        std::memset(&l, 0, sizeof(l));
+        l.dev = sl.dev;
+        l.ext = sl.ext;
+        l.slot = h->ext_to_slot[(size_t)sl.ext];
+        l.first_entry = sl.first_entry;
+        l.n = sl.n;
+        airband_hip_scan_state& st = start[k];
+        std::memset(&st, 0, sizeof(st));
+        const int from = pending ? h->scan_latch[h->batches_done & 1][(size_t)i] : h->scan_cur[(size_t)i];
+        st.idx = (int16_t)from;
+        st.hold = -1;
+        st.has_list = 1;
+        /* that entry may not be in the slot yet: the first exchange brings it in */
+        const bool move = h->scan_held[(size_t)i] != from;
+        sw[3 * k] = move ? l.slot : -1;
+        sw[3 * k + 1] = sl.first_entry + h->scan_held[(size_t)i];
+        sw[3 * k + 2] = sl.first_entry + from;
+    }
+    const int64_t cap = (max_records <= 0 || max_records > (int64_t)nl) ? (int64_t)nl : max_records;
+    hipError_t e = upload(c.d_lists, lists);
+    if (e == hipSuccess) e = upload(c.d_state, start);
+    if (e == hipSuccess) e = upload(c.d_sw, sw);
+    if (e == hipSuccess) e = c.d_stage.alloc_zeroed(nl);
+    if (e == hipSuccess) e = c.d_stage_n.alloc_zeroed(nl);
+    if (e == hipSuccess) e = c.d_events.alloc_zeroed((size_t)cap);
+    if (e == hipSuccess) e = c.d_count.alloc_zeroed(1);
+    if (e == hipSuccess) e = hipDeviceSynchronize(); /* the initial values are in place before a kernel on the handle's streams reads them */
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        h->scan_ctl = ScanControl();
+        return fail(h, AIRBAND_HIP_ENOMEM, std::string("scan control buffers: ") + hipGetErrorString(e));
+    }
+    c.idle_batches = idle_batches;
+    c.dwell_batches = dwell_batches < 1 ? 1 : dwell_batches;
+    c.max_records = (int)cap;
+    h->scan_ctl = std::move(c);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_scan_hold(airband_hip_handle* h, int32_t dev, int32_t freq_idx) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    ScanControl& c = h->scan_ctl;
+    if (c.idle_batches <= 0) return fail(h, AIRBAND_HIP_EINVAL, "scan control is off (airband_hip_set_scan_control)");
+    if (dev < 0 || dev >= h->plan.n_dev || h->scan_of_dev.empty() || h->scan_of_dev[dev] < 0) return fail(h, AIRBAND_HIP_EINVAL, "device has no scan list");
+    const int i = h->scan_of_dev[dev];
+    if (freq_idx < -1 || freq_idx >= h->plan.scan[(size_t)i].n) return fail(h, AIRBAND_HIP_EINVAL, "frequency index out of range");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    /* in the stream's order: behind the decisions already enqueued, in front of the next batch's */
+    const int16_t hold = (int16_t)freq_idx;
+    HIP_TRY(h, hipMemcpyAsync(&c.d_state.p[c.ctl_of[(size_t)i]].hold, &hold, sizeof(hold), hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME); /* `hold` is a stack variable */
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_scan_events(airband_hip_handle* h, int64_t* n_records, airband_hip_scan_event* records) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const ScanControl& c = h->scan_ctl;
+    if (c.idle_batches <= 0) return fail(h, AIRBAND_HIP_EINVAL, "scan control is off (airband_hip_set_scan_control)");
+    if (c.batch == 0) return AIRBAND_HIP_EAGAIN;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    int count = 0;
+    HIP_TRY(h, hipMemcpyAsync(&count, c.d_count.p, sizeof(int), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (count < 0 || (size_t)count > c.list_of.size()) return fail(h, AIRBAND_HIP_ERUNTIME, "record count out of range: " + std::to_string(count));
+    if (n_records) *n_records = count;
+    const size_t n = (size_t)(count < c.max_records ? count : c.max_records);
+    if (records && n) {
+        HIP_TRY(h, hipMemcpyAsync(records, c.d_events.p, n * sizeof(airband_hip_scan_event), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+        HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    }
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_scan_state(airband_hip_handle* h, int32_t first_dev, int32_t n_dev, airband_hip_scan_state* state) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const ScanControl& c = h->scan_ctl;
+    if (c.idle_batches <= 0) return fail(h, AIRBAND_HIP_EINVAL, "scan control is off (airband_hip_set_scan_control)");
+    if (first_dev < 0 || n_dev < 0 || (int64_t)first_dev + n_dev > h->plan.n_dev) return fail(h, AIRBAND_HIP_EINVAL, "device range out of bounds");
+    if (!state || n_dev == 0) return AIRBAND_HIP_OK;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    /* the lists are in ascending dongle order: those of the range are one run of the array -- one copy, then dealt out to the range's dongles */
+    int k0 = -1, n = 0;
+    for (int d = first_dev; d < first_dev + n_dev; d++)
+        if (h->scan_of_dev[(size_t)d] >= 0) {
+            if (k0 < 0) k0 = c.ctl_of[(size_t)h->scan_of_dev[(size_t)d]];
+            n++;
+        }
+    std::vector<airband_hip_scan_state> tmp((size_t)n);
+    if (n) HIP_TRY(h, hipMemcpyAsync(tmp.data(), c.d_state.p + k0, (size_t)n * sizeof(tmp[0]), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    for (int d = first_dev; d < first_dev + n_dev; d++) {
+        airband_hip_scan_state& o = state[d - first_dev];
+        const int i = h->scan_of_dev[(size_t)d];
+        if (i < 0) std::memset(&o, 0, sizeof(o));
+        else o = tmp[(size_t)(c.ctl_of[(size_t)i] - k0)];
+    }
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_device_scan_control(airband_hip_handle* h, int32_t** d_n_records, airband_hip_scan_event** d_records, airband_hip_scan_state** d_state) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const ScanControl& c = h->scan_ctl;
+    if (c.idle_batches <= 0) return fail(h, AIRBAND_HIP_EINVAL, "scan control is off (airband_hip_set_scan_control)");
+    if (d_n_records) *d_n_records = c.d_count.p;
+    if (d_records) *d_records = c.d_events.p;
+    if (d_state) *d_state = c.d_state.p;
     return AIRBAND_HIP_OK;
 }
 
@@ -1394,8 +1639,14 @@ int airband_hip_freq_stats(airband_hip_handle* h, int32_t dev, int32_t freq_idx,
         HIP_TRY(h, hipMemsetAsync(h->d_fs_zero.p, 0, sizeof(int), s), AIRBAND_HIP_ERUNTIME);
     }
     const int slot = h->ext_to_slot[sl.ext];
+    int held = h->scan_held[i];
+    if (h->scan_ctl.idle_batches > 0) { /* scan control: which entry the slot holds is on the device */
+        int idx = 0;
+        const int rc = scan_ctl_where(h, i, &idx, &held);
+        if (rc != AIRBAND_HIP_OK) return rc;
+    }
     /* the stats kernel of airband_hip_collect() on one image: the slot itself for the entry it holds, else the slot composed with the entry's bank */
-    if (freq_idx == h->scan_held[i]) {
+    if (freq_idx == held) {
         launch_stats(h->d_cc.p + slot, h->d_cs.p + slot, h->d_fs_zero.p, 1, h->d_fs_stats.p, s);
     } else {
         launch_scan_compose(scan_args(h), slot, sl.first_entry + freq_idx, h->d_fs_cc.p, h->d_fs_cs.p, s);

@@ -17,6 +17,7 @@
 
 #include "../../include/airband_hip.h"
 #include "common.h"
+#include "kernels.h" /* ScanCtlList */
 #include "params.h"
 
 namespace airband {
@@ -156,6 +157,21 @@ struct BandSurvey {
     DevBuf<int> d_bin_first, d_bins; /* by scope row: the prepare-time bins of the dongle's channels */
     DevBuf<airband_hip_band_summary> d_summary[2];
     DevBuf<airband_hip_band_peak> d_peaks[2];
+};
+
+/* what airband_hip_set_scan_control() set up: replaced as a whole, one without idle_batches is a handle whose lists the host hops (nothing allocated, nothing
+ * launched).  While it is there the host's scan_cur / scan_held / scan_latch and the per-frequency bits of cc_slots[slot].flags of the scan slots are NOT
+ * kept: the entry a slot holds is on the device (d_state, d_sw), and switching control off refreshes them. */
+struct ScanControl {
+    int idle_batches = 0;      /* 0 = no scan control */
+    int dwell_batches = 1, max_records = 0;
+    uint32_t batch = 0;        /* the control's batch number of the next launch */
+    std::vector<int> list_of;  /* by control index (ascending dongle order): the list in plan.scan */
+    std::vector<int> ctl_of;   /* by list in plan.scan: its control index */
+    DevBuf<ScanCtlList> d_lists;
+    DevBuf<airband_hip_scan_state> d_state;
+    DevBuf<airband_hip_scan_event> d_stage, d_events;
+    DevBuf<int> d_stage_n, d_sw, d_count;
 };
 
 struct BandScope {
@@ -311,6 +327,7 @@ struct airband_hip_handle {
     bool switch_used[2] = {false, false};
     int switch_buf = 0;
     airband::DevBuf<int> d_scan_mix_slots; /* slots of lists that mix AM and NFM entries (scan_mag_kernel) */
+    airband::ScanControl scan_ctl;         /* airband_hip_set_scan_control: the GPU hops the lists */
     airband::DevBuf<ChanConst> d_fs_cc; /* airband_hip_freq_stats: one composed image, its stats row */
     airband::DevBuf<ChanState> d_fs_cs;
     airband::DevBuf<airband_hip_channel_stats> d_fs_stats;

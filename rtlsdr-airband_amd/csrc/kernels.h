@@ -412,5 +412,33 @@ struct FollowArgs {
 };
 void launch_band_follow(const FollowArgs& a, hipStream_t stream);
 
+/* scan control (scan_control.hip): every scan list's hop decision of the batch, one thread per list, and the lists' records packed into one fleet-wide list in
+ * dongle order.  Launched on the batch's stage-2 stream behind everything that writes the batch's axcindicate; the switch list it leaves is what the exchange
+ * kernel in front of the next batch's demod kernels reads (ScanExchangeArgs::sw). */
+struct ScanCtlList {
+    int32_t dev, ext, slot;  /* the list's dongle, its channel (device-major) and that channel's demod slot */
+    int32_t first_entry, n;  /* its entries in the banks: [first_entry, first_entry + n) */
+    int32_t pad[3];
+}; /* 32 bytes */
+struct ScanControlArgs {
+    const DevConst* dev;
+    const uint8_t* axc;              /* [n_ch] the batch's axcindicate */
+    const ScanCtlList* lists;        /* [n_lists] ascending dongle order */
+    airband_hip_scan_state* state;   /* [n_lists] advanced in place */
+    airband_hip_scan_event* stage;   /* [n_lists] a list's record of this batch, stage_n[list] of them (0 or 1) */
+    int* stage_n;                    /* [n_lists] */
+    int* sw;                         /* [n_lists][3] (slot or -1, entry parked, entry brought in) */
+    airband_hip_scan_event* events;  /* [max_records] */
+    int* n_events;                   /* [1] */
+    int n_lists, n_dev, n_ch;
+    int idle_batches, dwell_batches; /* >= 1 */
+    int max_records;
+    uint32_t batch;                  /* the control's batch number k */
+};
+void launch_scan_control(const ScanControlArgs& a, hipStream_t stream);
+/* AB_F_VALID of one slot's live ChanConst::flags set or cleared in stream order, the other bits left as the exchange put them (airband_hip_device_enable on a
+ * handle whose host copy of a scan slot's flags does not follow the GPU's hops) */
+void launch_scan_set_valid(ChanConst* cc, int slot, int n_slots, int on, hipStream_t stream);
+
 }  // namespace airband
 #endif
