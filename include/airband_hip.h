@@ -570,6 +570,104 @@ int airband_hip_device_active_encoded(airband_hip_handle* h, void** d_audio, air
  * AIRBAND_HIP_EINVAL for NULL rows, n_rows < 0 (or too many to index), encoding AIRBAND_AUDIO_F32 or unknown; n_rows == 0 is AIRBAND_HIP_OK. */
 int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const float* rows, int64_t n_rows, void* audio, airband_hip_audio_row* info);
 
+/* ---- transmission spool ---------------------------------------------------------------------------------------------------------------
+ * The reference's file sinks in `split_on_transmission` mode (src/output.cpp:340-368, :396-453, :498-532; src/config.cpp:117-160) produce one clip per
+ * transmission: the file is opened by the first batch the file rule writes, every written batch is appended, and the file is closed once it is older than 1 s and
+ * has not been written for 0.5 s, or once it is older than an hour.  A host that wants those clips from airband_hip_collect_active_encoded() collects every
+ * batch, keeps an open / last-write clock per channel, appends rows to per-channel buffers and cuts them.  A gated handle with an encoding and a SPOOL keeps the
+ * encoded rows of every open transmission in a row pool on the GPU, applies the closing rule once per batch in batch counts (a batch is 125 ms) and hands over
+ * only FINISHED transmissions -- one 48-byte record each and their audio concatenated in one contiguous copy -- whenever the host comes for them.
+ * Raw-I/Q clips, mixer outputs, silence for batches that were not selected, wall-clock time stamps (the host maps batch numbers to time), per-channel parameters
+ * and MP3 are out of scope.
+ * The definition (normative; integers only, so two implementations of this text agree in every byte).
+ * Parameters: spool[total_channels], a byte mask (NULL: every channel whose gate is AIRBAND_GATE_SIGNAL); a spooled channel must have gate SIGNAL (the reference
+ * forbids `continuous` together with `split_on_transmission`).  pool_rows, export_rows, max_records; min_batches (8: the reference's 1.0 s), idle_batches (4:
+ * 0.5 s), max_batches (the reference's hour is 28 800; a caller sizes it to the pool).  A pool row holds one encoded row: wave_batch bytes (G.711), twice that
+ * (S16).
+ * The spool STEP runs once per batch behind the encoder, in the order the batches' results appear (pipelined handles, process_device, process_bins, scan lists,
+ * followers and regrouped stage 2 alike).  k is the number of steps run before this one (uint32, 0 for the first; differences are taken modulo 2^32).  A step
+ * has two phases, fleet-wide; phase A runs entirely before phase B, each in ascending channel order.
+ * Phase A (close).  A spooled channel with an open transmission finishes it if
+ *     idle:  k - open_batch > min_batches  and  k - last_batch > idle_batches,   or
+ *     long:  k - open_batch > max_batches;
+ *   reason = AIRBAND_SPOOL_IDLE if `idle` holds, otherwise AIRBAND_SPOOL_MAX; close_batch = k.  A finished transmission is appended to the FINISHED LIST, which
+ *   is therefore in (step, channel) order.  If the list already holds max_records uncollected transmissions it is DROPPED instead: its rows go back to the pool
+ *   and only the counters remember it.
+ * Phase B (append).  For every spooled channel the gate's rule selected in this batch -- channels whose row did not fit the gate's max_rows included:
+ *   1. without an open transmission, one opens: open_batch = k, everything else zero, first = wave_batch, end = 0;
+ *   2. the row is STORABLE if it is among the gate's first max_rows;
+ *   3. F = the pool rows that, after phase A of this step, are held neither by an open transmission nor by a finished, uncollected one.  The j-th storable row
+ *      of the step (ascending channel order, 0-based) is STORED iff j < F;
+ *   4. a stored row is appended to the clip and updates the transmission from its airband_hip_audio_row: peak = the maximum; n_clipped summed, saturating at
+ *      2^32 - 1; first = the first stored row's `first`; end = the last stored row's `end`; n_rows + 1;
+ *   5. a selected row that is not stored: n_lost + 1;
+ *   6. either way last_batch = k.
+ *   A transmission stores at most max_batches + 1 rows.  Batches in which the channel was not selected contribute nothing, as the reference's file holds nothing
+ *   for them.  A switched-off dongle's channels are not selected: their transmissions end by the idle rule.
+ * Flush.  Every open transmission finishes with reason AIRBAND_SPOOL_FLUSH and close_batch = the number of steps run so far; the finished list and the drop rule
+ *   as in phase A.  Not a batch: no phase B, k does not advance.
+ * Collect.  The longest prefix of the finished list whose n_rows sum to at most export_rows (export_rows >= max_batches + 1 is validated: a call always makes
+ *   progress): the records with row_offset = the sum of n_rows in front, their stored rows concatenated in that order, and how many transmissions still wait.
+ *   Their pool rows are free for every step enqueued after the call.
+ * Which pool row holds which audio is internal and never observable; who loses when the pool runs dry is, which is why rows are handed out by rank in channel
+ * order and not through an atomic cursor.
+ * A handle without a spool allocates nothing for this, launches nothing and returns the same bits. */
+#define AIRBAND_SPOOL_IDLE 1
+#define AIRBAND_SPOOL_MAX 2
+#define AIRBAND_SPOOL_FLUSH 3
+
+typedef struct airband_hip_transmission {
+    int32_t  channel;      /* device-major channel index */
+    uint32_t open_batch;   /* step that opened it */
+    uint32_t last_batch;   /* last step the channel was selected in */
+    uint32_t close_batch;  /* step that finished it (flush: the steps run so far) */
+    uint32_t n_rows;       /* rows stored: its share of the audio */
+    uint32_t n_lost;       /* selected rows that were not stored (pool dry, or past the gate's max_rows) */
+    uint32_t n_clipped;    /* clipped samples of the stored rows, saturating */
+    uint16_t peak;         /* max |q| over the stored rows */
+    uint16_t first;        /* `first` of the first stored row; wave_batch if no row was stored */
+    uint16_t end;          /* `end` of the last stored row; 0 if no row was stored */
+    uint16_t reason;       /* AIRBAND_SPOOL_* */
+    uint32_t row_offset;   /* first of its rows in the collect's audio */
+    uint32_t reserved[2];  /* 0 */
+} airband_hip_transmission; /* 48 bytes */
+
+typedef struct airband_hip_spool_counters {
+    uint64_t steps;                 /* steps enqueued so far */
+    uint64_t open_now;              /* open transmissions */
+    uint64_t waiting_now;           /* finished, uncollected */
+    uint64_t free_rows_now;         /* pool rows held by neither */
+    uint64_t finished_total;        /* transmissions that entered the finished list */
+    uint64_t dropped_transmissions; /* ... that met a full list instead */
+    uint64_t rows_stored_total;
+    uint64_t rows_lost_total;
+} airband_hip_spool_counters; /* 64 bytes */
+
+/* After airband_hip_set_output_encoding() (S16, ULAW or ALAW) and before the first batch; calling it again before then replaces the spool, pool_rows == 0
+ * removes it, and a gate or an encoding set again drops it with what it belonged to.  Validated before the device is touched: AIRBAND_HIP_EINVAL for a NULL
+ * handle, a handle without a gate or without an encoding, a spooled channel whose gate is not AIRBAND_GATE_SIGNAL, negative counts, max_batches < 1,
+ * export_rows < max_batches + 1, max_records < 1, a batch already enqueued.  AIRBAND_HIP_ENOMEM when the buffers cannot be had -- the handle then runs on as
+ * it was, gate and encoding included. */
+int airband_hip_set_transmission_spool(airband_hip_handle* h, const uint8_t* spool, int64_t pool_rows, int64_t export_rows, int64_t max_records, int32_t min_batches, int32_t idle_batches, int32_t max_batches);
+
+/* The collect of the definition, behind everything enqueued so far.  Synchronous; it has nothing to do with "the batch that is ready" (nothing is marked as
+ * collected) and never returns AIRBAND_HIP_EAGAIN; an empty list gives *n = 0.  records [*n] (room for max_records), audio [*n_rows][row bytes] (room for
+ * export_rows rows), *n_waiting transmissions stay behind.  The prefix is chosen and its rows are gathered into one export buffer on the GPU; the host copies
+ * three counts, then *n records and *n_rows rows, contiguous.  Any out-pointer may be NULL (the transmissions are taken off the list all the same).
+ * AIRBAND_HIP_EINVAL on a handle without a spool. */
+int airband_hip_collect_transmissions(airband_hip_handle* h, int64_t* n, airband_hip_transmission* records, void* audio, int64_t* n_rows, int64_t* n_waiting);
+
+/* The flush of the definition, in stream order behind the batches enqueued so far (on a pipelined handle airband_hip_flush() first brings the last batch's
+ * results and step).  AIRBAND_HIP_EINVAL on a handle without a spool. */
+int airband_hip_spool_flush(airband_hip_handle* h);
+
+/* The counters as they stand behind everything enqueued so far (synchronous).  AIRBAND_HIP_EINVAL on a handle without a spool or for NULL `out`. */
+int airband_hip_spool_counters_get(airband_hip_handle* h, airband_hip_spool_counters* out);
+
+/* Device-side views of the last airband_hip_collect_transmissions() (valid until the next one): d_export_audio [export_rows][row bytes], d_export_records
+ * [max_records], d_n_export [3]: transmissions exported, their rows, transmissions still waiting.  Any out-pointer may be NULL. */
+int airband_hip_device_transmission_spool(airband_hip_handle* h, void** d_export_audio, airband_hip_transmission** d_export_records, int32_t** d_n_export);
+
 /* ---- band scope -------------------------------------------------------------------------------------------------------------------
  * The channelizer keeps the few bins of every transform that carry a configured channel.  A handle with a band scope also keeps, per selected dongle and batch,
  * the POWER SPECTRUM OF THE WHOLE BAND over a handful of the batch's FFT windows: what the band looks like, where to put channels, an overloaded or deaf

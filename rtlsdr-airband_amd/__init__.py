@@ -36,6 +36,7 @@ EXPORTS = [
     "airband_hip_set_scan_control", "airband_hip_scan_hold", "airband_hip_collect_scan_events", "airband_hip_collect_scan_state", "airband_hip_device_scan_control",
     "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
     "airband_hip_set_output_encoding", "airband_hip_collect_active_encoded", "airband_hip_device_active_encoded", "airband_hip_encode_audio",
+    "airband_hip_set_transmission_spool", "airband_hip_collect_transmissions", "airband_hip_spool_flush", "airband_hip_spool_counters_get", "airband_hip_device_transmission_spool",
     "airband_hip_set_band_scope", "airband_hip_collect_band_scope", "airband_hip_device_band_scope",
     "airband_hip_set_band_survey", "airband_hip_collect_band_survey", "airband_hip_device_band_survey",
     "airband_hip_set_band_watch", "airband_hip_collect_band_events", "airband_hip_collect_band_tracks", "airband_hip_device_band_watch",
@@ -111,7 +112,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
-    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()):
+    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()):
         if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
             getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
@@ -423,6 +424,46 @@ class AirbandHip:
         info = np.empty((n,), capi.AUDIO_ROW_DTYPE)
         self._check(self.L.airband_hip_encode_audio(self.h, enc, rows.ctypes.data, n, audio.ctypes.data, info.ctypes.data))
         return audio, info
+
+    def set_transmission_spool(self, pool_rows, export_rows=None, max_records=None, mask=None, min_batches=8, idle_batches=4, max_batches=480):
+        """Transmission spool (airband_hip_set_transmission_spool): the GPU keeps the encoded rows of every open transmission and hands over finished ones.
+        export_rows: default max(pool_rows, max_batches + 1); max_records: default the channel count; mask: one byte per channel (None = every SIGNAL channel).
+        After set_output_encoding(), before the first batch; pool_rows 0 removes it."""
+        pool_rows = int(pool_rows)
+        export_rows = max(pool_rows, max_batches + 1) if export_rows is None else int(export_rows)
+        max_records = self.total_channels if max_records is None else int(max_records)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if m is not None and m.shape != (self.total_channels,):
+            raise ValueError("mask must have one byte per channel")
+        self._check(self.L.airband_hip_set_transmission_spool(self.h, None if m is None else m.ctypes.data, pool_rows, export_rows, max_records, min_batches, idle_batches, max_batches))
+        self.spool_export_rows, self.spool_max_records = (export_rows, max_records) if pool_rows else (0, 0)
+
+    def collect_transmissions(self) -> dict:
+        """The finished transmissions that fit the export buffer (airband_hip_collect_transmissions): records [n] of capi.TRANSMISSION_DTYPE, audio
+        [sum of n_rows][B] int16 ("s16") or uint8 (G.711) -- transmission i's rows are audio[row_offset : row_offset + n_rows] -- and n_waiting."""
+        enc = getattr(self, "audio_encoding", capi.AUDIO_F32)
+        records = np.empty((max(getattr(self, "spool_max_records", 0), 1),), capi.TRANSMISSION_DTYPE)
+        audio = np.empty((max(getattr(self, "spool_export_rows", 0), 1), self.B), self._audio_dtype(enc))
+        n, n_rows, n_waiting = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(self.L.airband_hip_collect_transmissions(self.h, C.byref(n), records.ctypes.data, audio.ctypes.data, C.byref(n_rows), C.byref(n_waiting)))
+        return dict(records=records[:n.value], audio=audio[:n_rows.value], n_waiting=int(n_waiting.value))
+
+    def spool_flush(self):
+        """Every open transmission finishes with reason capi.SPOOL_FLUSH (airband_hip_spool_flush)."""
+        self._check(self.L.airband_hip_spool_flush(self.h))
+
+    def spool_counters(self) -> dict:
+        """airband_hip_spool_counters_get as a dict (capi.SPOOL_COUNTER_NAMES)."""
+        out = capi.SpoolCounters()
+        self._check(self.L.airband_hip_spool_counters_get(self.h, C.byref(out)))
+        return {k: int(getattr(out, k)) for k in capi.SPOOL_COUNTER_NAMES}
+
+    def device_transmission_spool(self) -> dict:
+        """Device pointers of the last collect_transmissions() (valid until the next one): audio [export_rows][row bytes], records [max_records] of 48 bytes,
+        n_export [3] int32 (transmissions, rows, still waiting)."""
+        ptrs = [C.c_void_p() for _ in range(3)]
+        self._check(self.L.airband_hip_device_transmission_spool(self.h, *[C.byref(p) for p in ptrs]))
+        return {k: (p.value or 0) for k, p in zip(["audio", "records", "n_export"], ptrs)}
 
     def set_band_scope(self, mask=None, windows: int = 8, mean: bool = True, peak: bool = False):
         """Band scope (airband_hip_set_band_scope): per batch and selected dongle, the power spectrum of the whole band over `windows` of the batch's FFT windows.

@@ -41,6 +41,7 @@ HIP_SOURCES = {
     "demod.hip": ["-O3", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "gate.hip": ["-O3"],  # signal-gated collect: integer passes and a row copy
     "audio_pack.hip": ["-O3", "-ffp-contract=off"],  # encoded audio collect: one float multiplication per sample, then integers (int16 / G.711) and a row record
+    "tx_spool.hip": ["-O3"],  # transmission spool: integer passes over per-channel records, a row pool and row copies
     "band_scope.hip": ["-O3"],  # band scope: a wavefront FFT of a few windows per batch and dongle, mean and peak power per bin
     "band_survey.hip": ["-O3"],  # band survey: rank select, threshold and peak list of every scope row, integer passes over LDS
     "band_watch.hip": ["-O3"],  # band watch: carrier tracks per scope row advanced by the survey's list, the fleet's events packed in row order; integers only

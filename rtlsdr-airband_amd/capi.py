@@ -510,6 +510,143 @@ def audio_decode_reference(codes, encoding):
     raise ValueError("unknown encoding: %r" % (encoding,))
 
 
+# the transmission spool's (same header)
+SPOOL_IDLE, SPOOL_MAX, SPOOL_FLUSH = 1, 2, 3
+
+
+class Transmission(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("open_batch", C.c_uint32), ("last_batch", C.c_uint32), ("close_batch", C.c_uint32), ("n_rows", C.c_uint32),
+                ("n_lost", C.c_uint32), ("n_clipped", C.c_uint32), ("peak", C.c_uint16), ("first", C.c_uint16), ("end", C.c_uint16), ("reason", C.c_uint16),
+                ("row_offset", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class SpoolCounters(C.Structure):
+    _fields_ = [(n, C.c_uint64) for n in ("steps", "open_now", "waiting_now", "free_rows_now", "finished_total", "dropped_transmissions", "rows_stored_total",
+                                          "rows_lost_total")]
+
+
+TRANSMISSION_SPOOL_PROTOTYPES = {
+    "airband_hip_set_transmission_spool": [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32],
+    "airband_hip_collect_transmissions": [_vp, C.POINTER(_i64), _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)],
+    "airband_hip_spool_flush": [_vp],
+    "airband_hip_spool_counters_get": [_vp, C.POINTER(SpoolCounters)],
+    "airband_hip_device_transmission_spool": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
+}
+# numpy view of airband_hip_transmission
+TRANSMISSION_DTYPE = [("channel", "<i4"), ("open_batch", "<u4"), ("last_batch", "<u4"), ("close_batch", "<u4"), ("n_rows", "<u4"), ("n_lost", "<u4"),
+                      ("n_clipped", "<u4"), ("peak", "<u2"), ("first", "<u2"), ("end", "<u2"), ("reason", "<u2"), ("row_offset", "<u4"), ("reserved", "<u4", (2,))]
+SPOOL_COUNTER_NAMES = tuple(f[0] for f in SpoolCounters._fields_)
+
+
+class transmission_spool_reference:
+    """The transmission spool's definition (include/airband_hip.h, "transmission spool") in plain Python: an object that is fed, per batch, what
+    collect_active_encoded() of the same gate and encoding returns, and that has flush(), collect() and counters() like the handle.
+
+    mask: truth value per channel (the spooled channels, resolved: the header's NULL is "every SIGNAL channel"); row_bytes: bytes of an encoded row;
+    wave_batch: samples of a row.  step(n_active, channels, audio, info, selected=None): the gate's count, its list (the first max_rows selected channels,
+    ascending), their encoded rows [n][...] and records [n] of AUDIO_ROW_DTYPE; `selected` is every channel the gate's rule selected, needed only when the count
+    exceeds the list (the rows past max_rows are selected but not storable)."""
+
+    def __init__(self, mask, wave_batch, pool_rows, export_rows, max_records, min_batches=8, idle_batches=4, max_batches=480):
+        if max_batches < 1 or export_rows < max_batches + 1 or max_records < 1 or pool_rows < 1 or min_batches < 0 or idle_batches < 0:
+            raise ValueError("parameters the handle would refuse")
+        self.mask = [bool(m) for m in mask]
+        self.wave_batch, self.pool_rows, self.export_rows, self.max_records = int(wave_batch), int(pool_rows), int(export_rows), int(max_records)
+        self.min_batches, self.idle_batches, self.max_batches = int(min_batches), int(idle_batches), int(max_batches)
+        self.steps = 0
+        self.open = {}       # channel -> its running record (a dict) with "rows": the stored rows' bytes
+        self.finished = []   # the finished list
+        self.finished_total = self.dropped = self.rows_stored = self.rows_lost = 0
+
+    def _held(self):
+        return sum(t["n_rows"] for t in self.open.values()) + sum(t["n_rows"] for t in self.finished)
+
+    def _finish(self, c, reason, close_batch):
+        t = self.open.pop(c)
+        t.update(reason=reason, close_batch=close_batch)
+        if len(self.finished) >= self.max_records:
+            self.dropped += 1  # its rows go back to the pool with it
+        else:
+            self.finished.append(t)
+            self.finished_total += 1
+
+    def step(self, n_active, channels, audio, info, selected=None):
+        k = self.steps & 0xFFFFFFFF
+        channels = [int(c) for c in channels]
+        if selected is None:
+            if int(n_active) != len(channels):
+                raise ValueError("the gate selected %d channels and listed %d: pass `selected`" % (n_active, len(channels)))
+            selected = channels
+        selected = [int(c) for c in selected]
+        if selected != sorted(selected) or selected[:len(channels)] != channels or len(selected) != int(n_active):
+            raise ValueError("`selected` is not the gate's ascending selection with the list as its prefix")
+        # phase A, entirely before phase B
+        for c in sorted(self.open):
+            t = self.open[c]
+            age, quiet = (k - t["open_batch"]) & 0xFFFFFFFF, (k - t["last_batch"]) & 0xFFFFFFFF
+            idle = age > self.min_batches and quiet > self.idle_batches
+            if idle or age > self.max_batches:
+                self._finish(c, SPOOL_IDLE if idle else SPOOL_MAX, k)
+        # phase B
+        free = self.pool_rows - self._held()
+        row_of = {c: r for r, c in enumerate(channels)}
+        j = 0
+        for c in selected:
+            if not self.mask[c]:
+                continue
+            t = self.open.get(c)
+            if t is None:
+                t = self.open[c] = dict(channel=c, open_batch=k, last_batch=0, n_rows=0, n_lost=0, n_clipped=0, peak=0, first=self.wave_batch, end=0, rows=[])
+            stored = False
+            if c in row_of:  # storable
+                stored = j < free
+                j += 1
+            if stored:
+                r = row_of[c]
+                rec = info[r]
+                if int(rec["channel"]) != c:
+                    raise ValueError("record %d is channel %d, the list says %d" % (r, int(rec["channel"]), c))
+                t["rows"].append(audio[r].tobytes())
+                t["peak"] = max(t["peak"], int(rec["peak"]))
+                t["n_clipped"] = min(t["n_clipped"] + int(rec["n_clipped"]), 0xFFFFFFFF)
+                if t["n_rows"] == 0:
+                    t["first"] = int(rec["first"])
+                t["end"] = int(rec["end"])
+                t["n_rows"] += 1
+                self.rows_stored += 1
+            else:
+                t["n_lost"] += 1
+                self.rows_lost += 1
+            t["last_batch"] = k
+        self.steps += 1
+
+    def flush(self):
+        for c in sorted(self.open):
+            self._finish(c, SPOOL_FLUSH, self.steps & 0xFFFFFFFF)
+
+    def collect(self):
+        """dict(records [n] of TRANSMISSION_DTYPE, audio: the rows' bytes concatenated, n_rows, n_waiting)"""
+        import numpy as np
+
+        n = total = 0
+        while n < len(self.finished) and total + self.finished[n]["n_rows"] <= self.export_rows:
+            total += self.finished[n]["n_rows"]
+            n += 1
+        take, self.finished = self.finished[:n], self.finished[n:]
+        records = np.zeros(n, TRANSMISSION_DTYPE)
+        at = 0
+        for i, t in enumerate(take):
+            for name in ("channel", "open_batch", "last_batch", "close_batch", "n_rows", "n_lost", "n_clipped", "peak", "first", "end", "reason"):
+                records[i][name] = t[name]
+            records[i]["row_offset"] = at
+            at += t["n_rows"]
+        return dict(records=records, audio=b"".join(b"".join(t["rows"]) for t in take), n_rows=total, n_waiting=len(self.finished))
+
+    def counters(self):
+        return dict(steps=self.steps, open_now=len(self.open), waiting_now=len(self.finished), free_rows_now=self.pool_rows - self._held(),
+                    finished_total=self.finished_total, dropped_transmissions=self.dropped, rows_stored_total=self.rows_stored, rows_lost_total=self.rows_lost)
+
+
 def scope_window_hops(windows: int, wave_batch: int):
     """The batch's new hops whose FFT windows a band scope of `windows` windows per batch looks at: (j * WAVE_BATCH) / K, j = 0 .. K-1."""
     return [(j * wave_batch) // windows for j in range(windows)]

@@ -593,6 +593,45 @@ AudioPackArgs audio_pack_args(const airband_hip_handle* h) {
     return a;
 }
 
+/* the spool's own buffers, the gate's verdicts and the encoder's rows (airband_hip_set_transmission_spool); k: the step's number */
+SpoolArgs spool_args(const airband_hip_handle* h, uint32_t k) {
+    const OutputGate& g = h->gate;
+    const TransmissionSpool& sp = g.enc.spool;
+    SpoolArgs a;
+    a.spool = sp.d_spool.p;
+    a.chan = sp.d_chan.p;
+    a.ctl = sp.d_ctl.p;
+    a.close_mask = sp.d_close_mask.p;
+    a.app_mask = sp.d_app_mask.p;
+    a.close_count = sp.d_close_count.p;
+    a.app_count = sp.d_app_count.p;
+    a.gate_mask = g.d_mask.p;
+    a.gate_count = g.d_block_count.p;
+    a.free_stack = sp.d_free_stack.p;
+    a.next = sp.d_next.p;
+    a.pool = sp.d_pool.p;
+    a.copy_list = sp.d_copy_list.p;
+    a.enc_audio = g.enc.d_audio.p;
+    a.enc_info = g.enc.d_info.p;
+    a.fin = sp.d_fin.p;
+    a.exp_records = sp.d_exp_records.p;
+    a.exp_head = sp.d_exp_head.p;
+    a.exp_src = sp.d_exp_src.p;
+    a.exp_audio = sp.d_exp_audio.p;
+    a.n_ch = h->plan.total_ch;
+    a.max_rows = g.max_rows;
+    a.pool_rows = sp.pool_rows;
+    a.export_rows = sp.export_rows;
+    a.max_records = sp.max_records;
+    a.row_bytes = sp.row_bytes;
+    a.wave_batch = h->B;
+    a.min_batches = sp.min_batches;
+    a.idle_batches = sp.idle_batches;
+    a.max_batches = sp.max_batches;
+    a.k = k;
+    return a;
+}
+
 /* The band follow of the batch whose back half goes on stream s (airband_hip_set_band_follow), behind its demod kernels.  It reads the track tables the batch's
  * watch left, and the watch ran on the scope's stream: s is behind that already (scope_join() made the stage-1 stream wait for the scope, and a handle with
  * followers runs both halves of a batch on one stream), said again here because this is the point that depends on it.  The watch batch number of this batch is
@@ -735,6 +774,12 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
     if (h->mix.n_mixers > 0) launch_mix(mix_args(h), s);
     if (h->gate.max_rows > 0) launch_gate(gate_args(h), s); /* the batch's active channels and their rows, packed (gate.hip) */
     if (h->gate.max_rows > 0 && h->gate.enc.encoding != AIRBAND_AUDIO_F32) launch_audio_pack(audio_pack_args(h), 0, s); /* ... and encoded (audio_pack.hip) */
+    if (h->gate.max_rows > 0 && h->gate.enc.spool.pool_rows > 0) { /* ... and the spool's step of this batch (tx_spool.hip) */
+        TransmissionSpool& sp = h->gate.enc.spool;
+        launch_spool_step(spool_args(h, sp.steps), s);
+        sp.steps++;
+        sp.steps_total++;
+    }
     if (h->scan_ctl.idle_batches > 0) launch_scan_control_behind_demod(h, s); /* the lists' hops for the next batch, from this batch's axcindicate (AFC's verdict included) */
     (void)hipEventRecord(ev[4], s);
     hipError_t e = hipGetLastError();
@@ -2515,6 +2560,142 @@ int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const floa
     if (audio) HIP_TRY(h, hipMemcpy(audio, d_audio.p, n * row_bytes, hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
     if (info) HIP_TRY(h, hipMemcpy(info, d_info.p, n * sizeof(airband_hip_audio_row), hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipStreamSynchronize(nullptr), AIRBAND_HIP_ERUNTIME); /* the buffers go with this call */
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_set_transmission_spool(airband_hip_handle* h, const uint8_t* spool, int64_t pool_rows, int64_t export_rows, int64_t max_records, int32_t min_batches, int32_t idle_batches, int32_t max_batches) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    OutputGate& g = h->gate;
+    const Plan& p = h->plan;
+    if (g.max_rows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output gate (airband_hip_set_output_gate)");
+    if (g.enc.encoding == AIRBAND_AUDIO_F32) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output encoding (airband_hip_set_output_encoding)");
+    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the transmission spool is set before the first batch");
+    if (pool_rows < 0 || export_rows < 0 || max_records < 0 || min_batches < 0 || idle_batches < 0) return fail(h, AIRBAND_HIP_EINVAL, "negative count");
+    if (pool_rows == 0) { /* removed */
+        g.enc.spool = TransmissionSpool();
+        return AIRBAND_HIP_OK;
+    }
+    if (max_batches < 1) return fail(h, AIRBAND_HIP_EINVAL, "max_batches must be at least 1");
+    if (export_rows < (int64_t)max_batches + 1) return fail(h, AIRBAND_HIP_EINVAL, "export_rows must be at least max_batches + 1: a collect must be able to take the longest transmission");
+    if (max_records < 1) return fail(h, AIRBAND_HIP_EINVAL, "max_records must be at least 1");
+    if (pool_rows > 0x7fffffff || export_rows > 0x7fffffff || max_records > 0x7fffffff / 2) return fail(h, AIRBAND_HIP_EINVAL, "pool_rows, export_rows or max_records too large to index");
+    std::vector<uint8_t> mask((size_t)p.total_ch);
+    for (int c = 0; c < p.total_ch; c++) {
+        mask[c] = spool ? (spool[c] ? 1 : 0) : (g.gate[c] == AIRBAND_GATE_SIGNAL ? 1 : 0);
+        if (mask[c] && g.gate[c] != AIRBAND_GATE_SIGNAL)
+            return fail(h, AIRBAND_HIP_EINVAL, "spooled channel " + std::to_string(c) + " has a gate other than AIRBAND_GATE_SIGNAL");
+    }
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* built beside the encoding and moved in whole: a failed allocation leaves the handle as it was */
+    TransmissionSpool sp;
+    const size_t row_bytes = (size_t)h->B * audio_sample_bytes(g.enc.encoding), nb = (size_t)gate_blocks(p.total_ch), nm = ((size_t)p.total_ch + 63) / 64;
+    std::vector<int> stack((size_t)pool_rows);
+    for (size_t i = 0; i < stack.size(); i++) stack[i] = (int)i;
+    SpoolCtl ctl;
+    std::memset(&ctl, 0, sizeof(ctl));
+    ctl.free_top = (int32_t)pool_rows;
+    ctl.room = (int32_t)max_records;
+    hipError_t e = upload(sp.d_spool, mask);
+    if (e == hipSuccess) e = upload(sp.d_free_stack, stack);
+    if (e == hipSuccess) e = sp.d_ctl.alloc(1);
+    if (e == hipSuccess) e = hipMemcpy(sp.d_ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = sp.d_chan.alloc_zeroed((size_t)p.total_ch);
+    if (e == hipSuccess) e = sp.d_close_mask.alloc_zeroed(nm);
+    if (e == hipSuccess) e = sp.d_app_mask.alloc_zeroed(nm);
+    if (e == hipSuccess) e = sp.d_close_count.alloc_zeroed(nb);
+    if (e == hipSuccess) e = sp.d_app_count.alloc_zeroed(nb);
+    if (e == hipSuccess) e = sp.d_next.alloc_zeroed((size_t)pool_rows);
+    if (e == hipSuccess) e = sp.d_copy_list.alloc_zeroed(2 * (size_t)g.max_rows);
+    if (e == hipSuccess) e = sp.d_pool.alloc((size_t)pool_rows * row_bytes);
+    if (e == hipSuccess) e = sp.d_fin.alloc_zeroed((size_t)max_records);
+    if (e == hipSuccess) e = sp.d_exp_records.alloc_zeroed((size_t)max_records);
+    if (e == hipSuccess) e = sp.d_exp_head.alloc_zeroed((size_t)max_records);
+    if (e == hipSuccess) e = sp.d_exp_src.alloc_zeroed((size_t)export_rows);
+    if (e == hipSuccess) e = sp.d_exp_audio.alloc((size_t)export_rows * row_bytes);
+    if (e != hipSuccess) {
+        (void)hipGetLastError(); /* this call's error, reported here: not the next launch's */
+        return fail(h, AIRBAND_HIP_ENOMEM, std::string("transmission spool buffers: ") + hipGetErrorString(e));
+    }
+    sp.pool_rows = (int)pool_rows;
+    sp.export_rows = (int)export_rows;
+    sp.max_records = (int)max_records;
+    sp.row_bytes = (int)row_bytes;
+    sp.min_batches = (uint32_t)min_batches;
+    sp.idle_batches = (uint32_t)idle_batches;
+    sp.max_batches = (uint32_t)max_batches;
+    g.enc.spool = std::move(sp);
+    return AIRBAND_HIP_OK;
+}
+
+static const char* const NO_SPOOL = "the handle has no transmission spool (airband_hip_set_transmission_spool)";
+static bool has_spool(const airband_hip_handle* h) { return h->gate.max_rows > 0 && h->gate.enc.encoding != AIRBAND_AUDIO_F32 && h->gate.enc.spool.pool_rows > 0; }
+
+int airband_hip_collect_transmissions(airband_hip_handle* h, int64_t* n, airband_hip_transmission* records, void* audio, int64_t* n_rows, int64_t* n_waiting) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
+    const TransmissionSpool& sp = h->gate.enc.spool;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = h->stream;
+    order_behind_last_batch(h);
+    launch_spool_collect(spool_args(h, sp.steps), s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
+    /* how much there is is on the device: the counts first, then exactly those records and rows */
+    int32_t exp[3] = {0, 0, 0};
+    HIP_TRY(h, hipMemcpyAsync(exp, sp.d_ctl.p, sizeof(exp), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (exp[0] < 0 || exp[0] > sp.max_records || exp[1] < 0 || exp[1] > sp.export_rows || exp[2] < 0 || exp[2] > sp.max_records)
+        return fail(h, AIRBAND_HIP_ERUNTIME, "transmission spool counts out of range");
+    if (records && exp[0]) HIP_TRY(h, hipMemcpyAsync(records, sp.d_exp_records.p, (size_t)exp[0] * sizeof(airband_hip_transmission), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (audio && exp[1]) HIP_TRY(h, hipMemcpyAsync(audio, sp.d_exp_audio.p, (size_t)exp[1] * sp.row_bytes, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (n) *n = exp[0];
+    if (n_rows) *n_rows = exp[1];
+    if (n_waiting) *n_waiting = exp[2];
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_spool_flush(airband_hip_handle* h) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    order_behind_last_batch(h);
+    launch_spool_flush(spool_args(h, h->gate.enc.spool.steps), h->stream);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
+    /* a batch that ran on a caller's stream: the next one there knows nothing of the handle's stream, so the flush is complete before this returns */
+    if (h->ev_last_pending) HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_spool_counters_get(airband_hip_handle* h, airband_hip_spool_counters* out) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
+    if (!out) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    const TransmissionSpool& sp = h->gate.enc.spool;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    order_behind_last_batch(h);
+    SpoolCtl ctl;
+    HIP_TRY(h, hipMemcpyAsync(&ctl, sp.d_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, h->stream), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
+    out->steps = sp.steps_total;
+    out->open_now = ctl.open_now;
+    out->waiting_now = (uint64_t)(ctl.fin_count < 0 ? 0 : ctl.fin_count);
+    out->free_rows_now = (uint64_t)(ctl.free_top < 0 ? 0 : ctl.free_top);
+    out->finished_total = ctl.finished_total;
+    out->dropped_transmissions = ctl.dropped;
+    out->rows_stored_total = ctl.rows_stored;
+    out->rows_lost_total = ctl.rows_lost;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_device_transmission_spool(airband_hip_handle* h, void** d_export_audio, airband_hip_transmission** d_export_records, int32_t** d_n_export) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
+    const TransmissionSpool& sp = h->gate.enc.spool;
+    if (d_export_audio) *d_export_audio = sp.d_exp_audio.p;
+    if (d_export_records) *d_export_records = sp.d_exp_records.p;
+    if (d_n_export) *d_n_export = reinterpret_cast<int32_t*>(sp.d_ctl.p); /* SpoolCtl::exp, its first member */
     return AIRBAND_HIP_OK;
 }
 

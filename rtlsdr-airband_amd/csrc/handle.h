@@ -98,9 +98,26 @@ struct MixerWiring {
     DevBuf<uint8_t> d_stereo, d_signal;
 };
 
+/* what airband_hip_set_transmission_spool() set up, a part of the encoding whose rows it keeps: replaced as a whole, gone with the encoding (and so with the
+ * gate), one without pool_rows is an encoding without a spool (nothing allocated, nothing launched) */
+struct TransmissionSpool {
+    int pool_rows = 0;         /* 0 = no spool */
+    int export_rows = 0, max_records = 0, row_bytes = 0;
+    uint32_t min_batches = 0, idle_batches = 0, max_batches = 0;
+    uint32_t steps = 0;        /* steps enqueued so far: the next step's k */
+    uint64_t steps_total = 0;
+    DevBuf<uint8_t> d_spool, d_pool, d_exp_audio;
+    DevBuf<SpoolChan> d_chan;
+    DevBuf<SpoolCtl> d_ctl;
+    DevBuf<unsigned long long> d_close_mask, d_app_mask;
+    DevBuf<int> d_close_count, d_app_count, d_free_stack, d_next, d_copy_list, d_exp_head, d_exp_src;
+    DevBuf<airband_hip_transmission> d_fin, d_exp_records;
+};
+
 /* what airband_hip_set_output_encoding() set up, a part of the gate whose list it reads: replaced as a whole, gone with the gate, AIRBAND_AUDIO_F32 is a gate
  * without an encoding (nothing allocated, nothing launched) */
 struct OutputEncoding {
+    TransmissionSpool spool;
     int encoding = AIRBAND_AUDIO_F32;
     DevBuf<uint8_t> d_audio; /* [max_rows][wave_batch] bytes, or int16 for S16 */
     DevBuf<airband_hip_audio_row> d_info;

@@ -323,6 +323,56 @@ struct AudioPackArgs {
 };
 void launch_audio_pack(const AudioPackArgs& a, int grid, hipStream_t stream); /* grid: workgroups, 0 = min(max_rows, one per wavefront slot of the GPU) */
 
+/* transmission spool (tx_spool.hip): the encoded rows of every open transmission kept in a row pool, the closing rule applied once per batch, finished
+ * transmissions listed in (step, channel) order and exported as one contiguous run of rows */
+struct SpoolChan {
+    uint32_t open_batch, last_batch, n_rows, n_lost;
+    uint32_t n_clipped;
+    uint16_t peak, first, end, open; /* open: the channel has an open transmission; nothing else means anything without it */
+    int32_t head, tail;              /* its chain of pool rows (SpoolArgs::next); -1 while it has none */
+    uint32_t pad[4];
+}; /* 48 bytes */
+struct SpoolCtl {
+    int32_t exp[3];                  /* the last collect's: transmissions exported, their rows, transmissions still waiting */
+    int32_t free_top;                /* rows on the free stack */
+    int32_t fin_head, fin_count;     /* the finished list: a ring of max_records records */
+    int32_t room, fin_tail;          /* of the running step (written by the scan pass): records the list can take, where they go */
+    int32_t n_stored_step;           /* rows stored by the running step: summed by the append pass, applied by the copy pass */
+    int32_t pad;
+    unsigned long long open_now, finished_total, dropped, rows_stored, rows_lost;
+};
+struct SpoolArgs {
+    const uint8_t* spool;            /* [n_ch] the channel is spooled */
+    SpoolChan* chan;                 /* [n_ch] */
+    SpoolCtl* ctl;                   /* [1] */
+    unsigned long long* close_mask;  /* [ceil(n_ch / 64)] phase A's verdicts */
+    unsigned long long* app_mask;    /* [ceil(n_ch / 64)] phase B's channels: spooled and selected */
+    int* close_count;                /* [gate_blocks(n_ch)] */
+    int* app_count;                  /* [gate_blocks(n_ch)] */
+    const unsigned long long* gate_mask; /* the gate's verdicts and counts of this batch (GateArgs::mask, ::block_count) */
+    const int* gate_count;
+    int* free_stack;                 /* [pool_rows] */
+    int* next;                       /* [pool_rows] the row behind this one in its chain, -1 */
+    uint8_t* pool;                   /* [pool_rows][row_bytes] */
+    int* copy_list;                  /* [max_rows][2] (encoded row, pool row) of the step's stored rows, by rank */
+    const uint8_t* enc_audio;        /* the encoder's rows and records of this batch (AudioPackArgs::audio, ::info) */
+    const airband_hip_audio_row* enc_info;
+    airband_hip_transmission* fin;   /* [max_records] the ring; reserved[0] holds the chain's head while a record waits */
+    airband_hip_transmission* exp_records; /* [max_records] */
+    int* exp_head;                   /* [max_records] the exported transmissions' chains */
+    int* exp_src;                    /* [export_rows] the pool row of every exported row */
+    uint8_t* exp_audio;              /* [export_rows][row_bytes] */
+    int n_ch, max_rows;              /* the gate's */
+    int pool_rows, export_rows, max_records;
+    int row_bytes;                   /* a multiple of four */
+    int wave_batch;
+    uint32_t min_batches, idle_batches, max_batches;
+    uint32_t k;                      /* the step's number; flush: the steps run so far */
+};
+void launch_spool_step(const SpoolArgs& a, hipStream_t stream);    /* four launches: scan, close, append, copy */
+void launch_spool_flush(const SpoolArgs& a, hipStream_t stream);   /* two: scan, close */
+void launch_spool_collect(const SpoolArgs& a, hipStream_t stream); /* three: export, walk, gather */
+
 /* band scope (band_scope.hip): mean and peak of |X[k]|^2 over n_windows windows of the batch's input span, one workgroup per selected dongle */
 struct ScopeArgs {
     const uint8_t* iq;        /* device: dongle d's span starts at iq + d * iq_stride (the batch's stage-1 input) */
