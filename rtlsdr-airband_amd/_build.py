@@ -47,8 +47,13 @@ HIP_SOURCES = {
     "band_watch.hip": ["-O3"],  # band watch: carrier tracks per scope row advanced by the survey's list, the fleet's events packed in row order; integers only
     "band_follow.hip": ["-O3"],  # band follow: followers tuned onto the watch's confirmed tracks per scope row, their bins applied, the fleet's changes packed; integers only
     "scan_control.hip": ["-O3"],  # scan control: every scan list's hop decision per batch, the switch list the exchange kernel reads, the fleet's records packed; integers only
-    "airband_hip.cpp": ["-O2", "-x", "hip"],
+    "airband_hip.cpp": ["-O2", "-x", "hip"],  # the host driver (csrc/driver.h): prepare and the batch path, then the optional outputs and the mixers by feature
+    "driver_band.cpp": ["-O2", "-x", "hip"],
+    "driver_gate.cpp": ["-O2", "-x", "hip"],
+    "driver_scan.cpp": ["-O2", "-x", "hip"],
+    "driver_mix.cpp": ["-O2", "-x", "hip"],
 }
+BUILD_INFO_SOURCE = "airband_hip.cpp"  # defines airband_hip_build_info(): the one file that is told the build's defines
 HOST_SOURCES = {"params.cpp": ["-O2", "-ffp-contract=off", "-fno-fast-math"]}
 
 
@@ -137,7 +142,7 @@ def build(force: bool = False, verbose: bool = False) -> str:
         obj = os.path.join(OBJ, name + ".o")
         objs.append(obj)
         if force or _newer(src, obj):
-            info = ["-DAB_BUILD_DEFINES=\"%s\"" % " ".join(EXTRA)] if name == "airband_hip.cpp" else []
+            info = ["-DAB_BUILD_DEFINES=\"%s\"" % " ".join(EXTRA)] if name == BUILD_INFO_SOURCE else []
             cmd = [hipcc, "--offload-arch=" + ARCH, "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"] + flags + DEVICE_FLAGS + EXTRA + info + ["-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd))

@@ -4,24 +4,10 @@
  *
  * There is NO CPU fallback in this library: every data-path entry point needs the HIP device the handle was
  * prepared on and fails with AIRBAND_HIP_ENODEV / AIRBAND_HIP_ERUNTIME otherwise.
+ *
+ * Here: prepare, the batch path, the host ring, collect / read_* / timings, the signal generator; the optional outputs and the mixers: driver_*.cpp (driver.h).
  */
-#include <hip/hip_runtime.h>
-#include <dlfcn.h>
-
-#include <algorithm>
-#include <atomic>
-#include <cmath>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <mutex>
-#include <string>
-#include <vector>
-
-#include "handle.h"
-#include "kernels.h"
-#include "scan_bank.h"
+#include "driver.h"
 
 /* upper bound for the int8 coefficient tables of a handle -- one per distinct group of eight bins plus one per AFC group; past it prepare() picks the wavefront-FFT
  * channelizer (override for tests) */
@@ -36,29 +22,9 @@
 
 using namespace airband;
 
+thread_local std::string airband::g_prepare_error;
+
 namespace {
-
-thread_local std::string g_prepare_error;
-
-int fail(airband_hip_handle* h, int code, const std::string& msg) {
-    if (h) h->error = msg;
-    else g_prepare_error = msg;
-    return code;
-}
-
-#define HIP_TRY(h, expr, code)                                                                                   \
-    do {                                                                                                         \
-        hipError_t e_ = (expr);                                                                                  \
-        if (e_ != hipSuccess) return fail(h, code, std::string(#expr) + ": " + hipGetErrorString(e_));           \
-    } while (0)
-
-template <class T>
-hipError_t upload(DevBuf<T>& b, const std::vector<T>& v) {
-    hipError_t e = b.alloc(v.size());
-    if (e != hipSuccess) return e;
-    if (v.empty()) return hipSuccess;
-    return hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
-}
 
 /* Everything in flight must be done before the handle's memory goes away (the handle's members free themselves, handle.h): a batch enqueued on a
  * caller's stream, the front stream of a pipelined handle, the forked demod streams, the copy stream of the host ring. */
@@ -76,29 +42,8 @@ void destroy(airband_hip_handle* h) {
     delete h;
 }
 
-/* airband_hip_prepare_scan() holds the handle it is building in one of these: every failure exit releases it the way airband_hip_release() would.
- * Its HIP_TRY()s name PREPARING instead of the handle, which sends the message to the thread's prepare error -- the handle does not outlive a failure. */
+/* airband_hip_prepare_scan() holds the handle it is building in one of these: every failure exit releases it the way airband_hip_release() would */
 using HandlePtr = std::unique_ptr<airband_hip_handle, void (*)(airband_hip_handle*)>;
-constexpr airband_hip_handle* PREPARING = nullptr;
-
-/* Results of a batch that ran on a caller's stream: make the handle's own stream (on which collect / read_* / the stats kernel
- * are issued) wait for it on the GPU. */
-void order_behind_last_batch(airband_hip_handle* h) {
-    if (h->ev_last && h->ev_last_pending) (void)hipStreamWaitEvent(h->stream, h->ev_last, 0);
-}
-
-/* Work was enqueued on stream s.  If that is not the handle's own stream (a caller's: handed to process_device, or the one the last batch ran on), what the
- * handle does next on its own -- collect / read_* / synchronize / release, the next batch's sums -- has to come behind it: ev_last marks the place. */
-int results_enqueued_on(airband_hip_handle* h, hipStream_t s) {
-    if (s == h->stream) return AIRBAND_HIP_OK;
-    HIP_TRY(h, h->ev_last.ensure(), AIRBAND_HIP_ENODEV);
-    HIP_TRY(h, hipEventRecord(h->ev_last, s), AIRBAND_HIP_ERUNTIME);
-    h->ev_last_pending = true;
-    return AIRBAND_HIP_OK;
-}
-
-/* the stream on which the last batch's mixer sums become final */
-hipStream_t results_stream(airband_hip_handle* h) { return h->pipeline ? h->stream : (h->last_stream ? h->last_stream : h->stream); }
 
 /* Per-stage GPU times: every batch records into its own event set; finished sets are folded into running sums here. */
 void harvest_timings(airband_hip_handle* h, bool wait) {
@@ -154,14 +99,6 @@ void launch_retune_tables(airband_hip_handle* h, hipStream_t s, int epoch) {
     ra.epoch = epoch;
     launch_retune(ra, s);
 }
-
-/* the ring rows a batch's stage 1 produces */
-struct FrontRows {
-    int first_row, n_hops;
-};
-
-/* stage 1 of the next batch may be written while stage 2 still reads this one: rings two batches deep, a front stream, the channelizer held to five wavefronts per CU */
-bool deep_rings(const airband_hip_handle* h) { return h->pipeline || h->run_ahead; }
 
 /* the first batch also produces the AGC_EXTRA lead-in hops (waveend starts at 0, src/config.cpp:805) */
 FrontRows front_rows(const airband_hip_handle* h) {
@@ -294,407 +231,11 @@ int launch_last_hop_spectrum(airband_hip_handle* h, hipStream_t s) {
     return AIRBAND_HIP_OK;
 }
 
-/* The band scope of the batch whose stage 1 goes on stream s (airband_hip_set_band_scope): it depends on the batch's input only, like AFC's one-hop spectrum
- * above.  scope_fork() in front of stage 1: the kernel runs on the scope's own stream beside it.  scope_join() behind stage 1: s waits for it, so that EVERY point
- * that declares the batch's input consumed by recording an event on s behind stage 1 -- ev_stage_read of the host ring, front_done of pipelined and run-ahead
- * handles, the stream order a run-ahead batch's next stage 1 relies on -- is behind the scope's reads too, and the batch's results, which wait for stage 1, are
- * complete only once the scope is.  On a CALLER's stream there is no fork: the kernel goes on that stream behind stage 1. */
-bool scope_on_side(const airband_hip_handle* h, hipStream_t s) { return s == h->stream || s == h->front; }
-
-ScopeArgs scope_args(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, FrontRows r) {
-    BandScope& sc = h->scope;
-    const Plan& p = h->plan;
-    const int set = (int)(sc.launches % (uint64_t)sc.n_sets);
-    ScopeArgs a;
-    a.iq = (const uint8_t*)d_iq;
-    a.iq_stride = (long)stride_bytes;
-    a.dev = h->d_dev.p;
-    a.dev_of_row = sc.d_dev_of_row.p;
-    a.window = h->d_window.p;
-    a.twiddle = reinterpret_cast<const float2*>(h->d_twiddle.p);
-    a.mean = sc.d_mean[set].p;
-    a.peak = sc.d_peak[set].p;
-    a.prev_mean = sc.n_sets > 1 ? sc.d_mean[set ^ 1].p : nullptr;
-    a.prev_peak = sc.n_sets > 1 ? sc.d_peak[set ^ 1].p : nullptr;
-    a.n_rows = sc.n_rows;
-    a.fft_log = p.fft_log;
-    a.hop_samples = p.dev[0].hop_samples;
-    a.bytes_per_sample = p.dev[0].bytes_per_sample;
-    a.sfmt = p.dev[0].sfmt;
-    a.first_hop = r.n_hops - h->B; /* the first batch's AGC_EXTRA lead-in hops are never selected */
-    a.span_hops = r.n_hops;
-    a.wave_batch = h->B;
-    a.n_windows = sc.windows;
-    a.region_bytes = 0;
-    return a;
-}
-
-/* The band survey of the same batch (airband_hip_set_band_survey): directly behind the scope's kernel on whatever stream that went to, so that stream order alone
- * makes the rows complete, a switched-off dongle's carried-over row included.  Its results go to the set the scope's rows went to. */
-void launch_survey_behind_scope(airband_hip_handle* h, const ScopeArgs& sa, hipStream_t s) {
-    BandScope& sc = h->scope;
-    BandSurvey& sv = sc.survey;
-    if (sv.max_peaks <= 0) return;
-    const int set = (int)(sc.launches % (uint64_t)sc.n_sets);
-    SurveyArgs a;
-    a.rows = sv.trace == AIRBAND_SCOPE_MEAN ? sa.mean : sa.peak;
-    a.bin_first = sv.d_bin_first.p;
-    a.bins = sv.d_bins.p;
-    a.summary = sv.d_summary[set].p;
-    a.peaks = sv.d_peaks[set].p;
-    a.n_rows = sc.n_rows;
-    a.fft_log = sa.fft_log;
-    a.max_peaks = sv.max_peaks;
-    a.rank = sv.rank;
-    a.guard_bins = sv.guard_bins;
-    a.ratio = sv.ratio;
-    launch_band_survey(a, s);
-    /* the band watch of the same batch (airband_hip_set_band_watch), behind the survey it reads: the tables of the launch before are in the other set */
-    BandWatch& w = sv.watch;
-    if (w.max_tracks <= 0) return;
-    const int prev = sc.n_sets > 1 ? set ^ 1 : set;
-    WatchArgs wa;
-    wa.dev = h->d_dev.p;
-    wa.dev_of_row = sc.d_dev_of_row.p;
-    wa.summary = a.summary;
-    wa.peaks = a.peaks;
-    wa.tracks_in = w.d_tracks[prev].p;
-    wa.rows_in = w.d_rows[prev].p;
-    wa.tracks_out = w.d_tracks[set].p;
-    wa.rows_out = w.d_rows[set].p;
-    wa.stage = w.d_stage.p;
-    wa.events = w.d_events[set].p;
-    wa.n_events = w.d_count[set].p;
-    wa.n_rows = sc.n_rows;
-    wa.fft_log = sa.fft_log;
-    wa.max_peaks = sv.max_peaks;
-    wa.max_tracks = w.max_tracks;
-    wa.match_bins = w.match_bins;
-    wa.confirm_hits = w.confirm_hits;
-    wa.release_misses = w.release_misses;
-    wa.max_events = w.max_events;
-    wa.batch = w.batch++;
-    launch_band_watch(wa, s);
-}
-
-/* rows [r0, r0 + n) of a survey array of `per_row` elements a row -> the entries of the selected dongles among [first_dev, first_dev + n_dev): ONE copy, straight into
- * the caller's array where every dongle of the range is selected, through a host vector otherwise.  Entries of the other dongles are set to `blank`. */
-template <class T>
-int collect_survey_rows(airband_hip_handle* h, const T* d_src, size_t per_row, int first_dev, int n_dev, T* out, const T& blank, hipStream_t s) {
-    const BandScope& sc = h->scope;
-    int r0 = -1, n = 0;
-    for (int i = 0; i < n_dev; i++)
-        if (sc.row_of_dev[first_dev + i] >= 0) {
-            if (r0 < 0) r0 = sc.row_of_dev[first_dev + i];
-            n++; /* rows are dense in ascending dongle order: the range's rows are r0 .. r0 + n - 1 */
-        }
-    if (n == n_dev) {
-        if (n) HIP_TRY(h, hipMemcpyAsync(out, d_src + (size_t)r0 * per_row, (size_t)n * per_row * sizeof(T), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-        HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-        return AIRBAND_HIP_OK;
-    }
-    std::vector<T> tmp((size_t)n * per_row);
-    if (n) HIP_TRY(h, hipMemcpyAsync(tmp.data(), d_src + (size_t)r0 * per_row, tmp.size() * sizeof(T), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    for (int i = 0; i < n_dev; i++) {
-        const int row = sc.row_of_dev[first_dev + i];
-        if (row < 0) std::fill(out + (size_t)i * per_row, out + (size_t)(i + 1) * per_row, blank);
-        else std::copy(tmp.begin() + (size_t)(row - r0) * per_row, tmp.begin() + (size_t)(row - r0 + 1) * per_row, out + (size_t)i * per_row);
-    }
-    return AIRBAND_HIP_OK;
-}
-
-/* front batch front_batches has its scope in set (launches % n_sets); the set becomes the current one with the batch's back half (run_back_half) */
-void scope_launched(airband_hip_handle* h) {
-    BandScope& sc = h->scope;
-    sc.set_of_front[h->front_batches & 1] = (int)(sc.launches % (uint64_t)sc.n_sets);
-    sc.launches++;
-}
-
-int scope_fork(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, FrontRows r, hipStream_t s) {
-    BandScope& sc = h->scope;
-    if (sc.windows <= 0 || !scope_on_side(h, s)) return AIRBAND_HIP_OK;
-    HIP_TRY(h, hipEventRecord(sc.ev_fork, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamWaitEvent(sc.stream, sc.ev_fork, 0), AIRBAND_HIP_ERUNTIME);
-    if (h->ev_last && h->ev_last_pending) HIP_TRY(h, hipStreamWaitEvent(sc.stream, h->ev_last, 0), AIRBAND_HIP_ERUNTIME); /* a batch (and its scope) on a caller's stream */
-    const ScopeArgs sa = scope_args(h, d_iq, stride_bytes, r);
-    launch_band_scope(sa, sc.stream);
-    launch_survey_behind_scope(h, sa, sc.stream);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("band scope launch: ") + hipGetErrorString(e));
-    HIP_TRY(h, hipEventRecord(sc.ev_done, sc.stream), AIRBAND_HIP_ERUNTIME);
-    scope_launched(h);
-    return AIRBAND_HIP_OK;
-}
-
-int scope_join(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, FrontRows r, hipStream_t s) {
-    BandScope& sc = h->scope;
-    if (sc.windows <= 0) return AIRBAND_HIP_OK;
-    if (scope_on_side(h, s)) {
-        HIP_TRY(h, hipStreamWaitEvent(s, sc.ev_done, 0), AIRBAND_HIP_ERUNTIME);
-        return AIRBAND_HIP_OK;
-    }
-    /* the caller's stream, behind stage 1 -- and behind the scope launch before this one, whose rows a switched-off dongle's are carried over from */
-    if (sc.launches > 0) HIP_TRY(h, hipStreamWaitEvent(s, sc.ev_done, 0), AIRBAND_HIP_ERUNTIME);
-    const ScopeArgs sa = scope_args(h, d_iq, stride_bytes, r);
-    launch_band_scope(sa, s);
-    launch_survey_behind_scope(h, sa, s);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("band scope launch: ") + hipGetErrorString(e));
-    HIP_TRY(h, hipEventRecord(sc.ev_done, s), AIRBAND_HIP_ERUNTIME);
-    scope_launched(h);
-    return AIRBAND_HIP_OK;
-}
-
-ScanExchangeArgs scan_args(airband_hip_handle* h) {
-    ScanExchangeArgs a;
-    a.cc = h->d_cc.p;
-    a.cs = h->d_cs.p;
-    a.sqbuf = h->d_sqbuf.p;
-    a.bank_cc = h->d_bank_cc.p;
-    a.bank_cs = h->d_bank_cs.p;
-    a.bank_sq = h->d_bank_sq.p;
-    a.cs_mask = h->d_scan_mask.p;
-    a.cc_mask = h->d_scan_mask.p + AB_CS_DWORDS;
-    a.sw = nullptr;
-    a.n_switch = 0;
-    a.n_slots = h->n_slots;
-    a.n_entries = (int)h->plan.scan_cc.size();
-    return a;
-}
-
-/* front batch k is being enqueued: the scan entries in force now are its entries (airband_hip_set_freq_index latches per batch) */
-void scan_latch(airband_hip_handle* h, uint64_t k, int first_row, int n_rows) {
-    if (h->plan.scan.empty()) return;
-    if (h->scan_ctl.idle_batches == 0) h->scan_latch[k & 1] = h->scan_cur; /* (under scan control the entries are the GPU's: scan_before_demod) */
-    h->scan_first_row[k & 1] = first_row;
-    h->scan_n_rows[k & 1] = n_rows;
-}
-
 /* stage 1 of front batch front_batches is in its stream: latch its scan entries, move on to the next batch's ring rows */
 void front_enqueued(airband_hip_handle* h, int first_row, int n_rows) {
     scan_latch(h, h->front_batches, first_row, n_rows);
     h->row0_front = (h->row0_front + h->B) % h->R;
     h->front_batches++;
-}
-
-/* in front of the demod kernels of batch batches_done, on its stage-2 stream: the exchange of every scan channel whose latched entry is not the one its slot
- * holds (one launch for all of them), and |bin| of the lists that mix AM and NFM */
-int scan_before_demod(airband_hip_handle* h, hipStream_t s) {
-    const int b = (int)(h->batches_done & 1);
-    if (h->scan_ctl.idle_batches > 0) {
-        /* scan control: the switch list is the one the decision kernel left behind the batch before (or airband_hip_set_scan_control at the start), on this
-         * stream's order -- nothing is built, copied or waited for here.  One workgroup per list; an item with slot -1 leaves at the kernel's first test. */
-        ScanExchangeArgs a = scan_args(h);
-        a.sw = h->scan_ctl.d_sw.p;
-        a.n_switch = (int)h->scan_ctl.list_of.size();
-        launch_scan_exchange(a, s);
-        if (h->d_scan_mix_slots.n > 0)
-            launch_scan_mag(h->d_scan_mix_slots.p, (int)h->d_scan_mix_slots.n, h->d_mag.p, h->d_iq.p, h->scan_first_row[b], h->scan_n_rows[b], h->row0, h->R, s);
-        return AIRBAND_HIP_OK;
-    }
-    const std::vector<int>& want = h->scan_latch[b];
-    const int q = h->switch_buf;
-    int* list = h->h_switch[q].get();
-    int n = 0;
-    bool waited = false;
-    for (size_t i = 0; i < h->plan.scan.size(); i++) {
-        if (want[i] == h->scan_held[i]) continue;
-        if (!waited && h->switch_used[q]) HIP_TRY(h, hipEventSynchronize(h->ev_switch[q]), AIRBAND_HIP_ERUNTIME); /* the list of two batches ago has been read */
-        waited = true;
-        const ScanList& sl = h->plan.scan[i];
-        const int slot = h->ext_to_slot[sl.ext];
-        list[3 * n] = slot;
-        list[3 * n + 1] = sl.first_entry + h->scan_held[i];
-        list[3 * n + 2] = sl.first_entry + want[i];
-        n++;
-        h->scan_held[i] = want[i];
-        /* the host copy of the slot's flags (airband_hip_device_enable rewrites the word from it) follows the entry the slot holds */
-        ChanConst& hc = h->cc_slots[slot];
-        hc.flags = (hc.flags & ~AB_SCAN_FREQ_FLAGS) | (h->plan.scan_cc[sl.first_entry + want[i]].flags & AB_SCAN_FREQ_FLAGS);
-    }
-    if (n > 0) {
-        HIP_TRY(h, hipMemcpyAsync(h->d_switch[q].p, list, (size_t)n * 3 * sizeof(int), hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
-        ScanExchangeArgs a = scan_args(h);
-        a.sw = h->d_switch[q].p;
-        a.n_switch = n;
-        launch_scan_exchange(a, s);
-        HIP_TRY(h, hipEventRecord(h->ev_switch[q], s), AIRBAND_HIP_ERUNTIME);
-        h->switch_used[q] = true;
-        h->switch_buf = q ^ 1;
-    }
-    if (h->d_scan_mix_slots.n > 0)
-        launch_scan_mag(h->d_scan_mix_slots.p, (int)h->d_scan_mix_slots.n, h->d_mag.p, h->d_iq.p, h->scan_first_row[b], h->scan_n_rows[b], h->row0, h->R, s);
-    return AIRBAND_HIP_OK;
-}
-
-MixArgs mix_args(const airband_hip_handle* h) {
-    const MixerWiring& w = h->mix;
-    MixArgs ma;
-    ma.out_wave = h->d_out_wave.p + AB_OUT_PAD;
-    ma.wave_stride = h->wave_stride;
-    ma.out_axc = h->d_out_axc.p;
-    ma.in_chan = w.d_chan.p;
-    ma.in_ml = w.d_ml.p;
-    ma.in_mr = w.d_mr.p;
-    ma.run_first = w.d_run_first.p;
-    ma.run_mixer = w.d_run_mixer.p;
-    ma.mixer_first_run = w.d_first_run.p;
-    ma.mixer_stereo = w.d_stereo.p;
-    ma.run_left = w.d_run_left.p;
-    ma.run_right = w.d_run_right.p;
-    ma.run_signal = w.d_run_signal.p;
-    ma.n_runs = w.n_runs;
-    ma.left = w.d_left.p;
-    ma.right = w.d_right.p;
-    ma.has_signal = w.d_signal.p;
-    ma.n_mixers = w.n_mixers;
-    ma.wave_batch = h->B;
-    return ma;
-}
-
-GateArgs gate_args(const airband_hip_handle* h) {
-    const OutputGate& g = h->gate;
-    GateArgs a;
-    a.gate = g.d_gate.p;
-    a.axc = h->d_out_axc.p;
-    a.prev = g.d_prev.p;
-    a.mask = g.d_mask.p;
-    a.block_count = g.d_block_count.p;
-    a.index = g.d_index.p;
-    a.count = g.d_count.p;
-    a.n_ch = h->plan.total_ch;
-    a.max_rows = g.max_rows;
-    a.out_wave = h->d_out_wave.p;
-    a.out_iq = h->d_out_iq.p;
-    a.rows = g.d_rows.p;
-    a.iq_rows = g.d_iq_rows.p;
-    a.wave_stride = h->wave_stride;
-    a.wave_batch = h->B;
-    return a;
-}
-
-/* the gate's list and count, the rows the gather reads (airband_hip_set_output_encoding) */
-AudioPackArgs audio_pack_args(const airband_hip_handle* h) {
-    const OutputGate& g = h->gate;
-    AudioPackArgs a;
-    a.index = g.d_index.p;
-    a.count = g.d_count.p;
-    a.n_rows = 0;
-    a.max_rows = g.max_rows;
-    a.n_ch = h->plan.total_ch;
-    a.src = h->d_out_wave.p;
-    a.src_stride = h->wave_stride;
-    a.src_pad = AB_OUT_PAD;
-    a.audio = g.enc.d_audio.p;
-    a.info = g.enc.d_info.p;
-    a.wave_batch = h->B;
-    a.encoding = g.enc.encoding;
-    return a;
-}
-
-/* the spool's own buffers, the gate's verdicts and the encoder's rows (airband_hip_set_transmission_spool); k: the step's number */
-SpoolArgs spool_args(const airband_hip_handle* h, uint32_t k) {
-    const OutputGate& g = h->gate;
-    const TransmissionSpool& sp = g.enc.spool;
-    SpoolArgs a;
-    a.spool = sp.d_spool.p;
-    a.chan = sp.d_chan.p;
-    a.ctl = sp.d_ctl.p;
-    a.close_mask = sp.d_close_mask.p;
-    a.app_mask = sp.d_app_mask.p;
-    a.close_count = sp.d_close_count.p;
-    a.app_count = sp.d_app_count.p;
-    a.gate_mask = g.d_mask.p;
-    a.gate_count = g.d_block_count.p;
-    a.free_stack = sp.d_free_stack.p;
-    a.next = sp.d_next.p;
-    a.pool = sp.d_pool.p;
-    a.copy_list = sp.d_copy_list.p;
-    a.enc_audio = g.enc.d_audio.p;
-    a.enc_info = g.enc.d_info.p;
-    a.fin = sp.d_fin.p;
-    a.exp_records = sp.d_exp_records.p;
-    a.exp_head = sp.d_exp_head.p;
-    a.exp_src = sp.d_exp_src.p;
-    a.exp_audio = sp.d_exp_audio.p;
-    a.n_ch = h->plan.total_ch;
-    a.max_rows = g.max_rows;
-    a.pool_rows = sp.pool_rows;
-    a.export_rows = sp.export_rows;
-    a.max_records = sp.max_records;
-    a.row_bytes = sp.row_bytes;
-    a.wave_batch = h->B;
-    a.min_batches = sp.min_batches;
-    a.idle_batches = sp.idle_batches;
-    a.max_batches = sp.max_batches;
-    a.k = k;
-    return a;
-}
-
-/* The band follow of the batch whose back half goes on stream s (airband_hip_set_band_follow), behind its demod kernels.  It reads the track tables the batch's
- * watch left, and the watch ran on the scope's stream: s is behind that already (scope_join() made the stage-1 stream wait for the scope, and a handle with
- * followers runs both halves of a batch on one stream), said again here because this is the point that depends on it.  The watch batch number of this batch is
- * the last one launched: such a handle never has a second stage 1 in flight. */
-void launch_follow_behind_demod(airband_hip_handle* h, int* moved_epoch, int epoch, hipStream_t s) {
-    BandScope& sc = h->scope;
-    BandWatch& w = sc.survey.watch;
-    BandFollow& fo = w.follow;
-    if (scope_on_side(h, s)) (void)hipStreamWaitEvent(s, sc.ev_done, 0);
-    FollowArgs a;
-    a.dev = h->d_dev.p;
-    a.dev_of_row = sc.d_dev_of_row.p;
-    a.tracks = w.d_tracks[sc.cur].p;
-    a.fol_range = fo.d_range.p;
-    a.fol_slot = fo.d_slot.p;
-    a.fol_home = fo.d_home.p;
-    a.followers = fo.d_followers.p;
-    a.rows = fo.d_rows.p;
-    a.stage = fo.d_stage.p;
-    a.changes = fo.d_changes.p;
-    a.n_changes = fo.d_count.p;
-    a.cs = h->d_cs.p;
-    a.moved_epoch = moved_epoch;
-    a.epoch = epoch;
-    a.n_rows = sc.n_rows;
-    a.n_follow = (int)h->plan.follow_ext.size();
-    a.n_slots = h->n_slots;
-    a.fft_log = h->plan.fft_log;
-    a.max_tracks = w.max_tracks;
-    a.cap = fo.cap;
-    a.max_changes = fo.max_changes;
-    a.batch = w.batch - 1u;
-    launch_band_follow(a, s);
-}
-
-ScanControlArgs scan_control_args(airband_hip_handle* h) {
-    ScanControl& c = h->scan_ctl;
-    ScanControlArgs a;
-    a.dev = h->d_dev.p;
-    a.axc = h->d_out_axc.p;
-    a.lists = c.d_lists.p;
-    a.state = c.d_state.p;
-    a.stage = c.d_stage.p;
-    a.stage_n = c.d_stage_n.p;
-    a.sw = c.d_sw.p;
-    a.events = c.d_events.p;
-    a.n_events = c.d_count.p;
-    a.n_lists = (int)c.list_of.size();
-    a.n_dev = h->plan.n_dev;
-    a.n_ch = h->plan.total_ch;
-    a.idle_batches = c.idle_batches;
-    a.dwell_batches = c.dwell_batches;
-    a.max_records = c.max_records;
-    a.batch = c.batch;
-    return a;
-}
-
-/* The scan control of the batch whose back half goes on stream s (airband_hip_set_scan_control), behind everything that writes the batch's axcindicate.  The
- * switch list it writes is read by the exchange in front of the NEXT batch's demod kernels, which goes on the same stream (or, where a caller changes streams
- * between batches, behind ev_last like everything else of the next batch). */
-void launch_scan_control_behind_demod(airband_hip_handle* h, hipStream_t s) {
-    launch_scan_control(scan_control_args(h), s);
-    h->scan_ctl.batch++;
 }
 
 /* stage 2 + emit (+ mixers, + the output gate) of the batch whose stage-1 rows are already in the rings */
@@ -772,15 +313,8 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
         launch_emit_iq(ea, s);
     }
     if (h->mix.n_mixers > 0) launch_mix(mix_args(h), s);
-    if (h->gate.max_rows > 0) launch_gate(gate_args(h), s); /* the batch's active channels and their rows, packed (gate.hip) */
-    if (h->gate.max_rows > 0 && h->gate.enc.encoding != AIRBAND_AUDIO_F32) launch_audio_pack(audio_pack_args(h), 0, s); /* ... and encoded (audio_pack.hip) */
-    if (h->gate.max_rows > 0 && h->gate.enc.spool.pool_rows > 0) { /* ... and the spool's step of this batch (tx_spool.hip) */
-        TransmissionSpool& sp = h->gate.enc.spool;
-        launch_spool_step(spool_args(h, sp.steps), s);
-        sp.steps++;
-        sp.steps_total++;
-    }
-    if (h->scan_ctl.idle_batches > 0) launch_scan_control_behind_demod(h, s); /* the lists' hops for the next batch, from this batch's axcindicate (AFC's verdict included) */
+    if (has_gate(h)) launch_gate_behind_mix(h, s); /* the batch's active channels and their rows packed, encoded, spooled (driver_gate.cpp) */
+    if (has_scan_control(h)) launch_scan_control_behind_demod(h, s); /* the lists' hops for the next batch, from this batch's axcindicate (AFC's verdict included) */
     (void)hipEventRecord(ev[4], s);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
@@ -793,16 +327,6 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
     h->results_ready = true;
     harvest_timings(h, false);
     return AIRBAND_HIP_OK;
-}
-
-/* position k of the grouped mixer-input arrays: the channel it reads, or -1 while the connection (airband_hip_mixer_enable_input) or its dongle
- * (airband_hip_device_enable) is switched off -- a masked input is skipped like mixer->input_mask[i] == false (src/mixer.cpp:96-110,192) */
-hipError_t write_mix_input(airband_hip_handle* h, int k) {
-    const int ch = h->mix.chan_host[k];
-    const int v = (h->mix.user_on[k] && h->dev_enabled[h->plan.cc[ch].dev]) ? ch : -1;
-    hipError_t e = hipMemcpyAsync(h->mix.d_chan.p + k, &v, sizeof(int), hipMemcpyHostToDevice, h->stream);
-    if (e != hipSuccess) return e;
-    return hipStreamSynchronize(h->stream); /* `v` is a stack variable */
 }
 
 /* ---- airband_hip_prepare_scan() step by step, in the order it calls them ------------------------------------------------------------- */
@@ -1186,36 +710,6 @@ int prep_channelizer(airband_hip_handle* h) {
     return AIRBAND_HIP_OK;
 }
 
-/* scan lists: the banks, every entry's initial image, the masks, the switch lists' staging */
-int prep_scan(airband_hip_handle* h) {
-    const Plan& p = h->plan;
-    HIP_TRY(PREPARING, upload(h->d_bank_cc, p.scan_cc), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(PREPARING, upload(h->d_bank_cs, p.scan_cs0), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(PREPARING, h->d_bank_sq.alloc_zeroed(p.scan_cc.size() * AB_SQ_BUF), AIRBAND_HIP_ENOMEM);
-    const AbScanMasks mk = ab_scan_masks();
-    std::vector<uint32_t> masks(mk.cs, mk.cs + AB_CS_DWORDS);
-    masks.insert(masks.end(), mk.cc, mk.cc + AB_CC_DWORDS);
-    HIP_TRY(PREPARING, upload(h->d_scan_mask, masks), AIRBAND_HIP_ENOMEM);
-    const size_t nl = p.scan.size();
-    for (int q = 0; q < 2; q++) {
-        HIP_TRY(PREPARING, h->d_switch[q].alloc(nl * 3), AIRBAND_HIP_ENOMEM);
-        HIP_TRY(PREPARING, h->h_switch[q].alloc(nl * 3), AIRBAND_HIP_ENOMEM);
-        HIP_TRY(PREPARING, h->ev_switch[q].ensure(), AIRBAND_HIP_ENODEV);
-    }
-    std::vector<int> mix_slots;
-    h->scan_of_dev.assign(p.n_dev, -1);
-    for (size_t i = 0; i < nl; i++) {
-        h->scan_of_dev[p.scan[i].dev] = (int)i;
-        if (p.scan[i].mixed_am_nfm) mix_slots.push_back(h->ext_to_slot[p.scan[i].ext]);
-    }
-    if (!mix_slots.empty()) HIP_TRY(PREPARING, upload(h->d_scan_mix_slots, mix_slots), AIRBAND_HIP_ENOMEM);
-    h->scan_cur.assign(nl, 0);
-    h->scan_held.assign(nl, 0);
-    h->scan_latch[0].assign(nl, 0);
-    h->scan_latch[1].assign(nl, 0);
-    return AIRBAND_HIP_OK;
-}
-
 }  // namespace
 
 extern "C" {
@@ -1335,93 +829,13 @@ int airband_hip_get_geometry(const airband_hip_handle* h, airband_hip_geometry* 
     return AIRBAND_HIP_OK;
 }
 
-int airband_hip_set_mixers(airband_hip_handle* h, int32_t mixer_count, const airband_hip_mixer_input* in, int32_t n_in) {
-    if (!h || mixer_count < 1 || n_in < 0 || (!in && n_in > 0)) return fail(h, AIRBAND_HIP_EINVAL, "bad mixer arguments");
-    /* n_in == 0: a handle whose dongles feed no mixer still takes part in the exchange with all-zero partial sums */
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    const Plan& p = h->plan;
-    std::vector<int> first(mixer_count + 1, 0), chan(n_in);
-    std::vector<float> ml(n_in), mr(n_in);
-    std::vector<uint8_t> stereo(mixer_count, 0);
-    for (int i = 0; i < n_in; i++) {
-        if (in[i].mixer < 0 || in[i].mixer >= mixer_count || in[i].device < 0 || in[i].device >= p.n_dev || in[i].channel < 0 ||
-            in[i].channel >= p.dev[in[i].device].n_ch)
-            return fail(h, AIRBAND_HIP_EINVAL, "mixer input out of range");
-        first[in[i].mixer + 1]++;
-        if (in[i].balance != 0.0f) stereo[in[i].mixer] = 1; /* src/mixer.cpp:84-85 */
-    }
-    for (int m = 0; m < mixer_count; m++) first[m + 1] += first[m];
-    std::vector<int> cur(first.begin(), first.end() - 1);
-    std::vector<int> pos(n_in, 0);
-    for (int i = 0; i < n_in; i++) { /* stable: connection order inside a mixer is kept (summation order) */
-        const int k = cur[in[i].mixer]++;
-        pos[i] = k;
-        chan[k] = p.chan_base[in[i].device] + in[i].channel;
-        ml[k] = in[i].ampfactor * fminf(1.0f, 1.0f - in[i].balance); /* src/mixer.cpp:82-83,203-208 */
-        mr[k] = in[i].ampfactor * fminf(1.0f, 1.0f + in[i].balance);
-    }
-    std::vector<int> run_first, run_mixer, first_run(mixer_count + 1, 0);
-    for (int m = 0; m < mixer_count; m++) {
-        first_run[m] = (int)run_mixer.size();
-        for (int i = first[m]; i < first[m + 1]; i += AB_MIX_RUN) {
-            run_first.push_back(i);
-            run_mixer.push_back(m);
-        }
-    }
-    first_run[mixer_count] = (int)run_mixer.size();
-    run_first.push_back(n_in);
-    const int n_runs = (int)run_mixer.size();
-    /* the mixer kernels index runs / mixers with blockIdx.y: say so here rather than fail at the first launch */
-    if (n_runs > 65535 || mixer_count > 65535) return fail(h, AIRBAND_HIP_EBADSIZE, "more than 65 535 mixers (or runs of 64 mixer inputs) on one handle");
-    order_behind_last_batch(h);
-    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME); /* a batch under way still sums the old wiring */
-    h->mix = MixerWiring(); /* n_mixers == 0 until the new wiring is complete: a failure below leaves a handle without mixers, not one with freed tables */
-    MixerWiring& w = h->mix;
-    HIP_TRY(h, upload(w.d_run_first, run_first), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(w.d_run_mixer, run_mixer), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(w.d_first_run, first_run), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, w.d_run_left.alloc((size_t)n_runs * h->B), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, w.d_run_right.alloc((size_t)n_runs * h->B), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, w.d_run_signal.alloc((size_t)n_runs), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(w.d_chan, chan), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(w.d_first, first), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(w.d_ml, ml), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(w.d_mr, mr), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, upload(w.d_stereo, stereo), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, w.d_left.alloc((size_t)mixer_count * h->B), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, w.d_right.alloc((size_t)mixer_count * h->B), AIRBAND_HIP_ENOMEM);
-    HIP_TRY(h, w.d_signal.alloc((size_t)mixer_count), AIRBAND_HIP_ENOMEM);
-    w.pos = pos;
-    w.chan_host = chan;
-    w.user_on.assign(n_in, 1);
-    for (int k = 0; k < n_in; k++) /* inputs of dongles that are already switched off stay out */
-        if (!h->dev_enabled[p.cc[chan[k]].dev]) HIP_TRY(h, write_mix_input(h, k), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
-    w.n_runs = n_runs; /* published last */
-    w.n_mixers = mixer_count;
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_mixer_enable_input(airband_hip_handle* h, int32_t input_index, int32_t enabled) {
-    if (!h || h->mix.n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
-    if (input_index < 0 || input_index >= (int32_t)h->mix.pos.size()) return fail(h, AIRBAND_HIP_EINVAL, "mixer input index out of range");
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    const int k = h->mix.pos[input_index];
-    h->mix.user_on[k] = enabled ? 1 : 0;
-    HIP_TRY(h, write_mix_input(h, k), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
-    return AIRBAND_HIP_OK;
-}
-
 int airband_hip_device_enable(airband_hip_handle* h, int32_t dev, int32_t enabled) {
     if (!h) return AIRBAND_HIP_EINVAL;
     const Plan& p = h->plan;
     if (dev < 0 || dev >= p.n_dev) return fail(h, AIRBAND_HIP_EINVAL, "device index out of range");
     const uint8_t on = enabled ? 1 : 0;
     if (h->dev_enabled[dev].load() == on) return AIRBAND_HIP_OK;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
+    ON_OWN_STREAM(h, s);
     /* everything below is ordered on the handle's stream: the batches already enqueued still see the old state, the next one the new */
     h->plan.dev[dev].disabled = on ? 0 : 1;
     HIP_TRY(h, hipMemcpyAsync(&h->d_dev.p[dev], &h->plan.dev[dev], sizeof(DevConst), hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
@@ -1458,248 +872,6 @@ int airband_hip_device_enable(airband_hip_handle* h, int32_t dev, int32_t enable
     for (size_t k = 0; k < h->mix.chan_host.size(); k++)
         if (p.cc[h->mix.chan_host[k]].dev == dev) HIP_TRY(h, write_mix_input(h, (int)k), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME); /* the host buffers above go out of scope */
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_set_freq_index(airband_hip_handle* h, int32_t dev, int32_t freq_idx) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    if (dev < 0 || dev >= h->plan.n_dev || h->scan_of_dev.empty() || h->scan_of_dev[dev] < 0) return fail(h, AIRBAND_HIP_EINVAL, "device has no scan list");
-    const int i = h->scan_of_dev[dev];
-    if (freq_idx < 0 || freq_idx >= h->plan.scan[i].n) return fail(h, AIRBAND_HIP_EINVAL, "frequency index out of range");
-    if (h->scan_ctl.idle_batches > 0) return fail(h, AIRBAND_HIP_EINVAL, "the lists are under scan control (airband_hip_set_scan_control): the GPU sets the index");
-    h->scan_cur[i] = freq_idx; /* latched by the next batch that is enqueued */
-    return AIRBAND_HIP_OK;
-}
-
-/* Scan control: where list i (index in plan.scan) stands once everything enqueued on the handle has run -- *idx the entry in force for the next batch, *held the
- * entry its slot holds now (they differ between a hop's decision and the exchange in front of the next batch).  Two small copies and a synchronize. */
-static int scan_ctl_where(airband_hip_handle* h, int i, int* idx, int* held) {
-    const ScanControl& c = h->scan_ctl;
-    const int k = c.ctl_of[(size_t)i];
-    const ScanList& sl = h->plan.scan[(size_t)i];
-    hipStream_t s = h->stream;
-    airband_hip_scan_state st;
-    int sw[3];
-    HIP_TRY(h, hipMemcpyAsync(&st, c.d_state.p + k, sizeof(st), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipMemcpyAsync(sw, c.d_sw.p + 3 * (size_t)k, sizeof(sw), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (st.idx < 0 || st.idx >= sl.n) return fail(h, AIRBAND_HIP_ERUNTIME, "scan control: index out of range: " + std::to_string(st.idx));
-    *idx = st.idx;
-    *held = st.idx;
-    if (sw[0] >= 0) {
-        const int old = sw[1] - sl.first_entry;
-        if (old < 0 || old >= sl.n) return fail(h, AIRBAND_HIP_ERUNTIME, "scan control: switch item out of range: " + std::to_string(sw[1]));
-        *held = old;
-    }
-    return AIRBAND_HIP_OK;
-}
-
-/* Switching scan control off: the host's mirrors take over where the GPU left every list.  The stream is idle (the caller has synchronized). */
-static int scan_ctl_refresh_host(airband_hip_handle* h) {
-    const ScanControl& c = h->scan_ctl;
-    const size_t nl = c.list_of.size();
-    std::vector<airband_hip_scan_state> st(nl);
-    std::vector<int> sw(nl * 3);
-    HIP_TRY(h, hipMemcpy(st.data(), c.d_state.p, nl * sizeof(st[0]), hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipMemcpy(sw.data(), c.d_sw.p, nl * 3 * sizeof(int), hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
-    for (size_t k = 0; k < nl; k++) {
-        const int i = c.list_of[k];
-        const ScanList& sl = h->plan.scan[(size_t)i];
-        int idx = st[k].idx, held = sw[3 * k] >= 0 ? sw[3 * k + 1] - sl.first_entry : idx;
-        if (idx < 0 || idx >= sl.n || held < 0 || held >= sl.n) return fail(h, AIRBAND_HIP_ERUNTIME, "scan control: a list's index is out of range");
-        h->scan_cur[(size_t)i] = h->scan_latch[0][(size_t)i] = h->scan_latch[1][(size_t)i] = idx;
-        h->scan_held[(size_t)i] = held;
-        ChanConst& hc = h->cc_slots[(size_t)h->ext_to_slot[(size_t)sl.ext]];
-        hc.flags = (hc.flags & ~AB_SCAN_FREQ_FLAGS) | (h->plan.scan_cc[(size_t)(sl.first_entry + held)].flags & AB_SCAN_FREQ_FLAGS);
-    }
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_set_scan_control(airband_hip_handle* h, int32_t idle_batches, int32_t dwell_batches, int64_t max_records) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const Plan& p = h->plan;
-    if (p.scan.empty()) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no scan lists (airband_hip_prepare_scan)");
-    if (idle_batches < 0 || dwell_batches < 0) return fail(h, AIRBAND_HIP_EINVAL, "idle_batches and dwell_batches must not be negative");
-    for (const ScanList& sl : p.scan) /* idx, hold and last of airband_hip_scan_state and the records' indices are int16 */
-        if (idle_batches > 0 && sl.n > 32767) return fail(h, AIRBAND_HIP_EINVAL, "scan control takes lists of at most 32 767 entries (device " + std::to_string(sl.dev) + " has " + std::to_string(sl.n) + ")");
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    order_behind_last_batch(h);
-    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME); /* the decisions and exchanges enqueued so far have run */
-    if (h->scan_ctl.idle_batches > 0) { /* on -> off, and on -> on through off: the lists keep their entries */
-        const int rc = scan_ctl_refresh_host(h);
-        if (rc != AIRBAND_HIP_OK) return rc;
-        if (idle_batches == 0) {
-            h->scan_ctl = ScanControl();
-            return AIRBAND_HIP_OK;
-        }
-    } else if (idle_batches == 0) {
-        return AIRBAND_HIP_OK;
-    }
-    const size_t nl = p.scan.size();
-    ScanControl c; /* built beside the handle and moved in whole: a failed allocation leaves the handle as it was (an earlier control is off then, its lists the host's) */
-    c.list_of.resize(nl);
-    for (size_t i = 0; i < nl; i++) c.list_of[i] = (int)i;
-    std::sort(c.list_of.begin(), c.list_of.end(), [&](int x, int y) { return p.scan[(size_t)x].dev < p.scan[(size_t)y].dev; });
-    c.ctl_of.resize(nl);
-    std::vector<ScanCtlList> lists(nl);
-    std::vector<airband_hip_scan_state> start(nl);
-    std::vector<int> sw(nl * 3, 0);
-    /* a pipelined handle may have a batch whose stage 1 is enqueued and whose stage 2 is not: that batch runs with the entry it was enqueued with (scan_latch), and
-     * the lists start from there -- an index airband_hip_set_freq_index() named after that batch was enqueued has not been latched by any batch and is dropped */
-    const bool pending = h->front_batches > h->batches_done;
-    for (size_t k = 0; k < nl; k++) {
-        const int i = c.list_of[k];
-        const ScanList& sl = p.scan[(size_t)i];
-        c.ctl_of[(size_t)i] = (int)k;
-        ScanCtlList& l = lists[k];
-        std::memset(&l, 0, sizeof(l));
-        l.dev = sl.dev;
-        l.ext = sl.ext;
-        l.slot = h->ext_to_slot[(size_t)sl.ext];
-        l.first_entry = sl.first_entry;
-        l.n = sl.n;
-        airband_hip_scan_state& st = start[k];
-        std::memset(&st, 0, sizeof(st));
-        const int from = pending ? h->scan_latch[h->batches_done & 1][(size_t)i] : h->scan_cur[(size_t)i];
-        st.idx = (int16_t)from;
-        st.hold = -1;
-        st.has_list = 1;
-        /* that entry may not be in the slot yet: the first exchange brings it in */
-        const bool move = h->scan_held[(size_t)i] != from;
-        sw[3 * k] = move ? l.slot : -1;
-        sw[3 * k + 1] = sl.first_entry + h->scan_held[(size_t)i];
-        sw[3 * k + 2] = sl.first_entry + from;
-    }
-    const int64_t cap = (max_records <= 0 || max_records > (int64_t)nl) ? (int64_t)nl : max_records;
-    hipError_t e = upload(c.d_lists, lists);
-    if (e == hipSuccess) e = upload(c.d_state, start);
-    if (e == hipSuccess) e = upload(c.d_sw, sw);
-    if (e == hipSuccess) e = c.d_stage.alloc_zeroed(nl);
-    if (e == hipSuccess) e = c.d_stage_n.alloc_zeroed(nl);
-    if (e == hipSuccess) e = c.d_events.alloc_zeroed((size_t)cap);
-    if (e == hipSuccess) e = c.d_count.alloc_zeroed(1);
-    if (e == hipSuccess) e = hipDeviceSynchronize(); /* the initial values are in place before a kernel on the handle's streams reads them */
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        h->scan_ctl = ScanControl();
-        return fail(h, AIRBAND_HIP_ENOMEM, std::string("scan control buffers: ") + hipGetErrorString(e));
-    }
-    c.idle_batches = idle_batches;
-    c.dwell_batches = dwell_batches < 1 ? 1 : dwell_batches;
-    c.max_records = (int)cap;
-    h->scan_ctl = std::move(c);
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_scan_hold(airband_hip_handle* h, int32_t dev, int32_t freq_idx) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    ScanControl& c = h->scan_ctl;
-    if (c.idle_batches <= 0) return fail(h, AIRBAND_HIP_EINVAL, "scan control is off (airband_hip_set_scan_control)");
-    if (dev < 0 || dev >= h->plan.n_dev || h->scan_of_dev.empty() || h->scan_of_dev[dev] < 0) return fail(h, AIRBAND_HIP_EINVAL, "device has no scan list");
-    const int i = h->scan_of_dev[dev];
-    if (freq_idx < -1 || freq_idx >= h->plan.scan[(size_t)i].n) return fail(h, AIRBAND_HIP_EINVAL, "frequency index out of range");
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    /* in the stream's order: behind the decisions already enqueued, in front of the next batch's */
-    const int16_t hold = (int16_t)freq_idx;
-    HIP_TRY(h, hipMemcpyAsync(&c.d_state.p[c.ctl_of[(size_t)i]].hold, &hold, sizeof(hold), hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME); /* `hold` is a stack variable */
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_collect_scan_events(airband_hip_handle* h, int64_t* n_records, airband_hip_scan_event* records) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const ScanControl& c = h->scan_ctl;
-    if (c.idle_batches <= 0) return fail(h, AIRBAND_HIP_EINVAL, "scan control is off (airband_hip_set_scan_control)");
-    if (c.batch == 0) return AIRBAND_HIP_EAGAIN;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    int count = 0;
-    HIP_TRY(h, hipMemcpyAsync(&count, c.d_count.p, sizeof(int), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (count < 0 || (size_t)count > c.list_of.size()) return fail(h, AIRBAND_HIP_ERUNTIME, "record count out of range: " + std::to_string(count));
-    if (n_records) *n_records = count;
-    const size_t n = (size_t)(count < c.max_records ? count : c.max_records);
-    if (records && n) {
-        HIP_TRY(h, hipMemcpyAsync(records, c.d_events.p, n * sizeof(airband_hip_scan_event), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-        HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    }
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_collect_scan_state(airband_hip_handle* h, int32_t first_dev, int32_t n_dev, airband_hip_scan_state* state) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const ScanControl& c = h->scan_ctl;
-    if (c.idle_batches <= 0) return fail(h, AIRBAND_HIP_EINVAL, "scan control is off (airband_hip_set_scan_control)");
-    if (first_dev < 0 || n_dev < 0 || (int64_t)first_dev + n_dev > h->plan.n_dev) return fail(h, AIRBAND_HIP_EINVAL, "device range out of bounds");
-    if (!state || n_dev == 0) return AIRBAND_HIP_OK;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    /* the lists are in ascending dongle order: those of the range are one run of the array -- one copy, then dealt out to the range's dongles */
-    int k0 = -1, n = 0;
-    for (int d = first_dev; d < first_dev + n_dev; d++)
-        if (h->scan_of_dev[(size_t)d] >= 0) {
-            if (k0 < 0) k0 = c.ctl_of[(size_t)h->scan_of_dev[(size_t)d]];
-            n++;
-        }
-    std::vector<airband_hip_scan_state> tmp((size_t)n);
-    if (n) HIP_TRY(h, hipMemcpyAsync(tmp.data(), c.d_state.p + k0, (size_t)n * sizeof(tmp[0]), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    for (int d = first_dev; d < first_dev + n_dev; d++) {
-        airband_hip_scan_state& o = state[d - first_dev];
-        const int i = h->scan_of_dev[(size_t)d];
-        if (i < 0) std::memset(&o, 0, sizeof(o));
-        else o = tmp[(size_t)(c.ctl_of[(size_t)i] - k0)];
-    }
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_device_scan_control(airband_hip_handle* h, int32_t** d_n_records, airband_hip_scan_event** d_records, airband_hip_scan_state** d_state) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const ScanControl& c = h->scan_ctl;
-    if (c.idle_batches <= 0) return fail(h, AIRBAND_HIP_EINVAL, "scan control is off (airband_hip_set_scan_control)");
-    if (d_n_records) *d_n_records = c.d_count.p;
-    if (d_records) *d_records = c.d_events.p;
-    if (d_state) *d_state = c.d_state.p;
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_freq_stats(airband_hip_handle* h, int32_t dev, int32_t freq_idx, airband_hip_channel_stats* out) {
-    if (!h || !out) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
-    if (dev < 0 || dev >= h->plan.n_dev || h->scan_of_dev.empty() || h->scan_of_dev[dev] < 0) return fail(h, AIRBAND_HIP_EINVAL, "device has no scan list");
-    const int i = h->scan_of_dev[dev];
-    const ScanList& sl = h->plan.scan[i];
-    if (freq_idx < 0 || freq_idx >= sl.n) return fail(h, AIRBAND_HIP_EINVAL, "frequency index out of range");
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    if (!h->d_fs_zero.p) {
-        HIP_TRY(h, h->d_fs_cc.alloc(1), AIRBAND_HIP_ENOMEM);
-        HIP_TRY(h, h->d_fs_cs.alloc(1), AIRBAND_HIP_ENOMEM);
-        HIP_TRY(h, h->d_fs_stats.alloc(1), AIRBAND_HIP_ENOMEM);
-        HIP_TRY(h, h->d_fs_zero.alloc(1), AIRBAND_HIP_ENOMEM);
-        HIP_TRY(h, hipMemsetAsync(h->d_fs_zero.p, 0, sizeof(int), s), AIRBAND_HIP_ERUNTIME);
-    }
-    const int slot = h->ext_to_slot[sl.ext];
-    int held = h->scan_held[i];
-    if (h->scan_ctl.idle_batches > 0) { /* scan control: which entry the slot holds is on the device */
-        int idx = 0;
-        const int rc = scan_ctl_where(h, i, &idx, &held);
-        if (rc != AIRBAND_HIP_OK) return rc;
-    }
-    /* the stats kernel of airband_hip_collect() on one image: the slot itself for the entry it holds, else the slot composed with the entry's bank */
-    if (freq_idx == held) {
-        launch_stats(h->d_cc.p + slot, h->d_cs.p + slot, h->d_fs_zero.p, 1, h->d_fs_stats.p, s);
-    } else {
-        launch_scan_compose(scan_args(h), slot, sl.first_entry + freq_idx, h->d_fs_cc.p, h->d_fs_cs.p, s);
-        launch_stats(h->d_fs_cc.p, h->d_fs_cs.p, h->d_fs_zero.p, 1, h->d_fs_stats.p, s);
-    }
-    HIP_TRY(h, hipGetLastError(), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipMemcpyAsync(out, h->d_fs_stats.p, sizeof(airband_hip_channel_stats), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
     return AIRBAND_HIP_OK;
 }
 
@@ -1990,9 +1162,7 @@ static int collect_range(airband_hip_handle* h, int64_t first, int64_t n, float*
     if (first < 0 || n < 0 || first + n > h->plan.total_ch) return fail(h, AIRBAND_HIP_EINVAL, "channel range out of bounds");
     if (!h->results_ready && consume) return AIRBAND_HIP_EAGAIN;
     if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
+    ON_OWN_STREAM(h, s);
     const size_t nch = (size_t)n;
     if (stats && nch) {
         if (!h->d_stats.p) HIP_TRY(h, h->d_stats.alloc((size_t)h->plan.total_ch), AIRBAND_HIP_ENOMEM);
@@ -2023,694 +1193,6 @@ int airband_hip_collect(airband_hip_handle* h, float* waveout, float* iq_out, ch
 int airband_hip_collect_channels(airband_hip_handle* h, int64_t first_channel, int64_t n_channels, float* waveout, float* iq_out, char* axc,
                                  airband_hip_channel_stats* stats) {
     return collect_range(h, first_channel, n_channels, waveout, iq_out, axc, stats, false);
-}
-
-int airband_hip_set_output_gate(airband_hip_handle* h, const uint8_t* gate, int64_t max_rows) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    if (!gate) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
-    const Plan& p = h->plan;
-    if (max_rows < 1 || max_rows > p.total_ch) return fail(h, AIRBAND_HIP_EINVAL, "max_rows must lie in 1 .. total_channels");
-    for (int c = 0; c < p.total_ch; c++)
-        if (gate[c] > AIRBAND_GATE_ALWAYS) return fail(h, AIRBAND_HIP_EINVAL, "gate byte of channel " + std::to_string(c) + " is not an AIRBAND_GATE_* value");
-    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the output gate is set before the first batch");
-    if (h->B % 4) return fail(h, AIRBAND_HIP_EBADSIZE, "the gather moves four samples per lane: WAVE_BATCH must be a multiple of four");
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    /* built beside the handle and moved in whole: a failed allocation leaves the handle as it was */
-    OutputGate g;
-    g.gate.assign(gate, gate + p.total_ch);
-    std::vector<uint8_t> bytes(g.gate);
-    for (int c = 0; c < p.total_ch; c++)
-        if (!h->dev_enabled[p.cc[c].dev]) bytes[c] |= AB_GATE_OFF; /* dongles that are switched off already */
-    const size_t rows = (size_t)max_rows;
-    hipError_t e = upload(g.d_gate, bytes);
-    if (e == hipSuccess) e = g.d_prev.alloc_zeroed((size_t)p.total_ch);
-    if (e == hipSuccess) e = g.d_mask.alloc(((size_t)p.total_ch + 63) / 64);
-    if (e == hipSuccess) e = g.d_block_count.alloc((size_t)gate_blocks(p.total_ch));
-    if (e == hipSuccess) e = g.d_index.alloc(rows);
-    if (e == hipSuccess) e = g.d_count.alloc_zeroed(1);
-    if (e == hipSuccess) e = g.d_rows.alloc(rows * h->B);
-    if (e == hipSuccess && h->d_out_iq.p) e = g.d_iq_rows.alloc(rows * h->B * 2);
-    if (e != hipSuccess) {
-        (void)hipGetLastError(); /* the failed allocation is this call's error, reported here: not the next launch's */
-        return fail(h, AIRBAND_HIP_ENOMEM, std::string("output gate buffers: ") + hipGetErrorString(e));
-    }
-    g.max_rows = (int)max_rows;
-    h->gate = std::move(g);
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_set_band_scope(airband_hip_handle* h, const uint8_t* dev_mask, int32_t windows_per_batch, uint32_t traces) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const Plan& p = h->plan;
-    if (windows_per_batch < 1 || windows_per_batch > h->B) return fail(h, AIRBAND_HIP_EINVAL, "windows_per_batch must lie in 1 .. WAVE_BATCH");
-    if (traces == 0 || (traces & ~(uint32_t)(AIRBAND_SCOPE_MEAN | AIRBAND_SCOPE_PEAK))) return fail(h, AIRBAND_HIP_EINVAL, "traces must be a non-empty set of AIRBAND_SCOPE_* bits");
-    BandScope sc;
-    sc.row_of_dev.assign((size_t)p.n_dev, -1);
-    std::vector<int> dev_of_row;
-    for (int d = 0; d < p.n_dev; d++)
-        if (!dev_mask || dev_mask[d]) {
-            sc.row_of_dev[d] = (int)dev_of_row.size();
-            dev_of_row.push_back(d);
-        }
-    if (dev_of_row.empty()) return fail(h, AIRBAND_HIP_EINVAL, "the mask selects no dongle");
-    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the band scope is set before the first batch");
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    /* built beside the handle and moved in whole: a failed allocation leaves the handle as it was */
-    sc.windows = windows_per_batch;
-    sc.traces = traces;
-    sc.n_rows = (int)dev_of_row.size();
-    sc.n_sets = deep_rings(h) ? 2 : 1; /* where the next stage 1 may run before this batch's results are collected (the validity rule of the result buffers) */
-    const size_t n = (size_t)sc.n_rows * (size_t)h->N;
-    hipError_t e = upload(sc.d_row_of_dev, sc.row_of_dev);
-    if (e == hipSuccess) e = upload(sc.d_dev_of_row, dev_of_row);
-    for (int q = 0; q < sc.n_sets; q++) {
-        if (e == hipSuccess && (traces & AIRBAND_SCOPE_MEAN)) e = sc.d_mean[q].alloc_zeroed(n);
-        if (e == hipSuccess && (traces & AIRBAND_SCOPE_PEAK)) e = sc.d_peak[q].alloc_zeroed(n);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize(); /* the zeros are in place before a kernel on another stream writes the rows */
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&sc.stream.v, hipStreamNonBlocking);
-    if (e == hipSuccess) e = sc.ev_fork.ensure();
-    if (e == hipSuccess) e = sc.ev_done.ensure();
-    if (e != hipSuccess) {
-        (void)hipGetLastError(); /* this call's error, reported here: not the next launch's */
-        return fail(h, AIRBAND_HIP_ENOMEM, std::string("band scope buffers: ") + hipGetErrorString(e));
-    }
-    h->scope = std::move(sc);
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_collect_band_scope(airband_hip_handle* h, int32_t first_dev, int32_t n_dev, float* mean, float* peak) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const BandScope& sc = h->scope;
-    if (sc.windows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band scope (airband_hip_set_band_scope)");
-    if (first_dev < 0 || n_dev < 0 || (int64_t)first_dev + n_dev > h->plan.n_dev) return fail(h, AIRBAND_HIP_EINVAL, "device range out of bounds");
-    if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    const size_t N = (size_t)h->N;
-    float* const out[2] = {mean, peak};
-    const float* const src[2] = {sc.d_mean[sc.cur].p, sc.d_peak[sc.cur].p};
-    for (int t = 0; t < 2; t++) {
-        if (!out[t]) continue;
-        for (int i = 0; i < n_dev;) { /* runs of selected dongles are runs of rows: one copy each */
-            const int row = src[t] ? sc.row_of_dev[first_dev + i] : -1;
-            int j = i + 1;
-            if (row < 0) { /* not selected (or a trace the scope does not keep): zeros */
-                std::memset(out[t] + (size_t)i * N, 0, N * sizeof(float));
-            } else {
-                while (j < n_dev && sc.row_of_dev[first_dev + j] >= 0) j++;
-                HIP_TRY(h, hipMemcpyAsync(out[t] + (size_t)i * N, src[t] + (size_t)row * N, (size_t)(j - i) * N * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-            }
-            i = j;
-        }
-    }
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_device_band_scope(airband_hip_handle* h, float** d_mean, float** d_peak, int32_t** d_row_of_dev) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const BandScope& sc = h->scope;
-    if (sc.windows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band scope (airband_hip_set_band_scope)");
-    if (d_mean) *d_mean = sc.d_mean[sc.cur].p;
-    if (d_peak) *d_peak = sc.d_peak[sc.cur].p;
-    if (d_row_of_dev) *d_row_of_dev = sc.d_row_of_dev.p;
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_set_band_survey(airband_hip_handle* h, uint32_t trace, int32_t max_peaks, int32_t floor_permille, float threshold_ratio, int32_t guard_bins) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const Plan& p = h->plan;
-    BandScope& sc = h->scope;
-    if (sc.windows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band scope (airband_hip_set_band_scope)");
-    if ((trace != AIRBAND_SCOPE_MEAN && trace != AIRBAND_SCOPE_PEAK) || !(sc.traces & trace))
-        return fail(h, AIRBAND_HIP_EINVAL, "trace must be exactly one AIRBAND_SCOPE_* bit the scope keeps");
-    if (max_peaks < 1 || max_peaks > 64) return fail(h, AIRBAND_HIP_EINVAL, "max_peaks must lie in 1 .. 64");
-    if (floor_permille < 0 || floor_permille > 1000) return fail(h, AIRBAND_HIP_EINVAL, "floor_permille must lie in 0 .. 1000");
-    if (!std::isfinite(threshold_ratio) || !(threshold_ratio > 0.0f)) return fail(h, AIRBAND_HIP_EINVAL, "threshold_ratio must be finite and above 0");
-    if (guard_bins < -1 || guard_bins > h->N / 2) return fail(h, AIRBAND_HIP_EINVAL, "guard_bins must lie in -1 .. fft_size / 2");
-    if (p.fft_log < 8 || p.fft_log > 13) return fail(h, AIRBAND_HIP_EINVAL, "the band survey takes fft sizes 256 .. 8192");
-    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the band survey is set before the first batch");
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    /* built beside the handle and moved in whole: a failed allocation leaves the handle, its scope and an earlier survey as they were */
-    BandSurvey sv;
-    sv.trace = trace;
-    sv.rank = (int)std::min<int64_t>((int64_t)h->N - 1, (int64_t)h->N * floor_permille / 1000);
-    sv.guard_bins = guard_bins;
-    sv.ratio = threshold_ratio;
-    std::vector<int> bin_first(1, 0), bins;
-    for (int d = 0; d < p.n_dev; d++) {
-        if (sc.row_of_dev[d] < 0) continue;
-        for (int j = 0; j < p.dev[d].n_ch; j++) bins.push_back(p.cc[p.chan_base[d] + j].base_bin); /* the prepare-time bin: slot [0] of airband_hip_channel_constants() */
-        bin_first.push_back((int)bins.size());
-    }
-    const std::vector<airband_hip_band_peak> none((size_t)sc.n_rows * (size_t)max_peaks, airband_hip_band_peak{-1, 0.0f});
-    hipError_t e = upload(sv.d_bin_first, bin_first);
-    if (e == hipSuccess) e = upload(sv.d_bins, bins);
-    for (int q = 0; q < sc.n_sets; q++) {
-        if (e == hipSuccess) e = sv.d_summary[q].alloc_zeroed((size_t)sc.n_rows);
-        if (e == hipSuccess) e = upload(sv.d_peaks[q], none);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize(); /* the initial values are in place before a kernel on another stream writes the rows */
-    if (e != hipSuccess) {
-        (void)hipGetLastError(); /* this call's error, reported here: not the next launch's */
-        return fail(h, AIRBAND_HIP_ENOMEM, std::string("band survey buffers: ") + hipGetErrorString(e));
-    }
-    sv.max_peaks = max_peaks;
-    sc.survey = std::move(sv);
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_collect_band_survey(airband_hip_handle* h, int32_t first_dev, int32_t n_dev, airband_hip_band_summary* summary, airband_hip_band_peak* peaks) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const BandScope& sc = h->scope;
-    const BandSurvey& sv = sc.survey;
-    if (sc.windows <= 0 || sv.max_peaks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band survey (airband_hip_set_band_survey)");
-    if (first_dev < 0 || n_dev < 0 || (int64_t)first_dev + n_dev > h->plan.n_dev) return fail(h, AIRBAND_HIP_EINVAL, "device range out of bounds");
-    if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    if (summary) {
-        const int rc = collect_survey_rows(h, sv.d_summary[sc.cur].p, 1, first_dev, n_dev, summary, airband_hip_band_summary{}, s);
-        if (rc != AIRBAND_HIP_OK) return rc;
-    }
-    if (peaks) {
-        const int rc = collect_survey_rows(h, sv.d_peaks[sc.cur].p, (size_t)sv.max_peaks, first_dev, n_dev, peaks, airband_hip_band_peak{-1, 0.0f}, s);
-        if (rc != AIRBAND_HIP_OK) return rc;
-    }
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_device_band_survey(airband_hip_handle* h, airband_hip_band_summary** d_summary, airband_hip_band_peak** d_peaks) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const BandScope& sc = h->scope;
-    if (sc.windows <= 0 || sc.survey.max_peaks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band survey (airband_hip_set_band_survey)");
-    if (d_summary) *d_summary = sc.survey.d_summary[sc.cur].p;
-    if (d_peaks) *d_peaks = sc.survey.d_peaks[sc.cur].p;
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_set_band_watch(airband_hip_handle* h, int32_t max_tracks, int32_t match_bins, int32_t confirm_hits, int32_t release_misses, int64_t max_events) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    BandScope& sc = h->scope;
-    BandSurvey& sv = sc.survey;
-    if (sc.windows <= 0 || sv.max_peaks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band survey (airband_hip_set_band_survey)");
-    if (max_tracks < 1 || max_tracks > 64) return fail(h, AIRBAND_HIP_EINVAL, "max_tracks must lie in 1 .. 64");
-    if (match_bins < 0 || match_bins > h->N / 2) return fail(h, AIRBAND_HIP_EINVAL, "match_bins must lie in 0 .. fft_size / 2");
-    if (confirm_hits < 1 || confirm_hits > 255) return fail(h, AIRBAND_HIP_EINVAL, "confirm_hits must lie in 1 .. 255");
-    if (release_misses < 1 || release_misses > 255) return fail(h, AIRBAND_HIP_EINVAL, "release_misses must lie in 1 .. 255");
-    const int64_t per_row = (int64_t)max_tracks + sv.max_peaks, most = (int64_t)sc.n_rows * per_row;
-    if (max_events < 1 || max_events > most || max_events > INT32_MAX) return fail(h, AIRBAND_HIP_EINVAL, "max_events must lie in 1 .. rows * (max_tracks + max_peaks)");
-    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the band watch is set before the first batch");
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    /* built beside the handle and moved in whole: a failed allocation leaves the handle, its survey and an earlier watch as they were */
-    BandWatch w;
-    w.match_bins = match_bins;
-    w.confirm_hits = confirm_hits;
-    w.release_misses = release_misses;
-    w.max_events = (int)max_events;
-    airband_hip_band_track none;
-    std::memset(&none, 0, sizeof(none));
-    none.bin = -1;
-    const std::vector<airband_hip_band_track> free_slots((size_t)sc.n_rows * (size_t)max_tracks, none);
-    hipError_t e = w.d_stage.alloc((size_t)most);
-    for (int q = 0; q < sc.n_sets; q++) {
-        if (e == hipSuccess) e = upload(w.d_tracks[q], free_slots);
-        if (e == hipSuccess) e = w.d_rows[q].alloc_zeroed((size_t)sc.n_rows);
-        if (e == hipSuccess) e = w.d_events[q].alloc_zeroed((size_t)max_events);
-        if (e == hipSuccess) e = w.d_count[q].alloc_zeroed(1);
-    }
-    if (e == hipSuccess) e = hipDeviceSynchronize(); /* the initial values are in place before a kernel on another stream reads the tables */
-    if (e != hipSuccess) {
-        (void)hipGetLastError(); /* this call's error, reported here: not the next launch's */
-        return fail(h, AIRBAND_HIP_ENOMEM, std::string("band watch buffers: ") + hipGetErrorString(e));
-    }
-    w.max_tracks = max_tracks;
-    sv.watch = std::move(w);
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_collect_band_events(airband_hip_handle* h, int64_t* n_events, airband_hip_band_event* events) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const BandScope& sc = h->scope;
-    const BandWatch& w = sc.survey.watch;
-    if (sc.windows <= 0 || sc.survey.max_peaks <= 0 || w.max_tracks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band watch (airband_hip_set_band_watch)");
-    if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    /* how many events there are is on the device: the count first, then exactly those records */
-    int count = 0;
-    HIP_TRY(h, hipMemcpyAsync(&count, w.d_count[sc.cur].p, sizeof(int), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (count < 0 || (int64_t)count > (int64_t)sc.n_rows * (w.max_tracks + sc.survey.max_peaks)) return fail(h, AIRBAND_HIP_ERUNTIME, "event count out of range: " + std::to_string(count));
-    if (n_events) *n_events = count;
-    const size_t n = (size_t)(count < w.max_events ? count : w.max_events);
-    if (events && n) {
-        HIP_TRY(h, hipMemcpyAsync(events, w.d_events[sc.cur].p, n * sizeof(airband_hip_band_event), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-        HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    }
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_collect_band_tracks(airband_hip_handle* h, int32_t first_dev, int32_t n_dev, airband_hip_band_watch_row* rows, airband_hip_band_track* tracks) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const BandScope& sc = h->scope;
-    const BandWatch& w = sc.survey.watch;
-    if (sc.windows <= 0 || sc.survey.max_peaks <= 0 || w.max_tracks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band watch (airband_hip_set_band_watch)");
-    if (first_dev < 0 || n_dev < 0 || (int64_t)first_dev + n_dev > h->plan.n_dev) return fail(h, AIRBAND_HIP_EINVAL, "device range out of bounds");
-    if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    if (rows) {
-        const int rc = collect_survey_rows(h, w.d_rows[sc.cur].p, 1, first_dev, n_dev, rows, airband_hip_band_watch_row{}, s);
-        if (rc != AIRBAND_HIP_OK) return rc;
-    }
-    if (tracks) {
-        airband_hip_band_track none;
-        std::memset(&none, 0, sizeof(none));
-        none.bin = -1;
-        const int rc = collect_survey_rows(h, w.d_tracks[sc.cur].p, (size_t)w.max_tracks, first_dev, n_dev, tracks, none, s);
-        if (rc != AIRBAND_HIP_OK) return rc;
-    }
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_device_band_watch(airband_hip_handle* h, int32_t** d_n_events, airband_hip_band_event** d_events, airband_hip_band_watch_row** d_rows, airband_hip_band_track** d_tracks) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const BandScope& sc = h->scope;
-    const BandWatch& w = sc.survey.watch;
-    if (sc.windows <= 0 || sc.survey.max_peaks <= 0 || w.max_tracks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band watch (airband_hip_set_band_watch)");
-    if (d_n_events) *d_n_events = w.d_count[sc.cur].p;
-    if (d_events) *d_events = w.d_events[sc.cur].p;
-    if (d_rows) *d_rows = w.d_rows[sc.cur].p;
-    if (d_tracks) *d_tracks = w.d_tracks[sc.cur].p;
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_set_band_follow(airband_hip_handle* h, int64_t max_changes) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const Plan& p = h->plan;
-    BandScope& sc = h->scope;
-    BandWatch& w = sc.survey.watch;
-    if (sc.windows <= 0 || sc.survey.max_peaks <= 0 || w.max_tracks <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band watch (airband_hip_set_band_watch)");
-    const int64_t n_follow = (int64_t)p.follow_ext.size();
-    if (n_follow == 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no followers (airband_hip_prepare_follow)");
-    const int64_t most = n_follow + (int64_t)sc.n_rows * w.max_tracks;
-    if (max_changes < 1 || max_changes > most || max_changes > INT32_MAX) return fail(h, AIRBAND_HIP_EINVAL, "max_changes must lie in 1 .. followers + rows * max_tracks");
-    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the band follow is set before the first batch");
-    if (sc.n_sets != 1) return fail(h, AIRBAND_HIP_EINVAL, "a handle with followers keeps one set of scope rows"); /* (it never runs ahead: airband_hip_prepare_follow) */
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    /* the followers in prepare order are in ascending dongle order, as the scope's rows are: a row's followers are one range */
-    std::vector<int> range((size_t)sc.n_rows * 2, 0), slot, home;
-    std::vector<airband_hip_band_follower> start;
-    int most_per_row = 0;
-    for (size_t i = 0; i < p.follow_ext.size(); i++) {
-        const int ext = p.follow_ext[i];
-        const ChanConst& c = p.cc[(size_t)ext];
-        const int row = sc.row_of_dev[(size_t)c.dev];
-        if (row >= 0) {
-            if (range[(size_t)row * 2 + 1]++ == 0) range[(size_t)row * 2] = (int)i;
-            most_per_row = std::max(most_per_row, range[(size_t)row * 2 + 1]);
-        }
-        slot.push_back(h->ext_to_slot[(size_t)ext]);
-        home.push_back(c.base_bin);
-        airband_hip_band_follower f;
-        std::memset(&f, 0, sizeof(f));
-        f.channel = ext;
-        f.bin = c.base_bin;
-        f.track = -1;
-        start.push_back(f);
-    }
-    /* built beside the handle and moved in whole: a failed allocation leaves the handle, its watch and an earlier follow as they were */
-    BandFollow fo;
-    fo.cap = most_per_row + w.max_tracks;
-    hipError_t e = upload(fo.d_range, range);
-    if (e == hipSuccess) e = upload(fo.d_slot, slot);
-    if (e == hipSuccess) e = upload(fo.d_home, home);
-    if (e == hipSuccess) e = upload(fo.d_followers, start);
-    if (e == hipSuccess) e = fo.d_rows.alloc_zeroed((size_t)sc.n_rows);
-    if (e == hipSuccess) e = fo.d_stage.alloc((size_t)sc.n_rows * (size_t)fo.cap);
-    if (e == hipSuccess) e = fo.d_changes.alloc_zeroed((size_t)max_changes);
-    if (e == hipSuccess) e = fo.d_count.alloc_zeroed(1);
-    if (e == hipSuccess) e = hipDeviceSynchronize(); /* the initial values are in place before a kernel on another stream reads them */
-    if (e != hipSuccess) {
-        (void)hipGetLastError(); /* this call's error, reported here: not the next launch's */
-        return fail(h, AIRBAND_HIP_ENOMEM, std::string("band follow buffers: ") + hipGetErrorString(e));
-    }
-    fo.max_changes = (int)max_changes;
-    w.follow = std::move(fo);
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_collect_band_follow_changes(airband_hip_handle* h, int64_t* n_changes, airband_hip_band_follow_change* changes) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const BandScope& sc = h->scope;
-    const BandWatch& w = sc.survey.watch;
-    const BandFollow& fo = w.follow;
-    if (sc.windows <= 0 || sc.survey.max_peaks <= 0 || w.max_tracks <= 0 || fo.max_changes <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band follow (airband_hip_set_band_follow)");
-    if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    /* how many changes there are is on the device: the count first, then exactly those records */
-    int count = 0;
-    HIP_TRY(h, hipMemcpyAsync(&count, fo.d_count.p, sizeof(int), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (count < 0 || (int64_t)count > (int64_t)sc.n_rows * fo.cap) return fail(h, AIRBAND_HIP_ERUNTIME, "change count out of range: " + std::to_string(count));
-    if (n_changes) *n_changes = count;
-    const size_t n = (size_t)(count < fo.max_changes ? count : fo.max_changes);
-    if (changes && n) {
-        HIP_TRY(h, hipMemcpyAsync(changes, fo.d_changes.p, n * sizeof(airband_hip_band_follow_change), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-        HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    }
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_collect_band_followers(airband_hip_handle* h, airband_hip_band_follower* followers, airband_hip_band_follow_row* rows) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const BandScope& sc = h->scope;
-    const BandWatch& w = sc.survey.watch;
-    const BandFollow& fo = w.follow;
-    if (sc.windows <= 0 || sc.survey.max_peaks <= 0 || w.max_tracks <= 0 || fo.max_changes <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band follow (airband_hip_set_band_follow)");
-    if (h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    if (followers) {
-        HIP_TRY(h, hipMemcpyAsync(followers, fo.d_followers.p, fo.d_followers.n * sizeof(airband_hip_band_follower), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-        HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    }
-    if (rows) return collect_survey_rows(h, fo.d_rows.p, 1, 0, h->plan.n_dev, rows, airband_hip_band_follow_row{}, s);
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_device_band_follow(airband_hip_handle* h, int32_t** d_n_changes, airband_hip_band_follow_change** d_changes, airband_hip_band_follower** d_followers, airband_hip_band_follow_row** d_rows) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const BandWatch& w = h->scope.survey.watch;
-    const BandFollow& fo = w.follow;
-    if (h->scope.windows <= 0 || h->scope.survey.max_peaks <= 0 || w.max_tracks <= 0 || fo.max_changes <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no band follow (airband_hip_set_band_follow)");
-    if (d_n_changes) *d_n_changes = fo.d_count.p;
-    if (d_changes) *d_changes = fo.d_changes.p;
-    if (d_followers) *d_followers = fo.d_followers.p;
-    if (d_rows) *d_rows = fo.d_rows.p;
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_collect_active(airband_hip_handle* h, int64_t* n_active, int32_t* channel_index, float* waveout, float* iq_out, char* axc_all) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const OutputGate& g = h->gate;
-    if (g.max_rows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output gate (airband_hip_set_output_gate)");
-    if (!h->results_ready || h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    /* how many rows there are is on the device: the count first, then exactly those rows */
-    int count = 0;
-    HIP_TRY(h, hipMemcpyAsync(&count, g.d_count.p, sizeof(int), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (count < 0 || count > h->plan.total_ch) return fail(h, AIRBAND_HIP_ERUNTIME, "active count out of range: " + std::to_string(count));
-    const size_t n = (size_t)(count < g.max_rows ? count : g.max_rows), B = (size_t)h->B;
-    if (channel_index && n) HIP_TRY(h, hipMemcpyAsync(channel_index, g.d_index.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (waveout && n) HIP_TRY(h, hipMemcpyAsync(waveout, g.d_rows.p, n * B * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (iq_out && n) {
-        if (g.d_iq_rows.p)
-            HIP_TRY(h, hipMemcpyAsync(iq_out, g.d_iq_rows.p, n * B * 2 * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-        else
-            std::memset(iq_out, 0, n * B * 2 * sizeof(float));
-    }
-    if (axc_all) HIP_TRY(h, hipMemcpyAsync(axc_all, h->d_out_axc.p, (size_t)h->plan.total_ch, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (n_active) *n_active = count;
-    h->results_ready = false;
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_device_active(airband_hip_handle* h, int32_t** d_index, int32_t** d_count, float** d_rows, float** d_iq_rows) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const OutputGate& g = h->gate;
-    if (g.max_rows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output gate (airband_hip_set_output_gate)");
-    if (d_index) *d_index = g.d_index.p;
-    if (d_count) *d_count = g.d_count.p;
-    if (d_rows) *d_rows = g.d_rows.p;
-    if (d_iq_rows) *d_iq_rows = g.d_iq_rows.p;
-    return AIRBAND_HIP_OK;
-}
-
-static bool audio_encoding_known(int32_t e) { return e == AIRBAND_AUDIO_S16 || e == AIRBAND_AUDIO_ULAW || e == AIRBAND_AUDIO_ALAW; }
-static size_t audio_sample_bytes(int e) { return e == AIRBAND_AUDIO_S16 ? 2 : 1; }
-
-int airband_hip_set_output_encoding(airband_hip_handle* h, int32_t encoding) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    OutputGate& g = h->gate;
-    if (g.max_rows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output gate (airband_hip_set_output_gate)");
-    if (encoding != AIRBAND_AUDIO_F32 && !audio_encoding_known(encoding)) return fail(h, AIRBAND_HIP_EINVAL, "encoding is not an AIRBAND_AUDIO_* value");
-    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the output encoding is set before the first batch");
-    if (h->B % 4) return fail(h, AIRBAND_HIP_EBADSIZE, "the encoder moves four samples per lane: WAVE_BATCH must be a multiple of four");
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    /* built beside the gate and moved in whole: a failed allocation leaves the handle as it was */
-    OutputEncoding enc;
-    if (encoding != AIRBAND_AUDIO_F32) {
-        const size_t rows = (size_t)g.max_rows;
-        hipError_t e = enc.d_audio.alloc(rows * h->B * audio_sample_bytes(encoding));
-        if (e == hipSuccess) e = enc.d_info.alloc(rows);
-        if (e != hipSuccess) {
-            (void)hipGetLastError(); /* this call's error, reported here: not the next launch's */
-            return fail(h, AIRBAND_HIP_ENOMEM, std::string("output encoding buffers: ") + hipGetErrorString(e));
-        }
-        enc.encoding = encoding;
-    }
-    g.enc = std::move(enc);
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_collect_active_encoded(airband_hip_handle* h, int64_t* n_active, int32_t* channel_index, void* audio, airband_hip_audio_row* info, char* axc_all) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const OutputGate& g = h->gate;
-    if (g.max_rows <= 0 || g.enc.encoding == AIRBAND_AUDIO_F32) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output encoding (airband_hip_set_output_encoding)");
-    if (!h->results_ready || h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    /* how many rows there are is on the device: the count first, then exactly those rows */
-    int count = 0;
-    HIP_TRY(h, hipMemcpyAsync(&count, g.d_count.p, sizeof(int), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (count < 0 || count > h->plan.total_ch) return fail(h, AIRBAND_HIP_ERUNTIME, "active count out of range: " + std::to_string(count));
-    const size_t n = (size_t)(count < g.max_rows ? count : g.max_rows), row_bytes = (size_t)h->B * audio_sample_bytes(g.enc.encoding);
-    if (channel_index && n) HIP_TRY(h, hipMemcpyAsync(channel_index, g.d_index.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (audio && n) HIP_TRY(h, hipMemcpyAsync(audio, g.enc.d_audio.p, n * row_bytes, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (info && n) HIP_TRY(h, hipMemcpyAsync(info, g.enc.d_info.p, n * sizeof(airband_hip_audio_row), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (axc_all) HIP_TRY(h, hipMemcpyAsync(axc_all, h->d_out_axc.p, (size_t)h->plan.total_ch, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (n_active) *n_active = count;
-    h->results_ready = false;
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_device_active_encoded(airband_hip_handle* h, void** d_audio, airband_hip_audio_row** d_info) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    const OutputGate& g = h->gate;
-    if (g.max_rows <= 0 || g.enc.encoding == AIRBAND_AUDIO_F32) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output encoding (airband_hip_set_output_encoding)");
-    if (d_audio) *d_audio = g.enc.d_audio.p;
-    if (d_info) *d_info = g.enc.d_info.p;
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const float* rows, int64_t n_rows, void* audio, airband_hip_audio_row* info) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    if (!rows) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
-    if (!audio_encoding_known(encoding)) return fail(h, AIRBAND_HIP_EINVAL, "encoding is not AIRBAND_AUDIO_S16, _ULAW or _ALAW");
-    if (n_rows < 0 || n_rows > 0x7fffffff / 4) return fail(h, AIRBAND_HIP_EINVAL, "n_rows out of range");
-    if (h->B % 4) return fail(h, AIRBAND_HIP_EBADSIZE, "the encoder moves four samples per lane: WAVE_BATCH must be a multiple of four");
-    if (n_rows == 0) return AIRBAND_HIP_OK;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    /* buffers of the call's own, on the null stream: nothing of the handle is read or written */
-    const size_t n = (size_t)n_rows, B = (size_t)h->B, row_bytes = B * audio_sample_bytes(encoding);
-    DevBuf<float> d_rows;
-    DevBuf<uint8_t> d_audio;
-    DevBuf<airband_hip_audio_row> d_info;
-    hipError_t e = d_rows.alloc(n * B);
-    if (e == hipSuccess) e = d_audio.alloc(n * row_bytes);
-    if (e == hipSuccess) e = d_info.alloc(n);
-    if (e != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(h, AIRBAND_HIP_ENOMEM, std::string("encode_audio buffers: ") + hipGetErrorString(e));
-    }
-    HIP_TRY(h, hipMemcpy(d_rows.p, rows, n * B * sizeof(float), hipMemcpyHostToDevice), AIRBAND_HIP_ERUNTIME);
-    AudioPackArgs a;
-    a.index = nullptr;
-    a.count = nullptr;
-    a.n_rows = (int)n_rows;
-    a.max_rows = (int)n_rows;
-    a.n_ch = (int)n_rows;
-    a.src = d_rows.p;
-    a.src_stride = (long)B;
-    a.src_pad = 0;
-    a.audio = d_audio.p;
-    a.info = d_info.p;
-    a.wave_batch = h->B;
-    a.encoding = encoding;
-    launch_audio_pack(a, 0, nullptr);
-    e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
-    if (audio) HIP_TRY(h, hipMemcpy(audio, d_audio.p, n * row_bytes, hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
-    if (info) HIP_TRY(h, hipMemcpy(info, d_info.p, n * sizeof(airband_hip_audio_row), hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(nullptr), AIRBAND_HIP_ERUNTIME); /* the buffers go with this call */
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_set_transmission_spool(airband_hip_handle* h, const uint8_t* spool, int64_t pool_rows, int64_t export_rows, int64_t max_records, int32_t min_batches, int32_t idle_batches, int32_t max_batches) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    OutputGate& g = h->gate;
-    const Plan& p = h->plan;
-    if (g.max_rows <= 0) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output gate (airband_hip_set_output_gate)");
-    if (g.enc.encoding == AIRBAND_AUDIO_F32) return fail(h, AIRBAND_HIP_EINVAL, "the handle has no output encoding (airband_hip_set_output_encoding)");
-    if (h->front_batches > 0 || h->batches_done > 0) return fail(h, AIRBAND_HIP_EINVAL, "the transmission spool is set before the first batch");
-    if (pool_rows < 0 || export_rows < 0 || max_records < 0 || min_batches < 0 || idle_batches < 0) return fail(h, AIRBAND_HIP_EINVAL, "negative count");
-    if (pool_rows == 0) { /* removed */
-        g.enc.spool = TransmissionSpool();
-        return AIRBAND_HIP_OK;
-    }
-    if (max_batches < 1) return fail(h, AIRBAND_HIP_EINVAL, "max_batches must be at least 1");
-    if (export_rows < (int64_t)max_batches + 1) return fail(h, AIRBAND_HIP_EINVAL, "export_rows must be at least max_batches + 1: a collect must be able to take the longest transmission");
-    if (max_records < 1) return fail(h, AIRBAND_HIP_EINVAL, "max_records must be at least 1");
-    if (pool_rows > 0x7fffffff || export_rows > 0x7fffffff || max_records > 0x7fffffff / 2) return fail(h, AIRBAND_HIP_EINVAL, "pool_rows, export_rows or max_records too large to index");
-    std::vector<uint8_t> mask((size_t)p.total_ch);
-    for (int c = 0; c < p.total_ch; c++) {
-        mask[c] = spool ? (spool[c] ? 1 : 0) : (g.gate[c] == AIRBAND_GATE_SIGNAL ? 1 : 0);
-        if (mask[c] && g.gate[c] != AIRBAND_GATE_SIGNAL)
-            return fail(h, AIRBAND_HIP_EINVAL, "spooled channel " + std::to_string(c) + " has a gate other than AIRBAND_GATE_SIGNAL");
-    }
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    /* built beside the encoding and moved in whole: a failed allocation leaves the handle as it was */
-    TransmissionSpool sp;
-    const size_t row_bytes = (size_t)h->B * audio_sample_bytes(g.enc.encoding), nb = (size_t)gate_blocks(p.total_ch), nm = ((size_t)p.total_ch + 63) / 64;
-    std::vector<int> stack((size_t)pool_rows);
-    for (size_t i = 0; i < stack.size(); i++) stack[i] = (int)i;
-    SpoolCtl ctl;
-    std::memset(&ctl, 0, sizeof(ctl));
-    ctl.free_top = (int32_t)pool_rows;
-    ctl.room = (int32_t)max_records;
-    hipError_t e = upload(sp.d_spool, mask);
-    if (e == hipSuccess) e = upload(sp.d_free_stack, stack);
-    if (e == hipSuccess) e = sp.d_ctl.alloc(1);
-    if (e == hipSuccess) e = hipMemcpy(sp.d_ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = sp.d_chan.alloc_zeroed((size_t)p.total_ch);
-    if (e == hipSuccess) e = sp.d_close_mask.alloc_zeroed(nm);
-    if (e == hipSuccess) e = sp.d_app_mask.alloc_zeroed(nm);
-    if (e == hipSuccess) e = sp.d_close_count.alloc_zeroed(nb);
-    if (e == hipSuccess) e = sp.d_app_count.alloc_zeroed(nb);
-    if (e == hipSuccess) e = sp.d_next.alloc_zeroed((size_t)pool_rows);
-    if (e == hipSuccess) e = sp.d_copy_list.alloc_zeroed(2 * (size_t)g.max_rows);
-    if (e == hipSuccess) e = sp.d_pool.alloc((size_t)pool_rows * row_bytes);
-    if (e == hipSuccess) e = sp.d_fin.alloc_zeroed((size_t)max_records);
-    if (e == hipSuccess) e = sp.d_exp_records.alloc_zeroed((size_t)max_records);
-    if (e == hipSuccess) e = sp.d_exp_head.alloc_zeroed((size_t)max_records);
-    if (e == hipSuccess) e = sp.d_exp_src.alloc_zeroed((size_t)export_rows);
-    if (e == hipSuccess) e = sp.d_exp_audio.alloc((size_t)export_rows * row_bytes);
-    if (e != hipSuccess) {
-        (void)hipGetLastError(); /* this call's error, reported here: not the next launch's */
-        return fail(h, AIRBAND_HIP_ENOMEM, std::string("transmission spool buffers: ") + hipGetErrorString(e));
-    }
-    sp.pool_rows = (int)pool_rows;
-    sp.export_rows = (int)export_rows;
-    sp.max_records = (int)max_records;
-    sp.row_bytes = (int)row_bytes;
-    sp.min_batches = (uint32_t)min_batches;
-    sp.idle_batches = (uint32_t)idle_batches;
-    sp.max_batches = (uint32_t)max_batches;
-    g.enc.spool = std::move(sp);
-    return AIRBAND_HIP_OK;
-}
-
-static const char* const NO_SPOOL = "the handle has no transmission spool (airband_hip_set_transmission_spool)";
-static bool has_spool(const airband_hip_handle* h) { return h->gate.max_rows > 0 && h->gate.enc.encoding != AIRBAND_AUDIO_F32 && h->gate.enc.spool.pool_rows > 0; }
-
-int airband_hip_collect_transmissions(airband_hip_handle* h, int64_t* n, airband_hip_transmission* records, void* audio, int64_t* n_rows, int64_t* n_waiting) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
-    const TransmissionSpool& sp = h->gate.enc.spool;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    launch_spool_collect(spool_args(h, sp.steps), s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
-    /* how much there is is on the device: the counts first, then exactly those records and rows */
-    int32_t exp[3] = {0, 0, 0};
-    HIP_TRY(h, hipMemcpyAsync(exp, sp.d_ctl.p, sizeof(exp), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (exp[0] < 0 || exp[0] > sp.max_records || exp[1] < 0 || exp[1] > sp.export_rows || exp[2] < 0 || exp[2] > sp.max_records)
-        return fail(h, AIRBAND_HIP_ERUNTIME, "transmission spool counts out of range");
-    if (records && exp[0]) HIP_TRY(h, hipMemcpyAsync(records, sp.d_exp_records.p, (size_t)exp[0] * sizeof(airband_hip_transmission), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (audio && exp[1]) HIP_TRY(h, hipMemcpyAsync(audio, sp.d_exp_audio.p, (size_t)exp[1] * sp.row_bytes, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (n) *n = exp[0];
-    if (n_rows) *n_rows = exp[1];
-    if (n_waiting) *n_waiting = exp[2];
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_spool_flush(airband_hip_handle* h) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    order_behind_last_batch(h);
-    launch_spool_flush(spool_args(h, h->gate.enc.spool.steps), h->stream);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
-    /* a batch that ran on a caller's stream: the next one there knows nothing of the handle's stream, so the flush is complete before this returns */
-    if (h->ev_last_pending) HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_spool_counters_get(airband_hip_handle* h, airband_hip_spool_counters* out) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
-    if (!out) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
-    const TransmissionSpool& sp = h->gate.enc.spool;
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    order_behind_last_batch(h);
-    SpoolCtl ctl;
-    HIP_TRY(h, hipMemcpyAsync(&ctl, sp.d_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, h->stream), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
-    out->steps = sp.steps_total;
-    out->open_now = ctl.open_now;
-    out->waiting_now = (uint64_t)(ctl.fin_count < 0 ? 0 : ctl.fin_count);
-    out->free_rows_now = (uint64_t)(ctl.free_top < 0 ? 0 : ctl.free_top);
-    out->finished_total = ctl.finished_total;
-    out->dropped_transmissions = ctl.dropped;
-    out->rows_stored_total = ctl.rows_stored;
-    out->rows_lost_total = ctl.rows_lost;
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_device_transmission_spool(airband_hip_handle* h, void** d_export_audio, airband_hip_transmission** d_export_records, int32_t** d_n_export) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
-    const TransmissionSpool& sp = h->gate.enc.spool;
-    if (d_export_audio) *d_export_audio = sp.d_exp_audio.p;
-    if (d_export_records) *d_export_records = sp.d_exp_records.p;
-    if (d_n_export) *d_n_export = reinterpret_cast<int32_t*>(sp.d_ctl.p); /* SpoolCtl::exp, its first member */
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_collect_mixers(airband_hip_handle* h, float* left, float* right, uint8_t* has_signal) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    if (h->mix.n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = h->stream;
-    order_behind_last_batch(h);
-    const size_t n = (size_t)h->mix.n_mixers * h->B;
-    if (left) HIP_TRY(h, hipMemcpyAsync(left, h->mix.d_left.p, n * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (right) HIP_TRY(h, hipMemcpyAsync(right, h->mix.d_right.p, n * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (has_signal) HIP_TRY(h, hipMemcpyAsync(has_signal, h->mix.d_signal.p, (size_t)h->mix.n_mixers, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    return AIRBAND_HIP_OK;
 }
 
 int airband_hip_device_results(airband_hip_handle* h, float** d_waveout, float** d_iq_out, uint8_t** d_axc, float** d_mix_left, float** d_mix_right,
@@ -2883,219 +1365,6 @@ int airband_hip_generate_iq(airband_hip_handle* h, void* d_iq, size_t stride_byt
     if (!stream && h->run_ahead) h->serialise_next = true; /* the bytes may be the next batch's input: its stage 1, on the front stream, waits for this kernel */
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("siggen launch: ") + hipGetErrorString(e));
-    return AIRBAND_HIP_OK;
-}
-
-/* ---- the mixer exchange (include/airband_hip.h) ------------------------------------------------------------------------------------ */
-namespace {
-struct Rccl {
-    void* dl = nullptr;
-    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
-    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
-    ncclResult_t (*CommInitAll)(ncclComm_t*, int, const int*) = nullptr;
-    ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
-    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
-    ncclResult_t (*GroupStart)() = nullptr;
-    ncclResult_t (*GroupEnd)() = nullptr;
-    const char* (*GetErrorString)(ncclResult_t) = nullptr;
-    bool named = false;         /* loaded from AIRBAND_HIP_RCCL_LIB */
-    bool shared_gpu_ok = false; /* the library says (exported symbol airband_rccl_allows_shared_gpu) that two ranks of a communicator may sit on ONE GPU: the test stand-in does, RCCL does not */
-    std::string why;
-};
-Rccl g_rccl;
-std::mutex g_rccl_lock;
-
-/* librccl.so on first use: a process that never exchanges mixer sums never loads it */
-Rccl* rccl() {
-    std::lock_guard<std::mutex> guard(g_rccl_lock);
-    if (g_rccl.dl) return &g_rccl;
-    if (!g_rccl.why.empty()) return nullptr;
-    void* dl = nullptr;
-    std::string tried;
-    /* AIRBAND_HIP_RCCL_LIB names the library instead (a site's own RCCL build; the in-process stand-in tests/fake_rccl/ the GPU suite uses to run
-     * the exchange with two ranks on a one-GPU box).  Whether two ranks of a communicator may share a GPU is a capability the library exports
-     * (airband_rccl_allows_shared_gpu, below): the stand-in has it, RCCL does not. */
-    const char* named = getenv("AIRBAND_HIP_RCCL_LIB");
-    if (named && *named) {
-        dl = dlopen(named, RTLD_NOW | RTLD_GLOBAL);
-        if (!dl) {
-            const char* e = dlerror(); /* once: dlerror() clears the message it returns */
-            tried = std::string(named) + ": " + (e ? e : "not found");
-        }
-        g_rccl.named = dl != nullptr;
-    } else {
-        for (const char* name : {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so"}) {
-            dl = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
-            if (dl) break;
-            const char* e = dlerror();
-            if (tried.empty()) tried = std::string("librccl.so: ") + (e ? e : "not found");
-        }
-    }
-    if (!dl) {
-        g_rccl.why = tried.empty() ? std::string("librccl.so: not found") : tried;
-        return nullptr;
-    }
-#define AB_RCCL_SYM(field, name)                              \
-    *(void**)(&g_rccl.field) = dlsym(dl, name);               \
-    if (!g_rccl.field) {                                      \
-        g_rccl.why = std::string("librccl.so lacks ") + name; \
-        dlclose(dl);                                          \
-        return nullptr;                                       \
-    }
-    AB_RCCL_SYM(GetUniqueId, "ncclGetUniqueId") AB_RCCL_SYM(CommInitRank, "ncclCommInitRank") AB_RCCL_SYM(CommInitAll, "ncclCommInitAll")
-    AB_RCCL_SYM(AllReduce, "ncclAllReduce") AB_RCCL_SYM(CommDestroy, "ncclCommDestroy") AB_RCCL_SYM(GroupStart, "ncclGroupStart")
-    AB_RCCL_SYM(GroupEnd, "ncclGroupEnd") AB_RCCL_SYM(GetErrorString, "ncclGetErrorString")
-#undef AB_RCCL_SYM
-    {   /* a capability the library declares itself, not something inferred from how it was named: a site's own RCCL build named through AIRBAND_HIP_RCCL_LIB
-         * keeps the duplicate-GPU check of comm_init_all */
-        typedef int (*cap_fn)(void);
-        cap_fn cap = reinterpret_cast<cap_fn>(dlsym(dl, "airband_rccl_allows_shared_gpu"));
-        g_rccl.shared_gpu_ok = cap && cap() != 0;
-    }
-    g_rccl.dl = dl;
-    return &g_rccl;
-}
-
-#define RCCL_TRY(h, R, expr)                                                                                        \
-    do {                                                                                                            \
-        ncclResult_t r_ = (expr);                                                                                   \
-        if (r_ != ncclSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string(#expr ": ") + (R)->GetErrorString(r_)); \
-    } while (0)
-
-}  // namespace
-
-int airband_hip_mixer_set_stereo(airband_hip_handle* h, int32_t mixer, int32_t stereo) {
-    if (!h || h->mix.n_mixers <= 0 || mixer < 0 || mixer >= h->mix.n_mixers) return fail(h, AIRBAND_HIP_EINVAL, "mixer index out of range");
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    order_behind_last_batch(h);
-    const uint8_t v = stereo ? 1 : 0;
-    HIP_TRY(h, hipMemcpyAsync(h->mix.d_stereo.p + mixer, &v, 1, hipMemcpyHostToDevice, h->stream), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_comm_unique_id(uint8_t id[AIRBAND_HIP_COMM_ID_BYTES]) {
-    static_assert(sizeof(ncclUniqueId) == AIRBAND_HIP_COMM_ID_BYTES, "ncclUniqueId is 128 bytes");
-    Rccl* R = rccl();
-    if (!R) return fail(nullptr, AIRBAND_HIP_ENODEV, g_rccl.why);
-    ncclUniqueId u;
-    RCCL_TRY(nullptr, R, R->GetUniqueId(&u));
-    memcpy(id, &u, sizeof(u));
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_comm_init_rank(airband_hip_handle* h, const uint8_t id[AIRBAND_HIP_COMM_ID_BYTES], int32_t nranks, int32_t rank) {
-    if (!h || !id || nranks < 1 || rank < 0 || rank >= nranks) return fail(h, AIRBAND_HIP_EINVAL, "bad communicator arguments");
-    if (h->comm) return fail(h, AIRBAND_HIP_EINVAL, "the handle already has a communicator");
-    Rccl* R = rccl();
-    if (!R) return fail(h, AIRBAND_HIP_ENODEV, g_rccl.why);
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    ncclUniqueId u;
-    memcpy(&u, id, sizeof(u));
-    RCCL_TRY(h, R, R->CommInitRank(&h->comm, nranks, u, rank));
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_comm_init_all(airband_hip_handle** hs, int32_t n) {
-    if (!hs || n < 1) return fail(nullptr, AIRBAND_HIP_EINVAL, "bad communicator arguments");
-    std::vector<int> devs(n);
-    for (int i = 0; i < n; i++) {
-        if (!hs[i] || hs[i]->comm) return fail(hs[i], AIRBAND_HIP_EINVAL, "NULL handle, or a handle that already has a communicator");
-        devs[i] = hs[i]->hip_device;
-        if (hs[i]->mix.n_mixers != hs[0]->mix.n_mixers || hs[i]->B != hs[0]->B) return fail(hs[i], AIRBAND_HIP_EINVAL, "the handles of a clique need the same mixer_count and WAVE_BATCH");
-    }
-    Rccl* R = rccl();
-    if (!R) return fail(hs[0], AIRBAND_HIP_ENODEV, g_rccl.why);
-    if (!R->shared_gpu_ok) /* RCCL proper refuses a communicator with one GPU twice, late and with a generic message */
-        for (int i = 0; i < n; i++)
-            for (int k = 0; k < i; k++)
-                if (devs[k] == devs[i]) return fail(hs[i], AIRBAND_HIP_EINVAL, "two handles of the clique share a GPU: use airband_hip_add_mixers between them");
-    std::vector<ncclComm_t> comms(n, nullptr);
-    RCCL_TRY(hs[0], R, R->CommInitAll(comms.data(), n, devs.data()));
-    for (int i = 0; i < n; i++) hs[i]->comm = comms[i];
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_comm_group_begin(void) {
-    Rccl* R = rccl();
-    if (!R) return fail(nullptr, AIRBAND_HIP_ENODEV, g_rccl.why);
-    RCCL_TRY(nullptr, R, R->GroupStart());
-    return AIRBAND_HIP_OK;
-}
-
-int airband_hip_comm_group_end(void) {
-    Rccl* R = rccl();
-    if (!R) return fail(nullptr, AIRBAND_HIP_ENODEV, g_rccl.why);
-    RCCL_TRY(nullptr, R, R->GroupEnd());
-    return AIRBAND_HIP_OK;
-}
-
-/* SUM of the mixer waveforms (src/mixer.cpp:133-140), MAX of the signal flags (channel->axcindicate = SIGNAL if any input had signal, :209), in place */
-int airband_hip_allreduce_mixers(airband_hip_handle* h, void* stream) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    if (h->mix.n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
-    if (!h->comm) return fail(h, AIRBAND_HIP_EINVAL, "no communicator: airband_hip_comm_init_rank / _init_all first");
-    Rccl* R = rccl();
-    if (!R) return fail(h, AIRBAND_HIP_ENODEV, g_rccl.why);
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = stream ? (hipStream_t)stream : results_stream(h);
-    if (stream) {
-        const int rc = airband_hip_stream_wait_results(h, stream);
-        if (rc != AIRBAND_HIP_OK) return rc;
-    }
-    const size_t n = (size_t)h->mix.n_mixers * h->B;
-    RCCL_TRY(h, R, R->GroupStart());
-    RCCL_TRY(h, R, R->AllReduce(h->mix.d_left.p, h->mix.d_left.p, n, ncclFloat, ncclSum, h->comm, s));
-    RCCL_TRY(h, R, R->AllReduce(h->mix.d_right.p, h->mix.d_right.p, n, ncclFloat, ncclSum, h->comm, s));
-    RCCL_TRY(h, R, R->AllReduce(h->mix.d_signal.p, h->mix.d_signal.p, (size_t)h->mix.n_mixers, ncclUint8, ncclMax, h->comm, s));
-    RCCL_TRY(h, R, R->GroupEnd());
-    return results_enqueued_on(h, s); /* whatever the handle does next to these buffers (the next batch's sums, collect_mixers) comes behind the exchange */
-}
-
-int airband_hip_add_mixers(airband_hip_handle* dst, airband_hip_handle* src) {
-    if (!dst || !src || dst == src) return fail(dst, AIRBAND_HIP_EINVAL, "two different handles needed");
-    if (dst->mix.n_mixers <= 0 || dst->mix.n_mixers != src->mix.n_mixers || dst->B != src->B) return fail(dst, AIRBAND_HIP_EINVAL, "the handles need the same mixer_count and WAVE_BATCH");
-    if (dst->hip_device != src->hip_device) return fail(dst, AIRBAND_HIP_EINVAL, "handles on different GPUs exchange through airband_hip_allreduce_mixers");
-    HIP_TRY(dst, hipSetDevice(dst->hip_device), AIRBAND_HIP_ENODEV);
-    HIP_TRY(dst, dst->ev_peer.ensure(), AIRBAND_HIP_ENODEV);
-    hipStream_t s = results_stream(dst);
-    HIP_TRY(dst, hipEventRecord(dst->ev_peer, results_stream(src)), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(dst, hipStreamWaitEvent(s, dst->ev_peer, 0), AIRBAND_HIP_ERUNTIME);
-    launch_mix_add(dst->mix.d_left.p, dst->mix.d_right.p, dst->mix.d_signal.p, src->mix.d_left.p, src->mix.d_right.p, src->mix.d_signal.p, dst->mix.n_mixers, dst->B, s);
-    /* src's next batch must not overwrite its sums before they have been read */
-    const int rc_mark = results_enqueued_on(src, s);
-    if (rc_mark != AIRBAND_HIP_OK) return rc_mark;
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(dst, AIRBAND_HIP_ERUNTIME, std::string("mixer add launch: ") + hipGetErrorString(e));
-    return AIRBAND_HIP_OK;
-}
-
-/* A handle that ran no batch this round (every dongle of it switched off) still stands in the exchange: its partial sums are those of a
- * mixer whose inputs are all masked out (mixer_disable_input(), src/mixer.cpp:96-112) -- zeros, no signal.  Its buffers do NOT hold that by
- * themselves: the last batch's sums are still in them, and after an in-place all-reduce the whole node's. */
-int airband_hip_clear_mixers(airband_hip_handle* h) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    if (h->mix.n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
-    hipStream_t s = results_stream(h); /* behind whatever wrote or read the sums last: the handle's last batch, an exchange, add_mixers */
-    if (h->ev_last && h->ev_last_pending) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_last, 0), AIRBAND_HIP_ERUNTIME); /* a peer's add_mixers still reading them */
-    const size_t n = (size_t)h->mix.n_mixers * h->B;
-    HIP_TRY(h, hipMemsetAsync(h->mix.d_left.p, 0, n * sizeof(float), s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipMemsetAsync(h->mix.d_right.p, 0, n * sizeof(float), s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipMemsetAsync(h->mix.d_signal.p, 0, (size_t)h->mix.n_mixers, s), AIRBAND_HIP_ERUNTIME);
-    return results_enqueued_on(h, s); /* collect_mixers, or a later batch on another stream, comes behind the clear -- as behind allreduce_mixers */
-}
-
-int airband_hip_comm_destroy(airband_hip_handle* h) {
-    if (!h) return AIRBAND_HIP_EINVAL;
-    if (!h->comm) return AIRBAND_HIP_OK;
-    Rccl* R = rccl();
-    if (R) {
-        (void)hipSetDevice(h->hip_device);
-        (void)hipStreamSynchronize(h->stream);
-        (void)R->CommDestroy(h->comm);
-    }
-    h->comm = nullptr;
     return AIRBAND_HIP_OK;
 }
 

@@ -3,7 +3,7 @@
  * is include/airband_hip.h's ("encoded audio collect"); capi.audio_encode_reference() is the same in numpy.  One float32 multiplication per sample (this file is
  * compiled with -ffp-contract=off: nothing may fuse it with the rounding behind it), everything after it is integer arithmetic, so the bytes are checked as bytes.
  *
- * One launch per batch on a handle with an encoding, behind gate_index_kernel on the same stream (airband_hip.cpp, run_back_half); none on a handle without one.
+ * One launch per batch on a handle with an encoding, behind gate_index_kernel on the same stream (driver_gate.cpp, launch_gate_behind_mix, called by run_back_half); none on a handle without one.
  * It reads the SOURCE rows the gather reads -- out_wave + channel * wave_stride + AB_OUT_PAD -- not the packed float rows: it does not wait for the gather, and
  * the two read the same lines within microseconds of each other.
  *

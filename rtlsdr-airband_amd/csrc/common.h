@@ -1,4 +1,4 @@
-/* csrc/common.h -- data model shared by the host side (params.cpp, airband_hip.cpp) and the HIP kernels.
+/* csrc/common.h -- data model shared by the host side (params.cpp, airband_hip.cpp and driver_*.cpp) and the HIP kernels.
  *
  * Vocabulary follows the reference: a "dongle" is a device_t (reference: src/rtl_airband.h:249-272), a
  * "channel" is a channel_t with its single freq_t in multichannel mode (:223-247,:201-221), a "hop" is one

@@ -1,0 +1,133 @@
+/* csrc/driver.h -- what the files of the host driver share (airband_hip.cpp and driver_*.cpp): error reporting, the steps every entry point of an optional output
+ * repeats, and the hooks through which the batch path (airband_hip.cpp) reaches the feature files.  The helpers are static: the library exports none of them. */
+#pragma once
+
+#include <algorithm>
+#include <cmath>
+#include <cstdlib>
+#include <cstring>
+
+#include "handle.h"
+
+namespace airband {
+
+/* the ring rows a batch's stage 1 produces */
+struct FrontRows {
+    int first_row, n_hops;
+};
+
+#pragma GCC visibility push(hidden)
+extern thread_local std::string g_prepare_error; /* airband_hip.cpp: the message of a failure without a handle (airband_hip_last_error(NULL)) */
+/* the hooks of the batch path (airband_hip.cpp: launch_front, run_back_half), by the file that defines them.  driver_band.cpp: the scope (with its survey and watch) around stage 1, the follow behind the demod kernels */
+int scope_fork(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, FrontRows r, hipStream_t s);
+int scope_join(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, FrontRows r, hipStream_t s);
+void launch_follow_behind_demod(airband_hip_handle* h, int* moved_epoch, int epoch, hipStream_t s);
+/* driver_gate.cpp: the gate, the encoder and the spool's step behind the emit / mixer launches */
+void launch_gate_behind_mix(airband_hip_handle* h, hipStream_t s);
+/* driver_mix.cpp: what the batch's mixer sums are launched with; one mixer input switched on or off in the grouped arrays (airband_hip_device_enable) */
+MixArgs mix_args(const airband_hip_handle* h);
+hipError_t write_mix_input(airband_hip_handle* h, int k);
+/* driver_scan.cpp: prepare's step for handles with scan lists, the entries of a front batch, the exchange in front of the demod kernels, the hops behind them */
+int prep_scan(airband_hip_handle* h);
+void scan_latch(airband_hip_handle* h, uint64_t k, int first_row, int n_rows);
+int scan_before_demod(airband_hip_handle* h, hipStream_t s);
+void launch_scan_control_behind_demod(airband_hip_handle* h, hipStream_t s);
+#pragma GCC visibility pop
+
+static inline int fail(airband_hip_handle* h, int code, const std::string& msg) {
+    if (h) h->error = msg;
+    else g_prepare_error = msg;
+    return code;
+}
+
+#define HIP_TRY(h, expr, code)                                                                                   \
+    do {                                                                                                         \
+        hipError_t e_ = (expr);                                                                                  \
+        if (e_ != hipSuccess) return fail(h, code, std::string(#expr) + ": " + hipGetErrorString(e_));           \
+    } while (0)
+
+/* the HIP_TRY()s of prepare name this instead of the handle, which does not outlive a failure: the message goes to the thread's prepare error */
+constexpr airband_hip_handle* PREPARING = nullptr;
+
+template <class T>
+static hipError_t upload(DevBuf<T>& b, const std::vector<T>& v) {
+    hipError_t e = b.alloc(v.size());
+    if (e != hipSuccess) return e;
+    if (v.empty()) return hipSuccess;
+    return hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice);
+}
+
+/* Results of a batch that ran on a caller's stream: make the handle's own stream (on which collect / read_* / the stats kernel
+ * are issued) wait for it on the GPU. */
+static inline void order_behind_last_batch(airband_hip_handle* h) {
+    if (h->ev_last && h->ev_last_pending) (void)hipStreamWaitEvent(h->stream, h->ev_last, 0);
+}
+
+/* what a call does first before it copies or launches on the handle's own stream, `s` from here on: the handle's device, and behind such a batch */
+#define ON_OWN_STREAM(h, s)                                       \
+    hipStream_t s = (h)->stream;                                  \
+    HIP_TRY(h, hipSetDevice((h)->hip_device), AIRBAND_HIP_ENODEV); \
+    order_behind_last_batch(h)
+
+/* Work was enqueued on stream s.  If that is not the handle's own stream (a caller's: handed to process_device, or the one the last batch ran on), what the
+ * handle does next on its own -- collect / read_* / synchronize / release, the next batch's sums -- has to come behind it: ev_last marks the place. */
+static inline int results_enqueued_on(airband_hip_handle* h, hipStream_t s) {
+    if (s == h->stream) return AIRBAND_HIP_OK;
+    HIP_TRY(h, h->ev_last.ensure(), AIRBAND_HIP_ENODEV);
+    HIP_TRY(h, hipEventRecord(h->ev_last, s), AIRBAND_HIP_ERUNTIME);
+    h->ev_last_pending = true;
+    return AIRBAND_HIP_OK;
+}
+
+/* the stream on which the last batch's mixer sums become final */
+static inline hipStream_t results_stream(airband_hip_handle* h) { return h->pipeline ? h->stream : (h->last_stream ? h->last_stream : h->stream); }
+
+/* stage 1 of the next batch may be written while stage 2 still reads this one: rings two batches deep, a front stream, the channelizer held to five wavefronts per CU */
+static inline bool deep_rings(const airband_hip_handle* h) { return h->pipeline || h->run_ahead; }
+
+/* the optional outputs: is it there, and what a call says where it is not */
+static inline bool has_scope(const airband_hip_handle* h) { return h->scope.windows > 0; }
+static inline bool has_survey(const airband_hip_handle* h) { return has_scope(h) && h->scope.survey.max_peaks > 0; }
+static inline bool has_watch(const airband_hip_handle* h) { return has_survey(h) && h->scope.survey.watch.max_tracks > 0; }
+static inline bool has_follow(const airband_hip_handle* h) { return has_watch(h) && h->scope.survey.watch.follow.max_changes > 0; }
+static inline bool has_gate(const airband_hip_handle* h) { return h->gate.max_rows > 0; }
+static inline bool has_encoding(const airband_hip_handle* h) { return has_gate(h) && h->gate.enc.encoding != AIRBAND_AUDIO_F32; }
+static inline bool has_spool(const airband_hip_handle* h) { return has_encoding(h) && h->gate.enc.spool.pool_rows > 0; }
+static inline bool has_scan_control(const airband_hip_handle* h) { return h->scan_ctl.idle_batches > 0; }
+constexpr const char* NO_SCOPE = "the handle has no band scope (airband_hip_set_band_scope)";
+constexpr const char* NO_SURVEY = "the handle has no band survey (airband_hip_set_band_survey)";
+constexpr const char* NO_WATCH = "the handle has no band watch (airband_hip_set_band_watch)";
+constexpr const char* NO_FOLLOW = "the handle has no band follow (airband_hip_set_band_follow)";
+constexpr const char* NO_GATE = "the handle has no output gate (airband_hip_set_output_gate)";
+constexpr const char* NO_ENCODING = "the handle has no output encoding (airband_hip_set_output_encoding)";
+constexpr const char* NO_SPOOL = "the handle has no transmission spool (airband_hip_set_transmission_spool)";
+constexpr const char* NO_SCAN_CONTROL = "scan control is off (airband_hip_set_scan_control)";
+
+/* they are set before the first batch (the message stays a literal at each fail(): "the band watch is set before the first batch") */
+static inline bool started(const airband_hip_handle* h) { return h->front_batches > 0 || h->batches_done > 0; }
+static inline bool dev_range_ok(const airband_hip_handle* h, int32_t first_dev, int32_t n_dev) { return first_dev >= 0 && n_dev >= 0 && (int64_t)first_dev + n_dev <= h->plan.n_dev; }
+
+/* a set_*() whose allocations ended with `e`: the failed allocation is this call's error, reported here, not the next launch's.  `what` ends with ": " */
+static inline int alloc_failed(airband_hip_handle* h, hipError_t e, const char* what) {
+    (void)hipGetLastError();
+    return fail(h, AIRBAND_HIP_ENOMEM, std::string(what) + hipGetErrorString(e));
+}
+
+/* How long a list is is on the device: the count first, checked against the most the kernels can have written (`what` ends with ": ") and reported whole, then
+ * exactly those records, as many as the list keeps (`cap`).  Without `out` the count alone: one copy, one synchronize. */
+template <class T>
+static int collect_counted(airband_hip_handle* h, const int* d_count, int64_t most, int cap, const char* what, int64_t* n_out, const T* d_records, T* out, hipStream_t s) {
+    int count = 0;
+    HIP_TRY(h, hipMemcpyAsync(&count, d_count, sizeof(int), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (count < 0 || (int64_t)count > most) return fail(h, AIRBAND_HIP_ERUNTIME, what + std::to_string(count));
+    if (n_out) *n_out = count;
+    const size_t n = (size_t)(count < cap ? count : cap);
+    if (out && n) {
+        HIP_TRY(h, hipMemcpyAsync(out, d_records, n * sizeof(T), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+        HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    }
+    return AIRBAND_HIP_OK;
+}
+
+}  // namespace airband

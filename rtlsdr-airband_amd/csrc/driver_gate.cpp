@@ -1,0 +1,393 @@
+/* csrc/driver_gate.cpp -- the gated outputs of the host driver: the output gate, the encoding of its rows, airband_hip_encode_audio and the transmission spool
+ * (airband_hip_set_output_gate / _set_output_encoding / _set_transmission_spool and their collect / device entry points), and their launches behind the emit and
+ * mixer launches of a batch (hook of airband_hip.cpp: run_back_half). */
+#include "driver.h"
+
+using namespace airband;
+
+static GateArgs gate_args(const airband_hip_handle* h) {
+    const OutputGate& g = h->gate;
+    GateArgs a;
+    a.gate = g.d_gate.p;
+    a.axc = h->d_out_axc.p;
+    a.prev = g.d_prev.p;
+    a.mask = g.d_mask.p;
+    a.block_count = g.d_block_count.p;
+    a.index = g.d_index.p;
+    a.count = g.d_count.p;
+    a.n_ch = h->plan.total_ch;
+    a.max_rows = g.max_rows;
+    a.out_wave = h->d_out_wave.p;
+    a.out_iq = h->d_out_iq.p;
+    a.rows = g.d_rows.p;
+    a.iq_rows = g.d_iq_rows.p;
+    a.wave_stride = h->wave_stride;
+    a.wave_batch = h->B;
+    return a;
+}
+
+/* the gate's list and count, the rows the gather reads (airband_hip_set_output_encoding) */
+static AudioPackArgs audio_pack_args(const airband_hip_handle* h) {
+    const OutputGate& g = h->gate;
+    AudioPackArgs a;
+    a.index = g.d_index.p;
+    a.count = g.d_count.p;
+    a.n_rows = 0;
+    a.max_rows = g.max_rows;
+    a.n_ch = h->plan.total_ch;
+    a.src = h->d_out_wave.p;
+    a.src_stride = h->wave_stride;
+    a.src_pad = AB_OUT_PAD;
+    a.audio = g.enc.d_audio.p;
+    a.info = g.enc.d_info.p;
+    a.wave_batch = h->B;
+    a.encoding = g.enc.encoding;
+    return a;
+}
+
+/* the spool's own buffers, the gate's verdicts and the encoder's rows (airband_hip_set_transmission_spool); k: the step's number */
+static SpoolArgs spool_args(const airband_hip_handle* h, uint32_t k) {
+    const OutputGate& g = h->gate;
+    const TransmissionSpool& sp = g.enc.spool;
+    SpoolArgs a;
+    a.spool = sp.d_spool.p;
+    a.chan = sp.d_chan.p;
+    a.ctl = sp.d_ctl.p;
+    a.close_mask = sp.d_close_mask.p;
+    a.app_mask = sp.d_app_mask.p;
+    a.close_count = sp.d_close_count.p;
+    a.app_count = sp.d_app_count.p;
+    a.gate_mask = g.d_mask.p;
+    a.gate_count = g.d_block_count.p;
+    a.free_stack = sp.d_free_stack.p;
+    a.next = sp.d_next.p;
+    a.pool = sp.d_pool.p;
+    a.copy_list = sp.d_copy_list.p;
+    a.enc_audio = g.enc.d_audio.p;
+    a.enc_info = g.enc.d_info.p;
+    a.fin = sp.d_fin.p;
+    a.exp_records = sp.d_exp_records.p;
+    a.exp_head = sp.d_exp_head.p;
+    a.exp_src = sp.d_exp_src.p;
+    a.exp_audio = sp.d_exp_audio.p;
+    a.n_ch = h->plan.total_ch;
+    a.max_rows = g.max_rows;
+    a.pool_rows = sp.pool_rows;
+    a.export_rows = sp.export_rows;
+    a.max_records = sp.max_records;
+    a.row_bytes = sp.row_bytes;
+    a.wave_batch = h->B;
+    a.min_batches = sp.min_batches;
+    a.idle_batches = sp.idle_batches;
+    a.max_batches = sp.max_batches;
+    a.k = k;
+    return a;
+}
+
+static bool audio_encoding_known(int32_t e) { return e == AIRBAND_AUDIO_S16 || e == AIRBAND_AUDIO_ULAW || e == AIRBAND_AUDIO_ALAW; }
+static size_t audio_sample_bytes(int e) { return e == AIRBAND_AUDIO_S16 ? 2 : 1; }
+
+/* What airband_hip_collect_active() and airband_hip_collect_active_encoded() share.  How many rows there are is on the device: the count first, then exactly those
+ * rows -- the channel indices, what `rows(n, s)` enqueues of the call's own arrays, axcindicate of every channel, ONE synchronize.  Only then is the count
+ * reported and the batch marked as collected: a caller that sees an error sees neither.  (A HIP_TRY inside `rows` returns from the lambda; its code is checked here.) */
+template <class Rows>
+static int collect_active_rows(airband_hip_handle* h, int64_t* n_active, int32_t* channel_index, char* axc_all, Rows rows) {
+    const OutputGate& g = h->gate;
+    ON_OWN_STREAM(h, s);
+    int64_t count = 0;
+    int rc = collect_counted<int32_t>(h, g.d_count.p, h->plan.total_ch, g.max_rows, "active count out of range: ", &count, nullptr, nullptr, s);
+    if (rc != AIRBAND_HIP_OK) return rc;
+    const size_t n = (size_t)(count < g.max_rows ? count : g.max_rows);
+    if (channel_index && n) HIP_TRY(h, hipMemcpyAsync(channel_index, g.d_index.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    rc = rows(n, s);
+    if (rc != AIRBAND_HIP_OK) return rc;
+    if (axc_all) HIP_TRY(h, hipMemcpyAsync(axc_all, h->d_out_axc.p, (size_t)h->plan.total_ch, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (n_active) *n_active = count;
+    h->results_ready = false;
+    return AIRBAND_HIP_OK;
+}
+
+/* behind the emit / mixer launches of a gated handle's batch: its active channels and their rows, packed (gate.hip) ... */
+void airband::launch_gate_behind_mix(airband_hip_handle* h, hipStream_t s) {
+    launch_gate(gate_args(h), s);
+    if (has_encoding(h)) launch_audio_pack(audio_pack_args(h), 0, s); /* ... and encoded (audio_pack.hip) */
+    if (has_spool(h)) { /* ... and the spool's step of this batch (tx_spool.hip) */
+        TransmissionSpool& sp = h->gate.enc.spool;
+        launch_spool_step(spool_args(h, sp.steps), s);
+        sp.steps++;
+        sp.steps_total++;
+    }
+}
+
+extern "C" {
+
+int airband_hip_set_output_gate(airband_hip_handle* h, const uint8_t* gate, int64_t max_rows) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!gate) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    const Plan& p = h->plan;
+    if (max_rows < 1 || max_rows > p.total_ch) return fail(h, AIRBAND_HIP_EINVAL, "max_rows must lie in 1 .. total_channels");
+    for (int c = 0; c < p.total_ch; c++)
+        if (gate[c] > AIRBAND_GATE_ALWAYS) return fail(h, AIRBAND_HIP_EINVAL, "gate byte of channel " + std::to_string(c) + " is not an AIRBAND_GATE_* value");
+    if (started(h)) return fail(h, AIRBAND_HIP_EINVAL, "the output gate is set before the first batch");
+    if (h->B % 4) return fail(h, AIRBAND_HIP_EBADSIZE, "the gather moves four samples per lane: WAVE_BATCH must be a multiple of four");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* built beside the handle and moved in whole: a failed allocation leaves the handle as it was */
+    OutputGate g;
+    g.gate.assign(gate, gate + p.total_ch);
+    std::vector<uint8_t> bytes(g.gate);
+    for (int c = 0; c < p.total_ch; c++)
+        if (!h->dev_enabled[p.cc[c].dev]) bytes[c] |= AB_GATE_OFF; /* dongles that are switched off already */
+    const size_t rows = (size_t)max_rows;
+    hipError_t e = upload(g.d_gate, bytes);
+    if (e == hipSuccess) e = g.d_prev.alloc_zeroed((size_t)p.total_ch);
+    if (e == hipSuccess) e = g.d_mask.alloc(((size_t)p.total_ch + 63) / 64);
+    if (e == hipSuccess) e = g.d_block_count.alloc((size_t)gate_blocks(p.total_ch));
+    if (e == hipSuccess) e = g.d_index.alloc(rows);
+    if (e == hipSuccess) e = g.d_count.alloc_zeroed(1);
+    if (e == hipSuccess) e = g.d_rows.alloc(rows * h->B);
+    if (e == hipSuccess && h->d_out_iq.p) e = g.d_iq_rows.alloc(rows * h->B * 2);
+    if (e != hipSuccess) return alloc_failed(h, e, "output gate buffers: ");
+    g.max_rows = (int)max_rows;
+    h->gate = std::move(g);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_active(airband_hip_handle* h, int64_t* n_active, int32_t* channel_index, float* waveout, float* iq_out, char* axc_all) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const OutputGate& g = h->gate;
+    if (!has_gate(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_GATE);
+    if (!h->results_ready || h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
+    return collect_active_rows(h, n_active, channel_index, axc_all, [&](size_t n, hipStream_t s) -> int {
+        const size_t B = (size_t)h->B;
+        if (waveout && n) HIP_TRY(h, hipMemcpyAsync(waveout, g.d_rows.p, n * B * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+        if (iq_out && n) {
+            if (g.d_iq_rows.p)
+                HIP_TRY(h, hipMemcpyAsync(iq_out, g.d_iq_rows.p, n * B * 2 * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+            else
+                std::memset(iq_out, 0, n * B * 2 * sizeof(float));
+        }
+        return AIRBAND_HIP_OK;
+    });
+}
+
+int airband_hip_device_active(airband_hip_handle* h, int32_t** d_index, int32_t** d_count, float** d_rows, float** d_iq_rows) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const OutputGate& g = h->gate;
+    if (!has_gate(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_GATE);
+    if (d_index) *d_index = g.d_index.p;
+    if (d_count) *d_count = g.d_count.p;
+    if (d_rows) *d_rows = g.d_rows.p;
+    if (d_iq_rows) *d_iq_rows = g.d_iq_rows.p;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_set_output_encoding(airband_hip_handle* h, int32_t encoding) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    OutputGate& g = h->gate;
+    if (!has_gate(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_GATE);
+    if (encoding != AIRBAND_AUDIO_F32 && !audio_encoding_known(encoding)) return fail(h, AIRBAND_HIP_EINVAL, "encoding is not an AIRBAND_AUDIO_* value");
+    if (started(h)) return fail(h, AIRBAND_HIP_EINVAL, "the output encoding is set before the first batch");
+    if (h->B % 4) return fail(h, AIRBAND_HIP_EBADSIZE, "the encoder moves four samples per lane: WAVE_BATCH must be a multiple of four");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* built beside the gate and moved in whole: a failed allocation leaves the handle as it was */
+    OutputEncoding enc;
+    if (encoding != AIRBAND_AUDIO_F32) {
+        const size_t rows = (size_t)g.max_rows;
+        hipError_t e = enc.d_audio.alloc(rows * h->B * audio_sample_bytes(encoding));
+        if (e == hipSuccess) e = enc.d_info.alloc(rows);
+        if (e != hipSuccess) return alloc_failed(h, e, "output encoding buffers: ");
+        enc.encoding = encoding;
+    }
+    g.enc = std::move(enc);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_active_encoded(airband_hip_handle* h, int64_t* n_active, int32_t* channel_index, void* audio, airband_hip_audio_row* info, char* axc_all) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const OutputGate& g = h->gate;
+    if (!has_encoding(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_ENCODING);
+    if (!h->results_ready || h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
+    return collect_active_rows(h, n_active, channel_index, axc_all, [&](size_t n, hipStream_t s) -> int {
+        if (audio && n) HIP_TRY(h, hipMemcpyAsync(audio, g.enc.d_audio.p, n * h->B * audio_sample_bytes(g.enc.encoding), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+        if (info && n) HIP_TRY(h, hipMemcpyAsync(info, g.enc.d_info.p, n * sizeof(airband_hip_audio_row), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+        return AIRBAND_HIP_OK;
+    });
+}
+
+int airband_hip_device_active_encoded(airband_hip_handle* h, void** d_audio, airband_hip_audio_row** d_info) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const OutputGate& g = h->gate;
+    if (!has_encoding(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_ENCODING);
+    if (d_audio) *d_audio = g.enc.d_audio.p;
+    if (d_info) *d_info = g.enc.d_info.p;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const float* rows, int64_t n_rows, void* audio, airband_hip_audio_row* info) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!rows) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    if (!audio_encoding_known(encoding)) return fail(h, AIRBAND_HIP_EINVAL, "encoding is not AIRBAND_AUDIO_S16, _ULAW or _ALAW");
+    if (n_rows < 0 || n_rows > 0x7fffffff / 4) return fail(h, AIRBAND_HIP_EINVAL, "n_rows out of range");
+    if (h->B % 4) return fail(h, AIRBAND_HIP_EBADSIZE, "the encoder moves four samples per lane: WAVE_BATCH must be a multiple of four");
+    if (n_rows == 0) return AIRBAND_HIP_OK;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* buffers of the call's own, on the null stream: nothing of the handle is read or written */
+    const size_t n = (size_t)n_rows, B = (size_t)h->B, row_bytes = B * audio_sample_bytes(encoding);
+    DevBuf<float> d_rows;
+    DevBuf<uint8_t> d_audio;
+    DevBuf<airband_hip_audio_row> d_info;
+    hipError_t e = d_rows.alloc(n * B);
+    if (e == hipSuccess) e = d_audio.alloc(n * row_bytes);
+    if (e == hipSuccess) e = d_info.alloc(n);
+    if (e != hipSuccess) return alloc_failed(h, e, "encode_audio buffers: ");
+    HIP_TRY(h, hipMemcpy(d_rows.p, rows, n * B * sizeof(float), hipMemcpyHostToDevice), AIRBAND_HIP_ERUNTIME);
+    AudioPackArgs a;
+    a.index = nullptr;
+    a.count = nullptr;
+    a.n_rows = (int)n_rows;
+    a.max_rows = (int)n_rows;
+    a.n_ch = (int)n_rows;
+    a.src = d_rows.p;
+    a.src_stride = (long)B;
+    a.src_pad = 0;
+    a.audio = d_audio.p;
+    a.info = d_info.p;
+    a.wave_batch = h->B;
+    a.encoding = encoding;
+    launch_audio_pack(a, 0, nullptr);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
+    if (audio) HIP_TRY(h, hipMemcpy(audio, d_audio.p, n * row_bytes, hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
+    if (info) HIP_TRY(h, hipMemcpy(info, d_info.p, n * sizeof(airband_hip_audio_row), hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(nullptr), AIRBAND_HIP_ERUNTIME); /* the buffers go with this call */
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_set_transmission_spool(airband_hip_handle* h, const uint8_t* spool, int64_t pool_rows, int64_t export_rows, int64_t max_records, int32_t min_batches, int32_t idle_batches, int32_t max_batches) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    OutputGate& g = h->gate;
+    const Plan& p = h->plan;
+    if (!has_gate(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_GATE);
+    if (!has_encoding(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_ENCODING);
+    if (started(h)) return fail(h, AIRBAND_HIP_EINVAL, "the transmission spool is set before the first batch");
+    if (pool_rows < 0 || export_rows < 0 || max_records < 0 || min_batches < 0 || idle_batches < 0) return fail(h, AIRBAND_HIP_EINVAL, "negative count");
+    if (pool_rows == 0) { /* removed */
+        g.enc.spool = TransmissionSpool();
+        return AIRBAND_HIP_OK;
+    }
+    if (max_batches < 1) return fail(h, AIRBAND_HIP_EINVAL, "max_batches must be at least 1");
+    if (export_rows < (int64_t)max_batches + 1) return fail(h, AIRBAND_HIP_EINVAL, "export_rows must be at least max_batches + 1: a collect must be able to take the longest transmission");
+    if (max_records < 1) return fail(h, AIRBAND_HIP_EINVAL, "max_records must be at least 1");
+    if (pool_rows > 0x7fffffff || export_rows > 0x7fffffff || max_records > 0x7fffffff / 2) return fail(h, AIRBAND_HIP_EINVAL, "pool_rows, export_rows or max_records too large to index");
+    std::vector<uint8_t> mask((size_t)p.total_ch);
+    for (int c = 0; c < p.total_ch; c++) {
+        mask[c] = spool ? (spool[c] ? 1 : 0) : (g.gate[c] == AIRBAND_GATE_SIGNAL ? 1 : 0);
+        if (mask[c] && g.gate[c] != AIRBAND_GATE_SIGNAL)
+            return fail(h, AIRBAND_HIP_EINVAL, "spooled channel " + std::to_string(c) + " has a gate other than AIRBAND_GATE_SIGNAL");
+    }
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* built beside the encoding and moved in whole: a failed allocation leaves the handle as it was */
+    TransmissionSpool sp;
+    const size_t row_bytes = (size_t)h->B * audio_sample_bytes(g.enc.encoding), nb = (size_t)gate_blocks(p.total_ch), nm = ((size_t)p.total_ch + 63) / 64;
+    std::vector<int> stack((size_t)pool_rows);
+    for (size_t i = 0; i < stack.size(); i++) stack[i] = (int)i;
+    SpoolCtl ctl;
+    std::memset(&ctl, 0, sizeof(ctl));
+    ctl.free_top = (int32_t)pool_rows;
+    ctl.room = (int32_t)max_records;
+    hipError_t e = upload(sp.d_spool, mask);
+    if (e == hipSuccess) e = upload(sp.d_free_stack, stack);
+    if (e == hipSuccess) e = sp.d_ctl.alloc(1);
+    if (e == hipSuccess) e = hipMemcpy(sp.d_ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = sp.d_chan.alloc_zeroed((size_t)p.total_ch);
+    if (e == hipSuccess) e = sp.d_close_mask.alloc_zeroed(nm);
+    if (e == hipSuccess) e = sp.d_app_mask.alloc_zeroed(nm);
+    if (e == hipSuccess) e = sp.d_close_count.alloc_zeroed(nb);
+    if (e == hipSuccess) e = sp.d_app_count.alloc_zeroed(nb);
+    if (e == hipSuccess) e = sp.d_next.alloc_zeroed((size_t)pool_rows);
+    if (e == hipSuccess) e = sp.d_copy_list.alloc_zeroed(2 * (size_t)g.max_rows);
+    if (e == hipSuccess) e = sp.d_pool.alloc((size_t)pool_rows * row_bytes);
+    if (e == hipSuccess) e = sp.d_fin.alloc_zeroed((size_t)max_records);
+    if (e == hipSuccess) e = sp.d_exp_records.alloc_zeroed((size_t)max_records);
+    if (e == hipSuccess) e = sp.d_exp_head.alloc_zeroed((size_t)max_records);
+    if (e == hipSuccess) e = sp.d_exp_src.alloc_zeroed((size_t)export_rows);
+    if (e == hipSuccess) e = sp.d_exp_audio.alloc((size_t)export_rows * row_bytes);
+    if (e != hipSuccess) return alloc_failed(h, e, "transmission spool buffers: ");
+    sp.pool_rows = (int)pool_rows;
+    sp.export_rows = (int)export_rows;
+    sp.max_records = (int)max_records;
+    sp.row_bytes = (int)row_bytes;
+    sp.min_batches = (uint32_t)min_batches;
+    sp.idle_batches = (uint32_t)idle_batches;
+    sp.max_batches = (uint32_t)max_batches;
+    g.enc.spool = std::move(sp);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_transmissions(airband_hip_handle* h, int64_t* n, airband_hip_transmission* records, void* audio, int64_t* n_rows, int64_t* n_waiting) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
+    const TransmissionSpool& sp = h->gate.enc.spool;
+    ON_OWN_STREAM(h, s);
+    launch_spool_collect(spool_args(h, sp.steps), s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
+    /* how much there is is on the device: the counts first, then exactly those records and rows */
+    int32_t exp[3] = {0, 0, 0};
+    HIP_TRY(h, hipMemcpyAsync(exp, sp.d_ctl.p, sizeof(exp), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (exp[0] < 0 || exp[0] > sp.max_records || exp[1] < 0 || exp[1] > sp.export_rows || exp[2] < 0 || exp[2] > sp.max_records)
+        return fail(h, AIRBAND_HIP_ERUNTIME, "transmission spool counts out of range");
+    if (records && exp[0]) HIP_TRY(h, hipMemcpyAsync(records, sp.d_exp_records.p, (size_t)exp[0] * sizeof(airband_hip_transmission), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (audio && exp[1]) HIP_TRY(h, hipMemcpyAsync(audio, sp.d_exp_audio.p, (size_t)exp[1] * sp.row_bytes, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (n) *n = exp[0];
+    if (n_rows) *n_rows = exp[1];
+    if (n_waiting) *n_waiting = exp[2];
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_spool_flush(airband_hip_handle* h) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
+    ON_OWN_STREAM(h, s);
+    launch_spool_flush(spool_args(h, h->gate.enc.spool.steps), s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
+    /* a batch that ran on a caller's stream: the next one there knows nothing of the handle's stream, so the flush is complete before this returns */
+    if (h->ev_last_pending) HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_spool_counters_get(airband_hip_handle* h, airband_hip_spool_counters* out) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
+    if (!out) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    const TransmissionSpool& sp = h->gate.enc.spool;
+    ON_OWN_STREAM(h, s);
+    SpoolCtl ctl;
+    HIP_TRY(h, hipMemcpyAsync(&ctl, sp.d_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    out->steps = sp.steps_total;
+    out->open_now = ctl.open_now;
+    out->waiting_now = (uint64_t)(ctl.fin_count < 0 ? 0 : ctl.fin_count);
+    out->free_rows_now = (uint64_t)(ctl.free_top < 0 ? 0 : ctl.free_top);
+    out->finished_total = ctl.finished_total;
+    out->dropped_transmissions = ctl.dropped;
+    out->rows_stored_total = ctl.rows_stored;
+    out->rows_lost_total = ctl.rows_lost;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_device_transmission_spool(airband_hip_handle* h, void** d_export_audio, airband_hip_transmission** d_export_records, int32_t** d_n_export) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
+    const TransmissionSpool& sp = h->gate.enc.spool;
+    if (d_export_audio) *d_export_audio = sp.d_exp_audio.p;
+    if (d_export_records) *d_export_records = sp.d_exp_records.p;
+    if (d_n_export) *d_n_export = reinterpret_cast<int32_t*>(sp.d_ctl.p); /* SpoolCtl::exp, its first member */
+    return AIRBAND_HIP_OK;
+}
+
+} /* extern "C" */

@@ -1,0 +1,348 @@
+/* csrc/driver_mix.cpp -- the mixers of the host driver: the wiring (airband_hip_set_mixers / _mixer_enable_input / _mixer_set_stereo / _collect_mixers), what the sums
+ * behind a batch's demod kernels are launched with (run_back_half), and their exchange between handles over librccl.so (airband_hip_comm_* / *_mixers). */
+#include <dlfcn.h>
+
+#include "driver.h"
+
+using namespace airband;
+
+MixArgs airband::mix_args(const airband_hip_handle* h) {
+    const MixerWiring& w = h->mix;
+    MixArgs ma;
+    ma.out_wave = h->d_out_wave.p + AB_OUT_PAD;
+    ma.wave_stride = h->wave_stride;
+    ma.out_axc = h->d_out_axc.p;
+    ma.in_chan = w.d_chan.p;
+    ma.in_ml = w.d_ml.p;
+    ma.in_mr = w.d_mr.p;
+    ma.run_first = w.d_run_first.p;
+    ma.run_mixer = w.d_run_mixer.p;
+    ma.mixer_first_run = w.d_first_run.p;
+    ma.mixer_stereo = w.d_stereo.p;
+    ma.run_left = w.d_run_left.p;
+    ma.run_right = w.d_run_right.p;
+    ma.run_signal = w.d_run_signal.p;
+    ma.n_runs = w.n_runs;
+    ma.left = w.d_left.p;
+    ma.right = w.d_right.p;
+    ma.has_signal = w.d_signal.p;
+    ma.n_mixers = w.n_mixers;
+    ma.wave_batch = h->B;
+    return ma;
+}
+
+/* position k of the grouped mixer-input arrays: the channel it reads, or -1 while the connection (airband_hip_mixer_enable_input) or its dongle
+ * (airband_hip_device_enable) is switched off -- a masked input is skipped like mixer->input_mask[i] == false (src/mixer.cpp:96-110,192) */
+hipError_t airband::write_mix_input(airband_hip_handle* h, int k) {
+    const int ch = h->mix.chan_host[k];
+    const int v = (h->mix.user_on[k] && h->dev_enabled[h->plan.cc[ch].dev]) ? ch : -1;
+    hipError_t e = hipMemcpyAsync(h->mix.d_chan.p + k, &v, sizeof(int), hipMemcpyHostToDevice, h->stream);
+    if (e != hipSuccess) return e;
+    return hipStreamSynchronize(h->stream); /* `v` is a stack variable */
+}
+
+/* ---- the mixer exchange (include/airband_hip.h) ------------------------------------------------------------------------------------ */
+namespace {
+struct Rccl {
+    void* dl = nullptr;
+    ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
+    ncclResult_t (*CommInitRank)(ncclComm_t*, int, ncclUniqueId, int) = nullptr;
+    ncclResult_t (*CommInitAll)(ncclComm_t*, int, const int*) = nullptr;
+    ncclResult_t (*AllReduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
+    ncclResult_t (*CommDestroy)(ncclComm_t) = nullptr;
+    ncclResult_t (*GroupStart)() = nullptr;
+    ncclResult_t (*GroupEnd)() = nullptr;
+    const char* (*GetErrorString)(ncclResult_t) = nullptr;
+    bool named = false;         /* loaded from AIRBAND_HIP_RCCL_LIB */
+    bool shared_gpu_ok = false; /* the library says (exported symbol airband_rccl_allows_shared_gpu) that two ranks of a communicator may sit on ONE GPU: the test stand-in does, RCCL does not */
+    std::string why;
+};
+Rccl g_rccl;
+std::mutex g_rccl_lock;
+
+/* librccl.so on first use: a process that never exchanges mixer sums never loads it */
+Rccl* rccl() {
+    std::lock_guard<std::mutex> guard(g_rccl_lock);
+    if (g_rccl.dl) return &g_rccl;
+    if (!g_rccl.why.empty()) return nullptr;
+    void* dl = nullptr;
+    std::string tried;
+    /* AIRBAND_HIP_RCCL_LIB names the library instead (a site's own RCCL build; the in-process stand-in tests/fake_rccl/ the GPU suite uses to run
+     * the exchange with two ranks on a one-GPU box).  Whether two ranks of a communicator may share a GPU is a capability the library exports
+     * (airband_rccl_allows_shared_gpu, below): the stand-in has it, RCCL does not. */
+    const char* named = getenv("AIRBAND_HIP_RCCL_LIB");
+    if (named && *named) {
+        dl = dlopen(named, RTLD_NOW | RTLD_GLOBAL);
+        if (!dl) {
+            const char* e = dlerror(); /* once: dlerror() clears the message it returns */
+            tried = std::string(named) + ": " + (e ? e : "not found");
+        }
+        g_rccl.named = dl != nullptr;
+    } else {
+        for (const char* name : {"librccl.so", "librccl.so.1", "/opt/rocm/lib/librccl.so"}) {
+            dl = dlopen(name, RTLD_NOW | RTLD_GLOBAL);
+            if (dl) break;
+            const char* e = dlerror();
+            if (tried.empty()) tried = std::string("librccl.so: ") + (e ? e : "not found");
+        }
+    }
+    if (!dl) {
+        g_rccl.why = tried.empty() ? std::string("librccl.so: not found") : tried;
+        return nullptr;
+    }
+#define AB_RCCL_SYM(field, name)                              \
+    *(void**)(&g_rccl.field) = dlsym(dl, name);               \
+    if (!g_rccl.field) {                                      \
+        g_rccl.why = std::string("librccl.so lacks ") + name; \
+        dlclose(dl);                                          \
+        return nullptr;                                       \
+    }
+    AB_RCCL_SYM(GetUniqueId, "ncclGetUniqueId") AB_RCCL_SYM(CommInitRank, "ncclCommInitRank") AB_RCCL_SYM(CommInitAll, "ncclCommInitAll")
+    AB_RCCL_SYM(AllReduce, "ncclAllReduce") AB_RCCL_SYM(CommDestroy, "ncclCommDestroy") AB_RCCL_SYM(GroupStart, "ncclGroupStart")
+    AB_RCCL_SYM(GroupEnd, "ncclGroupEnd") AB_RCCL_SYM(GetErrorString, "ncclGetErrorString")
+#undef AB_RCCL_SYM
+    {   /* a capability the library declares itself, not something inferred from how it was named: a site's own RCCL build named through AIRBAND_HIP_RCCL_LIB
+         * keeps the duplicate-GPU check of comm_init_all */
+        typedef int (*cap_fn)(void);
+        cap_fn cap = reinterpret_cast<cap_fn>(dlsym(dl, "airband_rccl_allows_shared_gpu"));
+        g_rccl.shared_gpu_ok = cap && cap() != 0;
+    }
+    g_rccl.dl = dl;
+    return &g_rccl;
+}
+
+#define RCCL_TRY(h, R, expr)                                                                                        \
+    do {                                                                                                            \
+        ncclResult_t r_ = (expr);                                                                                   \
+        if (r_ != ncclSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string(#expr ": ") + (R)->GetErrorString(r_)); \
+    } while (0)
+
+}  // namespace
+
+extern "C" {
+
+int airband_hip_set_mixers(airband_hip_handle* h, int32_t mixer_count, const airband_hip_mixer_input* in, int32_t n_in) {
+    if (!h || mixer_count < 1 || n_in < 0 || (!in && n_in > 0)) return fail(h, AIRBAND_HIP_EINVAL, "bad mixer arguments");
+    /* n_in == 0: a handle whose dongles feed no mixer still takes part in the exchange with all-zero partial sums */
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    const Plan& p = h->plan;
+    std::vector<int> first(mixer_count + 1, 0), chan(n_in);
+    std::vector<float> ml(n_in), mr(n_in);
+    std::vector<uint8_t> stereo(mixer_count, 0);
+    for (int i = 0; i < n_in; i++) {
+        if (in[i].mixer < 0 || in[i].mixer >= mixer_count || in[i].device < 0 || in[i].device >= p.n_dev || in[i].channel < 0 ||
+            in[i].channel >= p.dev[in[i].device].n_ch)
+            return fail(h, AIRBAND_HIP_EINVAL, "mixer input out of range");
+        first[in[i].mixer + 1]++;
+        if (in[i].balance != 0.0f) stereo[in[i].mixer] = 1; /* src/mixer.cpp:84-85 */
+    }
+    for (int m = 0; m < mixer_count; m++) first[m + 1] += first[m];
+    std::vector<int> cur(first.begin(), first.end() - 1);
+    std::vector<int> pos(n_in, 0);
+    for (int i = 0; i < n_in; i++) { /* stable: connection order inside a mixer is kept (summation order) */
+        const int k = cur[in[i].mixer]++;
+        pos[i] = k;
+        chan[k] = p.chan_base[in[i].device] + in[i].channel;
+        ml[k] = in[i].ampfactor * fminf(1.0f, 1.0f - in[i].balance); /* src/mixer.cpp:82-83,203-208 */
+        mr[k] = in[i].ampfactor * fminf(1.0f, 1.0f + in[i].balance);
+    }
+    std::vector<int> run_first, run_mixer, first_run(mixer_count + 1, 0);
+    for (int m = 0; m < mixer_count; m++) {
+        first_run[m] = (int)run_mixer.size();
+        for (int i = first[m]; i < first[m + 1]; i += AB_MIX_RUN) {
+            run_first.push_back(i);
+            run_mixer.push_back(m);
+        }
+    }
+    first_run[mixer_count] = (int)run_mixer.size();
+    run_first.push_back(n_in);
+    const int n_runs = (int)run_mixer.size();
+    /* the mixer kernels index runs / mixers with blockIdx.y: say so here rather than fail at the first launch */
+    if (n_runs > 65535 || mixer_count > 65535) return fail(h, AIRBAND_HIP_EBADSIZE, "more than 65 535 mixers (or runs of 64 mixer inputs) on one handle");
+    order_behind_last_batch(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME); /* a batch under way still sums the old wiring */
+    h->mix = MixerWiring(); /* n_mixers == 0 until the new wiring is complete: a failure below leaves a handle without mixers, not one with freed tables */
+    MixerWiring& w = h->mix;
+    HIP_TRY(h, upload(w.d_run_first, run_first), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_run_mixer, run_mixer), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_first_run, first_run), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, w.d_run_left.alloc((size_t)n_runs * h->B), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, w.d_run_right.alloc((size_t)n_runs * h->B), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, w.d_run_signal.alloc((size_t)n_runs), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_chan, chan), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_first, first), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_ml, ml), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_mr, mr), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, upload(w.d_stereo, stereo), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, w.d_left.alloc((size_t)mixer_count * h->B), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, w.d_right.alloc((size_t)mixer_count * h->B), AIRBAND_HIP_ENOMEM);
+    HIP_TRY(h, w.d_signal.alloc((size_t)mixer_count), AIRBAND_HIP_ENOMEM);
+    w.pos = pos;
+    w.chan_host = chan;
+    w.user_on.assign(n_in, 1);
+    for (int k = 0; k < n_in; k++) /* inputs of dongles that are already switched off stay out */
+        if (!h->dev_enabled[p.cc[chan[k]].dev]) HIP_TRY(h, write_mix_input(h, k), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
+    w.n_runs = n_runs; /* published last */
+    w.n_mixers = mixer_count;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_mixer_enable_input(airband_hip_handle* h, int32_t input_index, int32_t enabled) {
+    if (!h || h->mix.n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
+    if (input_index < 0 || input_index >= (int32_t)h->mix.pos.size()) return fail(h, AIRBAND_HIP_EINVAL, "mixer input index out of range");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    const int k = h->mix.pos[input_index];
+    h->mix.user_on[k] = enabled ? 1 : 0;
+    HIP_TRY(h, write_mix_input(h, k), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_mixer_set_stereo(airband_hip_handle* h, int32_t mixer, int32_t stereo) {
+    if (!h || h->mix.n_mixers <= 0 || mixer < 0 || mixer >= h->mix.n_mixers) return fail(h, AIRBAND_HIP_EINVAL, "mixer index out of range");
+    ON_OWN_STREAM(h, s);
+    const uint8_t v = stereo ? 1 : 0;
+    HIP_TRY(h, hipMemcpyAsync(h->mix.d_stereo.p + mixer, &v, 1, hipMemcpyHostToDevice, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_mixers(airband_hip_handle* h, float* left, float* right, uint8_t* has_signal) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (h->mix.n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
+    ON_OWN_STREAM(h, s);
+    const size_t n = (size_t)h->mix.n_mixers * h->B;
+    if (left) HIP_TRY(h, hipMemcpyAsync(left, h->mix.d_left.p, n * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (right) HIP_TRY(h, hipMemcpyAsync(right, h->mix.d_right.p, n * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (has_signal) HIP_TRY(h, hipMemcpyAsync(has_signal, h->mix.d_signal.p, (size_t)h->mix.n_mixers, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_comm_unique_id(uint8_t id[AIRBAND_HIP_COMM_ID_BYTES]) {
+    static_assert(sizeof(ncclUniqueId) == AIRBAND_HIP_COMM_ID_BYTES, "ncclUniqueId is 128 bytes");
+    Rccl* R = rccl();
+    if (!R) return fail(nullptr, AIRBAND_HIP_ENODEV, g_rccl.why);
+    ncclUniqueId u;
+    RCCL_TRY(nullptr, R, R->GetUniqueId(&u));
+    memcpy(id, &u, sizeof(u));
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_comm_init_rank(airband_hip_handle* h, const uint8_t id[AIRBAND_HIP_COMM_ID_BYTES], int32_t nranks, int32_t rank) {
+    if (!h || !id || nranks < 1 || rank < 0 || rank >= nranks) return fail(h, AIRBAND_HIP_EINVAL, "bad communicator arguments");
+    if (h->comm) return fail(h, AIRBAND_HIP_EINVAL, "the handle already has a communicator");
+    Rccl* R = rccl();
+    if (!R) return fail(h, AIRBAND_HIP_ENODEV, g_rccl.why);
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    ncclUniqueId u;
+    memcpy(&u, id, sizeof(u));
+    RCCL_TRY(h, R, R->CommInitRank(&h->comm, nranks, u, rank));
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_comm_init_all(airband_hip_handle** hs, int32_t n) {
+    if (!hs || n < 1) return fail(nullptr, AIRBAND_HIP_EINVAL, "bad communicator arguments");
+    std::vector<int> devs(n);
+    for (int i = 0; i < n; i++) {
+        if (!hs[i] || hs[i]->comm) return fail(hs[i], AIRBAND_HIP_EINVAL, "NULL handle, or a handle that already has a communicator");
+        devs[i] = hs[i]->hip_device;
+        if (hs[i]->mix.n_mixers != hs[0]->mix.n_mixers || hs[i]->B != hs[0]->B) return fail(hs[i], AIRBAND_HIP_EINVAL, "the handles of a clique need the same mixer_count and WAVE_BATCH");
+    }
+    Rccl* R = rccl();
+    if (!R) return fail(hs[0], AIRBAND_HIP_ENODEV, g_rccl.why);
+    if (!R->shared_gpu_ok) /* RCCL proper refuses a communicator with one GPU twice, late and with a generic message */
+        for (int i = 0; i < n; i++)
+            for (int k = 0; k < i; k++)
+                if (devs[k] == devs[i]) return fail(hs[i], AIRBAND_HIP_EINVAL, "two handles of the clique share a GPU: use airband_hip_add_mixers between them");
+    std::vector<ncclComm_t> comms(n, nullptr);
+    RCCL_TRY(hs[0], R, R->CommInitAll(comms.data(), n, devs.data()));
+    for (int i = 0; i < n; i++) hs[i]->comm = comms[i];
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_comm_group_begin(void) {
+    Rccl* R = rccl();
+    if (!R) return fail(nullptr, AIRBAND_HIP_ENODEV, g_rccl.why);
+    RCCL_TRY(nullptr, R, R->GroupStart());
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_comm_group_end(void) {
+    Rccl* R = rccl();
+    if (!R) return fail(nullptr, AIRBAND_HIP_ENODEV, g_rccl.why);
+    RCCL_TRY(nullptr, R, R->GroupEnd());
+    return AIRBAND_HIP_OK;
+}
+
+/* SUM of the mixer waveforms (src/mixer.cpp:133-140), MAX of the signal flags (channel->axcindicate = SIGNAL if any input had signal, :209), in place */
+int airband_hip_allreduce_mixers(airband_hip_handle* h, void* stream) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (h->mix.n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
+    if (!h->comm) return fail(h, AIRBAND_HIP_EINVAL, "no communicator: airband_hip_comm_init_rank / _init_all first");
+    Rccl* R = rccl();
+    if (!R) return fail(h, AIRBAND_HIP_ENODEV, g_rccl.why);
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = stream ? (hipStream_t)stream : results_stream(h);
+    if (stream) {
+        const int rc = airband_hip_stream_wait_results(h, stream);
+        if (rc != AIRBAND_HIP_OK) return rc;
+    }
+    const size_t n = (size_t)h->mix.n_mixers * h->B;
+    RCCL_TRY(h, R, R->GroupStart());
+    RCCL_TRY(h, R, R->AllReduce(h->mix.d_left.p, h->mix.d_left.p, n, ncclFloat, ncclSum, h->comm, s));
+    RCCL_TRY(h, R, R->AllReduce(h->mix.d_right.p, h->mix.d_right.p, n, ncclFloat, ncclSum, h->comm, s));
+    RCCL_TRY(h, R, R->AllReduce(h->mix.d_signal.p, h->mix.d_signal.p, (size_t)h->mix.n_mixers, ncclUint8, ncclMax, h->comm, s));
+    RCCL_TRY(h, R, R->GroupEnd());
+    return results_enqueued_on(h, s); /* whatever the handle does next to these buffers (the next batch's sums, collect_mixers) comes behind the exchange */
+}
+
+int airband_hip_add_mixers(airband_hip_handle* dst, airband_hip_handle* src) {
+    if (!dst || !src || dst == src) return fail(dst, AIRBAND_HIP_EINVAL, "two different handles needed");
+    if (dst->mix.n_mixers <= 0 || dst->mix.n_mixers != src->mix.n_mixers || dst->B != src->B) return fail(dst, AIRBAND_HIP_EINVAL, "the handles need the same mixer_count and WAVE_BATCH");
+    if (dst->hip_device != src->hip_device) return fail(dst, AIRBAND_HIP_EINVAL, "handles on different GPUs exchange through airband_hip_allreduce_mixers");
+    HIP_TRY(dst, hipSetDevice(dst->hip_device), AIRBAND_HIP_ENODEV);
+    HIP_TRY(dst, dst->ev_peer.ensure(), AIRBAND_HIP_ENODEV);
+    hipStream_t s = results_stream(dst);
+    HIP_TRY(dst, hipEventRecord(dst->ev_peer, results_stream(src)), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(dst, hipStreamWaitEvent(s, dst->ev_peer, 0), AIRBAND_HIP_ERUNTIME);
+    launch_mix_add(dst->mix.d_left.p, dst->mix.d_right.p, dst->mix.d_signal.p, src->mix.d_left.p, src->mix.d_right.p, src->mix.d_signal.p, dst->mix.n_mixers, dst->B, s);
+    /* src's next batch must not overwrite its sums before they have been read */
+    const int rc_mark = results_enqueued_on(src, s);
+    if (rc_mark != AIRBAND_HIP_OK) return rc_mark;
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(dst, AIRBAND_HIP_ERUNTIME, std::string("mixer add launch: ") + hipGetErrorString(e));
+    return AIRBAND_HIP_OK;
+}
+
+/* A handle that ran no batch this round (every dongle of it switched off) still stands in the exchange: its partial sums are those of a
+ * mixer whose inputs are all masked out (mixer_disable_input(), src/mixer.cpp:96-112) -- zeros, no signal.  Its buffers do NOT hold that by
+ * themselves: the last batch's sums are still in them, and after an in-place all-reduce the whole node's. */
+int airband_hip_clear_mixers(airband_hip_handle* h) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (h->mix.n_mixers <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    hipStream_t s = results_stream(h); /* behind whatever wrote or read the sums last: the handle's last batch, an exchange, add_mixers */
+    if (h->ev_last && h->ev_last_pending) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_last, 0), AIRBAND_HIP_ERUNTIME); /* a peer's add_mixers still reading them */
+    const size_t n = (size_t)h->mix.n_mixers * h->B;
+    HIP_TRY(h, hipMemsetAsync(h->mix.d_left.p, 0, n * sizeof(float), s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipMemsetAsync(h->mix.d_right.p, 0, n * sizeof(float), s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipMemsetAsync(h->mix.d_signal.p, 0, (size_t)h->mix.n_mixers, s), AIRBAND_HIP_ERUNTIME);
+    return results_enqueued_on(h, s); /* collect_mixers, or a later batch on another stream, comes behind the clear -- as behind allreduce_mixers */
+}
+
+int airband_hip_comm_destroy(airband_hip_handle* h) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!h->comm) return AIRBAND_HIP_OK;
+    Rccl* R = rccl();
+    if (R) {
+        (void)hipSetDevice(h->hip_device);
+        (void)hipStreamSynchronize(h->stream);
+        (void)R->CommDestroy(h->comm);
+    }
+    h->comm = nullptr;
+    return AIRBAND_HIP_OK;
+}
+
+} /* extern "C" */

@@ -5,7 +5,7 @@
  * batch before (`active`), so the one batch a transmission ended in still goes out whole.  `prev` is that `active`, kept per channel on the device and advanced
  * once per batch by the select pass -- it follows the batches in the order stage 2 ran them, whatever enqueued them.
  *
- * Three launches per batch on a gated handle, behind the emit / mixer launches (airband_hip.cpp, run_back_half); none on a handle without a gate:
+ * Three launches per batch on a gated handle, behind the emit / mixer launches (driver_gate.cpp, launch_gate_behind_mix, called by run_back_half); none on a handle without a gate:
  *   gate_select_kernel   one lane per channel: the verdict, the new `prev`, one 64-bit ballot per wavefront, one count per workgroup;
  *   gate_index_kernel    the same lanes again: workgroup base = sum of the counts in front of it, lane rank = population count of the ballot's lower bits ->
  *                        the list of active channels in ASCENDING order whatever the workgroups' scheduling (no atomic cursor), and the total;

@@ -1,4 +1,5 @@
-/* csrc/handle.h -- private to airband_hip.cpp: the handle behind the C ABI and the types that own its HIP objects.
+/* csrc/handle.h -- private to the host driver (airband_hip.cpp and driver_*.cpp, which include driver.h after it): the handle behind the C ABI and the types
+ * that own its HIP objects.
  *
  * Everything the handle holds on the device frees itself when the handle is deleted.  What makes that safe -- nothing of it is still in
  * flight -- is destroy()'s job (airband_hip.cpp), not these destructors'.
@@ -134,51 +135,9 @@ struct OutputGate {
     DevBuf<float> d_rows, d_iq_rows;
 };
 
-/* what airband_hip_set_band_scope() set up: replaced as a whole, one without windows is a handle without a scope (nothing allocated, nothing launched, no
- * stream, no event).  Handles whose next stage 1 may run before the last batch's results are collected (pipelined, run-ahead) keep TWO sets of rows: the
- * scope of front batch k goes to a set of its own and becomes the current one when the batch's back half is enqueued, as the batch's results do. */
-/* what airband_hip_set_band_survey() set up, a part of the scope it reads: replaced as a whole, gone with the scope, one without max_peaks is a scope without
- * a survey (nothing allocated, nothing launched).  Its results follow the scope's rows: the same sets, the same `cur`. */
-/* what airband_hip_set_band_watch() set up, a part of the survey it reads: replaced as a whole, gone with the survey, one without max_tracks is a survey
- * without a watch (nothing allocated, nothing launched).  Its results follow the survey's: the same sets, the same `cur`; the tables a batch starts from are
- * the other set's where there are two. */
-/* what airband_hip_set_band_follow() set up, a part of the watch whose tables it reads: replaced as a whole, gone with the watch, one without max_changes is a
- * watch without a follow (nothing allocated, nothing launched).  A handle with followers never runs ahead: the scope keeps ONE set, and so does this. */
-struct BandFollow {
-    int max_changes = 0;       /* capacity of the fleet's list; 0 = no follow */
-    int cap = 0;               /* a row's staging slice: the most followers of a row + max_tracks */
-    DevBuf<int> d_range, d_slot, d_home; /* by scope row: first follower and count; by follower (prepare order): demod slot, home bin */
-    DevBuf<airband_hip_band_follower> d_followers;
-    DevBuf<airband_hip_band_follow_row> d_rows;
-    DevBuf<airband_hip_band_follow_change> d_changes, d_stage; /* d_stage: the rows' changes between the two kernels of one launch */
-    DevBuf<int> d_count;
-};
-
-struct BandWatch {
-    int max_tracks = 0;        /* 0 = no watch */
-    BandFollow follow;
-    int match_bins = 0, confirm_hits = 0, release_misses = 0, max_events = 0;
-    uint32_t batch = 0;        /* the watch batch number of the next launch */
-    DevBuf<airband_hip_band_track> d_tracks[2];
-    DevBuf<airband_hip_band_watch_row> d_rows[2];
-    DevBuf<airband_hip_band_event> d_events[2], d_stage; /* d_stage: the rows' events between the two kernels of one launch */
-    DevBuf<int> d_count[2];
-};
-
-struct BandSurvey {
-    int max_peaks = 0;         /* 0 = no survey */
-    BandWatch watch;
-    uint32_t trace = 0;        /* the one AIRBAND_SCOPE_* bit whose rows are surveyed */
-    int rank = 0, guard_bins = 0;
-    float ratio = 0.0f;
-    DevBuf<int> d_bin_first, d_bins; /* by scope row: the prepare-time bins of the dongle's channels */
-    DevBuf<airband_hip_band_summary> d_summary[2];
-    DevBuf<airband_hip_band_peak> d_peaks[2];
-};
-
-/* what airband_hip_set_scan_control() set up: replaced as a whole, one without idle_batches is a handle whose lists the host hops (nothing allocated, nothing
- * launched).  While it is there the host's scan_cur / scan_held / scan_latch and the per-frequency bits of cc_slots[slot].flags of the scan slots are NOT
- * kept: the entry a slot holds is on the device (d_state, d_sw), and switching control off refreshes them. */
+/* what airband_hip_set_scan_control() set up (the handle's scan members, below): replaced as a whole, one without idle_batches is a handle whose lists the host
+ * hops (nothing allocated, nothing launched).  While it is there the host's scan_cur / scan_held / scan_latch and the per-frequency bits of cc_slots[slot].flags of
+ * the scan slots are NOT kept: the entry a slot holds is on the device (d_state, d_sw), and switching control off refreshes them. */
 struct ScanControl {
     int idle_batches = 0;      /* 0 = no scan control */
     int dwell_batches = 1, max_records = 0;
@@ -191,6 +150,50 @@ struct ScanControl {
     DevBuf<int> d_stage_n, d_sw, d_count;
 };
 
+/* The band outputs, like the gated ones above, are declared innermost first: each is a member of the one it reads (follow in watch in survey in scope), so that
+ * replacing an outer one drops what hangs on it, and a member's type has to be complete.  Read them from BandScope upwards. */
+/* what airband_hip_set_band_follow() set up, a part of the watch whose tables it reads: replaced as a whole, gone with the watch, one without max_changes is a
+ * watch without a follow (nothing allocated, nothing launched).  A handle with followers never runs ahead: the scope keeps ONE set, and so does this. */
+struct BandFollow {
+    int max_changes = 0;       /* capacity of the fleet's list; 0 = no follow */
+    int cap = 0;               /* a row's staging slice: the most followers of a row + max_tracks */
+    DevBuf<int> d_range, d_slot, d_home; /* by scope row: first follower and count; by follower (prepare order): demod slot, home bin */
+    DevBuf<airband_hip_band_follower> d_followers;
+    DevBuf<airband_hip_band_follow_row> d_rows;
+    DevBuf<airband_hip_band_follow_change> d_changes, d_stage; /* d_stage: the rows' changes between the two kernels of one launch */
+    DevBuf<int> d_count;
+};
+
+/* what airband_hip_set_band_watch() set up, a part of the survey it reads: replaced as a whole, gone with the survey, one without max_tracks is a survey
+ * without a watch (nothing allocated, nothing launched).  Its results follow the survey's: the same sets, the same `cur`; the tables a batch starts from are
+ * the other set's where there are two. */
+struct BandWatch {
+    int max_tracks = 0;        /* 0 = no watch */
+    BandFollow follow;
+    int match_bins = 0, confirm_hits = 0, release_misses = 0, max_events = 0;
+    uint32_t batch = 0;        /* the watch batch number of the next launch */
+    DevBuf<airband_hip_band_track> d_tracks[2];
+    DevBuf<airband_hip_band_watch_row> d_rows[2];
+    DevBuf<airband_hip_band_event> d_events[2], d_stage; /* d_stage: the rows' events between the two kernels of one launch */
+    DevBuf<int> d_count[2];
+};
+
+/* what airband_hip_set_band_survey() set up, a part of the scope it reads: replaced as a whole, gone with the scope, one without max_peaks is a scope without
+ * a survey (nothing allocated, nothing launched).  Its results follow the scope's rows: the same sets, the same `cur`. */
+struct BandSurvey {
+    int max_peaks = 0;         /* 0 = no survey */
+    BandWatch watch;
+    uint32_t trace = 0;        /* the one AIRBAND_SCOPE_* bit whose rows are surveyed */
+    int rank = 0, guard_bins = 0;
+    float ratio = 0.0f;
+    DevBuf<int> d_bin_first, d_bins; /* by scope row: the prepare-time bins of the dongle's channels */
+    DevBuf<airband_hip_band_summary> d_summary[2];
+    DevBuf<airband_hip_band_peak> d_peaks[2];
+};
+
+/* what airband_hip_set_band_scope() set up: replaced as a whole, one without windows is a handle without a scope (nothing allocated, nothing launched, no
+ * stream, no event).  Handles whose next stage 1 may run before the last batch's results are collected (pipelined, run-ahead) keep TWO sets of rows: the
+ * scope of front batch k goes to a set of its own and becomes the current one when the batch's back half is enqueued, as the batch's results do. */
 struct BandScope {
     int windows = 0;           /* windows per batch; 0 = no scope */
     BandSurvey survey;

@@ -1,4 +1,4 @@
-/* csrc/kernels.h -- launch interfaces of the HIP kernels (host side: airband_hip.cpp). */
+/* csrc/kernels.h -- launch interfaces of the HIP kernels (host side: airband_hip.cpp and driver_*.cpp, see driver.h). */
 #ifndef AIRBAND_CSRC_KERNELS_H
 #define AIRBAND_CSRC_KERNELS_H
 

@@ -10,7 +10,7 @@
  * from an atomic cursor.  Rows that come BACK (a dropped transmission, a collect) are pushed through an atomic cursor: the order of the pushes only decides
  * which row holds which audio.
  *
- * Four launches per batch on a handle with a spool, behind the encoder on the same stream (airband_hip.cpp, run_back_half); none on a handle without one:
+ * Four launches per batch on a handle with a spool, behind the encoder on the same stream (driver_gate.cpp, launch_gate_behind_mix, called by run_back_half); none on a handle without one:
  *   spool_scan_kernel    one lane per channel: phase A's verdict and "spooled and selected by the gate", one ballot each per wavefront, one count each per
  *                        workgroup; thread 0 fixes what the step sees of the finished list (room, where records go) and clears the step's sum;
  *   spool_close_kernel   the same lanes: a closing channel's rank among the closers -> its record into the ring while rank < room, else dropped and its

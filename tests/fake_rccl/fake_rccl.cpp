@@ -1,5 +1,5 @@
 // tests/fake_rccl/fake_rccl.cpp -- TEST INFRASTRUCTURE: a stand-in for librccl.so with the eight entry points libairband_hip.so binds
-// (csrc/airband_hip.cpp, rccl()): ncclGetUniqueId, ncclCommInitRank, ncclCommInitAll, ncclAllReduce, ncclCommDestroy, ncclGroupStart,
+// (csrc/driver_mix.cpp, rccl()): ncclGetUniqueId, ncclCommInitRank, ncclCommInitAll, ncclAllReduce, ncclCommDestroy, ncclGroupStart,
 // ncclGroupEnd, ncclGetErrorString.  It exists so that the SHIPPING exchange code -- airband_hip_comm_init_all / _init_rank / _group_begin /
 // allreduce_mixers / _group_end, and the reference-side shim's use of them -- runs with MORE THAN ONE RANK on a box with one GPU (RCCL proper
 // refuses two ranks on one GPU) and, for the host logic, on a box with none.  Selected with AIRBAND_HIP_RCCL_LIB=<this library>.
@@ -276,7 +276,7 @@ ncclResult_t flush() {
 
 extern "C" {
 
-/* capability libairband_hip.so looks for (csrc/airband_hip.cpp, rccl()): ranks of one communicator may share a GPU here -- the duplicate-GPU check of
+/* capability libairband_hip.so looks for (csrc/driver_mix.cpp, rccl()): ranks of one communicator may share a GPU here -- the duplicate-GPU check of
  * airband_hip_comm_init_all, which protects callers from RCCL's late and generic refusal, is skipped for this library only */
 int airband_rccl_allows_shared_gpu(void) { return 1; }
 

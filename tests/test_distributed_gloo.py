@@ -71,7 +71,7 @@ class HostHandle:
         rc = self.L.ncclCommInitRank(C.byref(self.comm), nranks, u, rank)
         assert rc == 0, self.L.ncclGetErrorString(rc)
 
-    def allreduce_mixers(self):  # the calls of airband_hip_allreduce_mixers (csrc/airband_hip.cpp), in its order
+    def allreduce_mixers(self):  # the calls of airband_hip_allreduce_mixers (csrc/driver_mix.cpp), in its order
         L = self.L
         assert L.ncclGroupStart() == 0
         assert L.ncclAllReduce(self.left.ctypes.data, self.left.ctypes.data, self.left.size, NCCL_FLOAT, NCCL_SUM, self.comm, None) == 0
