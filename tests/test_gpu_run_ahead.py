@@ -29,14 +29,14 @@ def _mix(n_dev):
     return [(d, c, (d * 8 + c) % N_MIXERS, 1.0 + 0.1 * c, 0.25 if c == 5 else 0.0) for d in range(n_dev) for c in range(8)]
 
 
-def _handle(pkg, monkeypatch, devices, run_ahead, flags=0, mixers=True):
+def _handle(pkg, monkeypatch, devices, run_ahead, flags=0, mixers=True, wave_rate=WAVE_RATE):
     """A handle prepared with the run-ahead schedule switched on (the default: variable unset) or off (AIRBAND_HIP_RUN_AHEAD=0); the variable is read at prepare."""
     with monkeypatch.context() as m:
         if run_ahead:
             m.delenv("AIRBAND_HIP_RUN_AHEAD", raising=False)
         else:
             m.setenv("AIRBAND_HIP_RUN_AHEAD", "0")
-        h = pkg.AirbandHip(devices, wave_rate=WAVE_RATE, flags=flags)
+        h = pkg.AirbandHip(devices, wave_rate=wave_rate, flags=flags)
     if mixers:
         h.set_mixers(N_MIXERS, _mix(len(devices)))
     return h
