@@ -976,6 +976,28 @@ int airband_hip_derive_constants(const airband_hip_config* cfg, int32_t channel_
  * in float32 in the order of the kernel the configuration takes -- a flagged wide-hop one in csrc/channelizer_f32_wide.hip's (window segments, pieces, K = 4). */
 int airband_hip_dft_selftest(const airband_hip_config* cfg, int32_t windows, double* max_rel_err);
 
+/* What airband_hip_read_tables() reports about the coefficient tables of a matrix-core handle.  n_bsets tables in all: [0, n_host_bsets) built on the host,
+ * [n_host_bsets, n_shared_bsets) built on the device at prepare time, [n_shared_bsets, n_bsets) the private tables of groups with an AFC channel or a follower
+ * (the re-tune kernel builds and rewrites those).  "dft_mfma_i8": a table is pieces_per_table window pieces (1 up to fft 512, fft / 512 beyond) of
+ * [3 digits][k-step][64 lanes][16 bytes] int8, each with 16 doubles of offset correction.  "dft_mfma_f32": a table is pieces_per_table rows-of-rows
+ * [segment][piece] of [s][64 lanes] floats, the host builds every shared one (n_host_bsets == n_shared_bsets) and there is no offset correction. */
+typedef struct airband_hip_table_info {
+    int32_t n_bsets, n_shared_bsets, n_host_bsets;
+    int32_t pieces_per_table;
+    int64_t bytes_per_table;
+    int32_t edge_hi_zero;   /* the int8 kernel skips the top digit in its outer k-steps (0, 1, 14, 15 of 16) */
+    int32_t n_items;        /* work items = (dongle, group of eight channels) pairs, device-major */
+    char channelizer[16];   /* airband_hip_channelizer_name() */
+} airband_hip_table_info;
+
+/* Coefficient tables [first, first + n) of a matrix-core handle as they stand on the device, read-only (tests compare them with the defining sum): waits for
+ * everything enqueued on the handle, then copies out `tables` (n x bytes_per_table bytes: int8 fragments, or floats on a CF32 handle), `corr`
+ * (n x pieces_per_table x 16 doubles; left alone on a CF32 handle), `bset_bin` (n x 8: the bin each column pair is built for, -1 = unused) and `items`
+ * (3 x n_items: per work item the table it reads now, its home table and its private table -- the last two equal where it has none).  *info is always
+ * filled.  n == 0: only *info, the buffers may be NULL.  AIRBAND_HIP_EINVAL for a NULL handle, info or (n > 0) buffer, for a range outside [0, n_bsets), and
+ * for a handle on the wavefront FFT, which has no tables. */
+int airband_hip_read_tables(airband_hip_handle* h, int32_t first, int32_t n, airband_hip_table_info* info, void* tables, double* corr, int32_t* bset_bin, int32_t* items);
+
 /* Milliseconds the GPU spent on the last finished batch (HIP events on the streams the kernels run on):
  * [0] channelizer kernel, [1] demod kernels (+ per-kind emit), [2] joint emit / mixers (+ the output gate's select and gather, + the output encoding's kernel), [3] their sum.  Waits for the
  * enqueued batches. */

@@ -42,6 +42,7 @@ EXPORTS = [
     "airband_hip_set_band_watch", "airband_hip_collect_band_events", "airband_hip_collect_band_tracks", "airband_hip_device_band_watch",
     "airband_hip_prepare_follow", "airband_hip_set_band_follow", "airband_hip_collect_band_follow_changes", "airband_hip_collect_band_followers", "airband_hip_device_band_follow",
     "airband_hip_channelizer_reason", "airband_hip_wide_hop_lds_bytes", "airband_hip_schedule_info", "airband_hip_wide_hop_plan",
+    "airband_hip_read_tables",
 ]
 # Exported entries whose names carry digits.  Kept apart from EXPORTS, which tests/test_abi.py compares with the header's names through a pattern of letters and
 # underscores only: a name with a digit in EXPORTS can never equal what that pattern finds.
@@ -112,7 +113,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
-    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()):
+    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()) + list(capi.TABLES_PROTOTYPES.items()):
         if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
             getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
@@ -689,6 +690,32 @@ class AirbandHip:
 
     def channelizer_name(self) -> str:
         return self.L.airband_hip_channelizer_name(self.h).decode()
+
+    def table_info(self) -> dict:
+        """n_bsets, n_shared_bsets, n_host_bsets, pieces_per_table, bytes_per_table, edge_hi_zero, n_items, channelizer of a matrix-core handle's coefficient
+        tables (airband_hip_read_tables with an empty range).  AirbandError(EINVAL) on the wavefront FFT."""
+        info = capi.TableInfo()
+        self._check(self.L.airband_hip_read_tables(self.h, 0, 0, C.byref(info), None, None, None, None))
+        out = {f[0]: getattr(info, f[0]) for f in capi.TableInfo._fields_}
+        out["channelizer"] = out["channelizer"].decode()
+        out["edge_hi_zero"] = bool(out["edge_hi_zero"])
+        return out
+
+    def read_tables(self, first: int = 0, n: Optional[int] = None) -> dict:
+        """Coefficient tables [first, first + n) as they stand on the device (airband_hip_read_tables; waits for the handle): info (table_info()), tables
+        [n][bytes_per_table] int8 -- or [n][bytes_per_table / 4] float32 on a CF32 handle --, corr [n][pieces_per_table][16] float64 (zeros on CF32), bset_bin [n][8],
+        and per work item item_bset (the table it reads now), item_home, item_private."""
+        info = self.table_info()
+        n = info["n_bsets"] - int(first) if n is None else int(n)
+        f32 = info["channelizer"] == "dft_mfma_f32"
+        rows = max(n, 0)
+        tab = np.zeros((rows, info["bytes_per_table"] // 4), np.float32) if f32 else np.zeros((rows, info["bytes_per_table"]), np.int8)
+        corr = np.zeros((rows, info["pieces_per_table"], 16), np.float64)
+        bins = np.zeros((rows, 8), np.int32)
+        items = np.zeros((3, info["n_items"]), np.int32)
+        raw = capi.TableInfo()
+        self._check(self.L.airband_hip_read_tables(self.h, int(first), n, C.byref(raw), tab.ctypes.data, corr.ctypes.data, bins.ctypes.data, items.ctypes.data))
+        return dict(info=info, tables=tab, corr=corr, bset_bin=bins, item_bset=items[0], item_home=items[1], item_private=items[2])
 
     def channelizer_reason(self) -> str:
         """Why the handle has the channelizer it has; "" on a matrix-core kernel by the ordinary rule."""

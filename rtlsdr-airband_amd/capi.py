@@ -97,6 +97,16 @@ BAND_SCOPE_PROTOTYPES = {
     "airband_hip_device_band_scope": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
 }
 
+# airband_hip_read_tables (same header): the coefficient tables of a matrix-core handle, read back for tests
+class TableInfo(C.Structure):
+    _fields_ = [("n_bsets", C.c_int32), ("n_shared_bsets", C.c_int32), ("n_host_bsets", C.c_int32), ("pieces_per_table", C.c_int32), ("bytes_per_table", C.c_int64),
+                ("edge_hi_zero", C.c_int32), ("n_items", C.c_int32), ("channelizer", C.c_char * 16)]
+
+
+TABLES_PROTOTYPES = {
+    "airband_hip_read_tables": [_vp, _i32, _i32, C.POINTER(TableInfo), _vp, _vp, _vp, _vp],
+}
+
 # the band survey's (same header)
 _f32 = C.c_float
 BAND_SURVEY_PROTOTYPES = {

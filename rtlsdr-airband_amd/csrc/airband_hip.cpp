@@ -1256,6 +1256,48 @@ int airband_hip_channel_constants(const airband_hip_handle* h, int32_t channel_i
     return AIRBAND_HIP_OK;
 }
 
+int airband_hip_read_tables(airband_hip_handle* h, int32_t first, int32_t n, airband_hip_table_info* info, void* tables, double* corr, int32_t* bset_bin, int32_t* items) {
+    if (!h || !info) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    if (!h->use_dft && !h->use_f32) return fail(h, AIRBAND_HIP_EINVAL, "the handle runs on the wavefront FFT: it has no coefficient tables");
+    const Plan& p = h->plan;
+    const int N = p.fft_size;
+    const size_t n_items = p.item_dev.size();
+    std::memset(info, 0, sizeof(*info));
+    info->n_bsets = p.n_bsets;
+    info->n_shared_bsets = p.n_shared_bsets;
+    info->n_items = (int32_t)n_items;
+    if (h->use_dft) {
+        info->n_host_bsets = p.n_host_bsets;
+        info->pieces_per_table = N > 512 ? N / 512 : 1;
+        info->bytes_per_table = (int64_t)3 * (N > 512 ? 16 : N / 32) * 64 * 16 * info->pieces_per_table;
+        info->edge_hi_zero = p.b_edge_hi_zero ? 1 : 0;
+    } else { /* build_f32_tables: the host builds every shared float table */
+        info->n_host_bsets = p.n_shared_bsets;
+        info->pieces_per_table = f32_n_seg(N) * f32_nw(N);
+        info->bytes_per_table = (int64_t)128 * N;
+    }
+    std::snprintf(info->channelizer, sizeof(info->channelizer), "%s", airband_hip_channelizer_name(h));
+    if (first < 0 || n < 0 || (int64_t)first + n > p.n_bsets) return fail(h, AIRBAND_HIP_EINVAL, "table range out of bounds");
+    if (n == 0) return AIRBAND_HIP_OK;
+    if (!tables || !corr || !bset_bin || !items) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    const int rc = airband_hip_synchronize(h);
+    if (rc != AIRBAND_HIP_OK) return rc;
+    const size_t each = (size_t)info->bytes_per_table, per_corr = (size_t)info->pieces_per_table * 16;
+    const char* src = h->use_dft ? reinterpret_cast<const char*>(h->d_bfrag.p) : reinterpret_cast<const char*>(h->d_ftab.p);
+    HIP_TRY(h, hipMemcpyAsync(tables, src + (size_t)first * each, (size_t)n * each, hipMemcpyDeviceToHost, h->stream), AIRBAND_HIP_ERUNTIME);
+    if (h->use_dft) HIP_TRY(h, hipMemcpyAsync(corr, h->d_bcorr.p + (size_t)first * per_corr, (size_t)n * per_corr * sizeof(double), hipMemcpyDeviceToHost, h->stream), AIRBAND_HIP_ERUNTIME);
+    /* a CF32 handle without private tables never uploaded the bins and the home / private indices: nothing on the device moves them, the plan's are the truth */
+    if (h->d_bset_bin.p) HIP_TRY(h, hipMemcpyAsync(bset_bin, h->d_bset_bin.p + (size_t)first * 8, (size_t)n * 8 * sizeof(int), hipMemcpyDeviceToHost, h->stream), AIRBAND_HIP_ERUNTIME);
+    else std::memcpy(bset_bin, p.bset_bins.data() + (size_t)first * 8, (size_t)n * 8 * sizeof(int));
+    HIP_TRY(h, hipMemcpyAsync(items, h->d_item_bset.p, n_items * sizeof(int), hipMemcpyDeviceToHost, h->stream), AIRBAND_HIP_ERUNTIME);
+    if (h->d_item_home.p) HIP_TRY(h, hipMemcpyAsync(items + n_items, h->d_item_home.p, n_items * sizeof(int), hipMemcpyDeviceToHost, h->stream), AIRBAND_HIP_ERUNTIME);
+    else std::memcpy(items + n_items, p.item_home.data(), n_items * sizeof(int));
+    if (h->d_item_private.p) HIP_TRY(h, hipMemcpyAsync(items + 2 * n_items, h->d_item_private.p, n_items * sizeof(int), hipMemcpyDeviceToHost, h->stream), AIRBAND_HIP_ERUNTIME);
+    else std::memcpy(items + 2 * n_items, p.item_bset.data(), n_items * sizeof(int));
+    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
+    return AIRBAND_HIP_OK;
+}
+
 int airband_hip_last_timings(airband_hip_handle* h, float* ms4) {
     if (!h || !ms4) return AIRBAND_HIP_EINVAL;
     HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);

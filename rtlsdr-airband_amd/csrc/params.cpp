@@ -349,20 +349,18 @@ void build_f32_tables(Plan& p) {
 }
 
 /* shared coefficient tables the host builds; the rest are built on the device at prepare() time.  AIRBAND_HIP_HOST_TABLES_MAX overrides (tests: small fleets through the
- * device builder) */
+ * device builder); it is read once per build_dft_tables() call, so a process may prepare handles under different values */
 static int host_tables_max() {
-    static const int n = [] {
-        const char* e = getenv("AIRBAND_HIP_HOST_TABLES_MAX");
-        const long v = e ? strtol(e, nullptr, 10) : 4096;
-        return (int)(v < 0 ? 0 : v > (1 << 20) ? (1 << 20) : v);
-    }();
-    return n;
+    const char* e = getenv("AIRBAND_HIP_HOST_TABLES_MAX");
+    const long v = e ? strtol(e, nullptr, 10) : 4096;
+    return (int)(v < 0 ? 0 : v > (1 << 20) ? (1 << 20) : v);
 }
 
 void build_dft_tables(Plan& p, bool host_private) {
     /* fft_size > 512: one table per window piece of 512 samples (NP pieces); a table then covers K = 1024 bytes of the window */
     const int N = p.fft_size, NP = N > 512 ? N / 512 : 1, NS = N / NP, K = 2 * NS, KS = K / 64;
     const double S = AB_DFT_COEF_SCALE;
+    const int host_max = host_tables_max();
     p.b_unscale = 1.0 / (S * 127.5);
     p.item_dev.clear();
     p.item_group.clear();
@@ -438,7 +436,7 @@ void build_dft_tables(Plan& p, bool host_private) {
                 home = (int)shared_keys.size();
                 shared_keys.push_back(key);
                 shared_index.emplace(key, home);
-                if (host_private || shared_keys.size() <= (size_t)host_tables_max()) build(key); /* the rest: on the device */
+                if (host_private || shared_keys.size() <= (size_t)host_max) build(key); /* the rest: on the device */
             }
             last_shared = home;
             if (private_table) {
@@ -454,7 +452,7 @@ void build_dft_tables(Plan& p, bool host_private) {
         }
     }
     p.n_shared_bsets = (int)shared_keys.size();
-    p.n_host_bsets = host_private ? p.n_shared_bsets : std::min(p.n_shared_bsets, host_tables_max());
+    p.n_host_bsets = host_private ? p.n_shared_bsets : std::min(p.n_shared_bsets, host_max);
     p.n_bsets = p.n_shared_bsets + (int)private_keys.size();
     for (int& b : p.item_bset)
         if (b < 0) b = p.n_shared_bsets + (-b - 1);

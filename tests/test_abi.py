@@ -128,3 +128,23 @@ def test_null_and_misuse_do_not_crash(pkg, built):
     assert L.airband_hip_channelizer_name(None) == b"fft_wave64"
     bad = capi.Config(capi.ABI_VERSION + 7, 0, 9, 8000, 0, 0, 0, None)
     assert L.airband_hip_prepare(C.byref(bad), C.byref(h)) == capi.EINVAL
+
+
+def test_read_tables_is_declared_bound_and_checks_its_arguments(pkg, built):
+    """airband_hip_read_tables (the coefficient tables read back for tests/test_gpu_device_tables.py): in the header with a comment right above, in the library with the
+    prototype capi.py gives it, its info struct laid out as the header's, and a NULL handle refused before any device is touched."""
+    capi = pkg.capi
+    text = open(os.path.join(ROOT, "include", "airband_hip.h")).read()
+    decl = "int airband_hip_read_tables(airband_hip_handle* h, int32_t first, int32_t n, airband_hip_table_info* info, void* tables, double* corr, int32_t* bset_bin, int32_t* items);"
+    assert text[:text.index(decl)].rstrip().endswith("*/")
+    for field in ("int32_t n_bsets, n_shared_bsets, n_host_bsets;", "int32_t pieces_per_table;", "int64_t bytes_per_table;", "int32_t edge_hi_zero;", "int32_t n_items;", "char channelizer[16];"):
+        assert field in text, field
+    assert C.sizeof(capi.TableInfo) == 48 and capi.TableInfo.bytes_per_table.offset == 16 and capi.TableInfo.channelizer.offset == 32
+    L = pkg.load_library()
+    assert "airband_hip_read_tables" in pkg.EXPORTS
+    assert L.airband_hip_read_tables.argtypes == capi.TABLES_PROTOTYPES["airband_hip_read_tables"]
+    info = capi.TableInfo()
+    buf = np.full(64, 0x55, np.uint8)
+    assert L.airband_hip_read_tables(None, 0, 0, C.byref(info), None, None, None, None) == capi.EINVAL
+    assert L.airband_hip_read_tables(None, 0, 1, C.byref(info), buf.ctypes.data, buf.ctypes.data, buf.ctypes.data, buf.ctypes.data) == capi.EINVAL
+    assert (buf == 0x55).all() and info.n_bsets == 0
