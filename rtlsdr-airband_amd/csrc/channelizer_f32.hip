@@ -310,8 +310,7 @@ void launch_channelizer_f32(const F32Args& a0, hipStream_t stream) {
     F32Args a = a0;
     a.n_seg = f32_n_seg(a0.fft_size);
     a.seg = 0;
-    const int tile_bytes = (TILE_HOPS - 1) * a.hop_bytes + 8 * f32_seg_size(a.fft_size) + ((a.hop_bytes & 8) ? 16 : 0); /* (odd hops: the image may start 8 bytes in front of the tile) */
-    const bool small = tile_bytes <= 6 * 64 * f32_nw(a.fft_size) * 16; /* six pieces per thread: the register budget of three workgroups per CU (NW = 4) */
+    const bool small = f32_small_tile(a.fft_size, a.hop_bytes); /* six pieces per thread (kernels.h) */
     if (a.n_seg > 1) { /* fft_size 4096 / 8192: the fft 2048 kernel once per window segment */
         for (int seg = 0; seg < a.n_seg; seg++) {
             a.seg = seg;

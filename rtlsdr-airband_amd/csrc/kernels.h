@@ -210,12 +210,16 @@ int f32_partial_tiles(int n_hops_max); /* 16-hop tiles a work item may touch in 
 /* layout of the staged image (channelizer_f32.hip): 1 = hops of an odd number of samples (no padding, fragments from two 8-byte reads), 3 = hops of an odd number of 16-byte units (no padding), 2 = 16 bytes of padding per 256 stream
  * bytes (hops that are multiples of 256 bytes; offsets become immediates), 0 = 16 bytes per hop where the hop is an even number of 16-byte units.  fft 512 with the small tiles
  * of WAVE_RATE 16000 stays on 0: layout 2's 6 % more LDS would cost it its third workgroup per CU (measured: 22.1 -> 24.1 ms; every other variant gains, fft 2048 27 %) */
+/* THE small-tile rule (launch_channelizer_f32 picks MAX_LD = 6 or 12 by it): a tile's 16 hops of one window segment, plus the 16 bytes an image of odd hops may start in front of
+ * the tile, within six 16-byte pieces per thread -- the register budget of three workgroups per CU (NW = 4) */
+inline bool f32_small_tile(int fft_size, int hop_bytes) {
+    return 15 * hop_bytes + 8 * f32_seg_size(fft_size) + ((hop_bytes & 8) ? 16 : 0) <= 6 * 64 * f32_nw(fft_size) * 16;
+}
 inline int f32_layout(int fft_size, int hop_bytes) {
     if (hop_bytes & 8) return 1;
     if ((hop_bytes / 16) & 1) return 3; /* an odd number of 16-byte units per hop (2.4 MS/s: 1 200 / 2 400 bytes): the rows fall in different bank groups as they are -- no padding, offsets are immediates */
     if (hop_bytes % 256) return 0;
-    const bool small_tile = 15 * hop_bytes + 8 * f32_seg_size(fft_size) <= 6 * 64 * f32_nw(fft_size) * 16;
-    return (fft_size == 512 && small_tile) ? 0 : 2;
+    return (fft_size == 512 && f32_small_tile(fft_size, hop_bytes)) ? 0 : 2;
 }
 bool f32_supported(int fft_size, int hop_samples, int sfmt);
 int f32_pad_bytes(int hop_samples);

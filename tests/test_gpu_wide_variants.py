@@ -34,9 +34,9 @@ def tile_columns(b, B):
     return np.arange(0, 16 - first_row % 16), np.arange(B - (end_row % 16 or 16), B)
 
 
-def check_dongle(got, want, cols, what, pairs, rewritten=()):
+def check_dongle(got, want, cols, what, pairs, rewritten=(), elem_bar=BAR):
     """Bars (a) - (c) for one dongle's [channels][B x pairs] array of one batch.  Returns (whole, worst slice, worst element), all relative to the dongle's RMS.
-    rewritten: rows that are no longer stage 1's output (rewritten_rows) and are left out."""
+    rewritten: rows that are no longer stage 1's output (rewritten_rows) and are left out.  elem_bar: bar (c) where a caller has its own (tests/test_gpu_ordinary_variants.py)."""
     got, want = got.astype(np.float64), want.astype(np.float64)
     for c in rewritten:
         got[c] = want[c]
@@ -56,7 +56,7 @@ def check_dongle(got, want, cols, what, pairs, rewritten=()):
     print("%s: whole %.3g, worst slice %.3g (%s), worst element %.3g (channel %d, column %d)" % (what, whole, slices[worst_slice], worst_slice, elem, at[0], at[1] // pairs))
     assert whole <= BAR, "%s: relative RMS %g" % (what, whole)
     assert slices[worst_slice] <= BAR, "%s: %s is off by %g of the dongle's RMS" % (what, worst_slice, slices[worst_slice])
-    assert elem <= BAR, "%s: channel %d, column %d is off by %g of the dongle's RMS" % (what, at[0], at[1] // pairs, elem)
+    assert elem <= elem_bar, "%s: channel %d, column %d is off by %g of the dongle's RMS" % (what, at[0], at[1] // pairs, elem)
     return whole, slices[worst_slice], elem
 
 
@@ -72,10 +72,12 @@ def rewritten_rows(orc, d, device, ref):
     return rows
 
 
-def run_against_oracle(pkg, devices, iq, fft_log, wave_rate, n_batches, kernel, what, may_rewrite=False):
-    """The streams through the host path of a flagged handle, every batch's read_bins() against the oracle's raw_wavein / raw_iq dongle by dongle.
+def run_against_oracle(pkg, devices, iq, fft_log, wave_rate, n_batches, kernel, what, may_rewrite=False, flags=None, elem_bar=BAR, on_handle=None):
+    """The streams through the host path of a handle (flags: AIRBAND_HIP_FLAG_WIDE_HOPS unless given), every batch's read_bins() against the oracle's raw_wavein /
+    raw_iq dongle by dongle.  on_handle(hip, what): the caller's own look at the handle in front of the first batch.
     Returns (kernel name, worst whole-batch RMS, worst slice, worst element)."""
     capi = pkg.capi
+    flags = capi.FLAG_WIDE_HOPS if flags is None else flags
     orc = pyoracle.Oracle(devices, wave_rate=wave_rate, fft_log=fft_log)
     try:
         ref = [orc.run_device(d, iq[d], n_batches) for d in range(len(devices))]
@@ -90,11 +92,13 @@ def run_against_oracle(pkg, devices, iq, fft_log, wave_rate, n_batches, kernel, 
         for c in range(r["raw_wavein"].shape[1]):
             assert helpers.rms(r["raw_wavein"][:, c]) > 0.0, "%s: dongle %d channel %d: the oracle's row is empty" % (what, d, c)
     worst = [0.0, 0.0, 0.0]
-    with pkg.AirbandHip(devices, wave_rate=wave_rate, fft_log=fft_log, flags=capi.FLAG_WIDE_HOPS) as hip:
+    with pkg.AirbandHip(devices, wave_rate=wave_rate, fft_log=fft_log, flags=flags) as hip:
         name = hip.channelizer_name()
         what = "%s, %s" % (what, name)
         assert name == kernel, what
         assert hip.channelizer_reason() == "", what
+        if on_handle is not None:
+            on_handle(hip, what)
         B = hip.B
         pos = [0] * len(devices)
         for b in range(n_batches):
@@ -109,7 +113,7 @@ def run_against_oracle(pkg, devices, iq, fft_log, wave_rate, n_batches, kernel, 
             for d, r in enumerate(ref):
                 nc = len(devices[d]["channels"])
                 for got, want, pairs, kind in ((w[k:k + nc], r["raw_wavein"][b], 1, "|bin|"), (q[k:k + nc], r["raw_iq"][b], 2, "bin I/Q")):
-                    fig = check_dongle(got, want, cols, "%s; batch %d dongle %d %s" % (what, b, d, kind), pairs, rewritten[d] if pairs == 1 else ())
+                    fig = check_dongle(got, want, cols, "%s; batch %d dongle %d %s" % (what, b, d, kind), pairs, rewritten[d] if pairs == 1 else (), elem_bar)
                     worst = [max(x, y) for x, y in zip(worst, fig)]
                 k += nc
     return (name,) + tuple(worst)
