@@ -511,7 +511,8 @@ int airband_hip_device_active(airband_hip_handle* h, int32_t** d_index, int32_t*
  * Every row the gate delivers is float32 samples of 8 kHz or 16 kHz voice audio in +-1.0 (what the reference hands lame_encode_buffer_ieee_float, its UDP
  * stream and pulse).  A consumer that ships int16 or G.711 (8 kHz mono is exactly RTP payload types 0, PCMU, and 8, PCMA) copies four bytes per sample over
  * PCIe and converts on the host.  A gated handle with an output encoding converts on the GPU, behind the gate, the rows the gate selected: half the bytes for
- * int16, a quarter for G.711, and one 16-byte record per row.  Mixer outputs and raw-I/Q rows are out of scope: they stay float.
+ * int16, a quarter for G.711, and one 16-byte record per row.  Raw-I/Q rows are out of scope: they stay float.  Mixer outputs have a gate and an encoder of
+ * their own: see "gated mixer collect" below.
  * The definition (normative).  For one float32 sample x of a delivered row:
  *   x NaN:                  q = 0, not clipped;
  *   otherwise               v = x * 32767.0f -- ONE float32 multiplication, nothing fused with it;
@@ -570,6 +571,66 @@ int airband_hip_device_active_encoded(airband_hip_handle* h, void** d_audio, air
  * AIRBAND_HIP_EINVAL for NULL rows, n_rows < 0 (or too many to index), encoding AIRBAND_AUDIO_F32 or unknown; n_rows == 0 is AIRBAND_HIP_OK. */
 int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const float* rows, int64_t n_rows, void* audio, airband_hip_audio_row* info);
 
+/* ---- gated mixer collect -----------------------------------------------------------------------------------------------------------------
+ * A mixer's output channel is a channel like any other to the reference: mix_waveforms() sets its axcindicate to SIGNAL iff an input had signal
+ * (src/mixer.cpp:193-209), process_outputs() applies the same file / UDP / pulse skip rule to it (src/output.cpp:501,531,539,552), and a stereo mixer goes out
+ * with left and right interleaved (src/udp_stream.cpp:75-82).  airband_hip_collect_mixers() copies left, right and has_signal of EVERY mixer in float32, every
+ * batch.  A handle with a mixer gate compacts on the GPU the mixers that will be consumed, as float32 or encoded, so that the host copies those alone.
+ * The definition (normative).  Everything behind the encoder's one float multiplication is integer arithmetic, so the results are checked as bytes.
+ * Frames and rows.  W = 2 with AIRBAND_MIXER_GATE_STEREO, else 1.  The row of mixer m is B = wave_batch frames.  Frame t is left[m][t] when W = 1, or
+ *   left[m][t], right[m][t] when W = 2.  The values are those that airband_hip_collect_mixers() would return at the moment of the step, bit for bit.  A mono
+ *   mixer's right is the zeros it already is.
+ * Step.  For every mixer m in ascending order: signal = has_signal[m] != 0; active = gate[m] == ALWAYS || (gate[m] == SIGNAL && (signal || prev[m]));
+ *   prev[m] = signal.  prev starts at 0 when the gate is set.  *n_active is the number of active mixers.  The list is the first max_rows active mixers,
+ *   ascending.  No atomic cursor: who is dropped past max_rows is defined.  A mixer whose inputs are all masked has no signal: that is the rule for a
+ *   switched-off dongle, there is no per-mixer OFF flag.
+ * What a row is delivered as.  AIRBAND_AUDIO_F32: W * B float32, the bits of the sums.  S16 / ULAW / ALAW: W * B samples, each encoded exactly by the definition
+ *   of airband_hip_set_output_encoding() above -- the q step, the clipping rule and both laws are the same -- interleaved L, R when W = 2.
+ * Record.  One airband_hip_audio_row per delivered row when there is an encoding (none for AIRBAND_AUDIO_F32).  channel = m.  peak and n_clipped are taken
+ *   over all W * B samples (the count is at most 4000, so it fits).  first is the index of the first FRAME in which any sample has q != 0, or B if there is
+ *   none; end is one past the last such frame, or 0 if there is none.  reserved = 1 if the mixer's stereo flag (airband_hip_mixer_set_stereo, or a nonzero
+ *   balance) was set at the step, else 0.
+ * When the step runs.  Without AIRBAND_MIXER_GATE_MANUAL_STEP: exactly once per batch, behind that batch's mixer sums on the same stream, in every schedule --
+ *   sequential, run-ahead, AIRBAND_HIP_FLAG_PIPELINE, airband_hip_process_device on a caller's stream, and airband_hip_process_bins.  With it: nothing is
+ *   launched with the batch.  Each call of airband_hip_mixer_gate_step(h, stream) enqueues one step behind whatever last wrote the sums (the batch,
+ *   airband_hip_allreduce_mixers, airband_hip_add_mixers, airband_hip_clear_mixers), by the stream rule of airband_hip_allreduce_mixers() (stream NULL = the
+ *   handle's own results stream).  On a multi-GPU node the sums are final only after the exchange: the host calls it once per batch, after its exchange.
+ *   AIRBAND_HIP_EINVAL on a handle whose gate is not manual.
+ * Out of scope: a transmission spool over mixer rows, raw-I/Q, MP3, and per-mixer encodings.
+ * A handle without a mixer gate allocates nothing for this, launches nothing and returns the same bits. */
+#define AIRBAND_MIXER_GATE_STEREO      0x1u  /* rows are B frames of (left, right); without it B frames of left only */
+#define AIRBAND_MIXER_GATE_MANUAL_STEP 0x2u  /* the step is not enqueued with the batch: the host calls airband_hip_mixer_gate_step() */
+
+/* gate[mixer_count] of AIRBAND_GATE_* (NULL removes the gate; the other arguments are not looked at then); max_rows = capacity of the packed buffers
+ * (1 .. mixer_count); encoding = AIRBAND_AUDIO_* (F32 included); flags = AIRBAND_MIXER_GATE_*.  Allowed any time after airband_hip_set_mixers(): it orders itself
+ * behind the last batch the way airband_hip_set_mixers() does; calling it again replaces the gate (prev starts at 0 again); airband_hip_set_mixers() called
+ * again drops it.  Validated before the device is touched: AIRBAND_HIP_EINVAL for a NULL handle, no mixers, a gate byte above 2, max_rows outside
+ * 1 .. mixer_count, an unknown encoding, unknown flag bits; AIRBAND_HIP_EBADSIZE if wave_batch is not a multiple of four; AIRBAND_HIP_ENOMEM when the buffers
+ * cannot be had -- the handle then runs on as it was.  An encoded gate does not also pack float rows: it allocates and moves only what it delivers. */
+int airband_hip_set_mixer_gate(airband_hip_handle* h, const uint8_t* gate, int64_t max_rows, int32_t encoding, uint32_t flags);
+
+/* One step of a manual gate (see "When the step runs"); AIRBAND_HIP_EINVAL on a handle without a mixer gate or whose gate is not manual. */
+int airband_hip_mixer_gate_step(airband_hip_handle* h, void* stream);
+
+/* The result of the last step.  *n_active = mixers the rule selected (may exceed max_rows); with n = min(*n_active, max_rows):
+ *   mixer_index [n]              the listed mixers, ascending;
+ *   rows        [n][W * B]       float32 frames -- only valid on an AIRBAND_AUDIO_F32 gate;
+ *   audio       [n][W * B]       int16 (S16) or bytes (G.711), info [n] the rows' records -- only valid on an encoded gate; otherwise AIRBAND_HIP_EINVAL;
+ *   signal_all  [mixer_count]    every mixer's has_signal.
+ * The count is copied first, then exactly n entries of each non-NULL array; nothing past row n is written.  AIRBAND_HIP_EAGAIN before the first step.  It does
+ * not mark the batch as collected (airband_hip_collect_mixers() does not either). */
+int airband_hip_collect_active_mixers(airband_hip_handle* h, int64_t* n_active, int32_t* mixer_index, float* rows, void* audio, airband_hip_audio_row* info, uint8_t* signal_all);
+
+/* Device-side views of the same (valid until the next step): d_index [max_rows], d_count [1], d_rows [max_rows][W * B] (NULL on an encoded gate), d_audio and
+ * d_info [max_rows] (NULL on an AIRBAND_AUDIO_F32 gate).  Any out-pointer may be NULL. */
+int airband_hip_device_active_mixers(airband_hip_handle* h, int32_t** d_index, int32_t** d_count, float** d_rows, void** d_audio, airband_hip_audio_row** d_info);
+
+/* The same pack kernel on caller-provided HOST rows left, right [n_rows][wave_batch] float32 (right NULL: mono, W = 1): audio [n_rows][W * wave_batch] int16 or
+ * bytes, info [n_rows] with info[i].channel = i and reserved = (right != NULL) (either may be NULL).  With right == NULL its bytes equal
+ * airband_hip_encode_audio()'s on the same rows.  Needs no gate and touches no handle state; synchronous.  AIRBAND_HIP_EINVAL for NULL left, n_rows < 0 (or
+ * too many to index), encoding AIRBAND_AUDIO_F32 or unknown; n_rows == 0 is AIRBAND_HIP_OK. */
+int airband_hip_encode_mixer_audio(airband_hip_handle* h, int32_t encoding, const float* left, const float* right, int64_t n_rows, void* audio, airband_hip_audio_row* info);
+
 /* ---- transmission spool ---------------------------------------------------------------------------------------------------------------
  * The reference's file sinks in `split_on_transmission` mode (src/output.cpp:340-368, :396-453, :498-532; src/config.cpp:117-160) produce one clip per
  * transmission: the file is opened by the first batch the file rule writes, every written batch is appended, and the file is closed once it is older than 1 s and
@@ -577,7 +638,7 @@ int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const floa
  * batch, keeps an open / last-write clock per channel, appends rows to per-channel buffers and cuts them.  A gated handle with an encoding and a SPOOL keeps the
  * encoded rows of every open transmission in a row pool on the GPU, applies the closing rule once per batch in batch counts (a batch is 125 ms) and hands over
  * only FINISHED transmissions -- one 48-byte record each and their audio concatenated in one contiguous copy -- whenever the host comes for them.
- * Raw-I/Q clips, mixer outputs, silence for batches that were not selected, wall-clock time stamps (the host maps batch numbers to time), per-channel parameters
+ * Raw-I/Q clips, mixer outputs ("gated mixer collect" delivers their rows, not clips), silence for batches that were not selected, wall-clock time stamps (the host maps batch numbers to time), per-channel parameters
  * and MP3 are out of scope.
  * The definition (normative; integers only, so two implementations of this text agree in every byte).
  * Parameters: spool[total_channels], a byte mask (NULL: every channel whose gate is AIRBAND_GATE_SIGNAL); a spooled channel must have gate SIGNAL (the reference

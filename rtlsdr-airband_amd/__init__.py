@@ -36,6 +36,7 @@ EXPORTS = [
     "airband_hip_set_scan_control", "airband_hip_scan_hold", "airband_hip_collect_scan_events", "airband_hip_collect_scan_state", "airband_hip_device_scan_control",
     "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
     "airband_hip_set_output_encoding", "airband_hip_collect_active_encoded", "airband_hip_device_active_encoded", "airband_hip_encode_audio",
+    "airband_hip_set_mixer_gate", "airband_hip_mixer_gate_step", "airband_hip_collect_active_mixers", "airband_hip_device_active_mixers", "airband_hip_encode_mixer_audio",
     "airband_hip_set_transmission_spool", "airband_hip_collect_transmissions", "airband_hip_spool_flush", "airband_hip_spool_counters_get", "airband_hip_device_transmission_spool",
     "airband_hip_set_band_scope", "airband_hip_collect_band_scope", "airband_hip_device_band_scope",
     "airband_hip_set_band_survey", "airband_hip_collect_band_survey", "airband_hip_device_band_survey",
@@ -113,7 +114,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
-    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()) + list(capi.TABLES_PROTOTYPES.items()):
+    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()) + list(capi.TABLES_PROTOTYPES.items()) + list(capi.MIXER_GATE_PROTOTYPES.items()):
         if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
             getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
@@ -737,12 +738,83 @@ class AirbandHip:
         arr = (capi.MixerInput * len(inputs))(*[capi.MixerInput(int(a), int(b), int(c), float(d), float(e)) for a, b, c, d, e in inputs])
         self._check(self.L.airband_hip_set_mixers(self.h, n_mixers, arr, len(inputs)))
         self.n_mixers = n_mixers
+        self.mixer_gate = None  # new wiring drops the mixer gate
 
     def mixer_enable_input(self, input_index: int, enabled: bool):
         self._check(self.L.airband_hip_mixer_enable_input(self.h, input_index, 1 if enabled else 0))
 
     def mixer_set_stereo(self, mixer: int, stereo: bool):
         self._check(self.L.airband_hip_mixer_set_stereo(self.h, int(mixer), 1 if stereo else 0))
+
+    # ---- gated mixer collect (include/airband_hip.h) ----------------------------------------------------------------------------------
+    def set_mixer_gate(self, gate, max_rows: Optional[int] = None, encoding=None, stereo: bool = False, manual_step: bool = False):
+        """gate: one capi.GATE_* byte per mixer, None removes the gate; max_rows: capacity of the packed buffers, default every mixer; encoding: None (float32),
+        "s16", "ulaw", "alaw"; stereo: rows are frames of (left, right); manual_step: the host enqueues the step with mixer_gate_step(), after its exchange.
+        Any time after set_mixers() (airband_hip_set_mixer_gate)."""
+        if gate is None:
+            self._check(self.L.airband_hip_set_mixer_gate(self.h, None, 0, 0, 0))
+            self.mixer_gate = None
+            return
+        gate = np.ascontiguousarray(gate, np.uint8)
+        if gate.shape != (self.n_mixers,):
+            raise ValueError("gate needs one byte per mixer (%d), got shape %r" % (self.n_mixers, gate.shape))
+        rows = self.n_mixers if max_rows is None else int(max_rows)
+        enc = capi.AUDIO_F32 if encoding is None else capi.audio_encoding_value(encoding)
+        flags = (capi.MIXER_GATE_STEREO if stereo else 0) | (capi.MIXER_GATE_MANUAL_STEP if manual_step else 0)
+        self._check(self.L.airband_hip_set_mixer_gate(self.h, gate.ctypes.data, rows, enc, flags))
+        self.mixer_gate = dict(rows=rows, encoding=enc, width=2 if stereo else 1)
+
+    def mixer_gate_step(self, stream: int = 0):
+        """One step of a manual mixer gate, behind whatever wrote the sums last (airband_hip_mixer_gate_step); stream 0 = the handle's own."""
+        self._check(self.L.airband_hip_mixer_gate_step(self.h, C.c_void_p(stream) if stream else None))
+
+    def collect_active_mixers(self) -> dict:
+        """The last step's result (airband_hip_collect_active_mixers): n_active (may exceed the capacity), mixers [n] ascending, has_signal of every mixer, and
+        rows [n][W B] float32 on a float gate, or audio [n][W B] int16 / uint8 and info [n] of capi.AUDIO_ROW_DTYPE on an encoded one."""
+        g = getattr(self, "mixer_gate", None) or dict(rows=1, encoding=capi.AUDIO_F32, width=1)
+        cap, enc, wb = g["rows"], g["encoding"], g["width"] * self.B
+        n = C.c_int64(0)
+        idx = np.empty((cap,), np.int32)
+        sig = np.empty((self.n_mixers,), np.uint8)
+        rows = audio = info = None
+        if enc == capi.AUDIO_F32:
+            rows = np.empty((cap, wb), np.float32)
+        else:
+            audio = np.empty((cap, wb), self._audio_dtype(enc))
+            info = np.empty((cap,), capi.AUDIO_ROW_DTYPE)
+        self._check(self.L.airband_hip_collect_active_mixers(self.h, C.byref(n), idx.ctypes.data, rows.ctypes.data if rows is not None else None,
+                                                             audio.ctypes.data if audio is not None else None, info.ctypes.data if info is not None else None, sig.ctypes.data))
+        kept = min(int(n.value), cap)
+        out = dict(n_active=int(n.value), mixers=idx[:kept], has_signal=sig)
+        if rows is not None:
+            out["rows"] = rows[:kept]
+        else:
+            out["audio"], out["info"] = audio[:kept], info[:kept]
+        return out
+
+    def device_active_mixers(self) -> dict:
+        """Device pointers of the packed mixer rows (valid until the next step): index [max_rows] int32, count [1] int32, rows [max_rows][W B] float32 (0 on an
+        encoded gate), audio and info (0 on a float gate)."""
+        ptrs = [C.c_void_p() for _ in range(5)]
+        self._check(self.L.airband_hip_device_active_mixers(self.h, *[C.byref(p) for p in ptrs]))
+        return {k: (p.value or 0) for k, p in zip(["index", "count", "rows", "audio", "info"], ptrs)}
+
+    def encode_mixer_audio(self, left, right, encoding):
+        """The mixer pack kernel on host rows left, right [n][B] float32, right None for mono (airband_hip_encode_mixer_audio): (audio [n][W B] int16 or uint8,
+        info [n] of capi.AUDIO_ROW_DTYPE, channel = row)."""
+        enc = capi.audio_encoding_value(encoding)
+        left = np.ascontiguousarray(left, np.float32)
+        if left.ndim != 2 or left.shape[1] != self.B:
+            raise ValueError("left must be [n][%d], got shape %r" % (self.B, left.shape))
+        if right is not None:
+            right = np.ascontiguousarray(right, np.float32)
+            if right.shape != left.shape:
+                raise ValueError("right must have left's shape %r, got %r" % (left.shape, right.shape))
+        n = left.shape[0]
+        audio = np.empty((n, (2 if right is not None else 1) * self.B), self._audio_dtype(enc))
+        info = np.empty((n,), capi.AUDIO_ROW_DTYPE)
+        self._check(self.L.airband_hip_encode_mixer_audio(self.h, enc, left.ctypes.data, right.ctypes.data if right is not None else None, n, audio.ctypes.data, info.ctypes.data))
+        return audio, info
 
     # ---- the mixer exchange over RCCL (include/airband_hip.h): one handle per GPU, in one process or in one process each -----------------
     @staticmethod

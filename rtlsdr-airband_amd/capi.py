@@ -520,6 +520,67 @@ def audio_decode_reference(codes, encoding):
     raise ValueError("unknown encoding: %r" % (encoding,))
 
 
+# the gated mixer collect's (same header)
+MIXER_GATE_STEREO, MIXER_GATE_MANUAL_STEP = 0x1, 0x2
+MIXER_GATE_PROTOTYPES = {
+    "airband_hip_set_mixer_gate": [_vp, _vp, _i64, _i32, C.c_uint32],
+    "airband_hip_mixer_gate_step": [_vp, _vp],
+    "airband_hip_collect_active_mixers": [_vp, C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp],
+    "airband_hip_device_active_mixers": [_vp] + [C.POINTER(_vp)] * 5,
+    "airband_hip_encode_mixer_audio": [_vp, _i32, _vp, _vp, _i64, _vp, _vp],
+}
+
+
+def mixer_rows_reference(left, right, encoding, stereo, mixers=None, stereo_flags=None):
+    """The rows and records of the gated mixer collect (include/airband_hip.h) for the listed mixers: frames of left (stereo false) or of (left, right)
+    interleaved, float32 or encoded by audio_encode_reference()'s arithmetic.  Returns (rows [n][W B] float32 / int16 / uint8, info [n] of AUDIO_ROW_DTYPE or
+    None for AUDIO_F32).  mixers: default every row; stereo_flags [n_mixers]: the record's `reserved`, default 0."""
+    import numpy as np
+
+    enc = AUDIO_F32 if encoding is None else audio_encoding_value(encoding)
+    left = np.ascontiguousarray(left, np.float32)
+    n_all, B = left.shape
+    mixers = np.arange(n_all) if mixers is None else np.asarray(mixers, np.int64)
+    W = 2 if stereo else 1
+    if stereo:
+        right = np.ascontiguousarray(right, np.float32)
+        rows = np.stack([left[mixers], right[mixers]], axis=2).reshape(len(mixers), 2 * B)  # L, R, L, R, ...
+    else:
+        rows = left[mixers].reshape(len(mixers), B)
+    rows = np.ascontiguousarray(rows)
+    if enc == AUDIO_F32:
+        return rows, None
+    audio, info = audio_encode_reference(rows, enc)
+    info["channel"] = mixers
+    # sample-indexed -> frame-indexed (nothing: first = W B -> B, end = 0 -> 0)
+    info["first"] = info["first"].astype(np.int64) // W
+    info["end"] = (info["end"].astype(np.int64) + W - 1) // W
+    if stereo_flags is not None:
+        info["reserved"] = (np.asarray(stereo_flags)[mixers] != 0).astype(np.uint32)
+    return audio, info
+
+
+def mixer_gate_reference(gate, max_rows, encoding, stereo, batches):
+    """The gated mixer collect's definition (include/airband_hip.h) in numpy.  gate [n_mixers] GATE_* bytes; batches: a sequence of (left [n_mixers][B],
+    right, has_signal [n_mixers], stereo_flags [n_mixers]) as collect_mixers() returns them at each step, in order; `prev` is carried across them and starts at
+    0.  Returns one dict per batch: n_active, mixers (the first max_rows active mixers, ascending), rows (their bytes: float32 / int16 / uint8 [n][W B]) and
+    info (records, None for AUDIO_F32)."""
+    import numpy as np
+
+    gate = np.asarray(gate, np.uint8)
+    prev = np.zeros(len(gate), bool)
+    out = []
+    for left, right, has_signal, stereo_flags in batches:
+        signal = np.asarray(has_signal) != 0
+        active = (gate == GATE_ALWAYS) | ((gate == GATE_SIGNAL) & (signal | prev))
+        prev = signal
+        listed = np.flatnonzero(active)
+        kept = listed[:int(max_rows)]
+        rows, info = mixer_rows_reference(left, right, encoding, stereo, kept, stereo_flags)
+        out.append(dict(n_active=int(len(listed)), mixers=kept.astype(np.int32), rows=rows, info=info))
+    return out
+
+
 # the transmission spool's (same header)
 SPOOL_IDLE, SPOOL_MAX, SPOOL_FLUSH = 1, 2, 3
 

@@ -314,6 +314,7 @@ int run_back_half(airband_hip_handle* h, hipStream_t s) {
     }
     if (h->mix.n_mixers > 0) launch_mix(mix_args(h), s);
     if (has_gate(h)) launch_gate_behind_mix(h, s); /* the batch's active channels and their rows packed, encoded, spooled (driver_gate.cpp) */
+    if (has_mixer_gate(h) && !h->mix_gate.manual) launch_mixer_gate_step(h, s); /* the batch's active mixers and their rows packed (driver_mix.cpp); a manual gate's step is the host's to enqueue, behind its exchange */
     if (has_scan_control(h)) launch_scan_control_behind_demod(h, s); /* the lists' hops for the next batch, from this batch's axcindicate (AFC's verdict included) */
     (void)hipEventRecord(ev[4], s);
     hipError_t e = hipGetLastError();

@@ -27,6 +27,8 @@ void launch_gate_behind_mix(airband_hip_handle* h, hipStream_t s);
 /* driver_mix.cpp: what the batch's mixer sums are launched with; one mixer input switched on or off in the grouped arrays (airband_hip_device_enable) */
 MixArgs mix_args(const airband_hip_handle* h);
 hipError_t write_mix_input(airband_hip_handle* h, int k);
+/* driver_mix.cpp: the mixer gate's step (list, pack) behind whatever wrote the sums last on s: the batch (run_back_half) or airband_hip_mixer_gate_step() */
+void launch_mixer_gate_step(airband_hip_handle* h, hipStream_t s);
 /* driver_scan.cpp: prepare's step for handles with scan lists, the entries of a front batch, the exchange in front of the demod kernels, the hops behind them */
 int prep_scan(airband_hip_handle* h);
 void scan_latch(airband_hip_handle* h, uint64_t k, int first_row, int n_rows);
@@ -93,6 +95,7 @@ static inline bool has_follow(const airband_hip_handle* h) { return has_watch(h)
 static inline bool has_gate(const airband_hip_handle* h) { return h->gate.max_rows > 0; }
 static inline bool has_encoding(const airband_hip_handle* h) { return has_gate(h) && h->gate.enc.encoding != AIRBAND_AUDIO_F32; }
 static inline bool has_spool(const airband_hip_handle* h) { return has_encoding(h) && h->gate.enc.spool.pool_rows > 0; }
+static inline bool has_mixer_gate(const airband_hip_handle* h) { return h->mix.n_mixers > 0 && h->mix_gate.max_rows > 0; }
 static inline bool has_scan_control(const airband_hip_handle* h) { return h->scan_ctl.idle_batches > 0; }
 constexpr const char* NO_SCOPE = "the handle has no band scope (airband_hip_set_band_scope)";
 constexpr const char* NO_SURVEY = "the handle has no band survey (airband_hip_set_band_survey)";
@@ -101,6 +104,7 @@ constexpr const char* NO_FOLLOW = "the handle has no band follow (airband_hip_se
 constexpr const char* NO_GATE = "the handle has no output gate (airband_hip_set_output_gate)";
 constexpr const char* NO_ENCODING = "the handle has no output encoding (airband_hip_set_output_encoding)";
 constexpr const char* NO_SPOOL = "the handle has no transmission spool (airband_hip_set_transmission_spool)";
+constexpr const char* NO_MIXER_GATE = "the handle has no mixer gate (airband_hip_set_mixer_gate)";
 constexpr const char* NO_SCAN_CONTROL = "scan control is off (airband_hip_set_scan_control)";
 
 /* they are set before the first batch (the message stays a literal at each fail(): "the band watch is set before the first batch") */

@@ -1,5 +1,6 @@
 /* csrc/driver_mix.cpp -- the mixers of the host driver: the wiring (airband_hip_set_mixers / _mixer_enable_input / _mixer_set_stereo / _collect_mixers), what the sums
- * behind a batch's demod kernels are launched with (run_back_half), and their exchange between handles over librccl.so (airband_hip_comm_* / *_mixers). */
+ * behind a batch's demod kernels are launched with (run_back_half), their exchange between handles over librccl.so (airband_hip_comm_* / *_mixers), and the gated
+ * mixer collect over the sums (airband_hip_set_mixer_gate / _mixer_gate_step / _collect_active_mixers / _device_active_mixers / _encode_mixer_audio). */
 #include <dlfcn.h>
 
 #include "driver.h"
@@ -29,6 +30,46 @@ MixArgs airband::mix_args(const airband_hip_handle* h) {
     ma.n_mixers = w.n_mixers;
     ma.wave_batch = h->B;
     return ma;
+}
+
+/* ---- gated mixer collect (include/airband_hip.h; mixer_gate.hip) ------------------------------------------------------------------- */
+static bool mixer_encoding_known(int32_t e) { return e == AIRBAND_AUDIO_F32 || e == AIRBAND_AUDIO_S16 || e == AIRBAND_AUDIO_ULAW || e == AIRBAND_AUDIO_ALAW; }
+static size_t mixer_sample_bytes(int e) { return e == AIRBAND_AUDIO_F32 ? 4 : (e == AIRBAND_AUDIO_S16 ? 2 : 1); }
+static int mixer_gate_blocks(int n_mixers) { return gate_blocks(n_mixers); } /* the passes are the channel gate's (gate_passes.h) */
+
+/* ONE launch path for the automatic step (run_back_half) and the manual one (airband_hip_mixer_gate_step): the list from the sums' signal flags as they are on
+ * `s` now, then the listed mixers' rows packed */
+void airband::launch_mixer_gate_step(airband_hip_handle* h, hipStream_t s) {
+    MixerGate& g = h->mix_gate;
+    const MixerWiring& w = h->mix;
+    MixerGateArgs a;
+    a.gate = g.d_gate.p;
+    a.has_signal = w.d_signal.p;
+    a.prev = g.d_prev.p;
+    a.mask = g.d_mask.p;
+    a.block_count = g.d_block_count.p;
+    a.index = g.d_index.p;
+    a.count = g.d_count.p;
+    a.n_mixers = w.n_mixers;
+    a.max_rows = g.max_rows;
+    launch_mixer_gate_list(a, s);
+    MixerPackArgs p;
+    p.index = g.d_index.p;
+    p.count = g.d_count.p;
+    p.n_rows = 0;
+    p.max_rows = g.max_rows;
+    p.n_mixers = w.n_mixers;
+    p.left = w.d_left.p;
+    p.right = w.d_right.p;
+    p.stereo = w.d_stereo.p;
+    p.reserved_all = 0;
+    p.out = g.encoding == AIRBAND_AUDIO_F32 ? static_cast<void*>(g.d_rows.p) : static_cast<void*>(g.d_audio.p);
+    p.info = g.d_info.p;
+    p.wave_batch = h->B;
+    p.encoding = g.encoding;
+    p.width = g.width;
+    launch_mixer_pack(p, 0, s);
+    g.stepped = true;
 }
 
 /* position k of the grouped mixer-input arrays: the channel it reads, or -1 while the connection (airband_hip_mixer_enable_input) or its dongle
@@ -161,6 +202,7 @@ int airband_hip_set_mixers(airband_hip_handle* h, int32_t mixer_count, const air
     if (n_runs > 65535 || mixer_count > 65535) return fail(h, AIRBAND_HIP_EBADSIZE, "more than 65 535 mixers (or runs of 64 mixer inputs) on one handle");
     order_behind_last_batch(h);
     HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME); /* a batch under way still sums the old wiring */
+    h->mix_gate = MixerGate(); /* the gate read the old wiring's sums: it goes with them */
     h->mix = MixerWiring(); /* n_mixers == 0 until the new wiring is complete: a failure below leaves a handle without mixers, not one with freed tables */
     MixerWiring& w = h->mix;
     HIP_TRY(h, upload(w.d_run_first, run_first), AIRBAND_HIP_ENOMEM);
@@ -217,6 +259,145 @@ int airband_hip_collect_mixers(airband_hip_handle* h, float* left, float* right,
     if (right) HIP_TRY(h, hipMemcpyAsync(right, h->mix.d_right.p, n * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
     if (has_signal) HIP_TRY(h, hipMemcpyAsync(has_signal, h->mix.d_signal.p, (size_t)h->mix.n_mixers, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
     HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_set_mixer_gate(airband_hip_handle* h, const uint8_t* gate, int64_t max_rows, int32_t encoding, uint32_t flags) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    const int n = h->mix.n_mixers;
+    if (n <= 0) return fail(h, AIRBAND_HIP_EINVAL, "no mixers configured");
+    if (gate) {
+        if (max_rows < 1 || max_rows > n) return fail(h, AIRBAND_HIP_EINVAL, "max_rows must lie in 1 .. mixer_count");
+        for (int m = 0; m < n; m++)
+            if (gate[m] > AIRBAND_GATE_ALWAYS) return fail(h, AIRBAND_HIP_EINVAL, "gate byte of mixer " + std::to_string(m) + " is not an AIRBAND_GATE_* value");
+        if (!mixer_encoding_known(encoding)) return fail(h, AIRBAND_HIP_EINVAL, "encoding is not an AIRBAND_AUDIO_* value");
+        if (flags & ~(AIRBAND_MIXER_GATE_STEREO | AIRBAND_MIXER_GATE_MANUAL_STEP)) return fail(h, AIRBAND_HIP_EINVAL, "unknown AIRBAND_MIXER_GATE_* flag bits");
+        if (h->B % 4) return fail(h, AIRBAND_HIP_EBADSIZE, "the pack kernel moves four frames per lane: WAVE_BATCH must be a multiple of four");
+    }
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* built beside the handle and moved in whole: a failed allocation leaves the handle as it was */
+    MixerGate g;
+    if (gate) {
+        const size_t rows = (size_t)max_rows, width = (flags & AIRBAND_MIXER_GATE_STEREO) ? 2 : 1, row_samples = width * (size_t)h->B;
+        hipError_t e = upload(g.d_gate, std::vector<uint8_t>(gate, gate + n));
+        if (e == hipSuccess) e = g.d_prev.alloc_zeroed((size_t)n);
+        if (e == hipSuccess) e = g.d_mask.alloc(((size_t)n + 63) / 64);
+        if (e == hipSuccess) e = g.d_block_count.alloc((size_t)mixer_gate_blocks(n));
+        if (e == hipSuccess) e = g.d_index.alloc(rows);
+        if (e == hipSuccess) e = g.d_count.alloc_zeroed(1);
+        if (e == hipSuccess) { /* only what it delivers */
+            if (encoding == AIRBAND_AUDIO_F32) e = g.d_rows.alloc(rows * row_samples);
+            else e = g.d_audio.alloc(rows * row_samples * mixer_sample_bytes(encoding));
+        }
+        if (e == hipSuccess && encoding != AIRBAND_AUDIO_F32) e = g.d_info.alloc(rows);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr); /* the zeroes are there before a step on another stream reads them */
+        if (e != hipSuccess) return alloc_failed(h, e, "mixer gate buffers: ");
+        g.max_rows = (int)max_rows;
+        g.encoding = encoding;
+        g.width = (int)width;
+        g.manual = (flags & AIRBAND_MIXER_GATE_MANUAL_STEP) != 0;
+    }
+    /* behind the last batch, as airband_hip_set_mixers: a step under way still reads the gate that is replaced here */
+    order_behind_last_batch(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
+    h->mix_gate = std::move(g);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_mixer_gate_step(airband_hip_handle* h, void* stream) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_gate(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_GATE);
+    if (!h->mix_gate.manual) return fail(h, AIRBAND_HIP_EINVAL, "the mixer gate steps with every batch (set without AIRBAND_MIXER_GATE_MANUAL_STEP)");
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* the stream rule of airband_hip_allreduce_mixers: the caller's stream behind the results, or the stream the sums became final on */
+    hipStream_t s = stream ? (hipStream_t)stream : results_stream(h);
+    if (stream) {
+        const int rc = airband_hip_stream_wait_results(h, stream);
+        if (rc != AIRBAND_HIP_OK) return rc;
+    }
+    if (h->ev_last && h->ev_last_pending) HIP_TRY(h, hipStreamWaitEvent(s, h->ev_last, 0), AIRBAND_HIP_ERUNTIME); /* an exchange or a peer's add_mixers on a stream of its own */
+    launch_mixer_gate_step(h, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
+    return results_enqueued_on(h, s); /* collect_active_mixers, and the next batch's sums, come behind the step */
+}
+
+int airband_hip_collect_active_mixers(airband_hip_handle* h, int64_t* n_active, int32_t* mixer_index, float* rows, void* audio, airband_hip_audio_row* info, uint8_t* signal_all) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_gate(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_GATE);
+    const MixerGate& g = h->mix_gate;
+    if (rows && g.encoding != AIRBAND_AUDIO_F32) return fail(h, AIRBAND_HIP_EINVAL, "float rows are delivered by an AIRBAND_AUDIO_F32 mixer gate only");
+    if ((audio || info) && g.encoding == AIRBAND_AUDIO_F32) return fail(h, AIRBAND_HIP_EINVAL, "audio and records are delivered by an encoded mixer gate only");
+    if (!g.stepped) return AIRBAND_HIP_EAGAIN;
+    ON_OWN_STREAM(h, s);
+    /* how many rows there are is on the device: the count first, then exactly those entries of each array, ONE synchronize; only then is the count reported */
+    int64_t count = 0;
+    const int rc = collect_counted<int32_t>(h, g.d_count.p, h->mix.n_mixers, g.max_rows, "active mixer count out of range: ", &count, nullptr, nullptr, s);
+    if (rc != AIRBAND_HIP_OK) return rc;
+    const size_t n = (size_t)(count < g.max_rows ? count : g.max_rows), row_samples = (size_t)g.width * h->B;
+    if (mixer_index && n) HIP_TRY(h, hipMemcpyAsync(mixer_index, g.d_index.p, n * sizeof(int32_t), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (rows && n) HIP_TRY(h, hipMemcpyAsync(rows, g.d_rows.p, n * row_samples * sizeof(float), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (audio && n) HIP_TRY(h, hipMemcpyAsync(audio, g.d_audio.p, n * row_samples * mixer_sample_bytes(g.encoding), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (info && n) HIP_TRY(h, hipMemcpyAsync(info, g.d_info.p, n * sizeof(airband_hip_audio_row), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (signal_all) HIP_TRY(h, hipMemcpyAsync(signal_all, h->mix.d_signal.p, (size_t)h->mix.n_mixers, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (n_active) *n_active = count;
+    return AIRBAND_HIP_OK; /* the batch is not marked as collected: airband_hip_collect_mixers() does not do that either */
+}
+
+int airband_hip_device_active_mixers(airband_hip_handle* h, int32_t** d_index, int32_t** d_count, float** d_rows, void** d_audio, airband_hip_audio_row** d_info) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_gate(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_GATE);
+    const MixerGate& g = h->mix_gate;
+    if (d_index) *d_index = g.d_index.p;
+    if (d_count) *d_count = g.d_count.p;
+    if (d_rows) *d_rows = g.d_rows.p;
+    if (d_audio) *d_audio = g.d_audio.p;
+    if (d_info) *d_info = g.d_info.p;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_encode_mixer_audio(airband_hip_handle* h, int32_t encoding, const float* left, const float* right, int64_t n_rows, void* audio, airband_hip_audio_row* info) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!left) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    if (encoding == AIRBAND_AUDIO_F32 || !mixer_encoding_known(encoding)) return fail(h, AIRBAND_HIP_EINVAL, "encoding is not AIRBAND_AUDIO_S16, _ULAW or _ALAW");
+    if (n_rows < 0 || n_rows > 0x7fffffff / 8) return fail(h, AIRBAND_HIP_EINVAL, "n_rows out of range");
+    if (h->B % 4) return fail(h, AIRBAND_HIP_EBADSIZE, "the pack kernel moves four frames per lane: WAVE_BATCH must be a multiple of four");
+    if (n_rows == 0) return AIRBAND_HIP_OK;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* buffers of the call's own, on the null stream: nothing of the handle is read or written */
+    const size_t n = (size_t)n_rows, B = (size_t)h->B, width = right ? 2 : 1, row_bytes = width * B * mixer_sample_bytes(encoding);
+    DevBuf<float> d_left, d_right;
+    DevBuf<uint8_t> d_audio;
+    DevBuf<airband_hip_audio_row> d_info;
+    hipError_t e = d_left.alloc(n * B);
+    if (e == hipSuccess && right) e = d_right.alloc(n * B);
+    if (e == hipSuccess) e = d_audio.alloc(n * row_bytes);
+    if (e == hipSuccess) e = d_info.alloc(n);
+    if (e != hipSuccess) return alloc_failed(h, e, "encode_mixer_audio buffers: ");
+    HIP_TRY(h, hipMemcpy(d_left.p, left, n * B * sizeof(float), hipMemcpyHostToDevice), AIRBAND_HIP_ERUNTIME);
+    if (right) HIP_TRY(h, hipMemcpy(d_right.p, right, n * B * sizeof(float), hipMemcpyHostToDevice), AIRBAND_HIP_ERUNTIME);
+    MixerPackArgs a;
+    a.index = nullptr;
+    a.count = nullptr;
+    a.n_rows = (int)n_rows;
+    a.max_rows = (int)n_rows;
+    a.n_mixers = (int)n_rows;
+    a.left = d_left.p;
+    a.right = d_right.p;
+    a.stereo = nullptr;
+    a.reserved_all = right ? 1u : 0u;
+    a.out = d_audio.p;
+    a.info = d_info.p;
+    a.wave_batch = h->B;
+    a.encoding = encoding;
+    a.width = (int)width;
+    launch_mixer_pack(a, 0, nullptr);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
+    if (audio) HIP_TRY(h, hipMemcpy(audio, d_audio.p, n * row_bytes, hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
+    if (info) HIP_TRY(h, hipMemcpy(info, d_info.p, n * sizeof(airband_hip_audio_row), hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(nullptr), AIRBAND_HIP_ERUNTIME); /* the buffers go with this call */
     return AIRBAND_HIP_OK;
 }
 

@@ -14,19 +14,18 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "gate_passes.h"
 #include "kernels.h"
 
 namespace airband {
 
 namespace {
-constexpr int GATE_BLOCK = 1024; /* channels (lanes) per workgroup of the select / index passes: 524 288 channels are 512 counts to sum per workgroup */
-constexpr int GATE_WAVES = GATE_BLOCK / 64;
 typedef float v4f __attribute__((ext_vector_type(4)));
 }  // namespace
 
+/* (the two passes themselves are gate_passes.h's, shared with the mixer gate: here the verdict is the channel rule) */
 __global__ __launch_bounds__(GATE_BLOCK) void gate_select_kernel(GateArgs a) {
-    __shared__ int wave_count[GATE_WAVES];
-    const int c = blockIdx.x * GATE_BLOCK + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int c = blockIdx.x * GATE_BLOCK + threadIdx.x;
     bool active = false;
     if (c < a.n_ch) {
         const unsigned g = a.gate[c];
@@ -36,40 +35,11 @@ __global__ __launch_bounds__(GATE_BLOCK) void gate_select_kernel(GateArgs a) {
         active = on && (kind == AIRBAND_GATE_ALWAYS || (kind == AIRBAND_GATE_SIGNAL && (signal || a.prev[c] != 0)));
         a.prev[c] = signal ? 1 : 0;
     }
-    const unsigned long long m = __ballot(active); /* 64 lanes: bit i = lane i */
-    if (lane == 0) {
-        if (c < a.n_ch) a.mask[c >> 6] = m;
-        wave_count[w] = __popcll(m);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int n = 0;
-        for (int i = 0; i < GATE_WAVES; i++) n += wave_count[i];
-        a.block_count[blockIdx.x] = n;
-    }
+    gate_select_pass(active, c, a.n_ch, a.mask, a.block_count);
 }
 
 __global__ __launch_bounds__(GATE_BLOCK) void gate_index_kernel(GateArgs a) {
-    __shared__ int wave_count[GATE_WAVES];
-    __shared__ int base;
-    const int c = blockIdx.x * GATE_BLOCK + threadIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (threadIdx.x == 0) base = 0;
-    __syncthreads();
-    int before = 0; /* active channels of the workgroups in front of this one (integer sums: the order of the additions does not show) */
-    for (int j = threadIdx.x; j < (int)blockIdx.x; j += GATE_BLOCK) before += a.block_count[j];
-    if (before) atomicAdd(&base, before);
-    const unsigned long long m = (c - lane) < a.n_ch ? a.mask[c >> 6] : 0ull;
-    if (lane == 0) wave_count[w] = __popcll(m);
-    __syncthreads();
-    int pos = base;
-    for (int i = 0; i < w; i++) pos += wave_count[i];
-    pos += __popcll(m & ((1ull << lane) - 1ull));
-    if (((m >> lane) & 1ull) && pos < a.max_rows) a.index[pos] = c; /* past max_rows: counted, not listed */
-    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) {
-        int n = base;
-        for (int i = 0; i < GATE_WAVES; i++) n += wave_count[i];
-        a.count[0] = n;
-    }
+    gate_index_pass(blockIdx.x * GATE_BLOCK + threadIdx.x, a.n_ch, a.mask, a.block_count, a.index, a.count, a.max_rows);
 }
 
 /* blockIdx.y 0: the audio rows, 1: the raw-I/Q rows.  A workgroup takes rows blockIdx.x, blockIdx.x + gridDim.x, ...: the grid does not depend on the count, which

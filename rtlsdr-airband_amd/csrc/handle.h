@@ -99,6 +99,22 @@ struct MixerWiring {
     DevBuf<uint8_t> d_stereo, d_signal;
 };
 
+/* what airband_hip_set_mixer_gate() set up over the wiring's sums: replaced as a whole, dropped by airband_hip_set_mixers(), one without max_rows is a handle
+ * without a mixer gate (nothing allocated, nothing launched).  An encoded gate holds d_audio / d_info and no d_rows, a float gate d_rows alone. */
+struct MixerGate {
+    int max_rows = 0;          /* capacity of the packed buffers; 0 = no mixer gate */
+    int encoding = AIRBAND_AUDIO_F32;
+    int width = 1;             /* samples per frame: 2 with AIRBAND_MIXER_GATE_STEREO */
+    bool manual = false;       /* AIRBAND_MIXER_GATE_MANUAL_STEP: the host enqueues the step */
+    bool stepped = false;      /* a step has been enqueued: there is something to collect */
+    DevBuf<uint8_t> d_gate, d_prev;
+    DevBuf<unsigned long long> d_mask;
+    DevBuf<int> d_block_count, d_index, d_count;
+    DevBuf<float> d_rows;      /* [max_rows][width * wave_batch] */
+    DevBuf<uint8_t> d_audio;   /* [max_rows][width * wave_batch] bytes, or int16 for S16 */
+    DevBuf<airband_hip_audio_row> d_info;
+};
+
 /* what airband_hip_set_transmission_spool() set up, a part of the encoding whose rows it keeps: replaced as a whole, gone with the encoding (and so with the
  * gate), one without pool_rows is an encoding without a spool (nothing allocated, nothing launched) */
 struct TransmissionSpool {
@@ -323,6 +339,7 @@ struct airband_hip_handle {
     std::vector<ChanConst> cc_slots; /* host copy of d_cc (slot order): the VALID bit of a dongle's slots follows its enable state */
 
     airband::MixerWiring mix;
+    airband::MixerGate mix_gate; /* airband_hip_set_mixer_gate: gone with the wiring it reads */
     airband::OutputGate gate;
     airband::BandScope scope;
 

@@ -327,6 +327,35 @@ struct AudioPackArgs {
 };
 void launch_audio_pack(const AudioPackArgs& a, int grid, hipStream_t stream); /* grid: workgroups, 0 = min(max_rows, one per wavefront slot of the GPU) */
 
+/* gated mixer collect (mixer_gate.hip): the batch's active mixers, ascending (gate_passes.h), and their rows packed as float32, int16 or G.711 frames */
+struct MixerGateArgs {
+    const uint8_t* gate;       /* [n_mixers] AIRBAND_GATE_* */
+    const uint8_t* has_signal; /* [n_mixers] the sums' signal flags at the step */
+    uint8_t* prev;             /* [n_mixers] the mixer had signal at the step before */
+    unsigned long long* mask;  /* [ceil(n_mixers / 64)] */
+    int* block_count;          /* [gate_blocks(n_mixers)] */
+    int* index;                /* [max_rows] */
+    int* count;                /* [1] mixers the rule selected (may exceed max_rows) */
+    int n_mixers, max_rows;
+};
+struct MixerPackArgs {
+    const int* index;          /* [max_rows] row r is mixer index[r]; null: row r is source row r (airband_hip_encode_mixer_audio) */
+    const int* count;          /* [1] on the device (may exceed max_rows); null: n_rows */
+    int n_rows;
+    int max_rows, n_mixers;    /* the clamps: rows written, source rows there are */
+    const float* left;         /* [n_mixers][wave_batch], rows 16-byte aligned */
+    const float* right;        /* likewise; read only when width == 2 */
+    const uint8_t* stereo;     /* [n_mixers] the mixers' stereo flags -> the record's `reserved`; null: `reserved_all` */
+    unsigned reserved_all;
+    void* out;                 /* [max_rows][width * wave_batch] float32, int16 or bytes */
+    airband_hip_audio_row* info; /* [max_rows]; not written for AIRBAND_AUDIO_F32 */
+    int wave_batch;            /* a multiple of four */
+    int encoding;              /* AIRBAND_AUDIO_* */
+    int width;                 /* 1: frames of left; 2: frames of (left, right) */
+};
+void launch_mixer_gate_list(const MixerGateArgs& a, hipStream_t stream);
+void launch_mixer_pack(const MixerPackArgs& a, int grid, hipStream_t stream); /* grid: workgroups, 0 = min(max_rows, one per wavefront slot of the GPU) */
+
 /* transmission spool (tx_spool.hip): the encoded rows of every open transmission kept in a row pool, the closing rule applied once per batch, finished
  * transmissions listed in (step, channel) order and exported as one contiguous run of rows */
 struct SpoolChan {
