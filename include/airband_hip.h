@@ -597,6 +597,7 @@ int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const floa
  *   handle's own results stream).  On a multi-GPU node the sums are final only after the exchange: the host calls it once per batch, after its exchange.
  *   AIRBAND_HIP_EINVAL on a handle whose gate is not manual.
  * Out of scope: a transmission spool over mixer rows, raw-I/Q, MP3, and per-mixer encodings.
+ *   (The spool over mixer rows has since been added as an output of its own on top of an encoded gate: see "mixer transmission spool" below.)
  * A handle without a mixer gate allocates nothing for this, launches nothing and returns the same bits. */
 #define AIRBAND_MIXER_GATE_STEREO      0x1u  /* rows are B frames of (left, right); without it B frames of left only */
 #define AIRBAND_MIXER_GATE_MANUAL_STEP 0x2u  /* the step is not enqueued with the batch: the host calls airband_hip_mixer_gate_step() */
@@ -639,8 +640,9 @@ int airband_hip_encode_mixer_audio(airband_hip_handle* h, int32_t encoding, cons
  * encoded rows of every open transmission in a row pool on the GPU, applies the closing rule once per batch in batch counts (a batch is 125 ms) and hands over
  * only FINISHED transmissions -- one 48-byte record each and their audio concatenated in one contiguous copy -- whenever the host comes for them.
  * Raw-I/Q clips, mixer outputs ("gated mixer collect" delivers their rows, not clips), silence for batches that were not selected, wall-clock time stamps (the host maps batch numbers to time), per-channel parameters
- * and MP3 are out of scope.
- * The definition (normative; integers only, so two implementations of this text agree in every byte).
+ * and MP3 are out of scope.  (Clips of mixer outputs are the "mixer transmission spool" further down: the same definition read over the mixer gate's rows.)
+ * The definition (normative; integers only, so two implementations of this text agree in every byte).  It is the ONE definition of both spools;
+ * capi.transmission_spool_reference() is the same in plain Python.
  * Parameters: spool[total_channels], a byte mask (NULL: every channel whose gate is AIRBAND_GATE_SIGNAL); a spooled channel must have gate SIGNAL (the reference
  * forbids `continuous` together with `split_on_transmission`).  pool_rows, export_rows, max_records; min_batches (8: the reference's 1.0 s), idle_batches (4:
  * 0.5 s), max_batches (the reference's hour is 28 800; a caller sizes it to the pool).  A pool row holds one encoded row: wave_batch bytes (G.711), twice that
@@ -660,7 +662,9 @@ int airband_hip_encode_mixer_audio(airband_hip_handle* h, int32_t encoding, cons
  *   3. F = the pool rows that, after phase A of this step, are held neither by an open transmission nor by a finished, uncollected one.  The j-th storable row
  *      of the step (ascending channel order, 0-based) is STORED iff j < F;
  *   4. a stored row is appended to the clip and updates the transmission from its airband_hip_audio_row: peak = the maximum; n_clipped summed, saturating at
- *      2^32 - 1; first = the first stored row's `first`; end = the last stored row's `end`; n_rows + 1;
+ *      2^32 - 1; first = the first stored row's `first`; end = the last stored row's `end`; n_rows + 1; reserved[1] of the finished record = the bitwise OR
+ *      of the stored rows' airband_hip_audio_row.reserved (a channel's records carry 0, so a channel transmission's reserved[1] is 0; a mixer's carry its
+ *      stereo flag);
  *   5. a selected row that is not stored: n_lost + 1;
  *   6. either way last_batch = k.
  *   A transmission stores at most max_batches + 1 rows.  Batches in which the channel was not selected contribute nothing, as the reference's file holds nothing
@@ -690,7 +694,7 @@ typedef struct airband_hip_transmission {
     uint16_t end;          /* `end` of the last stored row; 0 if no row was stored */
     uint16_t reason;       /* AIRBAND_SPOOL_* */
     uint32_t row_offset;   /* first of its rows in the collect's audio */
-    uint32_t reserved[2];  /* 0 */
+    uint32_t reserved[2];  /* [0]: 0; [1]: OR of the stored rows' airband_hip_audio_row.reserved -- 0 for a channel, a mixer's stereo flag */
 } airband_hip_transmission; /* 48 bytes */
 
 typedef struct airband_hip_spool_counters {
@@ -728,6 +732,55 @@ int airband_hip_spool_counters_get(airband_hip_handle* h, airband_hip_spool_coun
 /* Device-side views of the last airband_hip_collect_transmissions() (valid until the next one): d_export_audio [export_rows][row bytes], d_export_records
  * [max_records], d_n_export [3]: transmissions exported, their rows, transmissions still waiting.  Any out-pointer may be NULL. */
 int airband_hip_device_transmission_spool(airband_hip_handle* h, void** d_export_audio, airband_hip_transmission** d_export_records, int32_t** d_n_export);
+
+/* ---- mixer transmission spool -----------------------------------------------------------------------------------------------------------
+ * The reference's most common recording set-up sums every channel of a dongle into one mixer and records the mixer's output channel with
+ * `split_on_transmission`; that channel is a channel like any other to it (src/mixer.cpp:193-209; src/output.cpp:340-368, :396-453, :498-532), so its clips
+ * close by the same rule.  A handle with an ENCODED mixer gate (S16, ULAW or ALAW) can carry a MIXER SPOOL: the encoded rows of every open mixer transmission
+ * kept in a row pool of its own on the GPU, the closing rule applied once per mixer gate step, finished transmissions handed over whenever the host comes.
+ * The definition (normative, integers only, checked as bytes) is the "transmission spool" text above, read like this:
+ *   What stands in for what.  "channel" is the mixer index m (airband_hip_transmission.channel = m); "the gate" is the mixer gate; "the encoder's row and
+ *     record" are the mixer pack's row and airband_hip_audio_row.
+ *   Row size.  A pool row is W * B samples: W * B bytes (G.711), twice that (S16) -- 1 000 to 8 000 bytes.
+ *   Frames.  wave_batch in the record rules is B frames: `first` and `end` count frames; first = B and end = 0 if no row was stored.
+ *   When a step runs.  One spool step per MIXER GATE STEP, behind that step's pack on the same stream: with an automatic gate once per batch in every schedule,
+ *     with AIRBAND_MIXER_GATE_MANUAL_STEP once per airband_hip_mixer_gate_step() call -- on a multi-GPU node after the exchange, so the spool never sees
+ *     partial sums.  k counts the spool steps since the spool was set, 0 for the first.
+ *   Mask.  spool[mixer_count]; NULL: every mixer whose gate is AIRBAND_GATE_SIGNAL.  A spooled mixer whose gate is not SIGNAL is AIRBAND_HIP_EINVAL.  On a
+ *     multi-GPU node every rank holds every sum after the exchange: the mask is how each rank spools its own share of the mixers.
+ *   Rows past max_rows.  Mixers the rule selected past the gate's max_rows are selected but not storable (n_lost), as for channels.  A mixer whose inputs are
+ *     all masked has no signal: its transmission ends by the idle rule.
+ *   Stereo flag.  reserved[1] of a finished record is the OR of the stored rows' airband_hip_audio_row.reserved: the mixer's stereo flag at each stored step
+ *     (phase B, point 4).  reserved[0] is 0.
+ *   Phases A and B, the ascending order, the finished list with max_records and the drop rule, the rank rule for a dry pool, flush, collect with
+ *     export_rows >= max_batches + 1: unchanged.
+ * A handle may carry a channel spool and a mixer spool at once: separate pools, state, lists and counters.  Per-mixer closing parameters, raw I/Q, MP3,
+ * wall-clock time stamps and silence for steps in which a mixer was not selected are out of scope.
+ * A handle without a mixer spool allocates nothing for this, launches nothing and returns the same bits. */
+
+/* Allowed whenever airband_hip_set_mixer_gate() is, on a handle whose mixer gate is encoded: it orders itself behind the last batch the same way.  Calling it
+ * again replaces the spool (k restarts at 0), pool_rows == 0 removes it, and airband_hip_set_mixer_gate() or airband_hip_set_mixers() called again drops it
+ * with the gate it belonged to.  Validated before the device is touched: AIRBAND_HIP_EINVAL for a NULL handle, no mixer gate or one with AIRBAND_AUDIO_F32, a
+ * spooled mixer whose gate is not AIRBAND_GATE_SIGNAL, negative counts, max_batches < 1, export_rows < max_batches + 1, max_records < 1.  AIRBAND_HIP_ENOMEM
+ * when the buffers cannot be had -- the handle then runs on as it was, gate included. */
+int airband_hip_set_mixer_spool(airband_hip_handle* h, const uint8_t* spool, int64_t pool_rows, int64_t export_rows, int64_t max_records, int32_t min_batches, int32_t idle_batches, int32_t max_batches);
+
+/* airband_hip_collect_transmissions() of the mixer spool, behind the last mixer gate step by the stream rule of airband_hip_collect_active_mixers():
+ * records [*n] with channel = the mixer (room for max_records), audio [*n_rows][W * B samples] (room for export_rows rows), *n_waiting stay behind.
+ * Synchronous, never AIRBAND_HIP_EAGAIN, any out-pointer may be NULL.  AIRBAND_HIP_EINVAL on a handle without a mixer spool. */
+int airband_hip_collect_mixer_transmissions(airband_hip_handle* h, int64_t* n, airband_hip_transmission* records, void* audio, int64_t* n_rows, int64_t* n_waiting);
+
+/* The flush of the definition over the open mixer transmissions, in stream order behind the steps enqueued so far; not a step: k does not advance.
+ * AIRBAND_HIP_EINVAL on a handle without a mixer spool. */
+int airband_hip_mixer_spool_flush(airband_hip_handle* h);
+
+/* The mixer spool's counters as they stand behind everything enqueued so far (synchronous); `steps` counts the spool steps since the spool was set.
+ * AIRBAND_HIP_EINVAL on a handle without a mixer spool or for NULL `out`. */
+int airband_hip_mixer_spool_counters_get(airband_hip_handle* h, airband_hip_spool_counters* out);
+
+/* Device-side views of the last airband_hip_collect_mixer_transmissions() (valid until the next one): d_export_audio [export_rows][row bytes],
+ * d_export_records [max_records], d_n_export [3]: transmissions exported, their rows, transmissions still waiting.  Any out-pointer may be NULL. */
+int airband_hip_device_mixer_spool(airband_hip_handle* h, void** d_export_audio, airband_hip_transmission** d_export_records, int32_t** d_n_export);
 
 /* ---- band scope -------------------------------------------------------------------------------------------------------------------
  * The channelizer keeps the few bins of every transform that carry a configured channel.  A handle with a band scope also keeps, per selected dongle and batch,

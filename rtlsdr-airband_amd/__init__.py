@@ -38,6 +38,7 @@ EXPORTS = [
     "airband_hip_set_output_encoding", "airband_hip_collect_active_encoded", "airband_hip_device_active_encoded", "airband_hip_encode_audio",
     "airband_hip_set_mixer_gate", "airband_hip_mixer_gate_step", "airband_hip_collect_active_mixers", "airband_hip_device_active_mixers", "airband_hip_encode_mixer_audio",
     "airband_hip_set_transmission_spool", "airband_hip_collect_transmissions", "airband_hip_spool_flush", "airband_hip_spool_counters_get", "airband_hip_device_transmission_spool",
+    "airband_hip_set_mixer_spool", "airband_hip_collect_mixer_transmissions", "airband_hip_mixer_spool_flush", "airband_hip_mixer_spool_counters_get", "airband_hip_device_mixer_spool",
     "airband_hip_set_band_scope", "airband_hip_collect_band_scope", "airband_hip_device_band_scope",
     "airband_hip_set_band_survey", "airband_hip_collect_band_survey", "airband_hip_device_band_survey",
     "airband_hip_set_band_watch", "airband_hip_collect_band_events", "airband_hip_collect_band_tracks", "airband_hip_device_band_watch",
@@ -114,7 +115,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
-    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()) + list(capi.TABLES_PROTOTYPES.items()) + list(capi.MIXER_GATE_PROTOTYPES.items()):
+    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()) + list(capi.TABLES_PROTOTYPES.items()) + list(capi.MIXER_GATE_PROTOTYPES.items()) + list(capi.MIXER_SPOOL_PROTOTYPES.items()):
         if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
             getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
@@ -798,6 +799,50 @@ class AirbandHip:
         ptrs = [C.c_void_p() for _ in range(5)]
         self._check(self.L.airband_hip_device_active_mixers(self.h, *[C.byref(p) for p in ptrs]))
         return {k: (p.value or 0) for k, p in zip(["index", "count", "rows", "audio", "info"], ptrs)}
+
+    # ---- mixer transmission spool (include/airband_hip.h) -----------------------------------------------------------------------------
+    def set_mixer_spool(self, pool_rows, export_rows=None, max_records=None, mask=None, min_batches=8, idle_batches=4, max_batches=480):
+        """Mixer spool (airband_hip_set_mixer_spool): the GPU keeps the encoded rows of every open mixer transmission and hands over finished ones.
+        export_rows: default max(pool_rows, max_batches + 1); max_records: default the mixer count; mask: one byte per mixer (None = every SIGNAL mixer).
+        Any time after set_mixer_gate() with an encoding; pool_rows 0 removes it; set_mixer_gate() or set_mixers() again drops it."""
+        pool_rows = int(pool_rows)
+        export_rows = max(pool_rows, max_batches + 1) if export_rows is None else int(export_rows)
+        max_records = self.n_mixers if max_records is None else int(max_records)
+        m = None if mask is None else np.ascontiguousarray(mask, np.uint8)
+        if m is not None and m.shape != (self.n_mixers,):
+            raise ValueError("mask must have one byte per mixer")
+        self._check(self.L.airband_hip_set_mixer_spool(self.h, None if m is None else m.ctypes.data, pool_rows, export_rows, max_records, min_batches, idle_batches, max_batches))
+        if getattr(self, "mixer_gate", None) is not None:
+            self.mixer_gate["spool"] = (export_rows, max_records) if pool_rows else (0, 0)
+
+    def collect_mixer_transmissions(self) -> dict:
+        """The finished mixer transmissions that fit the export buffer (airband_hip_collect_mixer_transmissions): records [n] of capi.TRANSMISSION_DTYPE
+        (channel = the mixer, reserved[1] = its stereo flag over the stored rows), audio [sum of n_rows][W B] int16 ("s16") or uint8 (G.711) -- transmission
+        i's rows are audio[row_offset : row_offset + n_rows] -- and n_waiting."""
+        g = getattr(self, "mixer_gate", None) or {}
+        export_rows, max_records = g.get("spool", (0, 0))
+        records = np.empty((max(max_records, 1),), capi.TRANSMISSION_DTYPE)
+        audio = np.empty((max(export_rows, 1), g.get("width", 1) * self.B), self._audio_dtype(g.get("encoding", capi.AUDIO_F32)))
+        n, n_rows, n_waiting = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(self.L.airband_hip_collect_mixer_transmissions(self.h, C.byref(n), records.ctypes.data, audio.ctypes.data, C.byref(n_rows), C.byref(n_waiting)))
+        return dict(records=records[:n.value], audio=audio[:n_rows.value], n_waiting=int(n_waiting.value))
+
+    def mixer_spool_flush(self):
+        """Every open mixer transmission finishes with reason capi.SPOOL_FLUSH (airband_hip_mixer_spool_flush)."""
+        self._check(self.L.airband_hip_mixer_spool_flush(self.h))
+
+    def mixer_spool_counters(self) -> dict:
+        """airband_hip_mixer_spool_counters_get as a dict (capi.SPOOL_COUNTER_NAMES)."""
+        out = capi.SpoolCounters()
+        self._check(self.L.airband_hip_mixer_spool_counters_get(self.h, C.byref(out)))
+        return {k: int(getattr(out, k)) for k in capi.SPOOL_COUNTER_NAMES}
+
+    def device_mixer_spool(self) -> dict:
+        """Device pointers of the last collect_mixer_transmissions() (valid until the next one): audio [export_rows][row bytes], records [max_records] of 48
+        bytes, n_export [3] int32 (transmissions, rows, still waiting)."""
+        ptrs = [C.c_void_p() for _ in range(3)]
+        self._check(self.L.airband_hip_device_mixer_spool(self.h, *[C.byref(p) for p in ptrs]))
+        return {k: (p.value or 0) for k, p in zip(["audio", "records", "n_export"], ptrs)}
 
     def encode_mixer_audio(self, left, right, encoding):
         """The mixer pack kernel on host rows left, right [n][B] float32, right None for mono (airband_hip_encode_mixer_audio): (audio [n][W B] int16 or uint8,

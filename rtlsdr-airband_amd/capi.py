@@ -609,9 +609,41 @@ TRANSMISSION_DTYPE = [("channel", "<i4"), ("open_batch", "<u4"), ("last_batch", 
 SPOOL_COUNTER_NAMES = tuple(f[0] for f in SpoolCounters._fields_)
 
 
+# the mixer transmission spool's (same header): the channel spool's record, counters and definition over the mixer gate's rows
+MIXER_SPOOL_PROTOTYPES = {
+    "airband_hip_set_mixer_spool": [_vp, _vp, _i64, _i64, _i64, _i32, _i32, _i32],
+    "airband_hip_collect_mixer_transmissions": [_vp, C.POINTER(_i64), _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)],
+    "airband_hip_mixer_spool_flush": [_vp],
+    "airband_hip_mixer_spool_counters_get": [_vp, C.POINTER(SpoolCounters)],
+    "airband_hip_device_mixer_spool": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
+}
+
+
+class mixer_gate_selection:
+    """Every mixer the mixer gate's rule selects, step by step (include/airband_hip.h, "gated mixer collect", Step): what the spool's model needs as `selected`
+    when the gate's count exceeds its list.  step(has_signal) -> the ascending mixers; `prev` is carried and starts at 0."""
+
+    def __init__(self, gate):
+        import numpy as np
+
+        self.gate = np.asarray(gate, np.uint8)
+        self.prev = np.zeros(len(self.gate), bool)
+
+    def step(self, has_signal):
+        import numpy as np
+
+        signal = np.asarray(has_signal) != 0
+        active = (self.gate == GATE_ALWAYS) | ((self.gate == GATE_SIGNAL) & (signal | self.prev))
+        self.prev = signal
+        return np.flatnonzero(active).astype(np.int32)
+
+
 class transmission_spool_reference:
-    """The transmission spool's definition (include/airband_hip.h, "transmission spool") in plain Python: an object that is fed, per batch, what
-    collect_active_encoded() of the same gate and encoding returns, and that has flush(), collect() and counters() like the handle.
+    """The definition of BOTH spools (include/airband_hip.h, "transmission spool" and "mixer transmission spool") in plain Python: an object that is fed, per
+    step, what collect_active_encoded() of the same gate and encoding returns -- for the mixer spool what collect_active_mixers() of the same encoded mixer gate
+    returns (n_active, mixers, audio, info), with wave_batch = B frames -- and that has flush(), collect() and counters() like the handle.  A finished record's
+    reserved[1] is the OR of the stored records' `reserved` (0 for channels, a mixer's stereo flag).  When a mixer gate's count exceeds its list, `selected`
+    comes from has_signal by the gate's rule (mixer_gate_selection).
 
     mask: truth value per channel (the spooled channels, resolved: the header's NULL is "every SIGNAL channel"); row_bytes: bytes of an encoded row;
     wave_batch: samples of a row.  step(n_active, channels, audio, info, selected=None): the gate's count, its list (the first max_rows selected channels,
@@ -667,7 +699,7 @@ class transmission_spool_reference:
                 continue
             t = self.open.get(c)
             if t is None:
-                t = self.open[c] = dict(channel=c, open_batch=k, last_batch=0, n_rows=0, n_lost=0, n_clipped=0, peak=0, first=self.wave_batch, end=0, rows=[])
+                t = self.open[c] = dict(channel=c, open_batch=k, last_batch=0, n_rows=0, n_lost=0, n_clipped=0, peak=0, first=self.wave_batch, end=0, flags=0, rows=[])
             stored = False
             if c in row_of:  # storable
                 stored = j < free
@@ -683,6 +715,7 @@ class transmission_spool_reference:
                 if t["n_rows"] == 0:
                     t["first"] = int(rec["first"])
                 t["end"] = int(rec["end"])
+                t["flags"] |= int(rec["reserved"])
                 t["n_rows"] += 1
                 self.rows_stored += 1
             else:
@@ -710,6 +743,7 @@ class transmission_spool_reference:
             for name in ("channel", "open_batch", "last_batch", "close_batch", "n_rows", "n_lost", "n_clipped", "peak", "first", "end", "reason"):
                 records[i][name] = t[name]
             records[i]["row_offset"] = at
+            records[i]["reserved"][1] = t["flags"]
             at += t["n_rows"]
         return dict(records=records, audio=b"".join(b"".join(t["rows"]) for t in take), n_rows=total, n_waiting=len(self.finished))
 

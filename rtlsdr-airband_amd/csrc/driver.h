@@ -16,6 +16,17 @@ struct FrontRows {
     int first_row, n_hops;
 };
 
+/* what a transmission spool reads of its source after the source's step: the channel spool of the output gate and the encoder, the mixer spool of the mixer
+ * gate and the mixer pack */
+struct SpoolSource {
+    const unsigned long long* mask; /* the gate's verdicts */
+    const int* block_count;         /* ... and its per-workgroup counts */
+    const uint8_t* audio;           /* the listed rows, encoded */
+    const airband_hip_audio_row* info;
+    int n, max_rows;                /* items (channels / mixers), the list's capacity */
+    int frames;                     /* wave_batch: `first` of a transmission without a stored row */
+};
+
 #pragma GCC visibility push(hidden)
 extern thread_local std::string g_prepare_error; /* airband_hip.cpp: the message of a failure without a handle (airband_hip_last_error(NULL)) */
 /* the hooks of the batch path (airband_hip.cpp: launch_front, run_back_half), by the file that defines them.  driver_band.cpp: the scope (with its survey and watch) around stage 1, the follow behind the demod kernels */
@@ -24,6 +35,17 @@ int scope_join(airband_hip_handle* h, const void* d_iq, size_t stride_bytes, Fro
 void launch_follow_behind_demod(airband_hip_handle* h, int* moved_epoch, int epoch, hipStream_t s);
 /* driver_gate.cpp: the gate, the encoder and the spool's step behind the emit / mixer launches */
 void launch_gate_behind_mix(airband_hip_handle* h, hipStream_t s);
+/* driver_gate.cpp: the spool's host side over a TransmissionSpool and its source, ONE path for the channel spool and the mixer spool (driver_mix.cpp): a set
+ * call's checks, allocate and initialise, the step, collect, flush, counters, device views */
+int spool_check(airband_hip_handle* h, const uint8_t* spool, const std::vector<uint8_t>& gate, const char* item, int64_t pool_rows, int64_t export_rows,
+                int64_t max_records, int32_t max_batches, std::vector<uint8_t>* mask);
+int spool_build(airband_hip_handle* h, TransmissionSpool& sp, const std::vector<uint8_t>& mask, int max_rows, size_t row_bytes, int64_t pool_rows, int64_t export_rows,
+                int64_t max_records, int32_t min_batches, int32_t idle_batches, int32_t max_batches, const char* what);
+void spool_step(TransmissionSpool& sp, const SpoolSource& src, hipStream_t s);
+int spool_collect(airband_hip_handle* h, const TransmissionSpool& sp, const SpoolSource& src, int64_t* n, airband_hip_transmission* records, void* audio, int64_t* n_rows, int64_t* n_waiting);
+int spool_flush(airband_hip_handle* h, const TransmissionSpool& sp, const SpoolSource& src);
+int spool_counters(airband_hip_handle* h, const TransmissionSpool& sp, airband_hip_spool_counters* out);
+void spool_device_views(const TransmissionSpool& sp, void** d_export_audio, airband_hip_transmission** d_export_records, int32_t** d_n_export);
 /* driver_mix.cpp: what the batch's mixer sums are launched with; one mixer input switched on or off in the grouped arrays (airband_hip_device_enable) */
 MixArgs mix_args(const airband_hip_handle* h);
 hipError_t write_mix_input(airband_hip_handle* h, int k);
@@ -96,6 +118,7 @@ static inline bool has_gate(const airband_hip_handle* h) { return h->gate.max_ro
 static inline bool has_encoding(const airband_hip_handle* h) { return has_gate(h) && h->gate.enc.encoding != AIRBAND_AUDIO_F32; }
 static inline bool has_spool(const airband_hip_handle* h) { return has_encoding(h) && h->gate.enc.spool.pool_rows > 0; }
 static inline bool has_mixer_gate(const airband_hip_handle* h) { return h->mix.n_mixers > 0 && h->mix_gate.max_rows > 0; }
+static inline bool has_mixer_spool(const airband_hip_handle* h) { return has_mixer_gate(h) && h->mix_gate.spool.pool_rows > 0; }
 static inline bool has_scan_control(const airband_hip_handle* h) { return h->scan_ctl.idle_batches > 0; }
 constexpr const char* NO_SCOPE = "the handle has no band scope (airband_hip_set_band_scope)";
 constexpr const char* NO_SURVEY = "the handle has no band survey (airband_hip_set_band_survey)";
@@ -105,6 +128,7 @@ constexpr const char* NO_GATE = "the handle has no output gate (airband_hip_set_
 constexpr const char* NO_ENCODING = "the handle has no output encoding (airband_hip_set_output_encoding)";
 constexpr const char* NO_SPOOL = "the handle has no transmission spool (airband_hip_set_transmission_spool)";
 constexpr const char* NO_MIXER_GATE = "the handle has no mixer gate (airband_hip_set_mixer_gate)";
+constexpr const char* NO_MIXER_SPOOL = "the handle has no mixer spool (airband_hip_set_mixer_spool)";
 constexpr const char* NO_SCAN_CONTROL = "scan control is off (airband_hip_set_scan_control)";
 
 /* they are set before the first batch (the message stays a literal at each fail(): "the band watch is set before the first batch") */

@@ -1,6 +1,7 @@
 /* csrc/driver_gate.cpp -- the gated outputs of the host driver: the output gate, the encoding of its rows, airband_hip_encode_audio and the transmission spool
  * (airband_hip_set_output_gate / _set_output_encoding / _set_transmission_spool and their collect / device entry points), and their launches behind the emit and
- * mixer launches of a batch (hook of airband_hip.cpp: run_back_half). */
+ * mixer launches of a batch (hook of airband_hip.cpp: run_back_half).  The spool's host side is written over a TransmissionSpool and a SpoolSource: the mixer
+ * spool (driver_mix.cpp: airband_hip_set_mixer_spool and its collect / flush / counters / device entry points) goes through the same functions. */
 #include "driver.h"
 
 using namespace airband;
@@ -45,10 +46,23 @@ static AudioPackArgs audio_pack_args(const airband_hip_handle* h) {
     return a;
 }
 
-/* the spool's own buffers, the gate's verdicts and the encoder's rows (airband_hip_set_transmission_spool); k: the step's number */
-static SpoolArgs spool_args(const airband_hip_handle* h, uint32_t k) {
+/* what the channel spool reads: the output gate's verdicts and the encoder's rows (airband_hip_set_transmission_spool) */
+static SpoolSource channel_spool_source(const airband_hip_handle* h) {
     const OutputGate& g = h->gate;
-    const TransmissionSpool& sp = g.enc.spool;
+    SpoolSource src;
+    src.mask = g.d_mask.p;
+    src.block_count = g.d_block_count.p;
+    src.audio = g.enc.d_audio.p;
+    src.info = g.enc.d_info.p;
+    src.n = h->plan.total_ch;
+    src.max_rows = g.max_rows;
+    src.frames = h->B;
+    return src;
+}
+
+/* ---- the spool's host side, over a TransmissionSpool and its source: the channel spool (below) and the mixer spool (driver_mix.cpp) go through these ---- */
+/* the spool's own buffers, the source's verdicts, rows and records; k: the step's number */
+static SpoolArgs spool_args(const TransmissionSpool& sp, const SpoolSource& src, uint32_t k) {
     SpoolArgs a;
     a.spool = sp.d_spool.p;
     a.chan = sp.d_chan.p;
@@ -57,31 +71,147 @@ static SpoolArgs spool_args(const airband_hip_handle* h, uint32_t k) {
     a.app_mask = sp.d_app_mask.p;
     a.close_count = sp.d_close_count.p;
     a.app_count = sp.d_app_count.p;
-    a.gate_mask = g.d_mask.p;
-    a.gate_count = g.d_block_count.p;
+    a.gate_mask = src.mask;
+    a.gate_count = src.block_count;
     a.free_stack = sp.d_free_stack.p;
     a.next = sp.d_next.p;
     a.pool = sp.d_pool.p;
     a.copy_list = sp.d_copy_list.p;
-    a.enc_audio = g.enc.d_audio.p;
-    a.enc_info = g.enc.d_info.p;
+    a.enc_audio = src.audio;
+    a.enc_info = src.info;
     a.fin = sp.d_fin.p;
     a.exp_records = sp.d_exp_records.p;
     a.exp_head = sp.d_exp_head.p;
     a.exp_src = sp.d_exp_src.p;
     a.exp_audio = sp.d_exp_audio.p;
-    a.n_ch = h->plan.total_ch;
-    a.max_rows = g.max_rows;
+    a.n_ch = src.n;
+    a.max_rows = src.max_rows;
     a.pool_rows = sp.pool_rows;
     a.export_rows = sp.export_rows;
     a.max_records = sp.max_records;
     a.row_bytes = sp.row_bytes;
-    a.wave_batch = h->B;
+    a.wave_batch = src.frames;
     a.min_batches = sp.min_batches;
     a.idle_batches = sp.idle_batches;
     a.max_batches = sp.max_batches;
     a.k = k;
     return a;
+}
+
+/* the arguments of a set call, checked before the device is touched: the counts, and the mask resolved against the source's gate bytes (`item`: "channel" / "mixer") */
+int airband::spool_check(airband_hip_handle* h, const uint8_t* spool, const std::vector<uint8_t>& gate, const char* item, int64_t pool_rows, int64_t export_rows,
+                         int64_t max_records, int32_t max_batches, std::vector<uint8_t>* mask) {
+    if (max_batches < 1) return fail(h, AIRBAND_HIP_EINVAL, "max_batches must be at least 1");
+    if (export_rows < (int64_t)max_batches + 1) return fail(h, AIRBAND_HIP_EINVAL, "export_rows must be at least max_batches + 1: a collect must be able to take the longest transmission");
+    if (max_records < 1) return fail(h, AIRBAND_HIP_EINVAL, "max_records must be at least 1");
+    if (pool_rows > 0x7fffffff || export_rows > 0x7fffffff || max_records > 0x7fffffff / 2) return fail(h, AIRBAND_HIP_EINVAL, "pool_rows, export_rows or max_records too large to index");
+    mask->assign(gate.size(), 0);
+    for (size_t c = 0; c < gate.size(); c++) {
+        (*mask)[c] = spool ? (spool[c] ? 1 : 0) : (gate[c] == AIRBAND_GATE_SIGNAL ? 1 : 0);
+        if ((*mask)[c] && gate[c] != AIRBAND_GATE_SIGNAL)
+            return fail(h, AIRBAND_HIP_EINVAL, std::string("spooled ") + item + " " + std::to_string(c) + " has a gate other than AIRBAND_GATE_SIGNAL");
+    }
+    return AIRBAND_HIP_OK;
+}
+
+/* allocate and initialise: `sp` is built beside what it will belong to and moved in whole by the caller, so a failed allocation leaves the handle as it was.
+ * n: items of the source; max_rows: its list's capacity; row_bytes: bytes of one of its rows.  `what` ends with ": " */
+int airband::spool_build(airband_hip_handle* h, TransmissionSpool& sp, const std::vector<uint8_t>& mask, int max_rows, size_t row_bytes, int64_t pool_rows,
+                         int64_t export_rows, int64_t max_records, int32_t min_batches, int32_t idle_batches, int32_t max_batches, const char* what) {
+    const size_t n = mask.size(), nb = (size_t)gate_blocks((int)n), nm = (n + 63) / 64;
+    std::vector<int> stack((size_t)pool_rows);
+    for (size_t i = 0; i < stack.size(); i++) stack[i] = (int)i;
+    SpoolCtl ctl;
+    std::memset(&ctl, 0, sizeof(ctl));
+    ctl.free_top = (int32_t)pool_rows;
+    ctl.room = (int32_t)max_records;
+    hipError_t e = upload(sp.d_spool, mask);
+    if (e == hipSuccess) e = upload(sp.d_free_stack, stack);
+    if (e == hipSuccess) e = sp.d_ctl.alloc(1);
+    if (e == hipSuccess) e = hipMemcpy(sp.d_ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = sp.d_chan.alloc_zeroed(n);
+    if (e == hipSuccess) e = sp.d_close_mask.alloc_zeroed(nm);
+    if (e == hipSuccess) e = sp.d_app_mask.alloc_zeroed(nm);
+    if (e == hipSuccess) e = sp.d_close_count.alloc_zeroed(nb);
+    if (e == hipSuccess) e = sp.d_app_count.alloc_zeroed(nb);
+    if (e == hipSuccess) e = sp.d_next.alloc_zeroed((size_t)pool_rows);
+    if (e == hipSuccess) e = sp.d_copy_list.alloc_zeroed(2 * (size_t)max_rows);
+    if (e == hipSuccess) e = sp.d_pool.alloc((size_t)pool_rows * row_bytes);
+    if (e == hipSuccess) e = sp.d_fin.alloc_zeroed((size_t)max_records);
+    if (e == hipSuccess) e = sp.d_exp_records.alloc_zeroed((size_t)max_records);
+    if (e == hipSuccess) e = sp.d_exp_head.alloc_zeroed((size_t)max_records);
+    if (e == hipSuccess) e = sp.d_exp_src.alloc_zeroed((size_t)export_rows);
+    if (e == hipSuccess) e = sp.d_exp_audio.alloc((size_t)export_rows * row_bytes);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); /* the zeroes are there before a step on another stream reads them */
+    if (e != hipSuccess) return alloc_failed(h, e, what);
+    sp.pool_rows = (int)pool_rows;
+    sp.export_rows = (int)export_rows;
+    sp.max_records = (int)max_records;
+    sp.row_bytes = (int)row_bytes;
+    sp.min_batches = (uint32_t)min_batches;
+    sp.idle_batches = (uint32_t)idle_batches;
+    sp.max_batches = (uint32_t)max_batches;
+    return AIRBAND_HIP_OK;
+}
+
+/* one step behind the source's rows on s (tx_spool.hip) */
+void airband::spool_step(TransmissionSpool& sp, const SpoolSource& src, hipStream_t s) {
+    launch_spool_step(spool_args(sp, src, sp.steps), s);
+    sp.steps++;
+    sp.steps_total++;
+}
+
+int airband::spool_collect(airband_hip_handle* h, const TransmissionSpool& sp, const SpoolSource& src, int64_t* n, airband_hip_transmission* records, void* audio, int64_t* n_rows, int64_t* n_waiting) {
+    ON_OWN_STREAM(h, s);
+    launch_spool_collect(spool_args(sp, src, sp.steps), s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
+    /* how much there is is on the device: the counts first, then exactly those records and rows */
+    int32_t exp[3] = {0, 0, 0};
+    HIP_TRY(h, hipMemcpyAsync(exp, sp.d_ctl.p, sizeof(exp), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (exp[0] < 0 || exp[0] > sp.max_records || exp[1] < 0 || exp[1] > sp.export_rows || exp[2] < 0 || exp[2] > sp.max_records)
+        return fail(h, AIRBAND_HIP_ERUNTIME, "transmission spool counts out of range");
+    if (records && exp[0]) HIP_TRY(h, hipMemcpyAsync(records, sp.d_exp_records.p, (size_t)exp[0] * sizeof(airband_hip_transmission), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (audio && exp[1]) HIP_TRY(h, hipMemcpyAsync(audio, sp.d_exp_audio.p, (size_t)exp[1] * sp.row_bytes, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (n) *n = exp[0];
+    if (n_rows) *n_rows = exp[1];
+    if (n_waiting) *n_waiting = exp[2];
+    return AIRBAND_HIP_OK;
+}
+
+int airband::spool_flush(airband_hip_handle* h, const TransmissionSpool& sp, const SpoolSource& src) {
+    ON_OWN_STREAM(h, s);
+    launch_spool_flush(spool_args(sp, src, sp.steps), s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
+    /* a batch (or a step) that ran on a caller's stream: the next one there knows nothing of the handle's stream, so the flush is complete before this returns */
+    if (h->ev_last_pending) HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
+    return AIRBAND_HIP_OK;
+}
+
+int airband::spool_counters(airband_hip_handle* h, const TransmissionSpool& sp, airband_hip_spool_counters* out) {
+    if (!out) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    ON_OWN_STREAM(h, s);
+    SpoolCtl ctl;
+    HIP_TRY(h, hipMemcpyAsync(&ctl, sp.d_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    out->steps = sp.steps_total;
+    out->open_now = ctl.open_now;
+    out->waiting_now = (uint64_t)(ctl.fin_count < 0 ? 0 : ctl.fin_count);
+    out->free_rows_now = (uint64_t)(ctl.free_top < 0 ? 0 : ctl.free_top);
+    out->finished_total = ctl.finished_total;
+    out->dropped_transmissions = ctl.dropped;
+    out->rows_stored_total = ctl.rows_stored;
+    out->rows_lost_total = ctl.rows_lost;
+    return AIRBAND_HIP_OK;
+}
+
+void airband::spool_device_views(const TransmissionSpool& sp, void** d_export_audio, airband_hip_transmission** d_export_records, int32_t** d_n_export) {
+    if (d_export_audio) *d_export_audio = sp.d_exp_audio.p;
+    if (d_export_records) *d_export_records = sp.d_exp_records.p;
+    if (d_n_export) *d_n_export = reinterpret_cast<int32_t*>(sp.d_ctl.p); /* SpoolCtl::exp, its first member */
 }
 
 static bool audio_encoding_known(int32_t e) { return e == AIRBAND_AUDIO_S16 || e == AIRBAND_AUDIO_ULAW || e == AIRBAND_AUDIO_ALAW; }
@@ -112,12 +242,7 @@ static int collect_active_rows(airband_hip_handle* h, int64_t* n_active, int32_t
 void airband::launch_gate_behind_mix(airband_hip_handle* h, hipStream_t s) {
     launch_gate(gate_args(h), s);
     if (has_encoding(h)) launch_audio_pack(audio_pack_args(h), 0, s); /* ... and encoded (audio_pack.hip) */
-    if (has_spool(h)) { /* ... and the spool's step of this batch (tx_spool.hip) */
-        TransmissionSpool& sp = h->gate.enc.spool;
-        launch_spool_step(spool_args(h, sp.steps), s);
-        sp.steps++;
-        sp.steps_total++;
-    }
+    if (has_spool(h)) spool_step(h->gate.enc.spool, channel_spool_source(h), s); /* ... and the spool's step of this batch (tx_spool.hip) */
 }
 
 extern "C" {
@@ -267,7 +392,6 @@ int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const floa
 int airband_hip_set_transmission_spool(airband_hip_handle* h, const uint8_t* spool, int64_t pool_rows, int64_t export_rows, int64_t max_records, int32_t min_batches, int32_t idle_batches, int32_t max_batches) {
     if (!h) return AIRBAND_HIP_EINVAL;
     OutputGate& g = h->gate;
-    const Plan& p = h->plan;
     if (!has_gate(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_GATE);
     if (!has_encoding(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_ENCODING);
     if (started(h)) return fail(h, AIRBAND_HIP_EINVAL, "the transmission spool is set before the first batch");
@@ -276,51 +400,15 @@ int airband_hip_set_transmission_spool(airband_hip_handle* h, const uint8_t* spo
         g.enc.spool = TransmissionSpool();
         return AIRBAND_HIP_OK;
     }
-    if (max_batches < 1) return fail(h, AIRBAND_HIP_EINVAL, "max_batches must be at least 1");
-    if (export_rows < (int64_t)max_batches + 1) return fail(h, AIRBAND_HIP_EINVAL, "export_rows must be at least max_batches + 1: a collect must be able to take the longest transmission");
-    if (max_records < 1) return fail(h, AIRBAND_HIP_EINVAL, "max_records must be at least 1");
-    if (pool_rows > 0x7fffffff || export_rows > 0x7fffffff || max_records > 0x7fffffff / 2) return fail(h, AIRBAND_HIP_EINVAL, "pool_rows, export_rows or max_records too large to index");
-    std::vector<uint8_t> mask((size_t)p.total_ch);
-    for (int c = 0; c < p.total_ch; c++) {
-        mask[c] = spool ? (spool[c] ? 1 : 0) : (g.gate[c] == AIRBAND_GATE_SIGNAL ? 1 : 0);
-        if (mask[c] && g.gate[c] != AIRBAND_GATE_SIGNAL)
-            return fail(h, AIRBAND_HIP_EINVAL, "spooled channel " + std::to_string(c) + " has a gate other than AIRBAND_GATE_SIGNAL");
-    }
+    std::vector<uint8_t> mask;
+    int rc = spool_check(h, spool, g.gate, "channel", pool_rows, export_rows, max_records, max_batches, &mask);
+    if (rc != AIRBAND_HIP_OK) return rc;
     HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
     /* built beside the encoding and moved in whole: a failed allocation leaves the handle as it was */
     TransmissionSpool sp;
-    const size_t row_bytes = (size_t)h->B * audio_sample_bytes(g.enc.encoding), nb = (size_t)gate_blocks(p.total_ch), nm = ((size_t)p.total_ch + 63) / 64;
-    std::vector<int> stack((size_t)pool_rows);
-    for (size_t i = 0; i < stack.size(); i++) stack[i] = (int)i;
-    SpoolCtl ctl;
-    std::memset(&ctl, 0, sizeof(ctl));
-    ctl.free_top = (int32_t)pool_rows;
-    ctl.room = (int32_t)max_records;
-    hipError_t e = upload(sp.d_spool, mask);
-    if (e == hipSuccess) e = upload(sp.d_free_stack, stack);
-    if (e == hipSuccess) e = sp.d_ctl.alloc(1);
-    if (e == hipSuccess) e = hipMemcpy(sp.d_ctl.p, &ctl, sizeof(ctl), hipMemcpyHostToDevice);
-    if (e == hipSuccess) e = sp.d_chan.alloc_zeroed((size_t)p.total_ch);
-    if (e == hipSuccess) e = sp.d_close_mask.alloc_zeroed(nm);
-    if (e == hipSuccess) e = sp.d_app_mask.alloc_zeroed(nm);
-    if (e == hipSuccess) e = sp.d_close_count.alloc_zeroed(nb);
-    if (e == hipSuccess) e = sp.d_app_count.alloc_zeroed(nb);
-    if (e == hipSuccess) e = sp.d_next.alloc_zeroed((size_t)pool_rows);
-    if (e == hipSuccess) e = sp.d_copy_list.alloc_zeroed(2 * (size_t)g.max_rows);
-    if (e == hipSuccess) e = sp.d_pool.alloc((size_t)pool_rows * row_bytes);
-    if (e == hipSuccess) e = sp.d_fin.alloc_zeroed((size_t)max_records);
-    if (e == hipSuccess) e = sp.d_exp_records.alloc_zeroed((size_t)max_records);
-    if (e == hipSuccess) e = sp.d_exp_head.alloc_zeroed((size_t)max_records);
-    if (e == hipSuccess) e = sp.d_exp_src.alloc_zeroed((size_t)export_rows);
-    if (e == hipSuccess) e = sp.d_exp_audio.alloc((size_t)export_rows * row_bytes);
-    if (e != hipSuccess) return alloc_failed(h, e, "transmission spool buffers: ");
-    sp.pool_rows = (int)pool_rows;
-    sp.export_rows = (int)export_rows;
-    sp.max_records = (int)max_records;
-    sp.row_bytes = (int)row_bytes;
-    sp.min_batches = (uint32_t)min_batches;
-    sp.idle_batches = (uint32_t)idle_batches;
-    sp.max_batches = (uint32_t)max_batches;
+    rc = spool_build(h, sp, mask, g.max_rows, (size_t)h->B * audio_sample_bytes(g.enc.encoding), pool_rows, export_rows, max_records, min_batches, idle_batches, max_batches,
+                     "transmission spool buffers: ");
+    if (rc != AIRBAND_HIP_OK) return rc;
     g.enc.spool = std::move(sp);
     return AIRBAND_HIP_OK;
 }
@@ -328,65 +416,25 @@ int airband_hip_set_transmission_spool(airband_hip_handle* h, const uint8_t* spo
 int airband_hip_collect_transmissions(airband_hip_handle* h, int64_t* n, airband_hip_transmission* records, void* audio, int64_t* n_rows, int64_t* n_waiting) {
     if (!h) return AIRBAND_HIP_EINVAL;
     if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
-    const TransmissionSpool& sp = h->gate.enc.spool;
-    ON_OWN_STREAM(h, s);
-    launch_spool_collect(spool_args(h, sp.steps), s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
-    /* how much there is is on the device: the counts first, then exactly those records and rows */
-    int32_t exp[3] = {0, 0, 0};
-    HIP_TRY(h, hipMemcpyAsync(exp, sp.d_ctl.p, sizeof(exp), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (exp[0] < 0 || exp[0] > sp.max_records || exp[1] < 0 || exp[1] > sp.export_rows || exp[2] < 0 || exp[2] > sp.max_records)
-        return fail(h, AIRBAND_HIP_ERUNTIME, "transmission spool counts out of range");
-    if (records && exp[0]) HIP_TRY(h, hipMemcpyAsync(records, sp.d_exp_records.p, (size_t)exp[0] * sizeof(airband_hip_transmission), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (audio && exp[1]) HIP_TRY(h, hipMemcpyAsync(audio, sp.d_exp_audio.p, (size_t)exp[1] * sp.row_bytes, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (n) *n = exp[0];
-    if (n_rows) *n_rows = exp[1];
-    if (n_waiting) *n_waiting = exp[2];
-    return AIRBAND_HIP_OK;
+    return spool_collect(h, h->gate.enc.spool, channel_spool_source(h), n, records, audio, n_rows, n_waiting);
 }
 
 int airband_hip_spool_flush(airband_hip_handle* h) {
     if (!h) return AIRBAND_HIP_EINVAL;
     if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
-    ON_OWN_STREAM(h, s);
-    launch_spool_flush(spool_args(h, h->gate.enc.spool.steps), s);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
-    /* a batch that ran on a caller's stream: the next one there knows nothing of the handle's stream, so the flush is complete before this returns */
-    if (h->ev_last_pending) HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
-    return AIRBAND_HIP_OK;
+    return spool_flush(h, h->gate.enc.spool, channel_spool_source(h));
 }
 
 int airband_hip_spool_counters_get(airband_hip_handle* h, airband_hip_spool_counters* out) {
     if (!h) return AIRBAND_HIP_EINVAL;
     if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
-    if (!out) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
-    const TransmissionSpool& sp = h->gate.enc.spool;
-    ON_OWN_STREAM(h, s);
-    SpoolCtl ctl;
-    HIP_TRY(h, hipMemcpyAsync(&ctl, sp.d_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    out->steps = sp.steps_total;
-    out->open_now = ctl.open_now;
-    out->waiting_now = (uint64_t)(ctl.fin_count < 0 ? 0 : ctl.fin_count);
-    out->free_rows_now = (uint64_t)(ctl.free_top < 0 ? 0 : ctl.free_top);
-    out->finished_total = ctl.finished_total;
-    out->dropped_transmissions = ctl.dropped;
-    out->rows_stored_total = ctl.rows_stored;
-    out->rows_lost_total = ctl.rows_lost;
-    return AIRBAND_HIP_OK;
+    return spool_counters(h, h->gate.enc.spool, out);
 }
 
 int airband_hip_device_transmission_spool(airband_hip_handle* h, void** d_export_audio, airband_hip_transmission** d_export_records, int32_t** d_n_export) {
     if (!h) return AIRBAND_HIP_EINVAL;
     if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
-    const TransmissionSpool& sp = h->gate.enc.spool;
-    if (d_export_audio) *d_export_audio = sp.d_exp_audio.p;
-    if (d_export_records) *d_export_records = sp.d_exp_records.p;
-    if (d_n_export) *d_n_export = reinterpret_cast<int32_t*>(sp.d_ctl.p); /* SpoolCtl::exp, its first member */
+    spool_device_views(h->gate.enc.spool, d_export_audio, d_export_records, d_n_export);
     return AIRBAND_HIP_OK;
 }
 

@@ -37,6 +37,20 @@ static bool mixer_encoding_known(int32_t e) { return e == AIRBAND_AUDIO_F32 || e
 static size_t mixer_sample_bytes(int e) { return e == AIRBAND_AUDIO_F32 ? 4 : (e == AIRBAND_AUDIO_S16 ? 2 : 1); }
 static int mixer_gate_blocks(int n_mixers) { return gate_blocks(n_mixers); } /* the passes are the channel gate's (gate_passes.h) */
 
+/* what the mixer spool reads: the mixer gate's verdicts and the pack's rows and records (airband_hip_set_mixer_spool) */
+static SpoolSource mixer_spool_source(const airband_hip_handle* h) {
+    const MixerGate& g = h->mix_gate;
+    SpoolSource src;
+    src.mask = g.d_mask.p;
+    src.block_count = g.d_block_count.p;
+    src.audio = g.d_audio.p;
+    src.info = g.d_info.p;
+    src.n = h->mix.n_mixers;
+    src.max_rows = g.max_rows;
+    src.frames = h->B;
+    return src;
+}
+
 /* ONE launch path for the automatic step (run_back_half) and the manual one (airband_hip_mixer_gate_step): the list from the sums' signal flags as they are on
  * `s` now, then the listed mixers' rows packed */
 void airband::launch_mixer_gate_step(airband_hip_handle* h, hipStream_t s) {
@@ -70,6 +84,7 @@ void airband::launch_mixer_gate_step(airband_hip_handle* h, hipStream_t s) {
     p.width = g.width;
     launch_mixer_pack(p, 0, s);
     g.stepped = true;
+    if (has_mixer_spool(h)) spool_step(g.spool, mixer_spool_source(h), s); /* ... and the mixer spool's step, once per gate step (tx_spool.hip) */
 }
 
 /* position k of the grouped mixer-input arrays: the channel it reads, or -1 while the connection (airband_hip_mixer_enable_input) or its dongle
@@ -292,6 +307,7 @@ int airband_hip_set_mixer_gate(airband_hip_handle* h, const uint8_t* gate, int64
         if (e == hipSuccess && encoding != AIRBAND_AUDIO_F32) e = g.d_info.alloc(rows);
         if (e == hipSuccess) e = hipStreamSynchronize(nullptr); /* the zeroes are there before a step on another stream reads them */
         if (e != hipSuccess) return alloc_failed(h, e, "mixer gate buffers: ");
+        g.gate.assign(gate, gate + n);
         g.max_rows = (int)max_rows;
         g.encoding = encoding;
         g.width = (int)width;
@@ -354,6 +370,57 @@ int airband_hip_device_active_mixers(airband_hip_handle* h, int32_t** d_index, i
     if (d_rows) *d_rows = g.d_rows.p;
     if (d_audio) *d_audio = g.d_audio.p;
     if (d_info) *d_info = g.d_info.p;
+    return AIRBAND_HIP_OK;
+}
+
+/* ---- mixer transmission spool (include/airband_hip.h; the host side is driver_gate.cpp's, the kernels tx_spool.hip's) ---------------------------------- */
+int airband_hip_set_mixer_spool(airband_hip_handle* h, const uint8_t* spool, int64_t pool_rows, int64_t export_rows, int64_t max_records, int32_t min_batches, int32_t idle_batches, int32_t max_batches) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_gate(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_GATE);
+    MixerGate& g = h->mix_gate;
+    if (g.encoding == AIRBAND_AUDIO_F32) return fail(h, AIRBAND_HIP_EINVAL, "the mixer spool keeps encoded rows: the mixer gate's encoding is AIRBAND_AUDIO_F32");
+    if (pool_rows < 0 || export_rows < 0 || max_records < 0 || min_batches < 0 || idle_batches < 0) return fail(h, AIRBAND_HIP_EINVAL, "negative count");
+    TransmissionSpool sp; /* built beside the gate and moved in whole: a failed allocation leaves the handle as it was; pool_rows == 0: an empty one, removed */
+    if (pool_rows > 0) {
+        std::vector<uint8_t> mask;
+        int rc = spool_check(h, spool, g.gate, "mixer", pool_rows, export_rows, max_records, max_batches, &mask);
+        if (rc != AIRBAND_HIP_OK) return rc;
+        HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+        rc = spool_build(h, sp, mask, g.max_rows, (size_t)g.width * h->B * mixer_sample_bytes(g.encoding), pool_rows, export_rows, max_records, min_batches, idle_batches,
+                         max_batches, "mixer spool buffers: ");
+        if (rc != AIRBAND_HIP_OK) return rc;
+    } else {
+        HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    }
+    /* behind the last batch, as airband_hip_set_mixer_gate: a step under way still reads and writes the spool that is replaced here */
+    order_behind_last_batch(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
+    g.spool = std::move(sp);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_mixer_transmissions(airband_hip_handle* h, int64_t* n, airband_hip_transmission* records, void* audio, int64_t* n_rows, int64_t* n_waiting) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_SPOOL);
+    return spool_collect(h, h->mix_gate.spool, mixer_spool_source(h), n, records, audio, n_rows, n_waiting);
+}
+
+int airband_hip_mixer_spool_flush(airband_hip_handle* h) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_SPOOL);
+    return spool_flush(h, h->mix_gate.spool, mixer_spool_source(h));
+}
+
+int airband_hip_mixer_spool_counters_get(airband_hip_handle* h, airband_hip_spool_counters* out) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_SPOOL);
+    return spool_counters(h, h->mix_gate.spool, out);
+}
+
+int airband_hip_device_mixer_spool(airband_hip_handle* h, void** d_export_audio, airband_hip_transmission** d_export_records, int32_t** d_n_export) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_SPOOL);
+    spool_device_views(h->mix_gate.spool, d_export_audio, d_export_records, d_n_export);
     return AIRBAND_HIP_OK;
 }
 

@@ -99,6 +99,23 @@ struct MixerWiring {
     DevBuf<uint8_t> d_stereo, d_signal;
 };
 
+/* what airband_hip_set_transmission_spool() set up, a part of the encoding whose rows it keeps -- or airband_hip_set_mixer_spool(), a part of the mixer gate whose
+ * rows it keeps: replaced as a whole, gone with the encoding (and so with the gate) or with the mixer gate, one without pool_rows is an encoding or a mixer gate
+ * without a spool (nothing allocated, nothing launched).  Declared in front of both owners: a member's type has to be complete */
+struct TransmissionSpool {
+    int pool_rows = 0;         /* 0 = no spool */
+    int export_rows = 0, max_records = 0, row_bytes = 0;
+    uint32_t min_batches = 0, idle_batches = 0, max_batches = 0;
+    uint32_t steps = 0;        /* steps enqueued so far: the next step's k */
+    uint64_t steps_total = 0;
+    DevBuf<uint8_t> d_spool, d_pool, d_exp_audio;
+    DevBuf<SpoolChan> d_chan;
+    DevBuf<SpoolCtl> d_ctl;
+    DevBuf<unsigned long long> d_close_mask, d_app_mask;
+    DevBuf<int> d_close_count, d_app_count, d_free_stack, d_next, d_copy_list, d_exp_head, d_exp_src;
+    DevBuf<airband_hip_transmission> d_fin, d_exp_records;
+};
+
 /* what airband_hip_set_mixer_gate() set up over the wiring's sums: replaced as a whole, dropped by airband_hip_set_mixers(), one without max_rows is a handle
  * without a mixer gate (nothing allocated, nothing launched).  An encoded gate holds d_audio / d_info and no d_rows, a float gate d_rows alone. */
 struct MixerGate {
@@ -113,22 +130,8 @@ struct MixerGate {
     DevBuf<float> d_rows;      /* [max_rows][width * wave_batch] */
     DevBuf<uint8_t> d_audio;   /* [max_rows][width * wave_batch] bytes, or int16 for S16 */
     DevBuf<airband_hip_audio_row> d_info;
-};
-
-/* what airband_hip_set_transmission_spool() set up, a part of the encoding whose rows it keeps: replaced as a whole, gone with the encoding (and so with the
- * gate), one without pool_rows is an encoding without a spool (nothing allocated, nothing launched) */
-struct TransmissionSpool {
-    int pool_rows = 0;         /* 0 = no spool */
-    int export_rows = 0, max_records = 0, row_bytes = 0;
-    uint32_t min_batches = 0, idle_batches = 0, max_batches = 0;
-    uint32_t steps = 0;        /* steps enqueued so far: the next step's k */
-    uint64_t steps_total = 0;
-    DevBuf<uint8_t> d_spool, d_pool, d_exp_audio;
-    DevBuf<SpoolChan> d_chan;
-    DevBuf<SpoolCtl> d_ctl;
-    DevBuf<unsigned long long> d_close_mask, d_app_mask;
-    DevBuf<int> d_close_count, d_app_count, d_free_stack, d_next, d_copy_list, d_exp_head, d_exp_src;
-    DevBuf<airband_hip_transmission> d_fin, d_exp_records;
+    std::vector<uint8_t> gate; /* the caller's bytes: a spooled mixer must be AIRBAND_GATE_SIGNAL */
+    TransmissionSpool spool;   /* airband_hip_set_mixer_spool: an encoded gate's, gone with the gate */
 };
 
 /* what airband_hip_set_output_encoding() set up, a part of the gate whose list it reads: replaced as a whole, gone with the gate, AIRBAND_AUDIO_F32 is a gate

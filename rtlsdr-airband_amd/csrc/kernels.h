@@ -357,14 +357,17 @@ void launch_mixer_gate_list(const MixerGateArgs& a, hipStream_t stream);
 void launch_mixer_pack(const MixerPackArgs& a, int grid, hipStream_t stream); /* grid: workgroups, 0 = min(max_rows, one per wavefront slot of the GPU) */
 
 /* transmission spool (tx_spool.hip): the encoded rows of every open transmission kept in a row pool, the closing rule applied once per batch, finished
- * transmissions listed in (step, channel) order and exported as one contiguous run of rows */
+ * transmissions listed in (step, channel) order and exported as one contiguous run of rows.  Written against "a mask, counts, rows, records": the channel spool
+ * fills SpoolArgs from the output gate and the encoder, the mixer spool from the mixer gate and the mixer pack (n_ch = mixer_count, row_bytes = W * wave_batch * bytes) */
 struct SpoolChan {
     uint32_t open_batch, last_batch, n_rows, n_lost;
     uint32_t n_clipped;
     uint16_t peak, first, end, open; /* open: the channel has an open transmission; nothing else means anything without it */
     int32_t head, tail;              /* its chain of pool rows (SpoolArgs::next); -1 while it has none */
-    uint32_t pad[4];
+    uint32_t flags;                  /* OR of the stored rows' airband_hip_audio_row.reserved: the record's reserved[1] */
+    uint32_t pad[2];
 }; /* 48 bytes */
+static_assert(sizeof(SpoolChan) == 48, "SpoolChan is 48 bytes");
 struct SpoolCtl {
     int32_t exp[3];                  /* the last collect's: transmissions exported, their rows, transmissions still waiting */
     int32_t free_top;                /* rows on the free stack */

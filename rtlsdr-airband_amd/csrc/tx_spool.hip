@@ -1,5 +1,6 @@
-/* csrc/tx_spool.hip -- transmission spool (airband_hip_set_transmission_spool / _collect_transmissions / _spool_flush): the encoded rows of every open
- * transmission kept in a row pool on the GPU, the reference's closing rule for `split_on_transmission` file sinks applied once per batch, and finished
+/* csrc/tx_spool.hip -- transmission spool (airband_hip_set_transmission_spool / _collect_transmissions / _spool_flush, and the mixer spool's
+ * airband_hip_set_mixer_spool / _collect_mixer_transmissions / _mixer_spool_flush over the mixer gate's rows: "channel" below is then a mixer, "the gate" the
+ * mixer gate, "the encoder" the mixer pack, and a row is W * wave_batch samples): the encoded rows of every open transmission kept in a row pool on the GPU, the reference's closing rule for `split_on_transmission` file sinks applied once per batch, and finished
  * transmissions handed over as 48-byte records and one contiguous run of rows.  The definition is include/airband_hip.h's ("transmission spool");
  * capi.transmission_spool_reference() is the same in plain Python.  Integers only: records and audio are checked as bytes.
  *
@@ -24,7 +25,7 @@
  * its chain into the source-row list and pushes the rows back) and spool_gather_kernel (row i of the export buffer = pool row src[i]).
  *
  * Rows are dense and wave_batch is only a multiple of four, so a row of 1 000 G.711 bytes starts on a multiple of 8, not 16: lanes move 8 bytes where the row's
- * bytes are a multiple of 8 (1 000, 2 000, 4 000 are), else 4.  The encoder's row is read once: non-temporal load; the store is ordinary.
+ * bytes are a multiple of 8 (1 000, 2 000, 4 000 are, and so is every mixer row: W * wave_batch * bytes is 1 000 .. 8 000), else 4.  The encoder's row is read once: non-temporal load; the store is ordinary.
  *
  * Every count and index read from device memory is clamped to its buffer before anything is indexed with it: the free count, the list's head and count, chain
  * links, n_rows, the step's stored count, the copy list's entries.
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(SPOOL_BLOCK) void spool_close_kernel(SpoolArgs a, i
             r.reason = (uint16_t)(reason ? reason : (idle ? AIRBAND_SPOOL_IDLE : AIRBAND_SPOOL_MAX));
             r.row_offset = 0;
             r.reserved[0] = (uint32_t)st.head;
-            r.reserved[1] = 0;
+            r.reserved[1] = st.flags;
             a.fin[(int)(((long)tail + rank) % a.max_records)] = r;
         } else {
             sp_release_chain(a, st.head, n, nullptr); /* dropped: the list is full */
@@ -188,6 +189,7 @@ __global__ __launch_bounds__(SPOOL_BLOCK) void spool_append_kernel(SpoolArgs a) 
         if (!st.open) {
             st.open_batch = a.k;
             st.n_rows = st.n_lost = st.n_clipped = 0;
+            st.flags = 0;
             st.peak = 0;
             st.first = (uint16_t)a.wave_batch;
             st.end = 0;
@@ -210,6 +212,7 @@ __global__ __launch_bounds__(SPOOL_BLOCK) void spool_append_kernel(SpoolArgs a) 
             st.n_clipped = sum < st.n_clipped ? 0xFFFFFFFFu : sum;
             if (st.n_rows == 0) st.first = info.first;
             st.end = info.end;
+            st.flags |= info.reserved; /* a mixer's stereo flag at this step; a channel's record carries 0 */
             st.n_rows++;
             a.copy_list[2 * j] = pos;
             a.copy_list[2 * j + 1] = row;
@@ -295,7 +298,7 @@ __global__ __launch_bounds__(SPOOL_BLOCK) void spool_export_kernel(SpoolArgs a) 
             a.exp_head[i] = (int)r.reserved[0];
             r.n_rows = (uint32_t)n;
             r.row_offset = (uint32_t)(upto - n);
-            r.reserved[0] = r.reserved[1] = 0;
+            r.reserved[0] = 0; /* the chain's head is the spool's own; reserved[1] is the record's: the OR of the stored rows' flags */
             a.exp_records[i] = r;
         }
         const unsigned long long mf = __ballot(fits); /* a prefix of the wavefront's lanes */
