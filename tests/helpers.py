@@ -1,7 +1,13 @@
 """Shared helpers for the parity tests (test infrastructure)."""
 from __future__ import annotations
 
+import glob
 import importlib
+import os
+import shutil
+import subprocess
+import sys
+import tempfile
 
 import numpy as np
 
@@ -658,3 +664,26 @@ def ctcss_bank_shape(pkg, target, wave_rate):
              bandwidth_hz=0, ampfactor=1.0, tau_us=-1, has_iq_outputs=0)
     v = pkg.derive_constants([dict(channels=[c])], 0, wave_rate=wave_rate)
     return int(v[11]), int(v[12])
+
+
+def traced_kernels(script, args, must_contain):
+    """scripts/<script> --child on a short run (4 dongles, 3 batches, then args) under `rocprofv3 --kernel-trace`: the text of the kernel-trace CSV files, in which
+    a test looks for the kernels a handle launched.  The program goes after `--`; counters are not collected.  must_contain: what every such run launches, so
+    that a trace without it is no trace -- each entry a kernel's name, or a tuple of names of which one must appear."""
+    rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
+    if not os.path.exists(rocprof):
+        import pytest  # (here: the scripts that borrow this module's signal plans need no pytest)
+        pytest.skip("no rocprofv3")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tempfile.mkdtemp(prefix="airband_trace_")
+    try:
+        cmd = [rocprof, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.join(root, "scripts", script),
+               "--child", "--dongles", "4", "--batches", "3"] + list(args)
+        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:]
+        text = "".join(open(f).read() for f in glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True))
+    finally:
+        shutil.rmtree(out, ignore_errors=True)
+    for names in must_contain:
+        assert any(k in text for k in ([names] if isinstance(names, str) else names)), "the trace holds no %r: %s" % (names, r.stdout[-1000:])
+    return text

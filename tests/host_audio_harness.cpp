@@ -13,71 +13,19 @@
 // Results file, per case: int32 kept = min(max(count, 0), max_rows), the kept rows' audio (wave_batch * 2 or * 1 bytes each), the kept records (16 bytes each).
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-// ---- what the shim lacks and audio_pack.hip uses: an integer shuffle ----
-static inline int __shfl_xor(int v, int mask) {
-    ab_emu::Group& g = ab_emu::my_wave();
-    const unsigned my = ab_emu::rendezvous(g, ab_emu::my_lane(), (unsigned)v);
-    const int src = (ab_emu::my_lane() ^ mask) & 63;
-    return g.put[my & 1][src] ? (int)g.slot[my & 1][src] : v;
-}
-
 #include "../rtlsdr-airband_amd/csrc/audio_pack.hip"
+#include "host_program.h"
 
 using namespace airband;
-
-namespace {
-
-struct Reader {
-    std::vector<unsigned char> d;
-    size_t at = 0;
-    void take(void* out, size_t n) {
-        if (at + n > d.size()) {
-            std::fprintf(stderr, "host_audio: cases file ends early\n");
-            std::exit(2);
-        }
-        if (n) std::memcpy(out, d.data() + at, n);
-        at += n;
-    }
-    int i32() {
-        int v;
-        take(&v, 4);
-        return v;
-    }
-};
-
-template <class T>
-T* aligned(size_t n) { // rows are moved 16 bytes at a time
-    void* p = std::aligned_alloc(64, ((n ? n : 1) * sizeof(T) + 63) / 64 * 64);
-    if (!p) std::exit(3);
-    return static_cast<T*>(p);
-}
+using namespace host_program;
 
 constexpr int GUARD_ROWS = 3;   // rows behind max_rows that nothing may write
 constexpr int PAD = 28;         // floats in front of a pitched source row (AB_OUT_PAD)
 
-}  // namespace
-
 int main(int argc, char** argv) {
-    if (argc != 3) {
-        std::fprintf(stderr, "usage: host_audio <cases> <results>\n");
-        return 2;
-    }
     Reader in;
-    {
-        FILE* f = std::fopen(argv[1], "rb");
-        if (!f) return 2;
-        unsigned char buf[1 << 16];
-        size_t n;
-        while ((n = std::fread(buf, 1, sizeof(buf), f)) > 0) in.d.insert(in.d.end(), buf, buf + n);
-        std::fclose(f);
-    }
-    FILE* out = std::fopen(argv[2], "wb");
-    if (!out) return 2;
+    FILE* out;
+    open_io(argc, argv, "host_audio", in, out);
     const int n_cases = in.i32();
     for (int c = 0; c < n_cases; c++) {
         const int encoding = in.i32(), B = in.i32(), n_ch = in.i32(), max_rows = in.i32(), count = in.i32(), grid = in.i32(), listed = in.i32();
@@ -90,10 +38,8 @@ int main(int argc, char** argv) {
         for (size_t i = 0; i < (size_t)n_ch * stride; i++) src[i] = 7777.0f; // what lies between the rows clips: reading it would show
         for (int r = 0; r < n_ch; r++) in.take(src + (size_t)r * stride + pad, 4 * (size_t)B);
         const size_t row_bytes = (size_t)B * (encoding == AIRBAND_AUDIO_S16 ? 2 : 1), total_rows = (size_t)max_rows + GUARD_ROWS;
-        unsigned char* audio = aligned<unsigned char>(total_rows * row_bytes);
-        airband_hip_audio_row* info = aligned<airband_hip_audio_row>(total_rows);
-        std::memset(audio, 0xEE, total_rows * row_bytes);
-        std::memset(info, 0xEE, total_rows * sizeof(info[0]));
+        unsigned char* audio = make<unsigned char>(total_rows * row_bytes, 0xEE);
+        airband_hip_audio_row* info = make<airband_hip_audio_row>(total_rows, 0xEE);
         int count_mem = count;
         AudioPackArgs a;
         std::memset(&a, 0, sizeof(a));
@@ -114,17 +60,14 @@ int main(int argc, char** argv) {
         std::fwrite(&kept, 4, 1, out);
         std::fwrite(audio, row_bytes, (size_t)kept, out);
         std::fwrite(info, sizeof(info[0]), (size_t)kept, out);
-        for (size_t i = (size_t)kept * row_bytes; i < total_rows * row_bytes; i++)
-            if (audio[i] != 0xEE) {
-                std::fprintf(stderr, "host_audio: case %d wrote audio byte %zu, behind the %d rows it kept\n", c, i, kept);
-                return 1;
-            }
-        const unsigned char* g = reinterpret_cast<const unsigned char*>(info + kept);
-        for (size_t i = 0; i < (total_rows - (size_t)kept) * sizeof(info[0]); i++)
-            if (g[i] != 0xEE) {
-                std::fprintf(stderr, "host_audio: case %d wrote a record behind the %d rows it kept\n", c, kept);
-                return 1;
-            }
+        if (!untouched(audio, (size_t)kept * row_bytes, total_rows * row_bytes, 0xEE)) {
+            std::fprintf(stderr, "host_audio: case %d wrote audio bytes behind the %d rows it kept\n", c, kept);
+            return 1;
+        }
+        if (!untouched(info, (size_t)kept * sizeof(info[0]), total_rows * sizeof(info[0]), 0xEE)) {
+            std::fprintf(stderr, "host_audio: case %d wrote a record behind the %d rows it kept\n", c, kept);
+            return 1;
+        }
         std::free(src);
         std::free(audio);
         std::free(info);

@@ -15,72 +15,19 @@
 //     re-tune stamp, int32 n_changes, then min(n_changes, max_changes) records of 16 bytes.  The stamp of batch b is b + 1.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-// ---- what the shim lacks and band_follow.hip / band_pack.h use: integer shuffles (as tests/host_watch_harness.cpp's) ----
-static inline unsigned ab_emu_shfl_u32(unsigned v, int src) {
-    ab_emu::Group& g = ab_emu::my_wave();
-    const unsigned my = ab_emu::rendezvous(g, ab_emu::my_lane(), v);
-    return (src >= 0 && src < 64 && g.put[my & 1][src]) ? g.slot[my & 1][src] : v;
-}
-static inline int __shfl(int v, int src) { return (int)ab_emu_shfl_u32((unsigned)v, src); }
-static inline unsigned __shfl_up(unsigned v, unsigned delta) { return ab_emu_shfl_u32(v, ab_emu::my_lane() - (int)delta); }
-
 #include "../rtlsdr-airband_amd/csrc/band_follow.hip"
+#include "host_program.h"
 
 using namespace airband;
-
-namespace {
-
-struct Reader {
-    std::vector<unsigned char> d;
-    size_t at = 0;
-    void take(void* out, size_t n) {
-        if (at + n > d.size()) {
-            std::fprintf(stderr, "host_follow: cases file ends early\n");
-            std::exit(2);
-        }
-        std::memcpy(out, d.data() + at, n);
-        at += n;
-    }
-    int i32() {
-        int v;
-        take(&v, 4);
-        return v;
-    }
-};
-
-template <class T>
-T* aligned(size_t n) { // 16-byte records are moved 16 bytes at a time
-    void* p = std::aligned_alloc(64, ((n ? n : 1) * sizeof(T) + 63) / 64 * 64);
-    if (!p) std::exit(3);
-    return static_cast<T*>(p);
-}
+using namespace host_program;
 
 constexpr int GUARD = 64;        // changes behind max_changes that nothing may write
 constexpr int POISON_BIN = -77;  // ChanState::bin of a slot that is no follower's
 
-}  // namespace
-
 int main(int argc, char** argv) {
-    if (argc != 3) {
-        std::fprintf(stderr, "usage: host_follow <cases> <results>\n");
-        return 2;
-    }
     Reader in;
-    {
-        FILE* f = std::fopen(argv[1], "rb");
-        if (!f) return 2;
-        unsigned char buf[1 << 16];
-        size_t n;
-        while ((n = std::fread(buf, 1, sizeof(buf), f)) > 0) in.d.insert(in.d.end(), buf, buf + n);
-        std::fclose(f);
-    }
-    FILE* out = std::fopen(argv[2], "wb");
-    if (!out) return 2;
+    FILE* out;
+    open_io(argc, argv, "host_follow", in, out);
     const int n_cases = in.i32();
     for (int c = 0; c < n_cases; c++) {
         const int n_rows = in.i32(), fft_log = in.i32(), T = in.i32(), E = in.i32(), n_batches = in.i32();
@@ -154,12 +101,10 @@ int main(int argc, char** argv) {
             std::fwrite(&count, 4, 1, out);
             const int kept = count < 0 ? 0 : count < E ? count : E;
             std::fwrite(changes, sizeof(changes[0]), kept, out);
-            const unsigned char* g = reinterpret_cast<const unsigned char*>(changes + kept);
-            for (size_t i = 0; i < sizeof(changes[0]) * ((size_t)E + GUARD - kept); i++)
-                if (g[i] != 0xEE) {
-                    std::fprintf(stderr, "host_follow: case %d batch %d wrote behind the %d changes it kept\n", c, b, kept);
-                    return 1;
-                }
+            if (!untouched(changes, sizeof(changes[0]) * (size_t)kept, sizeof(changes[0]) * ((size_t)E + GUARD), 0xEE)) {
+                std::fprintf(stderr, "host_follow: case %d batch %d wrote behind the %d changes it kept\n", c, b, kept);
+                return 1;
+            }
             for (int s = 0; s < n_slots; s++)
                 if (s % 3 != 1 && cs[(size_t)s].bin != POISON_BIN) {
                     std::fprintf(stderr, "host_follow: case %d batch %d wrote the bin of slot %d, which is no follower's\n", c, b, s);

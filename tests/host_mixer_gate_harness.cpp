@@ -16,83 +16,18 @@
 // bytes each), and for an encoding other than float32 the kept records (16 bytes each).
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-// ---- what the shim lacks and mixer_gate.hip uses ----
-static inline int __shfl_xor(int v, int mask) {
-    ab_emu::Group& g = ab_emu::my_wave();
-    const unsigned my = ab_emu::rendezvous(g, ab_emu::my_lane(), (unsigned)v);
-    const int src = (ab_emu::my_lane() ^ mask) & 63;
-    return g.put[my & 1][src] ? (int)g.slot[my & 1][src] : v;
-}
-static inline int __popcll(unsigned long long m) { return __builtin_popcountll(m); }
-static inline int atomicAdd(int* p, int v) { // one fiber runs at a time
-    const int old = *p;
-    *p = old + v;
-    return old;
-}
-
 #include "../rtlsdr-airband_amd/csrc/mixer_gate.hip"
+#include "host_program.h"
 
 using namespace airband;
-
-namespace {
-
-struct Reader {
-    std::vector<unsigned char> d;
-    size_t at = 0;
-    void take(void* out, size_t n) {
-        if (at + n > d.size()) {
-            std::fprintf(stderr, "host_mixer_gate: cases file ends early\n");
-            std::exit(2);
-        }
-        if (n) std::memcpy(out, d.data() + at, n);
-        at += n;
-    }
-    int i32() {
-        int v;
-        take(&v, 4);
-        return v;
-    }
-};
-
-template <class T>
-T* aligned(size_t n) { // rows are moved 16 bytes at a time
-    void* p = std::aligned_alloc(64, ((n ? n : 1) * sizeof(T) + 63) / 64 * 64);
-    if (!p) std::exit(3);
-    return static_cast<T*>(p);
-}
+using namespace host_program;
 
 constexpr int GUARD_ROWS = 3; // rows / list entries behind max_rows that nothing may write
 
-bool untouched(const void* p, size_t from, size_t to, unsigned char v) {
-    const unsigned char* b = static_cast<const unsigned char*>(p);
-    for (size_t i = from; i < to; i++)
-        if (b[i] != v) return false;
-    return true;
-}
-
-}  // namespace
-
 int main(int argc, char** argv) {
-    if (argc != 3) {
-        std::fprintf(stderr, "usage: host_mixer_gate <cases> <results>\n");
-        return 2;
-    }
     Reader in;
-    {
-        FILE* f = std::fopen(argv[1], "rb");
-        if (!f) return 2;
-        unsigned char buf[1 << 16];
-        size_t n;
-        while ((n = std::fread(buf, 1, sizeof(buf), f)) > 0) in.d.insert(in.d.end(), buf, buf + n);
-        std::fclose(f);
-    }
-    FILE* out = std::fopen(argv[2], "wb");
-    if (!out) return 2;
+    FILE* out;
+    open_io(argc, argv, "host_mixer_gate", in, out);
     const int n_cases = in.i32();
     for (int c = 0; c < n_cases; c++) {
         const int encoding = in.i32(), W = in.i32(), B = in.i32(), n_mix = in.i32(), max_rows = in.i32(), grid = in.i32(), n_steps = in.i32(), listed = in.i32();

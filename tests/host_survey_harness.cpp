@@ -12,21 +12,6 @@
 #include <cstring>
 #include <vector>
 
-// ---- what the shim lacks and band_survey.hip uses: an integer add on LDS, integer shuffles ----
-// (lanes are fibers of one host thread and leave it only at a rendezvous: a plain add IS atomic)
-static inline int atomicAdd(int* p, int v) {
-    const int old = *p;
-    *p = old + v;
-    return old;
-}
-static inline unsigned ab_emu_shfl_u32(unsigned v, int src) { // as the shim's ab_emu_shfl: every live lane deposits, then reads its source lane's deposit
-    ab_emu::Group& g = ab_emu::my_wave();
-    const unsigned my = ab_emu::rendezvous(g, ab_emu::my_lane(), v);
-    return (src >= 0 && src < 64 && g.put[my & 1][src]) ? g.slot[my & 1][src] : v;
-}
-static inline unsigned __shfl_xor(unsigned v, int mask) { return ab_emu_shfl_u32(v, ab_emu::my_lane() ^ mask); }
-static inline unsigned __shfl_up(unsigned v, unsigned delta) { return ab_emu_shfl_u32(v, ab_emu::my_lane() - (int)delta); } // lanes below delta keep their own
-
 #include "../rtlsdr-airband_amd/csrc/band_survey.hip"
 
 using namespace airband;

@@ -16,71 +16,18 @@
 //     pack == 0: the staged events of every row, rows[row].n_events records each;  pack != 0: int32 n_events, then min(n_events, max_events) records.
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <vector>
-
-// ---- what the shim lacks and band_watch.hip uses: integer shuffles (as tests/host_survey_harness.cpp's) ----
-static inline unsigned ab_emu_shfl_u32(unsigned v, int src) {
-    ab_emu::Group& g = ab_emu::my_wave();
-    const unsigned my = ab_emu::rendezvous(g, ab_emu::my_lane(), v);
-    return (src >= 0 && src < 64 && g.put[my & 1][src]) ? g.slot[my & 1][src] : v;
-}
-static inline unsigned __shfl_xor(unsigned v, int mask) { return ab_emu_shfl_u32(v, ab_emu::my_lane() ^ mask); }
-static inline unsigned __shfl_up(unsigned v, unsigned delta) { return ab_emu_shfl_u32(v, ab_emu::my_lane() - (int)delta); }
-
 #include "../rtlsdr-airband_amd/csrc/band_watch.hip"
+#include "host_program.h"
 
 using namespace airband;
-
-namespace {
-
-struct Reader {
-    std::vector<unsigned char> d;
-    size_t at = 0;
-    void take(void* out, size_t n) {
-        if (at + n > d.size()) {
-            std::fprintf(stderr, "host_watch: cases file ends early\n");
-            std::exit(2);
-        }
-        std::memcpy(out, d.data() + at, n);
-        at += n;
-    }
-    int i32() {
-        int v;
-        take(&v, 4);
-        return v;
-    }
-};
-
-template <class T>
-T* aligned(size_t n) { // 16-byte records are moved 16 bytes at a time
-    void* p = std::aligned_alloc(64, ((n ? n : 1) * sizeof(T) + 63) / 64 * 64);
-    if (!p) std::exit(3);
-    return static_cast<T*>(p);
-}
+using namespace host_program;
 
 constexpr int GUARD = 64; // events behind max_events that nothing may write
 
-}  // namespace
-
 int main(int argc, char** argv) {
-    if (argc != 3) {
-        std::fprintf(stderr, "usage: host_watch <cases> <results>\n");
-        return 2;
-    }
     Reader in;
-    {
-        FILE* f = std::fopen(argv[1], "rb");
-        if (!f) return 2;
-        unsigned char buf[1 << 16];
-        size_t n;
-        while ((n = std::fread(buf, 1, sizeof(buf), f)) > 0) in.d.insert(in.d.end(), buf, buf + n);
-        std::fclose(f);
-    }
-    FILE* out = std::fopen(argv[2], "wb");
-    if (!out) return 2;
+    FILE* out;
+    open_io(argc, argv, "host_watch", in, out);
     const int n_cases = in.i32();
     for (int c = 0; c < n_cases; c++) {
         const int n_rows = in.i32(), fft_log = in.i32(), max_peaks = in.i32(), T = in.i32(), M = in.i32(), C = in.i32(), R = in.i32(), E = in.i32(), n_batches = in.i32(),
@@ -165,12 +112,10 @@ int main(int argc, char** argv) {
                 std::fwrite(&count, 4, 1, out);
                 const int kept = count < 0 ? 0 : count < E ? count : E;
                 std::fwrite(events, sizeof(events[0]), kept, out);
-                const unsigned char* g = reinterpret_cast<const unsigned char*>(events + kept);
-                for (size_t i = 0; i < sizeof(events[0]) * ((size_t)E + GUARD - kept); i++)
-                    if (g[i] != 0xEE) {
-                        std::fprintf(stderr, "host_watch: case %d batch %d wrote behind the %d events it kept\n", c, b, kept);
-                        return 1;
-                    }
+                if (!untouched(events, sizeof(events[0]) * (size_t)kept, sizeof(events[0]) * ((size_t)E + GUARD), 0xEE)) {
+                    std::fprintf(stderr, "host_watch: case %d batch %d wrote behind the %d events it kept\n", c, b, kept);
+                    return 1;
+                }
             } else {
                 for (int r = 0; r < n_rows; r++) {
                     int n = rows[set][r].n_events;

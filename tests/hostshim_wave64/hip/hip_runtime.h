@@ -1,12 +1,13 @@
-// tests/hostshim_wave64/hip/hip_runtime.h -- TEST HARNESS ONLY.  A host stand-in for <hip/hip_runtime.h> that RUNS the stage-2 kernels of csrc/demod.hip
-// with their wavefront semantics: every work-item of a block is a fiber (ucontext) of one host thread, a "launch" runs the grid block after block, and the
-// cross-lane operations the kernels use -- __ballot, v_readlane / v_readfirstlane, __syncthreads, and the places where the code relies on the 64 lanes
-// of a wavefront executing in lockstep (AB_LOCKSTEP() in the source: LDS exchanges without a barrier) -- are rendezvous points of the fibers of a wavefront
-// (or block).  A lane that returns from the kernel leaves the wavefront, as on the GPU.  A collective reached by only some of the live lanes of a
-// wavefront is a deadlock here and is reported as one: it checks the rule the kernels are written to ("lane masks are only ever assigned in wave-uniform
-// control flow").  __HIPCC__ is defined, so csrc/squelch_fsm.h, csrc/exact_math.h and csrc/demod.hip take their DEVICE branches -- the code under test is
-// the code the GPU runs, lane masks and all.  Used by tests/host_wave64_harness.cpp (built by tests/test_host_wave64.py into a temporary directory);
-// nothing in the library includes or links this.
+// tests/hostshim_wave64/hip/hip_runtime.h -- TEST HARNESS ONLY.  A host stand-in for <hip/hip_runtime.h> that RUNS the library's kernels with their wavefront
+// semantics: every work-item of a block is a fiber (ucontext) of one host thread, a "launch" runs the grid block after block, and the cross-lane operations the
+// kernels use -- __ballot, the shuffles, v_readlane / v_readfirstlane, __syncthreads, and the places where the code relies on the 64 lanes of a wavefront
+// executing in lockstep (AB_LOCKSTEP() in the source: LDS exchanges without a barrier) -- are rendezvous points of the fibers of a wavefront (or block).  A lane
+// that returns from the kernel leaves the wavefront, as on the GPU.  A collective reached by only some of the live lanes of a wavefront is a deadlock here and is
+// reported as one: it checks the rule the kernels are written to ("lane masks are only ever assigned in wave-uniform control flow").  __HIPCC__ is defined, so
+// the .hip sources and the headers they share with the host take their DEVICE branches -- the code under test is the code the GPU runs, lane masks and all.
+// Every intrinsic a kernel needs is defined HERE, once: the harnesses (tests/host_*_harness.cpp -- stage 2 through host_demod_harness.cpp with -DAB_WAVE64_EMU, the
+// wavefront FFT, the band scope, survey, watch and follow, scan control, the audio encoder, the mixer gate, the spools) only include the kernel source and fill
+// its arguments.  tests/hostbed.py builds them into a temporary directory; nothing in the library includes or links this.
 #ifndef AIRBAND_TESTS_HOSTSHIM_WAVE64_HIP_RUNTIME_H
 #define AIRBAND_TESTS_HOSTSHIM_WAVE64_HIP_RUNTIME_H
 
@@ -223,7 +224,7 @@ static inline bool ab_emu_inverse_ballot(unsigned long long m) { return (m >> ab
 #define __builtin_amdgcn_readlane(v, l) ab_emu::readlane((unsigned)(v), (l))
 #define __builtin_amdgcn_sqrtf(x) sqrtf(x) /* v_sqrt_f32 is within 1 ulp; tests/test_exact_math.py covers what exact_math.h makes of either neighbour */
 
-/* ---- what csrc/channelizer_fft.hip needs on top (tests/host_fft_harness.cpp): shuffles as rendezvous points, a block's dynamic LDS, two vector types */
+/* ---- what the kernels beyond stage 2 need on top: two vector types, shuffles as rendezvous points, population counts, atomics, a block's dynamic LDS */
 struct char2 { signed char x, y; };
 struct short2 { short x, y; };
 static inline unsigned __brev(unsigned v) {
@@ -231,14 +232,35 @@ static inline unsigned __brev(unsigned v) {
     for (int i = 0; i < 32; i++) r |= ((v >> i) & 1u) << (31 - i);
     return r;
 }
-static inline float ab_emu_shfl(float v, int src) { /* ds_bpermute: every live lane deposits, then reads its source lane's deposit */
+/* ds_bpermute: every live lane deposits, then reads its source lane's deposit.  A source lane outside 0 .. 63, or one that has retired, leaves the caller its own
+   value (__shfl_up in the lanes below delta; the kernels never read a retired lane) */
+static inline unsigned ab_emu_shfl_u32(unsigned v, int src) {
     ab_emu::Group& g = ab_emu::my_wave();
-    const unsigned my = ab_emu::rendezvous(g, ab_emu::my_lane(), __float_as_uint(v));
-    src &= 63;
-    return g.put[my & 1][src] ? __uint_as_float(g.slot[my & 1][src]) : v;
+    const unsigned my = ab_emu::rendezvous(g, ab_emu::my_lane(), v);
+    return (src >= 0 && src < ab_emu::WAVE && g.put[my & 1][src]) ? g.slot[my & 1][src] : v;
 }
+static inline float ab_emu_shfl(float v, int src) { return __uint_as_float(ab_emu_shfl_u32(__float_as_uint(v), src)); }
 static inline float __shfl(float v, int src) { return ab_emu_shfl(v, src); }
+static inline unsigned __shfl(unsigned v, int src) { return ab_emu_shfl_u32(v, src); }
+static inline int __shfl(int v, int src) { return (int)ab_emu_shfl_u32((unsigned)v, src); }
 static inline float __shfl_xor(float v, int mask) { return ab_emu_shfl(v, ab_emu::my_lane() ^ mask); }
+static inline unsigned __shfl_xor(unsigned v, int mask) { return ab_emu_shfl_u32(v, ab_emu::my_lane() ^ mask); }
+static inline int __shfl_xor(int v, int mask) { return (int)ab_emu_shfl_u32((unsigned)v, ab_emu::my_lane() ^ mask); }
+static inline unsigned __shfl_up(unsigned v, unsigned delta) { return ab_emu_shfl_u32(v, ab_emu::my_lane() - (int)delta); }
+static inline int __shfl_up(int v, unsigned delta) { return (int)ab_emu_shfl_u32((unsigned)v, ab_emu::my_lane() - (int)delta); }
+static inline int __popcll(unsigned long long m) { return __builtin_popcountll(m); }
+/* atomics on LDS and global memory: lanes are fibers of one host thread and leave it only at a rendezvous, so a plain read-modify-write IS atomic */
+template <class T>
+static inline T atomicAdd(T* p, T v) {
+    const T old = *p;
+    *p = old + v;
+    return old;
+}
+static inline int atomicMax(int* p, int v) {
+    const int old = *p;
+    if (v > old) *p = v;
+    return old;
+}
 #define AB_WAVE_SYNC() ab_emu::lockstep() /* csrc/channelizer_fft.hip: lanes of one wavefront exchange data through LDS */
 #define AB_DYNAMIC_LDS_BYTES(name) uint8_t* const name = ab_emu::dynamic_lds /* one block runs at a time; writes past the launch's size are caught (ab_emu::launch) */
 enum { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };

@@ -4,18 +4,14 @@ Every comparison is byte for byte: behind the one float32 multiplication the def
 one are fed the same input; per batch the encoded rows and records must equal capi.audio_encode_reference() of the float rows the twin's collect_active()
 delivers, the count and the list must be the twin's, and everything else the two handles return must be the same bits.  encode_audio() is how the GPU meets
 the inputs a demodulator never produces: clipping, NaN, the infinities, ties."""
-import glob
 import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import ctypes as C
 import numpy as np
 import pytest
 
 import audio_cases as ac
+import helpers
 import test_gpu_gate as gg
 import test_output_gate as og
 
@@ -333,20 +329,7 @@ def test_errors_leave_a_working_handle(pkg, built):
 
 # ---- a handle without an encoding launches nothing new --------------------------------------------------------------------------------------------------
 def _traced_kernels(extra):
-    rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-    if not os.path.exists(rocprof):
-        pytest.skip("no rocprofv3")
-    out = tempfile.mkdtemp(prefix="airband_audio_trace_")
-    try:
-        cmd = [rocprof, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.join(ROOT, "scripts", "audio_encoding_profile.py"),
-               "--child", "--dongles", "4", "--batches", "3"] + extra
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:]
-        text = "".join(open(f).read() for f in glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True))
-    finally:
-        shutil.rmtree(out, ignore_errors=True)
-    assert "demod_kernel" in text or "back_kernel" in text, "the trace holds no stage-2 kernel: " + r.stdout[-1000:]
-    return text
+    return helpers.traced_kernels("audio_encoding_profile.py", extra, [("demod_kernel", "back_kernel")])
 
 
 def test_handle_without_an_encoding_launches_no_encode_kernel(pkg, built):

@@ -3,12 +3,7 @@
 Every comparison is bit for bit: the packed rows are copies.  Per batch, on ONE gated handle, collect_channels (does not consume) gives every row and
 axcindicate; collect_active must then return exactly the channels tests/test_output_gate.py::expected_active selects from the axcindicate history, in
 ascending order, and their rows.  A twin handle without a gate, fed the same input, must return the same full rows."""
-import glob
 import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import ctypes as C
 import numpy as np
@@ -407,20 +402,7 @@ def test_dongle_switched_off_and_back(pkg, built):
 
 # ---- a handle without a gate launches nothing new -------------------------------------------------------------------------------------------------------
 def _traced_kernels(extra):
-    rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-    if not os.path.exists(rocprof):
-        pytest.skip("no rocprofv3")
-    out = tempfile.mkdtemp(prefix="airband_gate_trace_")
-    try:
-        cmd = [rocprof, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.join(ROOT, "scripts", "gated_collect_profile.py"),
-               "--child", "--dongles", "4", "--batches", "3"] + extra
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:]
-        text = "".join(open(f).read() for f in glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True))
-    finally:
-        shutil.rmtree(out, ignore_errors=True)
-    assert "demod_kernel" in text or "back_kernel" in text, "the trace holds no stage-2 kernel: " + r.stdout[-1000:]
-    return text
+    return helpers.traced_kernels("gated_collect_profile.py", extra, [("demod_kernel", "back_kernel")])
 
 
 def test_ungated_handle_launches_no_gate_kernel(pkg, built):

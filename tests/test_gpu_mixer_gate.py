@@ -5,12 +5,7 @@ Every comparison is byte for byte.  Stage 2 is driven through process_bins with 
 history is known; the expectation is always capi.mixer_gate_reference applied to what collect_mixers() of the SAME handle returned per batch, which keeps
 these tests apart from stage-2 and mixer-sum parity (other tests' business)."""
 import ctypes as C
-import glob
 import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
@@ -383,20 +378,7 @@ def test_errors_leave_a_working_handle(pkg, built):
 
 # ---- a handle without a mixer gate launches nothing new -------------------------------------------------------------------------------------------------
 def _traced_kernels(extra):
-    rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-    if not os.path.exists(rocprof):
-        pytest.skip("no rocprofv3")
-    out = tempfile.mkdtemp(prefix="airband_mixer_gate_trace_")
-    try:
-        cmd = [rocprof, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.join(ROOT, "scripts", "mixer_gate_profile.py"),
-               "--child", "--dongles", "4", "--batches", "3"] + extra
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:]
-        text = "".join(open(f).read() for f in glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True))
-    finally:
-        shutil.rmtree(out, ignore_errors=True)
-    assert "mix_final_kernel" in text, "the trace holds no mixer kernel: " + r.stdout[-1000:]
-    return text
+    return helpers.traced_kernels("mixer_gate_profile.py", extra, ["mix_final_kernel"])
 
 
 def test_handle_without_a_mixer_gate_launches_none_of_the_kernels(pkg, built):

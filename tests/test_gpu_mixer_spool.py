@@ -5,13 +5,9 @@ Every comparison is byte for byte.  The expectation throughout is the definition
 collect_active_mixers() of the SAME handle returned -- which keeps these tests apart from the mixer gate's own (tests/test_gpu_mixer_gate.py) and from mixer-sum
 parity; `selected` comes from has_signal by the gate's rule (capi.mixer_gate_selection) and must agree with the gate's count and list.  Records, audio and
 counters are compared as bytes.  Each case asserts, from the model's output, that its run contained what the case is for."""
-import glob
 import importlib
 import os
-import shutil
-import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
@@ -419,20 +415,7 @@ def test_device_views_match_the_collect(pkg, built):
 
 # ---- 13: a handle with a mixer gate and no spool launches no spool kernel -----------------------------------------------------------------------------------
 def _traced_kernels(extra):
-    rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-    if not os.path.exists(rocprof):
-        pytest.skip("no rocprofv3")
-    out = tempfile.mkdtemp(prefix="airband_mixer_spool_trace_")
-    try:
-        cmd = [rocprof, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.join(ROOT, "scripts", "mixer_spool_profile.py"),
-               "--child", "--dongles", "4", "--batches", "3"] + extra
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:]
-        text = "".join(open(f).read() for f in glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True))
-    finally:
-        shutil.rmtree(out, ignore_errors=True)
-    assert "mix_final_kernel" in text and "mixer_pack_ulaw_stereo_kernel" in text, "the trace holds no mixer gate step: " + r.stdout[-1000:]
-    return text
+    return helpers.traced_kernels("mixer_spool_profile.py", extra, ["mix_final_kernel", "mixer_pack_ulaw_stereo_kernel"])
 
 
 def test_mixer_gate_without_a_spool_launches_no_spool_kernel(pkg, built):

@@ -5,16 +5,12 @@ Every comparison is byte for byte: the definition is integer arithmetic on the e
 fed the same input; capi.transmission_spool_reference() is fed the twin's collect_active_encoded() per batch; the spooled handle's collect_transmissions() --
 called only after the last batch and a flush unless a case says otherwise -- must give the model's records and audio, and its counters; everything else the
 two handles return must be the same bits.  Each case asserts, from the model's output, that its run contained what the case is for."""
-import glob
 import os
-import shutil
-import subprocess
-import sys
-import tempfile
 
 import numpy as np
 import pytest
 
+import helpers
 import spool_cases as sc
 import test_gpu_audio_encoding as ae
 import test_gpu_gate as gg
@@ -289,20 +285,7 @@ def test_errors_leave_a_working_handle(pkg, built):
 
 # ---- 10: a handle without a spool launches nothing new ----------------------------------------------------------------------------------------------------
 def _traced_kernels(extra):
-    rocprof = shutil.which("rocprofv3") or "/opt/rocm/bin/rocprofv3"
-    if not os.path.exists(rocprof):
-        pytest.skip("no rocprofv3")
-    out = tempfile.mkdtemp(prefix="airband_spool_trace_")
-    try:
-        cmd = [rocprof, "--kernel-trace", "--output-format", "csv", "-d", out, "--", sys.executable, os.path.join(ROOT, "scripts", "transmission_spool_profile.py"),
-               "--child", "--dongles", "4", "--batches", "3"] + extra
-        r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-        assert r.returncode == 0, r.stdout[-2000:]
-        text = "".join(open(f).read() for f in glob.glob(os.path.join(out, "**", "*kernel_trace.csv"), recursive=True))
-    finally:
-        shutil.rmtree(out, ignore_errors=True)
-    assert "demod_kernel" in text or "back_kernel" in text, "the trace holds no stage-2 kernel: " + r.stdout[-1000:]
-    return text
+    return helpers.traced_kernels("transmission_spool_profile.py", extra, [("demod_kernel", "back_kernel")])
 
 
 def test_handle_without_a_spool_launches_no_spool_kernel(pkg, built):

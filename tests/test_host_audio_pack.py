@@ -2,35 +2,21 @@
 tests/hostshim_wave64/ (lanes as fibers; shuffles are rendezvous points) into a stand-alone program (tests/host_audio_harness.cpp) that reads rows from a file
 and writes what the kernel left; compared byte for byte with the definition in numpy (capi.audio_encode_reference).  It checks the LOGIC of the code the GPU
 runs -- the float step, the segment search by leading zeros, the packing of four samples per lane, the row stride of the grid, the record's reduction, the
-clamps -- tests/test_gpu_audio_encoding.py is what a GPU says.  The same program built with -fsanitize=address,undefined runs two of the shapes."""
-import os
+clamps -- tests/test_gpu_audio_encoding.py is what a GPU says.  The same program built under ASan + UBSan (tests/hostbed.py) runs two of the shapes."""
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import audio_cases as ac
+import hostbed
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 capi = ac.capi
-
-
-def _build(out, extra):
-    cmd = [CLANG, "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-DAB_WAVE64_EMU", "-I" + os.path.join(HERE, "hostshim_wave64"),
-           "-I" + os.path.join(REPO, "include")] + extra + ["-o", out, os.path.join(HERE, "host_audio_harness.cpp")]
-    subprocess.run(cmd, check=True)
-    return out
 
 
 @pytest.fixture(scope="module")
 def hostaudio(tmp_path_factory):
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    d = tmp_path_factory.mktemp("hostaudio")
-    return dict(dir=str(d), exe=_build(str(d / "host_audio"), []))
+    return hostbed.program(tmp_path_factory, "host_audio", "host_audio_harness.cpp", extra=["-ffp-contract=off"])
 
 
 def _case(fmt, rows, count=None, max_rows=None, grid=2, index=None):
@@ -66,14 +52,6 @@ def _want(p):
     return struct.pack("<i", kept) + audio.tobytes() + info.tobytes()
 
 
-def _run(hostaudio, cases, name, exe=None, env=None):
-    src, dst = os.path.join(hostaudio["dir"], name + ".cases"), os.path.join(hostaudio["dir"], name + ".results")
-    open(src, "wb").write(_encode(cases))
-    r = subprocess.run([exe or hostaudio["exe"], src, dst], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return open(dst, "rb").read(), r.stdout
-
-
 def _compare(got, cases):
     at = 0
     for n, p in enumerate(cases):
@@ -99,7 +77,7 @@ def test_every_q_specials_and_ties(hostaudio, fmt, B):
     audio, info = capi.audio_encode_reference(rows, fmt)
     assert info["n_clipped"].sum() >= 6 and len(np.unique(audio)) >= (255 if fmt != "s16" else 65535)
     cases = [_case(fmt, rows)]
-    got, _ = _run(hostaudio, cases, "extremes_%s_%d" % (fmt, B))
+    got, _ = hostaudio.run(_encode(cases), "extremes_%s_%d" % (fmt, B))
     _compare(got, cases)
 
 
@@ -112,7 +90,7 @@ def test_row_counts_the_empty_case_and_the_stride(hostaudio, B):
         for n in (0, 1, 5):
             cases.append(_case(fmt, rows, count=n, max_rows=7))
             cases.append(_case(fmt, rows, index=[6, 0, 3, 3, 5][:n], max_rows=6))
-    got, _ = _run(hostaudio, cases, "counts_%d" % B)
+    got, _ = hostaudio.run(_encode(cases), "counts_%d" % B)
     _compare(got, cases)
 
 
@@ -126,12 +104,12 @@ def test_count_beyond_max_rows_writes_nothing_behind_them(hostaudio):
         cases.append(_case(fmt, rows, index=[1, 7], count=2 ** 31 - 1, max_rows=2))
         cases.append(_case(fmt, rows, index=[1, 7], count=-5, max_rows=2))
         cases.append(_case(fmt, rows, count=9, max_rows=3, grid=1))
-    got, _ = _run(hostaudio, cases, "overflow")
+    got, _ = hostaudio.run(_encode(cases), "overflow")
     _compare(got, cases)
     p = _case("s16", rows, index=[0, 8], max_rows=2)
     p["index"] = [12, -3]  # out of range either way: rows 8 and 0 are read, the record keeps what the list said
     q = dict(p, index=[8, 0])
-    got, _ = _run(hostaudio, [p], "clamp")
+    got, _ = hostaudio.run(_encode([p]), "clamp")
     want = _want(q)
     kept_audio = len(want) - 32
     assert got[:kept_audio] == want[:kept_audio]
@@ -152,7 +130,7 @@ def test_first_and_end(hostaudio, B):
     assert [(int(r["first"]), int(r["end"])) for r in info] == [(B, 0), (0, 1), (B - 1, B), (0, B), (B - 4, B - 3), (B, 0), (255, 701)]
     assert info["n_clipped"].tolist() == [0, 0, 0, 1, 0, 0, 1]
     cases = [_case(fmt, rows) for fmt in ac.FORMATS]
-    got, _ = _run(hostaudio, cases, "extent_%d" % B)
+    got, _ = hostaudio.run(_encode(cases), "extent_%d" % B)
     _compare(got, cases)
 
 
@@ -163,16 +141,13 @@ def test_seeded_random_rows(hostaudio):
     cases = [_case(fmt, rows, index=index) for fmt in ac.FORMATS]
     _, info = capi.audio_encode_reference(rows, "s16")
     assert (info["n_clipped"] > 0).any() and (info["peak"] == 0).any() and (info["first"] > 0).any()
-    got, _ = _run(hostaudio, cases, "random")
+    got, _ = hostaudio.run(_encode(cases), "random")
     _compare(got, cases)
 
 
 def test_two_shapes_under_host_sanitizers(hostaudio):
-    """The stand-alone program built with -fsanitize=address,undefined: the same bytes, no report."""
-    exe = _build(os.path.join(hostaudio["dir"], "host_audio_san"), ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"])
+    """The stand-alone program built under ASan + UBSan: the same bytes, no report."""
     rows = ac.random_rows(6, 2000, seed=3)
     cases = [_case("ulaw", ac.extremes_rows(1000)[-3:]), _case("s16", rows, index=[5, 1, 1, 0], count=11, max_rows=4), _case("alaw", rows, count=5, max_rows=6)]
-    env = dict(os.environ, ASAN_OPTIONS="detect_stack_use_after_return=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    got, log = _run(hostaudio, cases, "san", exe=exe, env=env)
-    assert "ERROR: AddressSanitizer" not in log and "runtime error" not in log, log[-4000:]
+    got, _ = hostaudio.sanitized().run(_encode(cases), "san")
     _compare(got, cases)

@@ -3,36 +3,22 @@ tests/hostshim_wave64/ (lanes as fibers; shuffles, ballots and barriers are rend
 reads sequences of batches from a file and writes what the kernels left; compared byte for byte with the definition in plain Python
 (capi.band_follow_reference) on seeded random track tables.  It checks the LOGIC of the code the GPU runs -- the cross-lane reads of step A, the ballots and
 their lowest bits in step B, the staging indices, the bins written to ChanState, the packed list -- tests/test_gpu_band_follow.py is what a GPU says.  The same
-program built with -fsanitize=address,undefined runs two of the shapes."""
-import os
+program built under ASan + UBSan (tests/hostbed.py) runs two of the shapes."""
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbed
 import watch_cases
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 capi = watch_cases.capi
 N_BATCHES, N_FFT = 12, 512
 
 
-def _build(out, extra):
-    cmd = [CLANG, "-x", "c++", "-std=c++17", "-O1", "-DAB_WAVE64_EMU", "-I" + os.path.join(HERE, "hostshim_wave64"), "-I" + os.path.join(REPO, "include")] + extra + [
-        "-o", out, os.path.join(HERE, "host_follow_harness.cpp")]
-    subprocess.run(cmd, check=True)
-    return out
-
-
 @pytest.fixture(scope="module")
 def hostfollow(tmp_path_factory):
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    d = tmp_path_factory.mktemp("hostfollow")
-    return dict(dir=str(d), exe=_build(str(d / "host_follow"), []))
+    return hostbed.program(tmp_path_factory, "host_follow", "host_follow_harness.cpp")
 
 
 def _tables(rng, n_rows, T, n_batches, busy, script=None):
@@ -129,14 +115,6 @@ def _simulate(p):
     return out, seen
 
 
-def _run(hostfollow, cases, name, exe=None, env=None):
-    src, dst = os.path.join(hostfollow["dir"], name + ".cases"), os.path.join(hostfollow["dir"], name + ".results")
-    open(src, "wb").write(_encode(cases))
-    r = subprocess.run([exe or hostfollow["exe"], src, dst], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return open(dst, "rb").read(), r.stdout
-
-
 def _compare(got, cases, sims):
     at = 0
     for n, (p, (want, _)) in enumerate(zip(cases, sims)):
@@ -159,7 +137,7 @@ def test_seeded_tables_equal_the_reference(hostfollow, shape):
     T, F = shape
     cases = [_case(seed, T, [F, F, max(1, F // 2)], off=[(4, 1), (5, 1), (6, 1)], first_batch=7 * seed) for seed in range(2)]
     sims = [_simulate(p) for p in cases]
-    got, _ = _run(hostfollow, cases, "t%df%d" % shape)
+    got, _ = hostfollow.run(_encode(cases), "t%df%d" % shape)
     _compare(got, cases, sims)
     kinds = sum((s[1]["kinds"] for s in sims), [])
     print("T %d F %d: %d TUNE %d MOVE %d HOME, %d unserved" % (T, F, kinds.count(1), kinds.count(2), kinds.count(3), sum(s[1]["unserved"] for s in sims)))
@@ -181,7 +159,7 @@ def test_a_slot_that_vanishes_and_is_refilled_the_batch_after(hostfollow):
     script.update({(k, 0, s): (Fr, -1) for k in range(N_BATCHES) for s in range(8) if s != 2})
     p = _case(3, 8, [1], busy=0.0, off=[(7, 0), (8, 0)], script=script)
     want, seen = _simulate(p)
-    got, _ = _run(hostfollow, [p], "refill")
+    got, _ = hostfollow.run(_encode([p]), "refill")
     _compare(got, [p], [(want, seen)])
     ch = [(k, int(c["kind"]), int(c["bin"]), int(c["track"])) for k, cs in enumerate(seen["changes"]) for c in cs]
     home = int(p["home"][1])
@@ -193,17 +171,14 @@ def test_fewer_records_than_changes(hostfollow):
     harness's guard zone), followers and rows are complete."""
     cases = [_case(11, 8, [2, 2, 2], E=2), _case(12, 64, [64, 64, 64], E=1)]
     sims = [_simulate(p) for p in cases]
-    got, _ = _run(hostfollow, cases, "clipped")
+    got, _ = hostfollow.run(_encode(cases), "clipped")
     _compare(got, cases, sims)
     assert all(s[1]["clipped"] > 0 for s in sims)
 
 
 def test_two_shapes_under_host_sanitizers(hostfollow):
-    """The stand-alone program built with -fsanitize=address,undefined: the same bytes, no report."""
-    exe = _build(os.path.join(hostfollow["dir"], "host_follow_san"), ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"])
+    """The stand-alone program built under ASan + UBSan: the same bytes, no report."""
     cases = [_case(21, 8, [2, 1, 2], E=3, off=[(2, 0)]), _case(22, 64, [64, 3, 1])]
     sims = [_simulate(p) for p in cases]
-    env = dict(os.environ, ASAN_OPTIONS="detect_stack_use_after_return=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    got, log = _run(hostfollow, cases, "san", exe=exe, env=env)
-    assert "ERROR: AddressSanitizer" not in log and "runtime error" not in log, log[-4000:]
+    got, _ = hostfollow.sanitized().run(_encode(cases), "san")
     _compare(got, cases, sims)

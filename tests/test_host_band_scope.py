@@ -6,16 +6,11 @@ runs (which windows, the passes over the bins, index maps, twiddles, the reducti
 what a GPU says."""
 import ctypes as C
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CSRC = os.path.join(REPO, "rtlsdr-airband_amd", "csrc")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+import hostbed
 
 pkg = importlib.import_module("rtlsdr-airband_amd")
 capi = pkg.capi
@@ -28,13 +23,7 @@ POWER_TOL = 2 * 2e-6
 
 @pytest.fixture(scope="module")
 def hostscope(tmp_path_factory):
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    out = str(tmp_path_factory.mktemp("hostscope") / "libhostscope.so")
-    cmd = [CLANG, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-DAB_WAVE64_EMU", "-I" + os.path.join(HERE, "hostshim_wave64"),
-           "-I" + os.path.join(REPO, "include"), "-o", out, os.path.join(HERE, "host_scope_harness.cpp"), os.path.join(CSRC, "params.cpp")]
-    subprocess.run(cmd, check=True)
-    lib = C.CDLL(out)
+    lib = C.CDLL(hostbed.build(["host_scope_harness.cpp", hostbed.PARAMS], tmp_path_factory.mktemp("hostscope") / "libhostscope.so", shared=True))
     vp = C.c_void_p
     lib.hostscope_run.argtypes = [C.POINTER(capi.Config), vp, C.c_long, C.c_int, C.c_int, vp, vp, vp, vp]
     lib.hostscope_geometry.argtypes = [C.POINTER(capi.Config), C.POINTER(C.c_int), C.POINTER(C.c_int)]

@@ -1,21 +1,15 @@
 """The band survey's kernel (csrc/band_survey.hip) with its wavefront semantics on the CPU: the kernel source compiled for the host through
-tests/hostshim_wave64/ (lanes as fibers; shuffles and barriers are rendezvous points; the LDS integer add and the integer shuffles the shim lacks come from
-tests/host_survey_harness.cpp), launched by the file's own launch_band_survey(), compared field by field and bit for bit with the definition in numpy
+tests/hostshim_wave64/ (lanes as fibers; shuffles and barriers are rendezvous points; the LDS integer add is a plain one) by tests/host_survey_harness.cpp, launched by the file's own launch_band_survey(), compared field by field and bit for bit with the definition in numpy
 (capi.band_survey_reference).  It checks the LOGIC of the code the GPU runs -- the radix select, the flags pass, the repeated workgroup maximum, the index
 masks (the shim aborts on a write past the launch's LDS) -- tests/test_gpu_band_survey.py is what a GPU says."""
 import ctypes as C
 import importlib
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbed
 import survey_cases
-
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 
 pkg = importlib.import_module("rtlsdr-airband_amd")
 capi = pkg.capi
@@ -23,13 +17,7 @@ capi = pkg.capi
 
 @pytest.fixture(scope="module")
 def hostsurvey(tmp_path_factory):
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    out = str(tmp_path_factory.mktemp("hostsurvey") / "libhostsurvey.so")
-    cmd = [CLANG, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-DAB_WAVE64_EMU", "-I" + os.path.join(HERE, "hostshim_wave64"),
-           "-I" + os.path.join(REPO, "include"), "-o", out, os.path.join(HERE, "host_survey_harness.cpp")]
-    subprocess.run(cmd, check=True)
-    lib = C.CDLL(out)
+    lib = C.CDLL(hostbed.build("host_survey_harness.cpp", tmp_path_factory.mktemp("hostsurvey") / "libhostsurvey.so", shared=True))
     vp, i = C.c_void_p, C.c_int
     lib.hostsurvey_run.argtypes = [vp, i, i, vp, vp, i, i, C.c_float, i, vp, vp]
     lib.hostsurvey_lds_bytes.restype = C.c_long

@@ -2,7 +2,7 @@
 tests/hostshim_wave64/ (lanes as fibers; shuffles, ballots and barriers are rendezvous points) into a stand-alone program (tests/host_watch_harness.cpp) that
 reads sequences of batches from a file and writes what the kernels left; compared byte for byte with the definition in plain Python
 (capi.band_watch_reference).  It checks the LOGIC of the code the GPU runs -- the key minimum, the ballots, the event indices, the carried prefix sum of the
-pack kernel -- tests/test_gpu_band_watch.py is what a GPU says.  The same program built with -fsanitize=address,undefined runs the fuzz's first seeds."""
+pack kernel -- tests/test_gpu_band_watch.py is what a GPU says.  The same program built under ASan + UBSan (tests/hostbed.py) runs the fuzz's first seeds."""
 import os
 import struct
 import subprocess
@@ -10,35 +10,15 @@ import subprocess
 import numpy as np
 import pytest
 
+import hostbed
 import watch_cases
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 capi = watch_cases.capi
-
-
-def _build(out, extra):
-    cmd = [CLANG, "-x", "c++", "-std=c++17", "-O1", "-DAB_WAVE64_EMU", "-I" + os.path.join(HERE, "hostshim_wave64"), "-I" + os.path.join(REPO, "include")] + extra + [
-        "-o", out, os.path.join(HERE, "host_watch_harness.cpp")]
-    subprocess.run(cmd, check=True)
-    return out
 
 
 @pytest.fixture(scope="module")
 def hostwatch(tmp_path_factory):
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    d = tmp_path_factory.mktemp("hostwatch")
-    return dict(dir=str(d), exe=_build(str(d / "host_watch"), []))
-
-
-def _run(hostwatch, blob, name, exe=None, env=None):
-    src, dst = os.path.join(hostwatch["dir"], name + ".cases"), os.path.join(hostwatch["dir"], name + ".results")
-    open(src, "wb").write(blob)
-    r = subprocess.run([exe or hostwatch["exe"], src, dst], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return open(dst, "rb").read(), r.stdout
+    return hostbed.program(tmp_path_factory, "host_watch", "host_watch_harness.cpp")
 
 
 def _run_split(hostwatch, cases, name, pieces=8):
@@ -46,9 +26,9 @@ def _run_split(hostwatch, cases, name, pieces=8):
     step = (len(cases) + pieces - 1) // pieces
     procs = []
     for i in range(0, len(cases), step):
-        src, dst = os.path.join(hostwatch["dir"], "%s%d.cases" % (name, i)), os.path.join(hostwatch["dir"], "%s%d.results" % (name, i))
+        src, dst = os.path.join(hostwatch.dir, "%s%d.cases" % (name, i)), os.path.join(hostwatch.dir, "%s%d.results" % (name, i))
         open(src, "wb").write(watch_cases.encode(cases[i:i + step]))
-        procs.append((subprocess.Popen([hostwatch["exe"], src, dst], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True), dst))
+        procs.append((subprocess.Popen([hostwatch.exe, src, dst], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True), dst))
     got = b""
     for proc, dst in procs:
         log, _ = proc.communicate()
@@ -80,14 +60,14 @@ def test_constructed_sequences(hostwatch, case):
     name, p, batches, check = case
     sim = watch_cases.simulate(p, batches)
     check(sim)  # the property, on the reference's output
-    got, _ = _run(hostwatch, watch_cases.encode([(p, batches)]), name)
+    got, _ = hostwatch.run(watch_cases.encode([(p, batches)]), name)
     _compare(got, [(p, batches)], [sim])
 
 
 def test_constructed_sequences_with_two_sets(hostwatch):
     """The same sequences where the tables a batch starts from are the other set's, as on a pipelined handle: every entry of the set written to is written."""
     cases = [(dict(p, two_sets=1), batches) for _, p, batches, _ in CONSTRUCTED if p["C"] != 255]
-    got, _ = _run(hostwatch, watch_cases.encode(cases), "two_sets")
+    got, _ = hostwatch.run(watch_cases.encode(cases), "two_sets")
     _compare(got, cases, [watch_cases.simulate(p, b) for p, b in cases])
 
 
@@ -144,7 +124,7 @@ def test_pack_kernel(hostwatch):
     shapes = _pack_shapes()
     made = [_pack_case(*s) for s in shapes]
     blob = struct.pack("<i", len(made)) + b"".join(m[1] for m in made)
-    got, _ = _run(hostwatch, blob, "pack")
+    got, _ = hostwatch.run(blob, "pack")
     at = 0
     for (n_rows, counts, E), (p, _, events) in zip(shapes, made):
         at += 24 * p["T"] * n_rows + 16 * n_rows  # tables and records: not the pack kernel's
@@ -158,15 +138,11 @@ def test_pack_kernel(hostwatch):
 
 
 def test_first_seeds_under_host_sanitizers(hostwatch, fuzz):
-    """The stand-alone program built with -fsanitize=address,undefined on the fuzz's first seeds and a pack case: the same bytes, no report."""
-    exe = _build(os.path.join(hostwatch["dir"], "host_watch_san"), ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"])
+    """The stand-alone program built under ASan + UBSan on the fuzz's first seeds and a pack case: the same bytes, no report."""
     cases, sims = fuzz
     cases, sims = cases[:2], sims[:2]  # (seed 0 runs the pack kernel too)
-    env = dict(os.environ, ASAN_OPTIONS="detect_stack_use_after_return=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    got, log = _run(hostwatch, watch_cases.encode(cases), "san", exe=exe, env=env)
-    assert "ERROR: AddressSanitizer" not in log and "runtime error" not in log, log[-4000:]
+    got, _ = hostwatch.sanitized().run(watch_cases.encode(cases), "san")
     _compare(got, cases, sims)
     p, blob, events = _pack_case(1025, [3] * 1025, 2000)
-    got, log = _run(hostwatch, struct.pack("<i", 1) + blob, "san_pack", exe=exe, env=env)
-    assert "ERROR: AddressSanitizer" not in log and "runtime error" not in log, log[-4000:]
+    got, _ = hostwatch.sanitized().run(struct.pack("<i", 1) + blob, "san_pack")
     assert got[-16 * 2000:] == events[:2000].tobytes()

@@ -7,15 +7,11 @@ FFT of the same converted, windowed samples (reference: src/rtl_airband.cpp:402-
 import ctypes as C
 import importlib
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CSRC = os.path.join(REPO, "rtlsdr-airband_amd", "csrc")
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+import hostbed
 
 pkg = importlib.import_module("rtlsdr-airband_amd")
 capi = pkg.capi
@@ -24,13 +20,7 @@ sg = pkg.siggen
 
 @pytest.fixture(scope="module")
 def hostfft(tmp_path_factory):
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    out = str(tmp_path_factory.mktemp("hostfft") / "libhostfft.so")
-    cmd = [CLANG, "-x", "c++", "-std=c++17", "-O1", "-fPIC", "-shared", "-DAB_WAVE64_EMU", "-I" + os.path.join(HERE, "hostshim_wave64"),
-           "-I" + os.path.join(REPO, "include"), "-o", out, os.path.join(HERE, "host_fft_harness.cpp"), os.path.join(CSRC, "params.cpp")]
-    subprocess.run(cmd, check=True)
-    lib = C.CDLL(out)
+    lib = C.CDLL(hostbed.build(["host_fft_harness.cpp", hostbed.PARAMS], tmp_path_factory.mktemp("hostfft") / "libhostfft.so", shared=True))
     vp = C.c_void_p
     lib.hostfft_run.argtypes = [C.POINTER(capi.Config), vp, C.c_long, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     lib.hostfft_hop_samples.argtypes = [C.POINTER(capi.Config)]

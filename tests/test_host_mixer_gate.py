@@ -3,19 +3,15 @@ the CPU: the kernel source compiled for the host through tests/hostshim_wave64/ 
 stand-alone program (tests/host_mixer_gate_harness.cpp) that reads steps from a file and writes what the kernels left; compared byte for byte with the definition
 in numpy (capi.mixer_gate_reference).  It checks the LOGIC of the code the GPU runs -- the rule and its memory, the ascending list across wavefronts and
 workgroups, the interleaving of left and right, the frame-indexed record, the row stride of the grid, the clamps -- tests/test_gpu_mixer_gate.py is what a GPU
-says.  The same program built with -fsanitize=address,undefined runs two of the shapes."""
-import os
+says.  The same program built under ASan + UBSan (tests/hostbed.py) runs two of the shapes."""
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import audio_cases as ac
+import hostbed
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 capi = ac.capi
 ENCODINGS = (None, "s16", "ulaw", "alaw")
 NEVER, SIGNAL, ALWAYS = capi.GATE_NEVER, capi.GATE_SIGNAL, capi.GATE_ALWAYS
@@ -25,19 +21,9 @@ def _enc(e):
     return capi.AUDIO_F32 if e is None else capi.AUDIO_ENCODINGS[e]
 
 
-def _build(out, extra):
-    cmd = [CLANG, "-x", "c++", "-std=c++17", "-O1", "-ffp-contract=off", "-DAB_WAVE64_EMU", "-I" + os.path.join(HERE, "hostshim_wave64"),
-           "-I" + os.path.join(REPO, "include")] + extra + ["-o", out, os.path.join(HERE, "host_mixer_gate_harness.cpp")]
-    subprocess.run(cmd, check=True)
-    return out
-
-
 @pytest.fixture(scope="module")
 def hostmix(tmp_path_factory):
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    d = tmp_path_factory.mktemp("hostmixgate")
-    return dict(dir=str(d), exe=_build(str(d / "host_mixer_gate"), []))
+    return hostbed.program(tmp_path_factory, "host_mixer_gate", "host_mixer_gate_harness.cpp", extra=["-ffp-contract=off"])
 
 
 def _case(enc, stereo, gate, steps, max_rows=None, grid=2, stereo_flags=None, listed=None):
@@ -83,14 +69,6 @@ def _want(p):
             b = struct.pack("<ii", count, kept) + np.array(index[:kept], "<i4").tobytes() + rows.tobytes()
             out.append(b + (info.tobytes() if info is not None else b""))
     return out
-
-
-def _run(hostmix, cases, name, exe=None, env=None):
-    src, dst = os.path.join(hostmix["dir"], name + ".cases"), os.path.join(hostmix["dir"], name + ".results")
-    open(src, "wb").write(_encode(cases))
-    r = subprocess.run([exe or hostmix["exe"], src, dst], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return open(dst, "rb").read(), r.stdout
 
 
 def _compare(got, cases):
@@ -150,7 +128,7 @@ def test_list_across_wavefronts_and_workgroups(hostmix, M):
         cases.append(_case("ulaw", True, gate, steps, max_rows=max(counts) - 1, stereo_flags=flags))    # below
         cases.append(_case("ulaw", True, gate, steps, max_rows=max(counts), stereo_flags=flags))        # equal
     cases.append(_case(None, False, gate, steps, max_rows=1, grid=1))
-    got, _ = _run(hostmix, cases, "list_%d" % M)
+    got, _ = hostmix.run(_encode(cases), "list_%d" % M)
     _compare(got, cases)
     if M >= 63:
         trailing = [m for k in range(1, 4) for m in ref[k]["mixers"] if gate[m] == SIGNAL and not steps[k][2][m]]
@@ -169,7 +147,7 @@ def test_rows_of_every_encoding_and_width(hostmix, enc, stereo, B):
     gate = np.array([ALWAYS, SIGNAL, ALWAYS, NEVER, SIGNAL, ALWAYS, SIGNAL], np.uint8)
     flags = np.array([1, 0, 1, 0, 1, 0, 0], np.uint8)
     cases = [_case(enc, stereo, gate, steps, grid=g, stereo_flags=flags) for g in (1, 2, 16)]
-    got, _ = _run(hostmix, cases, "rows_%s_%d_%d" % (enc, stereo, B))
+    got, _ = hostmix.run(_encode(cases), "rows_%s_%d_%d" % (enc, stereo, B))
     _compare(got, cases)
 
 
@@ -188,7 +166,7 @@ def test_edge_samples_in_left_right_and_both(hostmix, where):
     cases = [_case(enc, True, gate, steps) for enc in ENCODINGS] + [_case(enc, False, gate, steps) for enc in ("s16", "alaw")]
     ref = capi.mixer_gate_reference(gate, M, "s16", True, [(left, right, steps[0][2], np.zeros(M))])[0]
     assert ref["info"]["n_clipped"].sum() >= 6
-    got, _ = _run(hostmix, cases, "edges_" + where)
+    got, _ = hostmix.run(_encode(cases), "edges_" + where)
     _compare(got, cases)
 
 
@@ -207,7 +185,7 @@ def test_first_and_end_are_frames(hostmix):
     assert [(int(r["first"]), int(r["end"])) for r in ref["info"]] == [(300, 302), (0, 1), (B - 1, B), (700, 701), (255, 901), (B, 0)]
     assert ref["info"]["n_clipped"].tolist() == [0, 0, 1, 0, 1, 0]
     cases = [_case(enc, True, gate, steps) for enc in ENCODINGS] + [_case("ulaw", False, gate, steps)]
-    got, _ = _run(hostmix, cases, "extent")
+    got, _ = hostmix.run(_encode(cases), "extent")
     _compare(got, cases)
 
 
@@ -225,24 +203,21 @@ def test_padded_list_and_counts_out_of_range(hostmix):
         cases.append(_case(enc, True, gate, steps, listed=(2 ** 31 - 1, [1, 7]), max_rows=2, stereo_flags=flags))
         cases.append(_case(enc, False, gate, steps, listed=(-5, [1, 7]), max_rows=2, stereo_flags=flags))
         cases.append(_case(enc, False, gate, steps, listed=(2, [6, 3]), max_rows=6, grid=1, stereo_flags=flags))
-    got, _ = _run(hostmix, cases, "listed")
+    got, _ = hostmix.run(_encode(cases), "listed")
     _compare(got, cases)
     p = _case("s16", True, gate, steps, listed=(2, [0, 8]), max_rows=2, stereo_flags=flags)
     p["listed"] = (2, [12, -3])  # out of range either way: rows 8 and 0 are read, the record keeps what the list said
-    got, _ = _run(hostmix, [p], "clamp")
+    got, _ = hostmix.run(_encode([p]), "clamp")
     rows, info = capi.mixer_rows_reference(left, right, "s16", True, [8, 0], flags)
     info["channel"] = [12, -3]
     assert got == struct.pack("<ii", 2, 2) + np.array([12, -3], "<i4").tobytes() + rows.tobytes() + info.tobytes()
 
 
 def test_two_shapes_under_host_sanitizers(hostmix):
-    """The stand-alone program built with -fsanitize=address,undefined: the same bytes, no report."""
-    exe = _build(os.path.join(hostmix["dir"], "host_mixer_gate_san"), ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"])
+    """The stand-alone program built under ASan + UBSan: the same bytes, no report."""
     gate = _mixed_gate(65)
     cases = [_case("alaw", True, gate, _signal_steps(65, 8, 3, seed=5), max_rows=9),
              _case("s16", True, np.full(5, ALWAYS, np.uint8), _signal_steps(5, 2000, 1, seed=8, p_signal=1.0), grid=3, stereo_flags=[1, 0, 0, 1, 1]),
              _case(None, False, np.full(3, ALWAYS, np.uint8), [(ac.extremes_rows(1000)[-3:], ac.extremes_rows(1000)[:3], np.ones(3, np.uint8))], listed=(11, [2, 1]), max_rows=2)]
-    env = dict(os.environ, ASAN_OPTIONS="detect_stack_use_after_return=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    got, log = _run(hostmix, cases, "san", exe=exe, env=env)
-    assert "ERROR: AddressSanitizer" not in log and "runtime error" not in log, log[-4000:]
+    got, _ = hostmix.sanitized().run(_encode(cases), "san")
     _compare(got, cases)

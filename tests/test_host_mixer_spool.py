@@ -1,39 +1,23 @@
 """The spool kernels (csrc/tx_spool.hip) on MIXER-shaped input, with their wavefront semantics on the CPU: the kernel source compiled for the host through
-tests/hostshim_wave64/ into a stand-alone program (tests/host_mixer_spool_harness.cpp) that fills SpoolArgs the way the driver does for a mixer spool -- the
+tests/hostshim_wave64/ into a stand-alone program (tests/host_spool_harness.cpp, in its mixer mode) that fills SpoolArgs the way the driver does for a mixer spool -- the
 mixer count, the mixer gate's verdicts from gate bytes and has_signal flags, rows of W * B samples (1 000 .. 8 000 bytes), records whose stereo flags change from
 step to step, wave_batch = B frames -- and runs a script of steps, flushes and collects.  What the collects returned is compared byte for byte, records and
 audio and the counters, with capi.transmission_spool_reference() fed the same steps (`selected` from has_signal by the gate's rule: capi.mixer_gate_selection).
-tests/test_gpu_mixer_spool.py is what a GPU says.  The same program built with -fsanitize=address,undefined runs two of the shapes, directly."""
-import os
-import struct
-import subprocess
-
+tests/test_gpu_mixer_spool.py is what a GPU says.  The same program built under ASan + UBSan (tests/hostbed.py) runs two of the shapes, directly."""
 import numpy as np
 import pytest
 
+import hostbed
 import spool_cases as sc
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 capi = sc.capi
 NEVER, SIGNAL, ALWAYS = capi.GATE_NEVER, capi.GATE_SIGNAL, capi.GATE_ALWAYS
 FRAMES = {1000: 1000, 2000: 2000, 4000: 2000, 8000: 2000}  # row bytes -> B: (W 1, ulaw, 8000), (W 1, ulaw, 16000), (W 2, ulaw, 16000), (W 2, s16, 16000)
 
 
-def _build(out, extra):
-    cmd = [CLANG, "-x", "c++", "-std=c++17", "-O1", "-DAB_WAVE64_EMU", "-I" + os.path.join(HERE, "hostshim_wave64"), "-I" + os.path.join(REPO, "include")] + extra + \
-          ["-o", out, os.path.join(HERE, "host_mixer_spool_harness.cpp")]
-    subprocess.run(cmd, check=True)
-    return out
-
-
 @pytest.fixture(scope="module")
 def hostspool(tmp_path_factory):
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    d = tmp_path_factory.mktemp("hostmixerspool")
-    return dict(dir=str(d), exe=_build(str(d / "host_mixer_spool"), []))
+    return hostbed.program(tmp_path_factory, "host_mixer_spool", "host_spool_harness.cpp")
 
 
 def schedule(n_mix, n_steps, seed, max_rows, row_bytes, p_start=0.12, p_stop=0.35):
@@ -77,71 +61,7 @@ def schedule(n_mix, n_steps, seed, max_rows, row_bytes, p_start=0.12, p_stop=0.3
 
 
 def _script(gate, mask, steps, ops, max_rows, row_bytes, **p):
-    """the harness's script and the model's answer to it: (blob, expected results, model)"""
-    blob = struct.pack("<10i", len(gate), max_rows, row_bytes, FRAMES[row_bytes], p["pool_rows"], p["export_rows"], p["max_records"], p["min_batches"], p["idle_batches"],
-                       p["max_batches"])
-    blob += gate.tobytes() + mask.tobytes()
-    model = capi.transmission_spool_reference(mask, FRAMES[row_bytes], **p)
-    want = b""
-
-    def collect():
-        got = model.collect()
-        return struct.pack("<3i", len(got["records"]), got["n_rows"], got["n_waiting"]) + got["records"].tobytes() + got["audio"], got["n_waiting"]
-
-    for k, s in enumerate(steps):
-        blob += struct.pack("<i", 0) + s["signal"].tobytes()
-        for r in range(len(s["mixers"])):
-            blob += s["audio"][r].tobytes() + s["info"][r].tobytes()
-        model.step(len(s["selected"]), s["mixers"], s["audio"], s["info"], selected=s["selected"])
-        for op in ops.get(k, ""):
-            blob += struct.pack("<i", 1 if op == "f" else 2)
-            if op == "f":
-                model.flush()
-            else:
-                want += collect()[0]
-    blob += struct.pack("<i", 1)
-    model.flush()
-    while True:
-        blob += struct.pack("<i", 2)
-        w, waiting = collect()
-        want += w
-        if not waiting:
-            break
-    cn = model.counters()
-    want += struct.pack("<8Q", *[cn[k] for k in capi.SPOOL_COUNTER_NAMES])
-    return blob, want, model
-
-
-def _run(hostspool, blob, name, exe=None, env=None):
-    src, dst = os.path.join(hostspool["dir"], name + ".script"), os.path.join(hostspool["dir"], name + ".results")
-    open(src, "wb").write(blob)
-    r = subprocess.run([exe or hostspool["exe"], src, dst], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return open(dst, "rb").read(), r.stdout
-
-
-def _collects(blob, row_bytes):
-    """the results file taken apart: ([(records, audio bytes, n_waiting)], counters)"""
-    out, at = [], 0
-    while at + 12 <= len(blob) - 64:
-        n, rows, waiting = struct.unpack("<3i", blob[at:at + 12])
-        recs = np.frombuffer(blob[at + 12:at + 12 + 48 * n], sc.REC)
-        out.append((recs, blob[at + 12 + 48 * n:at + 12 + 48 * n + row_bytes * rows], waiting))
-        at += 12 + 48 * n + row_bytes * rows
-    return out, struct.unpack("<8Q", blob[-64:])
-
-
-def _compare(got, want, row_bytes, what):
-    """walk both results collect by collect, so that a difference is named"""
-    if got == want:
-        return
-    g, w = _collects(got, row_bytes), _collects(want, row_bytes)
-    for i, ((gr, ga, gw), (wr, wa, ww)) in enumerate(zip(g[0], w[0])):
-        assert (len(gr), len(ga), gw) == (len(wr), len(wa), ww), "%s: collect %d: counts got %r want %r" % (what, i, (len(gr), len(ga) // row_bytes, gw), (len(wr), len(wa) // row_bytes, ww))
-        bad = [j for j in range(len(wr)) if gr[j].tobytes() != wr[j].tobytes()]
-        assert not bad, "%s: collect %d: records %r: got %r %r want %r %r" % (what, i, bad[:3], sc.brief(gr[bad[:3]]), gr[bad[:3]]["reserved"].tolist(), sc.brief(wr[bad[:3]]), wr[bad[:3]]["reserved"].tolist())
-        assert ga == wa, "%s: collect %d: audio bytes" % (what, i)
-    raise AssertionError("%s: counters got %r want %r (%d collects, %d wanted)" % (what, g[1], w[1], len(g[0]), len(w[0])))
+    return sc.script(mask, steps, ops, max_rows, row_bytes, FRAMES[row_bytes], gate=gate, **p)
 
 
 SHAPES = [
@@ -164,7 +84,7 @@ def test_random_mixer_schedules_equal_the_model(hostspool, n_mix, row_bytes, poo
     blob, want, model = _script(gate, mask, steps, ops, max_rows or n_mix, row_bytes, pool_rows=pool_rows, export_rows=max_batches + 1, max_records=max_records,
                                 min_batches=3 if not big else 2, idle_batches=1, max_batches=max_batches)
     cn = model.counters()
-    collects, _ = _collects(want, row_bytes)
+    collects, _ = sc.collects(want, row_bytes)
     recs = np.concatenate([c[0] for c in collects])
     assert cn["finished_total"] > 0 and cn["rows_stored_total"] > 0 and len(recs) == cn["finished_total"]
     assert all(mask[m] for m in recs["channel"]) and (recs["reserved"][:, 0] == 0).all()
@@ -183,18 +103,15 @@ def test_random_mixer_schedules_equal_the_model(hostspool, n_mix, row_bytes, poo
         assert any(len(s["selected"]) > max_rows for s in steps)
     if big and not max_rows:  # (with a list of seven records and 40 rows its clip is among the dropped ones)
         assert recs["channel"].max() >= 1024, "no clip of the second workgroup's mixer"
-    got, _ = _run(hostspool, blob, "random_%d_%d_%d_%d" % (n_mix, row_bytes, pool_rows, max_records))
-    _compare(got, want, row_bytes, "%d mixers, rows of %d bytes, pool %d, list %d" % (n_mix, row_bytes, pool_rows, max_records))
+    got, _ = hostspool.run(blob, "random_%d_%d_%d_%d" % (n_mix, row_bytes, pool_rows, max_records))
+    sc.compare(got, want, row_bytes, "%d mixers, rows of %d bytes, pool %d, list %d" % (n_mix, row_bytes, pool_rows, max_records))
 
 
 def test_two_shapes_under_host_sanitizers(hostspool):
-    """The stand-alone program built with -fsanitize=address,undefined and run directly: the same bytes, no report."""
-    exe = _build(os.path.join(hostspool["dir"], "host_mixer_spool_san"), ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"])
-    env = dict(os.environ, ASAN_OPTIONS="detect_stack_use_after_return=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    """The stand-alone program built under ASan + UBSan and run directly: the same bytes, no report."""
     for n_mix, row_bytes, pool_rows, max_records, max_batches, max_rows, n_steps in (SHAPES[7], SHAPES[8]):
         gate, mask, steps = schedule(n_mix, 24, seed=n_mix + pool_rows, max_rows=max_rows or n_mix, row_bytes=row_bytes)
         blob, want, _ = _script(gate, mask, steps, {8: "c", 15: "fc"}, max_rows or n_mix, row_bytes, pool_rows=pool_rows, export_rows=max_batches + 1,
                                 max_records=max_records, min_batches=3, idle_batches=1, max_batches=max_batches)
-        got, log = _run(hostspool, blob, "san_%d" % n_mix, exe=exe, env=env)
-        assert "ERROR: AddressSanitizer" not in log and "runtime error" not in log, log[-4000:]
-        _compare(got, want, row_bytes, "sanitized, %d mixers" % n_mix)
+        got, _ = hostspool.sanitized().run(blob, "san_%d" % n_mix)
+        sc.compare(got, want, row_bytes, "sanitized, %d mixers" % n_mix)

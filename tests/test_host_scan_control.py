@@ -2,36 +2,23 @@
 tests/hostshim_wave64/ into a stand-alone program (tests/host_scan_control_harness.cpp) that reads sequences of batches from a file and writes what the kernels
 left; compared byte for byte with the definition in plain Python (capi.scan_control_reference) on seeded random axcindicate bytes, enable masks and holds.  It
 checks the LOGIC of the code the GPU runs -- the decision, the switch list the exchange kernel is fed, the packed record list across a pack chunk --
-tests/test_gpu_scan_control.py is what a GPU says.  The same program built with -fsanitize=address,undefined runs two of the shapes."""
+tests/test_gpu_scan_control.py is what a GPU says.  The same program built under ASan + UBSan (tests/hostbed.py) runs two of the shapes."""
 import importlib
-import os
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
+import hostbed
+
 capi = importlib.import_module("rtlsdr-airband_amd").capi
 N_BATCHES = 14
 LEAVE = -2  # the harness's "leave the list's hold as it is"
 
 
-def _build(out, extra):
-    cmd = [CLANG, "-x", "c++", "-std=c++17", "-O1", "-DAB_WAVE64_EMU", "-I" + os.path.join(HERE, "hostshim_wave64"), "-I" + os.path.join(REPO, "include")] + extra + [
-        "-o", out, os.path.join(HERE, "host_scan_control_harness.cpp")]
-    subprocess.run(cmd, check=True)
-    return out
-
-
 @pytest.fixture(scope="module")
 def hostscan(tmp_path_factory):
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    d = tmp_path_factory.mktemp("hostscan")
-    return dict(dir=str(d), exe=_build(str(d / "host_scan_control"), []))
+    return hostbed.program(tmp_path_factory, "host_scan_control", "host_scan_control_harness.cpp")
 
 
 def _case(seed, n_lists, idle=2, dwell=1, E=None, first_batch=0, p_signal=0.25, n_batches=N_BATCHES):
@@ -105,14 +92,6 @@ def _simulate(p):
     return out, seen
 
 
-def _run(hostscan, cases, name, exe=None, env=None):
-    src, dst = os.path.join(hostscan["dir"], name + ".cases"), os.path.join(hostscan["dir"], name + ".results")
-    open(src, "wb").write(_encode(cases))
-    r = subprocess.run([exe or hostscan["exe"], src, dst], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return open(dst, "rb").read(), r.stdout
-
-
 def _compare(got, cases, sims):
     at = 0
     for n, (p, (want, _)) in enumerate(zip(cases, sims)):
@@ -137,7 +116,7 @@ def test_seeded_sequences_equal_the_reference(hostscan, n_lists):
         cases += [_case(s, 1, idle=1, dwell=1) for s in range(3, 8)]
         assert {p["lists"][0][4] for p in cases} >= {1, 2}
     sims = [_simulate(p) for p in cases]
-    got, _ = _run(hostscan, cases, "n%d" % n_lists)
+    got, _ = hostscan.run(_encode(cases), "n%d" % n_lists)
     _compare(got, cases, sims)
     kinds = sum((s[1]["kinds"] for s in sims), [])
     print("%d lists: %d HOP %d ACTIVITY (%d RETAG), %d wraps, %d hops to a hold, %d frozen list-batches" % (
@@ -155,18 +134,15 @@ def test_fewer_records_than_there_are(hostscan):
     zone), states and switch lists are complete."""
     cases = [_case(11, 65, E=3), _case(12, 1025, E=1), _case(13, 1025, E=500, idle=1, p_signal=0.05)]
     sims = [_simulate(p) for p in cases]
-    got, _ = _run(hostscan, cases, "clipped")
+    got, _ = hostscan.run(_encode(cases), "clipped")
     _compare(got, cases, sims)
     assert all(s[1]["clipped"] > 0 for s in sims)
     assert max(len(r) for r in sims[2][1]["records"]) > 500  # hundreds of records kept, and the cut falls inside the pack kernel's first chunk of lists
 
 
 def test_two_shapes_under_host_sanitizers(hostscan):
-    """The stand-alone program built with -fsanitize=address,undefined: the same bytes, no report."""
-    exe = _build(os.path.join(hostscan["dir"], "host_scan_control_san"), ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"])
+    """The stand-alone program built under ASan + UBSan: the same bytes, no report."""
     cases = [_case(21, 65, E=4), _case(22, 1025, n_batches=6)]
     sims = [_simulate(p) for p in cases]
-    env = dict(os.environ, ASAN_OPTIONS="detect_stack_use_after_return=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    got, log = _run(hostscan, cases, "san", exe=exe, env=env)
-    assert "ERROR: AddressSanitizer" not in log and "runtime error" not in log, log[-4000:]
+    got, _ = hostscan.sanitized().run(_encode(cases), "san")
     _compare(got, cases, sims)

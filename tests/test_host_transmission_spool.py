@@ -1,107 +1,28 @@
 """The transmission spool's kernels (csrc/tx_spool.hip) with their wavefront semantics on the CPU: the kernel source compiled for the host through
-tests/hostshim_wave64/ (lanes as fibers; ballots, shuffles and barriers are rendezvous points) into a stand-alone program (tests/host_spool_harness.cpp) that
+tests/hostshim_wave64/ (lanes as fibers; ballots, shuffles and barriers are rendezvous points) into a stand-alone program (tests/host_spool_harness.cpp, in its channel mode) that
 reads a script of steps, flushes and collects from a file and writes what the collects returned; compared byte for byte, records and audio and the counters,
 with the definition in plain Python (capi.transmission_spool_reference) on random selection schedules.  It checks the LOGIC of the code the GPU runs -- the
 verdicts, the ranks across wavefronts and workgroups, the chains and the free stack, the ring of finished records, the prefix of the collect, the clamps --
-tests/test_gpu_transmission_spool.py is what a GPU says.  The same program built with -fsanitize=address,undefined runs two of the shapes."""
-import os
+tests/test_gpu_transmission_spool.py is what a GPU says.  The same program built under ASan + UBSan (tests/hostbed.py) runs two of the shapes."""
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import hostbed
 import spool_cases as sc
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-REPO = os.path.dirname(HERE)
-CLANG = "/opt/rocm/lib/llvm/bin/clang++"
 capi = sc.capi
 ROW_BYTES, B = 16, 16
 
 
-def _build(out, extra):
-    cmd = [CLANG, "-x", "c++", "-std=c++17", "-O1", "-DAB_WAVE64_EMU", "-I" + os.path.join(HERE, "hostshim_wave64"), "-I" + os.path.join(REPO, "include")] + extra + \
-          ["-o", out, os.path.join(HERE, "host_spool_harness.cpp")]
-    subprocess.run(cmd, check=True)
-    return out
-
-
 @pytest.fixture(scope="module")
 def hostspool(tmp_path_factory):
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    d = tmp_path_factory.mktemp("hostspool")
-    return dict(dir=str(d), exe=_build(str(d / "host_spool"), []))
+    return hostbed.program(tmp_path_factory, "host_spool", "host_spool_harness.cpp")
 
 
 def _script(mask, steps, ops, max_rows, row_bytes, **p):
-    """the harness's script and the model's answer to it: (blob, expected results)"""
-    n_ch = len(mask)
-    blob = struct.pack("<10i", n_ch, max_rows, row_bytes, B, p["pool_rows"], p["export_rows"], p["max_records"], p["min_batches"], p["idle_batches"], p["max_batches"])
-    blob += np.asarray(mask, np.uint8).tobytes()
-    model = capi.transmission_spool_reference(mask, B, **p)
-    want = b""
-
-    def collect():
-        got = model.collect()
-        return struct.pack("<3i", len(got["records"]), got["n_rows"], got["n_waiting"]) + got["records"].tobytes() + got["audio"], got["n_waiting"]
-
-    for k, s in enumerate(steps):
-        sel = np.zeros(n_ch, np.uint8)
-        sel[s["selected"]] = 1
-        blob += struct.pack("<i", 0) + sel.tobytes()
-        for r in range(len(s["channels"])):
-            blob += s["audio"][r].tobytes() + s["info"][r].tobytes()
-        model.step(len(s["selected"]), s["channels"], s["audio"], s["info"], selected=s["selected"])
-        for op in ops.get(k, ""):
-            blob += struct.pack("<i", 1 if op == "f" else 2)
-            if op == "f":
-                model.flush()
-            else:
-                want += collect()[0]
-    blob += struct.pack("<i", 1)
-    model.flush()
-    while True:
-        blob += struct.pack("<i", 2)
-        w, waiting = collect()
-        want += w
-        if not waiting:
-            break
-    cn = model.counters()
-    want += struct.pack("<8Q", *[cn[k] for k in capi.SPOOL_COUNTER_NAMES])
-    return blob, want, model
-
-
-def _run(hostspool, blob, name, exe=None, env=None):
-    src, dst = os.path.join(hostspool["dir"], name + ".script"), os.path.join(hostspool["dir"], name + ".results")
-    open(src, "wb").write(blob)
-    r = subprocess.run([exe or hostspool["exe"], src, dst], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=env)
-    assert r.returncode == 0, r.stdout[-4000:]
-    return open(dst, "rb").read(), r.stdout
-
-
-def _compare(got, want, row_bytes, what):
-    """walk both results collect by collect, so that a difference is named"""
-    if got == want:
-        return
-    at = 0
-    n_collect = 0
-    while at + 12 <= len(want) - 64:
-        n, rows, waiting = struct.unpack("<3i", want[at:at + 12])
-        size = 12 + 48 * n + row_bytes * rows
-        g, w = got[at:at + size], want[at:at + size]
-        if g != w:
-            gh = struct.unpack("<3i", g[:12]) if len(g) >= 12 else None
-            detail = "counts got %r want %r" % (gh, (n, rows, waiting))
-            if gh == (n, rows, waiting):
-                gr, wr = np.frombuffer(g[12:12 + 48 * n], sc.REC), np.frombuffer(w[12:12 + 48 * n], sc.REC)
-                bad = [i for i in range(n) if gr[i].tobytes() != wr[i].tobytes()]
-                detail = "records %r: got %r want %r" % (bad[:3], sc.brief(gr[bad[:3]]), sc.brief(wr[bad[:3]])) if bad else "audio bytes"
-            raise AssertionError("%s: collect %d differs: %s" % (what, n_collect, detail))
-        at += size
-        n_collect += 1
-    raise AssertionError("%s: counters got %r want %r" % (what, struct.unpack("<8Q", got[-64:]) if len(got) >= 64 else None, struct.unpack("<8Q", want[-64:])))
+    return sc.script(mask, steps, ops, max_rows, row_bytes, B, **p)
 
 
 SHAPES = [
@@ -128,8 +49,8 @@ def test_random_schedules_equal_the_model(hostspool, n_ch, pool_rows, max_record
         assert cn["rows_lost_total"] > 0
     if max_records == 1 and n_ch > 1:
         assert cn["dropped_transmissions"] > 0
-    got, _ = _run(hostspool, blob, "random_%d_%d_%d_%d" % (n_ch, pool_rows, max_records, max_batches))
-    _compare(got, want, row_bytes, "%d channels, pool %d, list %d" % (n_ch, pool_rows, max_records))
+    got, _ = hostspool.run(blob, "random_%d_%d_%d_%d" % (n_ch, pool_rows, max_records, max_batches))
+    sc.compare(got, want, row_bytes, "%d channels, pool %d, list %d" % (n_ch, pool_rows, max_records))
 
 
 def test_every_reason_and_more_than_one_workgroup(hostspool):
@@ -144,18 +65,15 @@ def test_every_reason_and_more_than_one_workgroup(hostspool):
         reasons |= set(np.frombuffer(want[at + 12:at + 12 + 48 * n], sc.REC)["reason"].tolist())
         at += 12 + 48 * n + ROW_BYTES * rows
     assert reasons == {capi.SPOOL_IDLE, capi.SPOOL_MAX, capi.SPOOL_FLUSH}
-    got, _ = _run(hostspool, blob, "blocks")
-    _compare(got, want, ROW_BYTES, "2100 channels")
+    got, _ = hostspool.run(blob, "blocks")
+    sc.compare(got, want, ROW_BYTES, "2100 channels")
 
 
 def test_two_shapes_under_host_sanitizers(hostspool):
-    """The stand-alone program built with -fsanitize=address,undefined: the same bytes, no report."""
-    exe = _build(os.path.join(hostspool["dir"], "host_spool_san"), ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"])
-    env = dict(os.environ, ASAN_OPTIONS="detect_stack_use_after_return=0:halt_on_error=1", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
+    """The stand-alone program built under ASan + UBSan: the same bytes, no report."""
     for n_ch, pool_rows, max_records, max_batches, max_rows, row_bytes in (SHAPES[7], SHAPES[12]):
         mask, steps = sc.schedule(n_ch, 24, seed=n_ch + pool_rows, max_rows=max_rows, row_bytes=row_bytes, wave_batch=B)
         blob, want, _ = _script(mask, steps, {8: "c", 15: "fc"}, max_rows or n_ch, row_bytes, pool_rows=pool_rows, export_rows=max_batches + 1, max_records=max_records,
                                 min_batches=3, idle_batches=1, max_batches=max_batches)
-        got, log = _run(hostspool, blob, "san_%d" % n_ch, exe=exe, env=env)
-        assert "ERROR: AddressSanitizer" not in log and "runtime error" not in log, log[-4000:]
-        _compare(got, want, row_bytes, "sanitized, %d channels" % n_ch)
+        got, _ = hostspool.sanitized().run(blob, "san_%d" % n_ch)
+        sc.compare(got, want, row_bytes, "sanitized, %d channels" % n_ch)

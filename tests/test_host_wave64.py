@@ -8,26 +8,20 @@ Test infrastructure: it tests the logic of the code the GPU runs; the GPU parity
 """
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import helpers
+import hostbed
 import pyoracle
-from test_host_demod import CLANG, CSRC, HERE, REPO, HostDemod, _bursty, capi, pkg, sg
+from test_host_demod import HostDemod, _bursty, capi, pkg, sg
 
 
 @pytest.fixture(scope="module")
 def wave64(tmp_path_factory):
-    if not os.path.exists(CLANG):
-        pytest.skip("no host clang++ in this image")
-    out = str(tmp_path_factory.mktemp("hostwave64") / "libhostwave64.so")
-    cmd = [CLANG, "-x", "c++", "-std=c++17", "-O2", "-ffp-contract=off", "-fno-fast-math", "-fPIC", "-shared", "-DAB_WAVE64_EMU",
-           "-I" + os.path.join(HERE, "hostshim_wave64"), "-I" + os.path.join(REPO, "include")] + os.environ.get("AIRBAND_HOST_DEFINES", "").split() + [
-           "-o", out, os.path.join(HERE, "host_demod_harness.cpp"), os.path.join(CSRC, "params.cpp")]
-    subprocess.run(cmd, check=True)
-    lib = C.CDLL(out)
+    lib = C.CDLL(hostbed.build(["host_demod_harness.cpp", hostbed.PARAMS], tmp_path_factory.mktemp("hostwave64") / "libhostwave64.so", shared=True,
+                               extra=["-O2", "-ffp-contract=off", "-fno-fast-math"] + os.environ.get("AIRBAND_HOST_DEFINES", "").split()))
     vp = C.c_void_p
     lib.hostdemod_create.argtypes = [C.POINTER(capi.Config), C.c_int, C.POINTER(vp)]
     lib.hostdemod_destroy.argtypes = [vp]

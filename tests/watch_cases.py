@@ -1,4 +1,4 @@
-"""Shared by the band watch's tests: sequences of batches as the host harness (tests/host_watch_harness.cpp) reads them, what capi.band_watch_reference() makes
+"""Shared by the band watch's tests: sequences of batches as the host harness (tests/host_watch_harness.cpp, run through tests/hostbed.py) reads them, what capi.band_watch_reference() makes
 of them as the bytes the harness writes, and the constructed sequences with the properties the definition promises for each (asserted on the reference's own
 output, so that a byte-for-byte comparison against it proves them of the kernel)."""
 import importlib
