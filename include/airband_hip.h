@@ -571,6 +571,98 @@ int airband_hip_device_active_encoded(airband_hip_handle* h, void** d_audio, air
  * AIRBAND_HIP_EINVAL for NULL rows, n_rows < 0 (or too many to index), encoding AIRBAND_AUDIO_F32 or unknown; n_rows == 0 is AIRBAND_HIP_OK. */
 int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const float* rows, int64_t n_rows, void* audio, airband_hip_audio_row* info);
 
+/* ---- RTP packet stream ------------------------------------------------------------------------------------------------------------------
+ * airband_hip_collect_active_encoded() hands the host rows of wave_batch samples -- 1 000 or 2 000, which is 6.25 RTP frames of 20 ms.  The reference's live
+ * sink (src/udp_stream.cpp:68-84) sends one float32 datagram per batch: above any MTU, without sequence number, timestamp or stream identity.  A host that
+ * feeds RTP receivers therefore keeps a residue, a sequence number and a talkspurt flag per channel and cuts, copies and heads up every packet itself.  A gated
+ * handle with an encoding and an RTP stream does that on the GPU, once per batch behind the encoder: the listed rows become complete RTP packets (RFC 3550
+ * header, RFC 3551 payload) of a fixed frame length, the remainder is carried per channel from batch to batch, and the host copies one count, one 16-byte record
+ * per packet and one contiguous block of packet slots, ready for sendmmsg().
+ * The definition (normative).  Integers only: two implementations of this text agree in every byte.
+ * Parameters.  sources[total_channels] (below; a streamed channel must not have gate AIRBAND_GATE_NEVER); frame_samples = F, a multiple of 4 with
+ *   40 <= F <= wave_batch and 12 + F * sample_bytes <= 1472 (one UDP payload under a 1 500-byte MTU; sample_bytes is 1 for G.711 and 2 for S16); max_packets >= 1.
+ *   B = wave_batch.  B and F are multiples of 4, so every carry length is one too: all moves are whole dwords.
+ * State per streamed channel, as it starts when the stream is set: seq = seq0; carry_n = 0; carry[F - 4] encoded samples; talking = 0; packets = 0 and octets = 0,
+ *   both uint32 and wrapping.  The handle counts the steps since the stream was set: k = 0, 1, ...
+ * Step k, once per batch in every schedule, behind that batch's encoder.  Channels are visited in ascending order.  "Listed": the channel is among the first
+ *   max_rows channels of the gate's list for this batch; its encoded row is airband_hip_collect_active_encoded()'s.
+ *   Listed:  S = the carry_n carried samples followed by the row's B samples; ts_start = ts0 + k * B - carry_n (mod 2^32); p = len(S) / F packets are emitted,
+ *            packet j carries S[jF .. jF + F) with timestamp ts_start + jF; packet 0 has the marker bit set iff talking was 0; the len(S) mod F samples left
+ *            over are the new carry; talking = 1.
+ *   Not listed and carry_n > 0 (selected by the rule but dropped past max_rows; dongle switched off; gate closed):  ONE flush packet with the carry_n samples,
+ *            not padded, timestamp ts0 + k * B - carry_n, marker 0, record flag FLUSH; carry_n = 0 and talking = 0.
+ *   Not listed and carry_n == 0:  talking = 0; nothing is emitted.
+ *   Every emitted packet takes the channel's seq, and then seq = seq + 1 (mod 2^16), packets += 1, octets += its payload bytes -- packets dropped for capacity
+ *   too, so that a receiver sees the loss.  packets and octets are what an RTCP sender report needs.
+ * Order and capacity.  The batch's packets are ranked by (channel ascending, time ascending); the packet of rank i is written iff i < max_packets; the count is
+ *   the total and may exceed max_packets.
+ * Packet bytes.  Slot i starts at i * slot_bytes, slot_bytes = 16 * ceil((12 + F * sample_bytes) / 16) (airband_hip_rtp_slot_bytes).  Byte 0 = 0x80; byte 1 =
+ *   marker << 7 | payload_type; bytes 2-3 seq, 4-7 timestamp, 8-11 ssrc, all big-endian; the payload from byte 12: for G.711 the encoder's bytes, for S16 each
+ *   sample BIG-endian (L16 is network order: the encoder's little-endian int16 byte-swapped).  Only the first `length` bytes of a slot are defined.
+ * Counters: steps; packets and octets (every emitted packet, the dropped ones included); dropped_packets (rank >= max_packets); lost_rows (streamed channels
+ *   selected by the rule but past max_rows), all summed over the steps.
+ * Out of scope: mixer rows (the kernels are written over a mask, its counts and encoded rows, so they can follow); trimming by the row record's first / end;
+ *   comfort noise; RTCP itself; a flush call at shutdown; sockets.
+ * A handle without an RTP stream allocates nothing for this, launches nothing and returns the same bits. */
+typedef struct airband_hip_rtp_source {
+    uint32_t ssrc;
+    uint32_t ts0;
+    uint16_t seq0;
+    uint8_t  payload_type;  /* 0 .. 127 */
+    uint8_t  stream;        /* 0: not streamed */
+} airband_hip_rtp_source;   /* 12 bytes */
+
+#define AIRBAND_RTP_MARKER 1u /* airband_hip_rtp_packet.flags */
+#define AIRBAND_RTP_FLUSH 2u
+
+typedef struct airband_hip_rtp_packet {
+    int32_t  channel;
+    uint32_t timestamp;
+    uint16_t seq;
+    uint16_t length;     /* header + payload bytes */
+    uint16_t flags;      /* AIRBAND_RTP_MARKER | AIRBAND_RTP_FLUSH */
+    uint16_t reserved;   /* 0 */
+} airband_hip_rtp_packet; /* 16 bytes */
+
+typedef struct airband_hip_rtp_state {
+    uint32_t packets;
+    uint32_t octets;
+    uint16_t seq;        /* the next one */
+    uint16_t carry;      /* carry_n */
+    uint32_t flags;      /* bit 0: talking */
+} airband_hip_rtp_state; /* 16 bytes */
+
+typedef struct airband_hip_rtp_counters {
+    int64_t steps, packets, dropped_packets, octets, lost_rows;
+} airband_hip_rtp_counters;
+
+/* slot_bytes for an AIRBAND_AUDIO_* encoding and a frame length.  A pure function, needs no GPU.  AIRBAND_HIP_EINVAL for AIRBAND_AUDIO_F32 or an unknown
+ * encoding, AIRBAND_HIP_EBADSIZE for a frame_samples that is no multiple of 4, below 40, or whose packet exceeds 1472 bytes. */
+int airband_hip_rtp_slot_bytes(int32_t encoding, int32_t frame_samples);
+
+/* After airband_hip_set_output_encoding() and before the first batch; calling it again before then replaces the stream, sources == NULL removes it, and
+ * airband_hip_set_output_encoding() or airband_hip_set_output_gate() called again drops it.  Validated before the device is touched: AIRBAND_HIP_EINVAL for a
+ * NULL handle, a handle without an encoding, a payload_type above 127, a streamed channel whose gate is AIRBAND_GATE_NEVER, max_packets < 1 (or too many to
+ * index), a batch already enqueued; AIRBAND_HIP_EBADSIZE for frame_samples outside the bounds above.  AIRBAND_HIP_ENOMEM when the buffers cannot be had -- the
+ * handle then runs on as it was. */
+int airband_hip_set_rtp_stream(airband_hip_handle* h, const airband_hip_rtp_source* sources, int32_t frame_samples, int64_t max_packets);
+
+/* The batch's packets.  The count comes first (*n_packets, may exceed max_packets); then exactly n = min(count, max_packets) records, n * slot_bytes bytes of
+ * packets and axcindicate of every channel are copied; nothing past them is written.  Any pointer may be NULL.  Marks the batch as collected and
+ * AIRBAND_HIP_EAGAIN exactly as airband_hip_collect_active_encoded().  AIRBAND_HIP_EINVAL on a handle without an RTP stream. */
+int airband_hip_collect_rtp_packets(airband_hip_handle* h, int64_t* n_packets, airband_hip_rtp_packet* records, void* packets, char* axc_all);
+
+/* The sender state of channels [first_channel, first_channel + n_channels) behind everything enqueued so far (synchronous; an unstreamed channel's record is
+ * zeros).  AIRBAND_HIP_EINVAL on a handle without an RTP stream, for NULL `state` or a range outside the handle's channels. */
+int airband_hip_collect_rtp_state(airband_hip_handle* h, int64_t first_channel, int64_t n_channels, airband_hip_rtp_state* state);
+
+/* The counters as they stand behind everything enqueued so far (synchronous).  AIRBAND_HIP_EINVAL on a handle without an RTP stream or for NULL `out`. */
+int airband_hip_rtp_counters_get(airband_hip_handle* h, airband_hip_rtp_counters* out);
+
+/* Device-side views (valid until the next process call): d_n_packets [1], d_records [max_packets], d_packets [max_packets][slot_bytes], d_state
+ * [total_channels].  Any out-pointer may be NULL. */
+int airband_hip_device_rtp_stream(airband_hip_handle* h, int32_t** d_n_packets, airband_hip_rtp_packet** d_records, void** d_packets, airband_hip_rtp_state** d_state);
+
 /* ---- gated mixer collect -----------------------------------------------------------------------------------------------------------------
  * A mixer's output channel is a channel like any other to the reference: mix_waveforms() sets its axcindicate to SIGNAL iff an input had signal
  * (src/mixer.cpp:193-209), process_outputs() applies the same file / UDP / pulse skip rule to it (src/output.cpp:501,531,539,552), and a stereo mixer goes out

@@ -38,6 +38,7 @@ EXPORTS = [
     "airband_hip_set_output_encoding", "airband_hip_collect_active_encoded", "airband_hip_device_active_encoded", "airband_hip_encode_audio",
     "airband_hip_set_mixer_gate", "airband_hip_mixer_gate_step", "airband_hip_collect_active_mixers", "airband_hip_device_active_mixers", "airband_hip_encode_mixer_audio",
     "airband_hip_set_transmission_spool", "airband_hip_collect_transmissions", "airband_hip_spool_flush", "airband_hip_spool_counters_get", "airband_hip_device_transmission_spool",
+    "airband_hip_set_rtp_stream", "airband_hip_collect_rtp_packets", "airband_hip_collect_rtp_state", "airband_hip_rtp_counters_get", "airband_hip_device_rtp_stream", "airband_hip_rtp_slot_bytes",
     "airband_hip_set_mixer_spool", "airband_hip_collect_mixer_transmissions", "airband_hip_mixer_spool_flush", "airband_hip_mixer_spool_counters_get", "airband_hip_device_mixer_spool",
     "airband_hip_set_band_scope", "airband_hip_collect_band_scope", "airband_hip_device_band_scope",
     "airband_hip_set_band_survey", "airband_hip_collect_band_survey", "airband_hip_device_band_survey",
@@ -115,7 +116,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
-    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()) + list(capi.TABLES_PROTOTYPES.items()) + list(capi.MIXER_GATE_PROTOTYPES.items()) + list(capi.MIXER_SPOOL_PROTOTYPES.items()):
+    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()) + list(capi.TABLES_PROTOTYPES.items()) + list(capi.MIXER_GATE_PROTOTYPES.items()) + list(capi.MIXER_SPOOL_PROTOTYPES.items()) + list(capi.RTP_STREAM_PROTOTYPES.items()):
         if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
             getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
@@ -361,7 +362,9 @@ class AirbandHip:
         rows = self.total_channels if max_rows is None else int(max_rows)
         self._check(self.L.airband_hip_set_output_gate(self.h, gate.ctypes.data, rows))
         self.gate_rows = rows
+        self.gate_bytes = gate.copy()  # set_rtp_stream()'s default sources: every channel whose gate is not NEVER
         self.audio_encoding = capi.AUDIO_F32  # a new gate drops the encoding
+        self.rtp = None  # ... and the RTP stream with it
 
     def collect_active(self, *, iq: bool = False) -> dict:
         """The batch collect() would return, packed to the channels the gate selected (airband_hip_collect_active): n_active (may exceed the capacity: only
@@ -392,6 +395,7 @@ class AirbandHip:
         enc = capi.AUDIO_F32 if encoding is None else capi.audio_encoding_value(encoding)
         self._check(self.L.airband_hip_set_output_encoding(self.h, enc))
         self.audio_encoding = enc
+        self.rtp = None  # a new encoding drops the RTP stream
 
     def _audio_dtype(self, enc):
         return np.dtype("<i2") if enc == capi.AUDIO_S16 else np.dtype(np.uint8)
@@ -467,6 +471,67 @@ class AirbandHip:
         ptrs = [C.c_void_p() for _ in range(3)]
         self._check(self.L.airband_hip_device_transmission_spool(self.h, *[C.byref(p) for p in ptrs]))
         return {k: (p.value or 0) for k, p in zip(["audio", "records", "n_export"], ptrs)}
+
+    # ---- RTP packet stream (include/airband_hip.h) ---------------------------------------------------------------------------------------
+    def set_rtp_stream(self, frame_samples=None, sources=None, max_packets=None, *, remove: bool = False):
+        """RTP packet stream (airband_hip_set_rtp_stream): the GPU frames the gate's encoded rows as RTP packets of frame_samples, carrying the remainder per
+        channel.  frame_samples: default wave_rate // 50 (20 ms); sources: [total_channels] of capi.RTP_SOURCE_DTYPE, default every channel whose gate is not
+        NEVER with ssrc = its index, ts0 = 0, seq0 = 0 and payload type 0 / 8 / 96 for ulaw / alaw / s16; max_packets: default what a step can emit at most.
+        After set_output_encoding(), before the first batch; remove=True removes it."""
+        if remove:
+            self._check(self.L.airband_hip_set_rtp_stream(self.h, None, 0, 0))
+            self.rtp = None
+            return
+        enc = getattr(self, "audio_encoding", capi.AUDIO_F32)
+        F = int(self.geometry.wave_rate) // 50 if frame_samples is None else int(frame_samples)
+        if sources is None:
+            src = np.zeros(self.total_channels, capi.RTP_SOURCE_DTYPE)
+            src["ssrc"] = np.arange(self.total_channels)
+            src["payload_type"] = capi.RTP_PAYLOAD_TYPES.get(enc, 0)
+            src["stream"] = getattr(self, "gate_bytes", np.zeros(self.total_channels, np.uint8)) != capi.GATE_NEVER
+        else:
+            src = np.ascontiguousarray(sources, capi.RTP_SOURCE_DTYPE)
+            if src.shape != (self.total_channels,):
+                raise ValueError("sources needs one record per channel (%d), got shape %r" % (self.total_channels, src.shape))
+        if max_packets is None:
+            max_packets = max(1, int(np.count_nonzero(src["stream"])) * ((max(F, 4) - 4 + self.B) // max(F, 1)))
+        self._check(self.L.airband_hip_set_rtp_stream(self.h, src.ctypes.data, F, int(max_packets)))
+        self.rtp = dict(frame_samples=F, max_packets=int(max_packets), slot_bytes=self._check(self.L.airband_hip_rtp_slot_bytes(enc, F)), sources=src)
+
+    def _rtp(self):
+        return getattr(self, "rtp", None) or dict(frame_samples=0, max_packets=1, slot_bytes=16, sources=None)
+
+    def collect_rtp_packets(self) -> dict:
+        """The batch's RTP packets (airband_hip_collect_rtp_packets): n_packets (may exceed max_packets: only the first max_packets were written then), records
+        [n] of capi.RTP_PACKET_DTYPE, packets [n][slot_bytes] uint8 -- packet i is packets[i, :records[i]["length"]] -- and axcindicate of every channel."""
+        r = self._rtp()
+        n = C.c_int64(0)
+        records = np.empty((r["max_packets"],), capi.RTP_PACKET_DTYPE)
+        packets = np.empty((r["max_packets"], r["slot_bytes"]), np.uint8)
+        axc = np.empty((self.total_channels,), np.uint8)
+        self._check(self.L.airband_hip_collect_rtp_packets(self.h, C.byref(n), records.ctypes.data, packets.ctypes.data, axc.ctypes.data))
+        kept = min(int(n.value), r["max_packets"])
+        return dict(n_packets=int(n.value), records=records[:kept], packets=packets[:kept], axcindicate=axc)
+
+    def collect_rtp_state(self, first_channel: int = 0, n_channels: Optional[int] = None):
+        """The channels' sender state (airband_hip_collect_rtp_state): [n_channels] of capi.RTP_STATE_DTYPE, default every channel."""
+        n = self.total_channels - int(first_channel) if n_channels is None else int(n_channels)
+        st = np.empty((max(n, 0),), capi.RTP_STATE_DTYPE)
+        self._check(self.L.airband_hip_collect_rtp_state(self.h, int(first_channel), n, st.ctypes.data))
+        return st
+
+    def rtp_counters(self) -> dict:
+        """airband_hip_rtp_counters_get as a dict (capi.RTP_COUNTER_NAMES)."""
+        out = capi.RtpCounters()
+        self._check(self.L.airband_hip_rtp_counters_get(self.h, C.byref(out)))
+        return {k: int(getattr(out, k)) for k in capi.RTP_COUNTER_NAMES}
+
+    def device_rtp_stream(self) -> dict:
+        """Device pointers of the batch's packets (valid until the next process call): n_packets [1] int32, records [max_packets] of 16 bytes, packets
+        [max_packets][slot_bytes], state [total_channels] of 16 bytes."""
+        ptrs = [C.c_void_p() for _ in range(4)]
+        self._check(self.L.airband_hip_device_rtp_stream(self.h, *[C.byref(p) for p in ptrs]))
+        return {k: (p.value or 0) for k, p in zip(["n_packets", "records", "packets", "state"], ptrs)}
 
     def set_band_scope(self, mask=None, windows: int = 8, mean: bool = True, peak: bool = False):
         """Band scope (airband_hip_set_band_scope): per batch and selected dongle, the power spectrum of the whole band over `windows` of the batch's FFT windows.

@@ -43,6 +43,7 @@ HIP_SOURCES = {
     "audio_pack.hip": ["-O3", "-ffp-contract=off"],  # encoded audio collect: one float multiplication per sample, then integers (int16 / G.711) and a row record
     "mixer_gate.hip": ["-O3", "-ffp-contract=off"],  # gated mixer collect: the gate's integer passes over the mixers, then the encoder's arithmetic on frames of left / right
     "tx_spool.hip": ["-O3"],  # transmission spool: integer passes over per-channel records, a row pool and row copies
+    "rtp_stream.hip": ["-O3"],  # RTP packet stream: integer passes over per-channel sender state, prefix sums, and dword copies of rows into packet slots
     "band_scope.hip": ["-O3"],  # band scope: a wavefront FFT of a few windows per batch and dongle, mean and peak power per bin
     "band_survey.hip": ["-O3"],  # band survey: rank select, threshold and peak list of every scope row, integer passes over LDS
     "band_watch.hip": ["-O3"],  # band watch: carrier tracks per scope row advanced by the survey's list, the fleet's events packed in row order; integers only

@@ -752,6 +752,155 @@ class transmission_spool_reference:
                     finished_total=self.finished_total, dropped_transmissions=self.dropped, rows_stored_total=self.rows_stored, rows_lost_total=self.rows_lost)
 
 
+# the RTP packet stream's (same header)
+RTP_MARKER, RTP_FLUSH = 1, 2
+RTP_PAYLOAD_TYPES = {AUDIO_ULAW: 0, AUDIO_ALAW: 8, AUDIO_S16: 96}  # PCMU, PCMA, and the first dynamic type for L16 at 8 or 16 kHz
+
+
+class RtpSource(C.Structure):
+    _fields_ = [("ssrc", C.c_uint32), ("ts0", C.c_uint32), ("seq0", C.c_uint16), ("payload_type", C.c_uint8), ("stream", C.c_uint8)]
+
+
+class RtpPacket(C.Structure):
+    _fields_ = [("channel", C.c_int32), ("timestamp", C.c_uint32), ("seq", C.c_uint16), ("length", C.c_uint16), ("flags", C.c_uint16), ("reserved", C.c_uint16)]
+
+
+class RtpState(C.Structure):
+    _fields_ = [("packets", C.c_uint32), ("octets", C.c_uint32), ("seq", C.c_uint16), ("carry", C.c_uint16), ("flags", C.c_uint32)]
+
+
+class RtpCounters(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("steps", "packets", "dropped_packets", "octets", "lost_rows")]
+
+
+RTP_STREAM_PROTOTYPES = {
+    "airband_hip_rtp_slot_bytes": [_i32, _i32],
+    "airband_hip_set_rtp_stream": [_vp, _vp, _i32, _i64],
+    "airband_hip_collect_rtp_packets": [_vp, C.POINTER(_i64), _vp, _vp, _vp],
+    "airband_hip_collect_rtp_state": [_vp, _i64, _i64, _vp],
+    "airband_hip_rtp_counters_get": [_vp, C.POINTER(RtpCounters)],
+    "airband_hip_device_rtp_stream": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
+}
+# numpy views of airband_hip_rtp_source, _rtp_packet and _rtp_state
+RTP_SOURCE_DTYPE = [("ssrc", "<u4"), ("ts0", "<u4"), ("seq0", "<u2"), ("payload_type", "u1"), ("stream", "u1")]
+RTP_PACKET_DTYPE = [("channel", "<i4"), ("timestamp", "<u4"), ("seq", "<u2"), ("length", "<u2"), ("flags", "<u2"), ("reserved", "<u2")]
+RTP_STATE_DTYPE = [("packets", "<u4"), ("octets", "<u4"), ("seq", "<u2"), ("carry", "<u2"), ("flags", "<u4")]
+RTP_COUNTER_NAMES = tuple(f[0] for f in RtpCounters._fields_)
+
+
+def rtp_slot_bytes(encoding, frame_samples) -> int:
+    """slot_bytes of the header's definition: 16 * ceil((12 + F * sample_bytes) / 16); ValueError for what airband_hip_rtp_slot_bytes() refuses."""
+    enc = audio_encoding_value(encoding)
+    if enc not in (AUDIO_S16, AUDIO_ULAW, AUDIO_ALAW):
+        raise ValueError("no encoding")
+    sb, F = (2 if enc == AUDIO_S16 else 1), int(frame_samples)
+    if F % 4 or F < 40 or 12 + F * sb > 1472:
+        raise ValueError("frame_samples the handle would refuse")
+    return (12 + F * sb + 15) // 16 * 16
+
+
+class rtp_stream_reference:
+    """The RTP packet stream's definition (include/airband_hip.h, "RTP packet stream") in plain Python / numpy: a stateful object that is fed, per step, what
+    collect_active_encoded() of the same gate and encoding returns.
+
+    sources: [n_channels] of RTP_SOURCE_DTYPE; encoding: "s16" / "ulaw" / "alaw" or an AUDIO_* value; wave_batch; frame_samples; max_packets.
+    step(channels, audio, dropped=()): the gate's list (the first max_rows selected channels, ascending), their encoded rows [n][wave_batch] (int16 for "s16",
+    else uint8) and the channels the rule selected but the list dropped past max_rows.  Returns (count, records, slots): the total (may exceed max_packets),
+    records [min(count, max_packets)] of RTP_PACKET_DTYPE and slots [that many][slot_bytes] uint8, zero behind a packet's `length` (those bytes are undefined on
+    the handle).  state() -> [n_channels] of RTP_STATE_DTYPE; counters() -> dict of RTP_COUNTER_NAMES."""
+
+    def __init__(self, sources, encoding, wave_batch, frame_samples, max_packets):
+        import numpy as np
+
+        self.enc = audio_encoding_value(encoding)
+        self.B, self.F, self.max_packets = int(wave_batch), int(frame_samples), int(max_packets)
+        self.slot_bytes = rtp_slot_bytes(self.enc, self.F)
+        if self.B % 4 or self.F > self.B or self.max_packets < 1:
+            raise ValueError("parameters the handle would refuse")
+        self.sb = 2 if self.enc == AUDIO_S16 else 1
+        self.src = np.array(sources, RTP_SOURCE_DTYPE).reshape(-1).copy()
+        if (self.src["payload_type"] > 127).any():
+            raise ValueError("payload_type above 127")
+        n = len(self.src)
+        self.seq = [int(s) for s in self.src["seq0"]]
+        self.carry = [b""] * n  # payload bytes as they go on the wire
+        self.talking = [False] * n
+        self.packets, self.octets = [0] * n, [0] * n
+        self.k = 0
+        self.totals = dict(packets=0, dropped_packets=0, octets=0, lost_rows=0)
+
+    def _wire(self, row):
+        import numpy as np
+
+        row = np.ascontiguousarray(row)
+        if self.enc == AUDIO_S16:
+            return row.astype("<i2").astype(">i2").tobytes()  # L16 is network order
+        return row.astype(np.uint8).tobytes()
+
+    def step(self, channels, audio, dropped=()):
+        import numpy as np
+
+        channels = [int(c) for c in channels]
+        if channels != sorted(set(channels)):
+            raise ValueError("the list is not ascending")
+        row_of = {c: r for r, c in enumerate(channels)}
+        dropped = set(int(c) for c in dropped)
+        B, F, sb = self.B, self.F, self.sb
+        out = []  # (channel, timestamp, seq, flags, header + payload)
+        for c in range(len(self.src)):
+            s = self.src[c]
+            if not s["stream"]:
+                continue
+            if c in dropped:
+                self.totals["lost_rows"] += 1
+            cn = len(self.carry[c]) // sb
+            ts_start = (int(s["ts0"]) + self.k * B - cn) & 0xFFFFFFFF
+            emitted = []  # (timestamp, flags, payload)
+            if c in row_of:
+                S = self.carry[c] + self._wire(audio[row_of[c]])
+                assert len(S) == (cn + B) * sb
+                p = (cn + B) // F
+                for j in range(p):
+                    emitted.append(((ts_start + j * F) & 0xFFFFFFFF, RTP_MARKER if j == 0 and not self.talking[c] else 0, S[j * F * sb:(j + 1) * F * sb]))
+                self.carry[c] = S[p * F * sb:]
+                self.talking[c] = True
+            else:
+                if cn > 0:
+                    emitted.append((ts_start, RTP_FLUSH, self.carry[c]))
+                    self.carry[c] = b""
+                self.talking[c] = False
+            for ts, flags, payload in emitted:
+                seq = self.seq[c]
+                header = bytes([0x80, ((flags & RTP_MARKER) << 7) | int(s["payload_type"]), seq >> 8, seq & 0xFF]) + ts.to_bytes(4, "big") + int(s["ssrc"]).to_bytes(4, "big")
+                out.append((c, ts, seq, flags, header + payload))
+                self.seq[c] = (seq + 1) & 0xFFFF
+                self.packets[c] = (self.packets[c] + 1) & 0xFFFFFFFF
+                self.octets[c] = (self.octets[c] + len(payload)) & 0xFFFFFFFF
+                self.totals["packets"] += 1
+                self.totals["octets"] += len(payload)
+        self.k += 1
+        count, n = len(out), min(len(out), self.max_packets)
+        self.totals["dropped_packets"] += count - n
+        records = np.zeros(n, RTP_PACKET_DTYPE)
+        slots = np.zeros((n, self.slot_bytes), np.uint8)
+        for i, (c, ts, seq, flags, data) in enumerate(out[:n]):
+            records[i] = (c, ts, seq, len(data), flags, 0)
+            slots[i, :len(data)] = np.frombuffer(data, np.uint8)
+        return count, records, slots
+
+    def state(self):
+        import numpy as np
+
+        st = np.zeros(len(self.src), RTP_STATE_DTYPE)
+        for c in range(len(self.src)):
+            if self.src[c]["stream"]:
+                st[c] = (self.packets[c], self.octets[c], self.seq[c], len(self.carry[c]) // self.sb, 1 if self.talking[c] else 0)
+        return st
+
+    def counters(self):
+        return dict(steps=self.k, **self.totals)
+
+
 def scope_window_hops(windows: int, wave_batch: int):
     """The batch's new hops whose FFT windows a band scope of `windows` windows per batch looks at: (j * WAVE_BATCH) / K, j = 0 .. K-1."""
     return [(j * wave_batch) // windows for j in range(windows)]

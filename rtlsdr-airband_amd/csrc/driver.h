@@ -117,6 +117,7 @@ static inline bool has_follow(const airband_hip_handle* h) { return has_watch(h)
 static inline bool has_gate(const airband_hip_handle* h) { return h->gate.max_rows > 0; }
 static inline bool has_encoding(const airband_hip_handle* h) { return has_gate(h) && h->gate.enc.encoding != AIRBAND_AUDIO_F32; }
 static inline bool has_spool(const airband_hip_handle* h) { return has_encoding(h) && h->gate.enc.spool.pool_rows > 0; }
+static inline bool has_rtp(const airband_hip_handle* h) { return has_encoding(h) && h->gate.enc.rtp.max_packets > 0; }
 static inline bool has_mixer_gate(const airband_hip_handle* h) { return h->mix.n_mixers > 0 && h->mix_gate.max_rows > 0; }
 static inline bool has_mixer_spool(const airband_hip_handle* h) { return has_mixer_gate(h) && h->mix_gate.spool.pool_rows > 0; }
 static inline bool has_scan_control(const airband_hip_handle* h) { return h->scan_ctl.idle_batches > 0; }
@@ -127,6 +128,7 @@ constexpr const char* NO_FOLLOW = "the handle has no band follow (airband_hip_se
 constexpr const char* NO_GATE = "the handle has no output gate (airband_hip_set_output_gate)";
 constexpr const char* NO_ENCODING = "the handle has no output encoding (airband_hip_set_output_encoding)";
 constexpr const char* NO_SPOOL = "the handle has no transmission spool (airband_hip_set_transmission_spool)";
+constexpr const char* NO_RTP = "the handle has no RTP stream (airband_hip_set_rtp_stream)";
 constexpr const char* NO_MIXER_GATE = "the handle has no mixer gate (airband_hip_set_mixer_gate)";
 constexpr const char* NO_MIXER_SPOOL = "the handle has no mixer spool (airband_hip_set_mixer_spool)";
 constexpr const char* NO_SCAN_CONTROL = "scan control is off (airband_hip_set_scan_control)";

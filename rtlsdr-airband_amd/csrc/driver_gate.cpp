@@ -1,7 +1,8 @@
 /* csrc/driver_gate.cpp -- the gated outputs of the host driver: the output gate, the encoding of its rows, airband_hip_encode_audio and the transmission spool
  * (airband_hip_set_output_gate / _set_output_encoding / _set_transmission_spool and their collect / device entry points), and their launches behind the emit and
  * mixer launches of a batch (hook of airband_hip.cpp: run_back_half).  The spool's host side is written over a TransmissionSpool and a SpoolSource: the mixer
- * spool (driver_mix.cpp: airband_hip_set_mixer_spool and its collect / flush / counters / device entry points) goes through the same functions. */
+ * spool (driver_mix.cpp: airband_hip_set_mixer_spool and its collect / flush / counters / device entry points) goes through the same functions.  The RTP packet
+ * stream (airband_hip_set_rtp_stream and its collect / state / counters / device entry points) is a second reader of the encoder's rows, beside the spool. */
 #include "driver.h"
 
 using namespace airband;
@@ -217,6 +218,55 @@ void airband::spool_device_views(const TransmissionSpool& sp, void** d_export_au
 static bool audio_encoding_known(int32_t e) { return e == AIRBAND_AUDIO_S16 || e == AIRBAND_AUDIO_ULAW || e == AIRBAND_AUDIO_ALAW; }
 static size_t audio_sample_bytes(int e) { return e == AIRBAND_AUDIO_S16 ? 2 : 1; }
 
+/* ---- the RTP stream's host side, over an RtpStream and the source whose rows it frames ---- */
+static RtpArgs rtp_args(const RtpStream& r, const SpoolSource& src, uint32_t k) {
+    RtpArgs a;
+    a.sources = r.d_sources.p;
+    a.state = r.d_state.p;
+    a.carry = r.d_carry.p;
+    a.ctl = r.d_ctl.p;
+    a.plan = r.d_plan.p;
+    a.blocks = r.d_blocks.p;
+    a.work = r.d_work.p;
+    a.gate_mask = src.mask;
+    a.gate_count = src.block_count;
+    a.enc_audio = src.audio;
+    a.records = r.d_records.p;
+    a.packets = r.d_packets.p;
+    a.n_ch = src.n;
+    a.max_rows = src.max_rows;
+    a.wave_batch = src.frames;
+    a.frame_samples = r.frame_samples;
+    a.sample_bytes = r.sample_bytes;
+    a.carry_cap = r.carry_cap;
+    a.carry_stride = r.carry_stride;
+    a.slot_bytes = r.slot_bytes;
+    a.max_packets = r.max_packets;
+    a.k = k;
+    return a;
+}
+
+/* one step behind the source's rows on s (rtp_stream.hip) */
+static void rtp_step(RtpStream& r, const SpoolSource& src, hipStream_t s) {
+    launch_rtp_step(rtp_args(r, src, r.steps), r.write_grid, s);
+    r.steps++;
+    r.steps_total++;
+}
+
+/* the frame length's bounds (the header's): AIRBAND_HIP_OK, or the code with *why set */
+static int rtp_frame_check(int32_t encoding, int64_t frame_samples, int64_t wave_batch, const char** why) {
+    if (!audio_encoding_known(encoding)) {
+        *why = "encoding is not AIRBAND_AUDIO_S16, _ULAW or _ALAW";
+        return AIRBAND_HIP_EINVAL;
+    }
+    *why = "frame_samples must be a multiple of 4 with 40 <= frame_samples <= wave_batch and 12 + frame_samples * sample_bytes <= 1472";
+    if (frame_samples % 4 || frame_samples < 40 || (wave_batch > 0 && frame_samples > wave_batch)) return AIRBAND_HIP_EBADSIZE;
+    if (12 + frame_samples * (int64_t)audio_sample_bytes(encoding) > 1472) return AIRBAND_HIP_EBADSIZE;
+    return AIRBAND_HIP_OK;
+}
+
+static int rtp_slot_bytes(int32_t encoding, int32_t frame_samples) { return (int)((12 + (size_t)frame_samples * audio_sample_bytes(encoding) + 15) / 16 * 16); }
+
 /* What airband_hip_collect_active() and airband_hip_collect_active_encoded() share.  How many rows there are is on the device: the count first, then exactly those
  * rows -- the channel indices, what `rows(n, s)` enqueues of the call's own arrays, axcindicate of every channel, ONE synchronize.  Only then is the count
  * reported and the batch marked as collected: a caller that sees an error sees neither.  (A HIP_TRY inside `rows` returns from the lambda; its code is checked here.) */
@@ -243,6 +293,7 @@ void airband::launch_gate_behind_mix(airband_hip_handle* h, hipStream_t s) {
     launch_gate(gate_args(h), s);
     if (has_encoding(h)) launch_audio_pack(audio_pack_args(h), 0, s); /* ... and encoded (audio_pack.hip) */
     if (has_spool(h)) spool_step(h->gate.enc.spool, channel_spool_source(h), s); /* ... and the spool's step of this batch (tx_spool.hip) */
+    if (has_rtp(h)) rtp_step(h->gate.enc.rtp, channel_spool_source(h), s);       /* ... and the RTP stream's (rtp_stream.hip): another reader of the same rows */
 }
 
 extern "C" {
@@ -435,6 +486,134 @@ int airband_hip_device_transmission_spool(airband_hip_handle* h, void** d_export
     if (!h) return AIRBAND_HIP_EINVAL;
     if (!has_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_SPOOL);
     spool_device_views(h->gate.enc.spool, d_export_audio, d_export_records, d_n_export);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_rtp_slot_bytes(int32_t encoding, int32_t frame_samples) {
+    const char* why = "";
+    const int rc = rtp_frame_check(encoding, frame_samples, 0, &why);
+    return rc != AIRBAND_HIP_OK ? rc : rtp_slot_bytes(encoding, frame_samples);
+}
+
+int airband_hip_set_rtp_stream(airband_hip_handle* h, const airband_hip_rtp_source* sources, int32_t frame_samples, int64_t max_packets) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    OutputGate& g = h->gate;
+    if (!has_gate(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_GATE);
+    if (!has_encoding(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_ENCODING);
+    if (started(h)) return fail(h, AIRBAND_HIP_EINVAL, "the RTP stream is set before the first batch");
+    if (!sources) { /* removed */
+        g.enc.rtp = RtpStream();
+        return AIRBAND_HIP_OK;
+    }
+    const char* why = "";
+    int rc = rtp_frame_check(g.enc.encoding, frame_samples, h->B, &why);
+    if (rc != AIRBAND_HIP_OK) return fail(h, rc, why);
+    const int n_ch = h->plan.total_ch, B = h->B, F = frame_samples, sb = (int)audio_sample_bytes(g.enc.encoding), slot = rtp_slot_bytes(g.enc.encoding, F);
+    int gcd = B, rest = F;
+    while (rest) {
+        const int t = gcd % rest;
+        gcd = rest;
+        rest = t;
+    }
+    const int carry_cap = F - gcd; /* a carry is a multiple of gcd(B, F) below F */
+    const int64_t most = (int64_t)n_ch * ((carry_cap + B) / F);
+    if (max_packets < 1 || max_packets > 0x7fffffff || most > 0x7fffffff) return fail(h, AIRBAND_HIP_EINVAL, "max_packets must be at least 1, and it and the most packets of a step small enough to index");
+    size_t n_streamed = 0;
+    for (int c = 0; c < n_ch; c++) {
+        if (!sources[c].stream) continue;
+        n_streamed++;
+        if (sources[c].payload_type > 127) return fail(h, AIRBAND_HIP_EINVAL, "payload_type of channel " + std::to_string(c) + " is above 127");
+        if (g.gate[c] == AIRBAND_GATE_NEVER) return fail(h, AIRBAND_HIP_EINVAL, "streamed channel " + std::to_string(c) + " has gate AIRBAND_GATE_NEVER");
+    }
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* built beside the encoding and moved in whole: a failed allocation leaves the handle as it was */
+    RtpStream r;
+    std::vector<airband_hip_rtp_source> src(sources, sources + n_ch);
+    std::vector<airband_hip_rtp_state> state((size_t)n_ch);
+    std::memset(state.data(), 0, state.size() * sizeof(state[0]));
+    for (int c = 0; c < n_ch; c++)
+        if (src[c].stream) state[c].seq = src[c].seq0;
+    const size_t carry_stride = (size_t)carry_cap * sb;
+    hipError_t e = upload(r.d_sources, src);
+    if (e == hipSuccess) e = upload(r.d_state, state);
+    if (e == hipSuccess) e = r.d_carry.alloc_zeroed((size_t)n_ch * carry_stride + 4);
+    if (e == hipSuccess) e = r.d_ctl.alloc_zeroed(1);
+    if (e == hipSuccess) e = r.d_plan.alloc_zeroed((size_t)n_ch);
+    if (e == hipSuccess) e = r.d_blocks.alloc_zeroed((size_t)gate_blocks(n_ch));
+    if (e == hipSuccess) e = r.d_work.alloc_zeroed((size_t)n_ch);
+    if (e == hipSuccess) e = r.d_records.alloc_zeroed((size_t)max_packets);
+    if (e == hipSuccess) e = r.d_packets.alloc_zeroed((size_t)max_packets * slot);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); /* the zeroes are there before a step on another stream reads them */
+    if (e != hipSuccess) return alloc_failed(h, e, "RTP stream buffers: ");
+    r.max_packets = (int)max_packets;
+    r.frame_samples = F;
+    r.sample_bytes = sb;
+    r.slot_bytes = slot;
+    r.carry_cap = carry_cap;
+    r.carry_stride = (int)carry_stride;
+    r.write_grid = (int)(n_streamed < 1 ? 1 : (n_streamed < 8192 ? n_streamed : 8192));
+    g.enc.rtp = std::move(r);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_rtp_packets(airband_hip_handle* h, int64_t* n_packets, airband_hip_rtp_packet* records, void* packets, char* axc_all) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_RTP);
+    if (!h->results_ready || h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
+    const RtpStream& r = h->gate.enc.rtp;
+    ON_OWN_STREAM(h, s);
+    /* how many packets there are is on the device: the count first, then exactly those records and slots, ONE synchronize behind them */
+    int64_t count = 0;
+    const int64_t most = (int64_t)h->plan.total_ch * ((r.carry_cap + h->B) / r.frame_samples);
+    int rc = collect_counted<int32_t>(h, &r.d_ctl.p->n_packets, most, r.max_packets, "RTP packet count out of range: ", &count, nullptr, nullptr, s);
+    if (rc != AIRBAND_HIP_OK) return rc;
+    const size_t n = (size_t)(count < r.max_packets ? count : r.max_packets);
+    if (records && n) HIP_TRY(h, hipMemcpyAsync(records, r.d_records.p, n * sizeof(airband_hip_rtp_packet), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (packets && n) HIP_TRY(h, hipMemcpyAsync(packets, r.d_packets.p, n * (size_t)r.slot_bytes, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (axc_all) HIP_TRY(h, hipMemcpyAsync(axc_all, h->d_out_axc.p, (size_t)h->plan.total_ch, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (n_packets) *n_packets = count;
+    h->results_ready = false;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_rtp_state(airband_hip_handle* h, int64_t first_channel, int64_t n_channels, airband_hip_rtp_state* state) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_RTP);
+    if (!state) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    if (first_channel < 0 || n_channels < 0 || first_channel + n_channels > h->plan.total_ch) return fail(h, AIRBAND_HIP_EINVAL, "channel range outside the handle's channels");
+    if (n_channels == 0) return AIRBAND_HIP_OK;
+    ON_OWN_STREAM(h, s);
+    HIP_TRY(h, hipMemcpyAsync(state, h->gate.enc.rtp.d_state.p + first_channel, (size_t)n_channels * sizeof(airband_hip_rtp_state), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_rtp_counters_get(airband_hip_handle* h, airband_hip_rtp_counters* out) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_RTP);
+    if (!out) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    const RtpStream& r = h->gate.enc.rtp;
+    ON_OWN_STREAM(h, s);
+    RtpCtl ctl;
+    HIP_TRY(h, hipMemcpyAsync(&ctl, r.d_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    out->steps = (int64_t)r.steps_total;
+    out->packets = (int64_t)ctl.packets;
+    out->dropped_packets = (int64_t)ctl.dropped;
+    out->octets = (int64_t)ctl.octets;
+    out->lost_rows = (int64_t)ctl.lost_rows;
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_device_rtp_stream(airband_hip_handle* h, int32_t** d_n_packets, airband_hip_rtp_packet** d_records, void** d_packets, airband_hip_rtp_state** d_state) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_RTP);
+    const RtpStream& r = h->gate.enc.rtp;
+    if (d_n_packets) *d_n_packets = &r.d_ctl.p->n_packets; /* RtpCtl's first member */
+    if (d_records) *d_records = r.d_records.p;
+    if (d_packets) *d_packets = r.d_packets.p;
+    if (d_state) *d_state = r.d_state.p;
     return AIRBAND_HIP_OK;
 }
 

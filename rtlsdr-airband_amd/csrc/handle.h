@@ -134,10 +134,29 @@ struct MixerGate {
     TransmissionSpool spool;   /* airband_hip_set_mixer_spool: an encoded gate's, gone with the gate */
 };
 
+/* what airband_hip_set_rtp_stream() set up, a part of the encoding whose rows it frames: replaced as a whole, gone with the encoding (and so with the gate), one
+ * without max_packets is an encoding without a stream (nothing allocated, nothing launched) */
+struct RtpStream {
+    int max_packets = 0;       /* 0 = no stream */
+    int frame_samples = 0, sample_bytes = 0, slot_bytes = 0, carry_cap = 0, carry_stride = 0;
+    int write_grid = 0;        /* workgroups of the write pass: min(streamed channels, one per wavefront slot of the GPU) */
+    uint32_t steps = 0;        /* steps enqueued so far: the next step's k */
+    uint64_t steps_total = 0;
+    DevBuf<airband_hip_rtp_source> d_sources;
+    DevBuf<airband_hip_rtp_state> d_state;
+    DevBuf<uint8_t> d_carry, d_packets;
+    DevBuf<RtpCtl> d_ctl;
+    DevBuf<RtpPlan> d_plan;
+    DevBuf<RtpBlock> d_blocks;
+    DevBuf<RtpWork> d_work;
+    DevBuf<airband_hip_rtp_packet> d_records;
+};
+
 /* what airband_hip_set_output_encoding() set up, a part of the gate whose list it reads: replaced as a whole, gone with the gate, AIRBAND_AUDIO_F32 is a gate
  * without an encoding (nothing allocated, nothing launched) */
 struct OutputEncoding {
     TransmissionSpool spool;
+    RtpStream rtp;
     int encoding = AIRBAND_AUDIO_F32;
     DevBuf<uint8_t> d_audio; /* [max_rows][wave_batch] bytes, or int16 for S16 */
     DevBuf<airband_hip_audio_row> d_info;

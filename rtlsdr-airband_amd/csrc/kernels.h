@@ -409,6 +409,46 @@ void launch_spool_step(const SpoolArgs& a, hipStream_t stream);    /* four launc
 void launch_spool_flush(const SpoolArgs& a, hipStream_t stream);   /* two: scan, close */
 void launch_spool_collect(const SpoolArgs& a, hipStream_t stream); /* three: export, walk, gather */
 
+/* RTP packet stream (rtp_stream.hip): the encoded rows a gate lists cut into RTP packets of frame_samples, the remainder carried per channel, one record per
+ * packet, ranked (channel, time) by prefix sums.  Written against "a mask, counts, encoded rows": the driver fills them from the output gate and the encoder */
+struct RtpPlan {
+    int32_t np, row;                 /* packets the step gives the channel; its row in the encoder's buffer, -1: not listed */
+};
+struct RtpWork {
+    int32_t channel, first, row, pad; /* a channel with packets: its first slot, its row (-1: the flush packet) */
+};
+struct RtpBlock {
+    int32_t packets, work, lost, octets; /* sums over one workgroup's channels */
+};
+struct RtpCtl {
+    int32_t n_packets;               /* the step's packets (may exceed max_packets) */
+    int32_t n_work;                  /* channels with packets in the step */
+    int32_t pad[2];
+    unsigned long long packets, dropped, octets, lost_rows;
+};
+struct RtpArgs {
+    const airband_hip_rtp_source* sources; /* [n_ch] */
+    airband_hip_rtp_state* state;    /* [n_ch] */
+    uint8_t* carry;                  /* [n_ch][carry_stride] encoded samples */
+    RtpCtl* ctl;                     /* [1] */
+    RtpPlan* plan;                   /* [n_ch] */
+    RtpBlock* blocks;                /* [gate_blocks(n_ch)] */
+    RtpWork* work;                   /* [n_ch] */
+    const unsigned long long* gate_mask; /* the gate's verdicts and counts of this batch (GateArgs::mask, ::block_count) */
+    const int* gate_count;
+    const uint8_t* enc_audio;        /* the encoder's rows of this batch (AudioPackArgs::audio) */
+    airband_hip_rtp_packet* records; /* [max_packets] */
+    uint8_t* packets;                /* [max_packets][slot_bytes] */
+    int n_ch, max_rows;              /* the gate's */
+    int wave_batch, frame_samples;   /* multiples of four */
+    int sample_bytes;                /* 1 or 2 */
+    int carry_cap;                   /* the longest carry in samples: frame_samples - gcd(wave_batch, frame_samples) */
+    int carry_stride;                /* bytes of a channel's carry buffer: carry_cap * sample_bytes */
+    int slot_bytes, max_packets;
+    uint32_t k;                      /* the step's number */
+};
+void launch_rtp_step(const RtpArgs& a, int grid, hipStream_t stream); /* three launches: count, scan, write; grid: workgroups of the write pass, 0 = min(n_ch, one per wavefront slot of the GPU) */
+
 /* band scope (band_scope.hip): mean and peak of |X[k]|^2 over n_windows windows of the batch's input span, one workgroup per selected dongle */
 struct ScopeArgs {
     const uint8_t* iq;        /* device: dongle d's span starts at iq + d * iq_stride (the batch's stage-1 input) */
