@@ -602,7 +602,8 @@ int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const floa
  * Counters: steps; packets and octets (every emitted packet, the dropped ones included); dropped_packets (rank >= max_packets); lost_rows (streamed channels
  *   selected by the rule but past max_rows), all summed over the steps.
  * Out of scope: mixer rows (the kernels are written over a mask, its counts and encoded rows, so they can follow); trimming by the row record's first / end;
- *   comfort noise; RTCP itself; a flush call at shutdown; sockets.
+ *   comfort noise; RTCP itself; a flush call at shutdown; sockets.  (Mixer rows have since followed as an output of their own on top of an encoded mixer
+ *   gate, with a flush call: see "mixer RTP stream" below.)
  * A handle without an RTP stream allocates nothing for this, launches nothing and returns the same bits. */
 typedef struct airband_hip_rtp_source {
     uint32_t ssrc;
@@ -873,6 +874,72 @@ int airband_hip_mixer_spool_counters_get(airband_hip_handle* h, airband_hip_spoo
 /* Device-side views of the last airband_hip_collect_mixer_transmissions() (valid until the next one): d_export_audio [export_rows][row bytes],
  * d_export_records [max_records], d_n_export [3]: transmissions exported, their rows, transmissions still waiting.  Any out-pointer may be NULL. */
 int airband_hip_device_mixer_spool(airband_hip_handle* h, void** d_export_audio, airband_hip_transmission** d_export_records, int32_t** d_n_export);
+
+/* ---- mixer RTP stream ---------------------------------------------------------------------------------------------------------------------
+ * "Every channel of a dongle summed into one mixer" is the reference's most common set-up, and a fleet that listens to mixers gets whole rows of 1 000 or
+ * 2 000 frames from airband_hip_collect_active_mixers(): 6.25 packets of 20 ms.  A handle with an ENCODED mixer gate (S16, ULAW or ALAW) can carry a MIXER RTP
+ * STREAM: the rows the mixer gate lists cut into complete RTP packets on the GPU, the remainder carried per mixer from step to step, by the same kernels as the
+ * channel stream.  The definition (normative, integers only, checked as bytes) is the "RTP packet stream" text above read over mixers, with these differences
+ * and no others:
+ *   What stands in for what.  "channel" is the mixer index m (airband_hip_rtp_packet.channel = m); "the gate" is the mixer gate; "the encoded row" is the mixer
+ *     pack's, airband_hip_collect_active_mixers()'s.
+ *   Frames.  W = 2 on a gate with AIRBAND_MIXER_GATE_STEREO, else 1.  A row is B = wave_batch frames of W encoded samples.  frame_samples = F counts FRAMES: a
+ *     packet carries F frames = F * W samples.  carry_n, airband_hip_rtp_state.carry, RTP timestamps and ts0 + k * B - carry_n all count frames (an RTP clock
+ *     ticks once per frame whatever the channel count, RFC 3551).  Payload bytes are frames * W * sample_bytes; `length` counts bytes.  L16 stereo is L, R
+ *     interleaved, each big-endian: the pack's order.
+ *   Bounds.  F is a multiple of 4 with 40 <= F <= B and 12 + F * W * sample_bytes <= 1472: S16 stereo allows F <= 364, G.711 stereo F <= 728.  The carry
+ *     buffer holds F - gcd(B, F) frames.  F, B and every carry being multiples of 4 frames, every move stays a whole, aligned dword.  slot_bytes =
+ *     16 * ceil((12 + F * W * sample_bytes) / 16) (airband_hip_mixer_rtp_slot_bytes).
+ *   Step.  One RTP step per MIXER GATE STEP, behind that step's pack on the same stream: with an automatic gate once per batch in every schedule, with
+ *     AIRBAND_MIXER_GATE_MANUAL_STEP once per airband_hip_mixer_gate_step() call -- on a multi-GPU node after the exchange, so partial sums are never framed.
+ *     k counts the steps since the stream was set.  "Listed": among the first max_rows active mixers of that step.  A mixer the rule selected past max_rows
+ *     counts as a lost row and flushes its carry, as for channels.
+ *   Sources.  sources[mixer_count] of airband_hip_rtp_source.  On a multi-GPU node every rank holds every sum after the exchange: stream == 0 is how each rank
+ *     streams its own share of the mixers.  A streamed mixer whose gate is AIRBAND_GATE_NEVER is AIRBAND_HIP_EINVAL.
+ *   Flush.  airband_hip_mixer_rtp_flush() enqueues, in stream order, a step in which NO mixer is listed: every carrying mixer emits its one short FLUSH packet
+ *     with timestamp ts0 + k * B - carry_n, k being the steps so far, and loses its carry; talking is cleared for every streamed mixer.  seq, packets, octets
+ *     and the counters packets / octets / dropped_packets advance as for any packet; k, the gate's `prev`, the gate's list and the `steps` counter do not.  The
+ *     flush's packets REPLACE the last step's as the result to collect: collect first.
+ *   Records, ranks (mixer ascending, time ascending, by prefix sums), capacity (seq advances for packets dropped past max_packets) and the counters
+ *     (airband_hip_rtp_counters): unchanged.
+ * A handle may carry a channel stream, a mixer stream and both spools at once, each with its own state.  RTCP itself, sockets, comfort noise, trimming by
+ * first / end, per-mixer frame lengths or encodings and a flush for the channel stream (its result is tied to batch collection) are out of scope.
+ * A handle without a mixer RTP stream allocates nothing for this, launches nothing and returns the same bits. */
+
+/* slot_bytes of the mixer stream for an encoding, a frame length in frames and a width W (1 or 2).  A pure function, needs no GPU; with width 1 it equals
+ * airband_hip_rtp_slot_bytes().  AIRBAND_HIP_EINVAL for AIRBAND_AUDIO_F32, an unknown encoding or a width other than 1 and 2, AIRBAND_HIP_EBADSIZE for a
+ * frame_samples that is no multiple of 4, below 40, or whose packet exceeds 1472 bytes. */
+int airband_hip_mixer_rtp_slot_bytes(int32_t encoding, int32_t frame_samples, int32_t width);
+
+/* Allowed whenever airband_hip_set_mixer_spool() is, on a handle whose mixer gate is encoded: it orders itself behind the last batch the same way.  Calling it
+ * again replaces the stream (k and every mixer's state restart), sources == NULL removes it, and airband_hip_set_mixer_gate() or airband_hip_set_mixers()
+ * called again drops it with the gate it belonged to.  Validated before the device is touched, with the channel stream's codes: AIRBAND_HIP_EINVAL for a NULL
+ * handle, no mixer gate or one with AIRBAND_AUDIO_F32, a payload_type above 127, a streamed mixer whose gate is AIRBAND_GATE_NEVER, max_packets < 1 (or too
+ * many to index); AIRBAND_HIP_EBADSIZE for frame_samples outside the bounds above.  AIRBAND_HIP_ENOMEM when the buffers cannot be had -- the handle then runs
+ * on as it was, gate included. */
+int airband_hip_set_mixer_rtp_stream(airband_hip_handle* h, const airband_hip_rtp_source* sources, int32_t frame_samples, int64_t max_packets);
+
+/* The packets of the last step or flush, behind it by the stream rule of airband_hip_collect_active_mixers().  The count comes first (*n_packets, may exceed
+ * max_packets); then exactly n = min(count, max_packets) records (channel = the mixer), n * slot_bytes bytes of packets and has_signal of every mixer are
+ * copied; nothing past them is written.  Any pointer may be NULL.  AIRBAND_HIP_EAGAIN before the first step or flush since the stream was set.  Does not mark
+ * a batch as collected.  AIRBAND_HIP_EINVAL on a handle without a mixer RTP stream. */
+int airband_hip_collect_mixer_rtp_packets(airband_hip_handle* h, int64_t* n_packets, airband_hip_rtp_packet* records, void* packets, uint8_t* signal_all);
+
+/* The sender state of mixers [first_mixer, first_mixer + n_mixers) behind everything enqueued so far (synchronous; an unstreamed mixer's record is zeros; carry
+ * counts frames).  AIRBAND_HIP_EINVAL on a handle without a mixer RTP stream, for NULL `state` or a range outside the handle's mixers. */
+int airband_hip_collect_mixer_rtp_state(airband_hip_handle* h, int64_t first_mixer, int64_t n_mixers, airband_hip_rtp_state* state);
+
+/* The mixer stream's counters as they stand behind everything enqueued so far (synchronous); `steps` counts the steps since the stream was set, flushes not
+ * included.  AIRBAND_HIP_EINVAL on a handle without a mixer RTP stream or for NULL `out`. */
+int airband_hip_mixer_rtp_counters_get(airband_hip_handle* h, airband_hip_rtp_counters* out);
+
+/* The flush of the definition, in stream order behind the steps enqueued so far; not a step: k does not advance.  COLLECT FIRST: the flush's packets replace
+ * the last step's as what airband_hip_collect_mixer_rtp_packets() returns.  AIRBAND_HIP_EINVAL on a handle without a mixer RTP stream. */
+int airband_hip_mixer_rtp_flush(airband_hip_handle* h);
+
+/* Device-side views (valid until the next step or flush): d_n_packets [1], d_records [max_packets], d_packets [max_packets][slot_bytes], d_state
+ * [mixer_count].  Any out-pointer may be NULL. */
+int airband_hip_device_mixer_rtp_stream(airband_hip_handle* h, int32_t** d_n_packets, airband_hip_rtp_packet** d_records, void** d_packets, airband_hip_rtp_state** d_state);
 
 /* ---- band scope -------------------------------------------------------------------------------------------------------------------
  * The channelizer keeps the few bins of every transform that carry a configured channel.  A handle with a band scope also keeps, per selected dongle and batch,

@@ -40,6 +40,7 @@ EXPORTS = [
     "airband_hip_set_transmission_spool", "airband_hip_collect_transmissions", "airband_hip_spool_flush", "airband_hip_spool_counters_get", "airband_hip_device_transmission_spool",
     "airband_hip_set_rtp_stream", "airband_hip_collect_rtp_packets", "airband_hip_collect_rtp_state", "airband_hip_rtp_counters_get", "airband_hip_device_rtp_stream", "airband_hip_rtp_slot_bytes",
     "airband_hip_set_mixer_spool", "airband_hip_collect_mixer_transmissions", "airband_hip_mixer_spool_flush", "airband_hip_mixer_spool_counters_get", "airband_hip_device_mixer_spool",
+    "airband_hip_set_mixer_rtp_stream", "airband_hip_collect_mixer_rtp_packets", "airband_hip_collect_mixer_rtp_state", "airband_hip_mixer_rtp_counters_get", "airband_hip_mixer_rtp_flush", "airband_hip_device_mixer_rtp_stream", "airband_hip_mixer_rtp_slot_bytes",
     "airband_hip_set_band_scope", "airband_hip_collect_band_scope", "airband_hip_device_band_scope",
     "airband_hip_set_band_survey", "airband_hip_collect_band_survey", "airband_hip_device_band_survey",
     "airband_hip_set_band_watch", "airband_hip_collect_band_events", "airband_hip_collect_band_tracks", "airband_hip_device_band_watch",
@@ -116,7 +117,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
-    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()) + list(capi.TABLES_PROTOTYPES.items()) + list(capi.MIXER_GATE_PROTOTYPES.items()) + list(capi.MIXER_SPOOL_PROTOTYPES.items()) + list(capi.RTP_STREAM_PROTOTYPES.items()):
+    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()) + list(capi.TABLES_PROTOTYPES.items()) + list(capi.MIXER_GATE_PROTOTYPES.items()) + list(capi.MIXER_SPOOL_PROTOTYPES.items()) + list(capi.RTP_STREAM_PROTOTYPES.items()) + list(capi.MIXER_RTP_PROTOTYPES.items()):
         if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
             getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
@@ -828,7 +829,7 @@ class AirbandHip:
         enc = capi.AUDIO_F32 if encoding is None else capi.audio_encoding_value(encoding)
         flags = (capi.MIXER_GATE_STEREO if stereo else 0) | (capi.MIXER_GATE_MANUAL_STEP if manual_step else 0)
         self._check(self.L.airband_hip_set_mixer_gate(self.h, gate.ctypes.data, rows, enc, flags))
-        self.mixer_gate = dict(rows=rows, encoding=enc, width=2 if stereo else 1)
+        self.mixer_gate = dict(rows=rows, encoding=enc, width=2 if stereo else 1, gate=gate.copy())
 
     def mixer_gate_step(self, stream: int = 0):
         """One step of a manual mixer gate, behind whatever wrote the sums last (airband_hip_mixer_gate_step); stream 0 = the handle's own."""
@@ -908,6 +909,75 @@ class AirbandHip:
         ptrs = [C.c_void_p() for _ in range(3)]
         self._check(self.L.airband_hip_device_mixer_spool(self.h, *[C.byref(p) for p in ptrs]))
         return {k: (p.value or 0) for k, p in zip(["audio", "records", "n_export"], ptrs)}
+
+    # ---- mixer RTP stream (include/airband_hip.h) -------------------------------------------------------------------------------------
+    def set_mixer_rtp_stream(self, frame_samples=None, sources=None, max_packets=None, *, remove: bool = False):
+        """Mixer RTP stream (airband_hip_set_mixer_rtp_stream): the GPU frames the mixer gate's encoded rows as RTP packets of frame_samples FRAMES (W samples
+        each on a stereo gate), carrying the remainder per mixer.  frame_samples: default wave_rate // 50 (20 ms); sources: [n_mixers] of capi.RTP_SOURCE_DTYPE,
+        default every mixer whose gate is not NEVER with ssrc = its index, ts0 = 0, seq0 = 0 and payload type 0 / 8 / 96 for ulaw / alaw / s16; max_packets:
+        default what a step can emit at most.  Any time after set_mixer_gate() with an encoding; remove=True removes it; set_mixer_gate() or set_mixers() again
+        drops it."""
+        g = getattr(self, "mixer_gate", None)
+        if remove:
+            self._check(self.L.airband_hip_set_mixer_rtp_stream(self.h, None, 0, 0))
+            if g is not None:
+                g.pop("rtp", None)
+            return
+        enc, width = (g["encoding"], g["width"]) if g else (capi.AUDIO_F32, 1)
+        F = int(self.geometry.wave_rate) // 50 if frame_samples is None else int(frame_samples)
+        if sources is None:
+            src = np.zeros(self.n_mixers, capi.RTP_SOURCE_DTYPE)
+            src["ssrc"] = np.arange(self.n_mixers)
+            src["payload_type"] = capi.RTP_PAYLOAD_TYPES.get(enc, 0)
+            src["stream"] = (g["gate"] if g else np.zeros(self.n_mixers, np.uint8)) != capi.GATE_NEVER
+        else:
+            src = np.ascontiguousarray(sources, capi.RTP_SOURCE_DTYPE)
+            if src.shape != (self.n_mixers,):
+                raise ValueError("sources needs one record per mixer (%d), got shape %r" % (self.n_mixers, src.shape))
+        if max_packets is None:
+            max_packets = max(1, int(np.count_nonzero(src["stream"])) * ((max(F, 4) - 4 + self.B) // max(F, 1)))
+        self._check(self.L.airband_hip_set_mixer_rtp_stream(self.h, src.ctypes.data, F, int(max_packets)))
+        g["rtp"] = dict(frame_samples=F, max_packets=int(max_packets), slot_bytes=self._check(self.L.airband_hip_mixer_rtp_slot_bytes(enc, F, width)), sources=src)
+
+    def _mixer_rtp(self):
+        return (getattr(self, "mixer_gate", None) or {}).get("rtp") or dict(frame_samples=0, max_packets=1, slot_bytes=16, sources=None)
+
+    def collect_mixer_rtp_packets(self) -> dict:
+        """The last step's (or flush's) RTP packets (airband_hip_collect_mixer_rtp_packets): n_packets (may exceed max_packets: only the first max_packets were
+        written then), records [n] of capi.RTP_PACKET_DTYPE (channel = the mixer), packets [n][slot_bytes] uint8 -- packet i is
+        packets[i, :records[i]["length"]] -- and has_signal of every mixer."""
+        r = self._mixer_rtp()
+        n = C.c_int64(0)
+        records = np.empty((r["max_packets"],), capi.RTP_PACKET_DTYPE)
+        packets = np.empty((r["max_packets"], r["slot_bytes"]), np.uint8)
+        sig = np.empty((getattr(self, "n_mixers", 0),), np.uint8)
+        self._check(self.L.airband_hip_collect_mixer_rtp_packets(self.h, C.byref(n), records.ctypes.data, packets.ctypes.data, sig.ctypes.data))
+        kept = min(int(n.value), r["max_packets"])
+        return dict(n_packets=int(n.value), records=records[:kept], packets=packets[:kept], has_signal=sig)
+
+    def collect_mixer_rtp_state(self, first_mixer: int = 0, n_mixers: Optional[int] = None):
+        """The mixers' sender state (airband_hip_collect_mixer_rtp_state): [n_mixers] of capi.RTP_STATE_DTYPE, default every mixer; carry counts frames."""
+        n = getattr(self, "n_mixers", 0) - int(first_mixer) if n_mixers is None else int(n_mixers)
+        st = np.empty((max(n, 0),), capi.RTP_STATE_DTYPE)
+        self._check(self.L.airband_hip_collect_mixer_rtp_state(self.h, int(first_mixer), n, st.ctypes.data))
+        return st
+
+    def mixer_rtp_counters(self) -> dict:
+        """airband_hip_mixer_rtp_counters_get as a dict (capi.RTP_COUNTER_NAMES)."""
+        out = capi.RtpCounters()
+        self._check(self.L.airband_hip_mixer_rtp_counters_get(self.h, C.byref(out)))
+        return {k: int(getattr(out, k)) for k in capi.RTP_COUNTER_NAMES}
+
+    def mixer_rtp_flush(self):
+        """Every carrying mixer emits its short FLUSH packet (airband_hip_mixer_rtp_flush); collect the last step's packets first: the flush's replace them."""
+        self._check(self.L.airband_hip_mixer_rtp_flush(self.h))
+
+    def device_mixer_rtp_stream(self) -> dict:
+        """Device pointers of the last step's packets (valid until the next step or flush): n_packets [1] int32, records [max_packets] of 16 bytes, packets
+        [max_packets][slot_bytes], state [n_mixers] of 16 bytes."""
+        ptrs = [C.c_void_p() for _ in range(4)]
+        self._check(self.L.airband_hip_device_mixer_rtp_stream(self.h, *[C.byref(p) for p in ptrs]))
+        return {k: (p.value or 0) for k, p in zip(["n_packets", "records", "packets", "state"], ptrs)}
 
     def encode_mixer_audio(self, left, right, encoding):
         """The mixer pack kernel on host rows left, right [n][B] float32, right None for mono (airband_hip_encode_mixer_audio): (audio [n][W B] int16 or uint8,

@@ -781,6 +781,16 @@ RTP_STREAM_PROTOTYPES = {
     "airband_hip_rtp_counters_get": [_vp, C.POINTER(RtpCounters)],
     "airband_hip_device_rtp_stream": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
 }
+# the mixer RTP stream's (same header): the channel stream's records, state, counters and definition over the mixer gate's rows
+MIXER_RTP_PROTOTYPES = {
+    "airband_hip_mixer_rtp_slot_bytes": [_i32, _i32, _i32],
+    "airband_hip_set_mixer_rtp_stream": [_vp, _vp, _i32, _i64],
+    "airband_hip_collect_mixer_rtp_packets": [_vp, C.POINTER(_i64), _vp, _vp, _vp],
+    "airband_hip_collect_mixer_rtp_state": [_vp, _i64, _i64, _vp],
+    "airband_hip_mixer_rtp_counters_get": [_vp, C.POINTER(RtpCounters)],
+    "airband_hip_mixer_rtp_flush": [_vp],
+    "airband_hip_device_mixer_rtp_stream": [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)],
+}
 # numpy views of airband_hip_rtp_source, _rtp_packet and _rtp_state
 RTP_SOURCE_DTYPE = [("ssrc", "<u4"), ("ts0", "<u4"), ("seq0", "<u2"), ("payload_type", "u1"), ("stream", "u1")]
 RTP_PACKET_DTYPE = [("channel", "<i4"), ("timestamp", "<u4"), ("seq", "<u2"), ("length", "<u2"), ("flags", "<u2"), ("reserved", "<u2")]
@@ -788,20 +798,30 @@ RTP_STATE_DTYPE = [("packets", "<u4"), ("octets", "<u4"), ("seq", "<u2"), ("carr
 RTP_COUNTER_NAMES = tuple(f[0] for f in RtpCounters._fields_)
 
 
-def rtp_slot_bytes(encoding, frame_samples) -> int:
-    """slot_bytes of the header's definition: 16 * ceil((12 + F * sample_bytes) / 16); ValueError for what airband_hip_rtp_slot_bytes() refuses."""
+def mixer_rtp_slot_bytes(encoding, frame_samples, width=1) -> int:
+    """slot_bytes of the header's definition ("mixer RTP stream"): 16 * ceil((12 + F * W * sample_bytes) / 16), F in frames of W samples; ValueError for what
+    airband_hip_mixer_rtp_slot_bytes() refuses."""
     enc = audio_encoding_value(encoding)
     if enc not in (AUDIO_S16, AUDIO_ULAW, AUDIO_ALAW):
         raise ValueError("no encoding")
-    sb, F = (2 if enc == AUDIO_S16 else 1), int(frame_samples)
-    if F % 4 or F < 40 or 12 + F * sb > 1472:
+    if width not in (1, 2):
+        raise ValueError("width is neither 1 nor 2")
+    fb, F = (2 if enc == AUDIO_S16 else 1) * int(width), int(frame_samples)
+    if F % 4 or F < 40 or 12 + F * fb > 1472:
         raise ValueError("frame_samples the handle would refuse")
-    return (12 + F * sb + 15) // 16 * 16
+    return (12 + F * fb + 15) // 16 * 16
+
+
+def rtp_slot_bytes(encoding, frame_samples) -> int:
+    """slot_bytes of the header's definition: 16 * ceil((12 + F * sample_bytes) / 16); ValueError for what airband_hip_rtp_slot_bytes() refuses."""
+    return mixer_rtp_slot_bytes(encoding, frame_samples, 1)
 
 
 class rtp_stream_reference:
-    """The RTP packet stream's definition (include/airband_hip.h, "RTP packet stream") in plain Python / numpy: a stateful object that is fed, per step, what
-    collect_active_encoded() of the same gate and encoding returns.
+    """The definition of BOTH RTP streams (include/airband_hip.h, "RTP packet stream" and "mixer RTP stream") in plain Python / numpy: a stateful object that
+    is fed, per step, what collect_active_encoded() of the same gate and encoding returns -- for the mixer stream what collect_active_mixers() of the same
+    encoded mixer gate returns (mixers, audio), with width = W samples per frame: rows are [n][W * wave_batch], and wave_batch, frame_samples, the carry and
+    the timestamps count frames.  flush(): the step in which nobody is listed and k does not advance (the mixer stream's airband_hip_mixer_rtp_flush).
 
     sources: [n_channels] of RTP_SOURCE_DTYPE; encoding: "s16" / "ulaw" / "alaw" or an AUDIO_* value; wave_batch; frame_samples; max_packets.
     step(channels, audio, dropped=()): the gate's list (the first max_rows selected channels, ascending), their encoded rows [n][wave_batch] (int16 for "s16",
@@ -809,15 +829,15 @@ class rtp_stream_reference:
     records [min(count, max_packets)] of RTP_PACKET_DTYPE and slots [that many][slot_bytes] uint8, zero behind a packet's `length` (those bytes are undefined on
     the handle).  state() -> [n_channels] of RTP_STATE_DTYPE; counters() -> dict of RTP_COUNTER_NAMES."""
 
-    def __init__(self, sources, encoding, wave_batch, frame_samples, max_packets):
+    def __init__(self, sources, encoding, wave_batch, frame_samples, max_packets, width=1):
         import numpy as np
 
         self.enc = audio_encoding_value(encoding)
-        self.B, self.F, self.max_packets = int(wave_batch), int(frame_samples), int(max_packets)
-        self.slot_bytes = rtp_slot_bytes(self.enc, self.F)
+        self.B, self.F, self.max_packets, self.W = int(wave_batch), int(frame_samples), int(max_packets), int(width)
+        self.slot_bytes = mixer_rtp_slot_bytes(self.enc, self.F, self.W)
         if self.B % 4 or self.F > self.B or self.max_packets < 1:
             raise ValueError("parameters the handle would refuse")
-        self.sb = 2 if self.enc == AUDIO_S16 else 1
+        self.sb = (2 if self.enc == AUDIO_S16 else 1) * self.W  # bytes of a frame
         self.src = np.array(sources, RTP_SOURCE_DTYPE).reshape(-1).copy()
         if (self.src["payload_type"] > 127).any():
             raise ValueError("payload_type above 127")
@@ -837,7 +857,11 @@ class rtp_stream_reference:
             return row.astype("<i2").astype(">i2").tobytes()  # L16 is network order
         return row.astype(np.uint8).tobytes()
 
-    def step(self, channels, audio, dropped=()):
+    def flush(self):
+        """nobody is listed: every carrying channel emits its flush packet, talking is cleared; k and `steps` do not advance.  Returns what step() returns."""
+        return self.step((), (), advance=False)
+
+    def step(self, channels, audio, dropped=(), advance=True):
         import numpy as np
 
         channels = [int(c) for c in channels]
@@ -878,7 +902,8 @@ class rtp_stream_reference:
                 self.octets[c] = (self.octets[c] + len(payload)) & 0xFFFFFFFF
                 self.totals["packets"] += 1
                 self.totals["octets"] += len(payload)
-        self.k += 1
+        if advance:
+            self.k += 1
         count, n = len(out), min(len(out), self.max_packets)
         self.totals["dropped_packets"] += count - n
         records = np.zeros(n, RTP_PACKET_DTYPE)

@@ -16,15 +16,16 @@ struct FrontRows {
     int first_row, n_hops;
 };
 
-/* what a transmission spool reads of its source after the source's step: the channel spool of the output gate and the encoder, the mixer spool of the mixer
- * gate and the mixer pack */
+/* what a transmission spool or an RTP stream reads of its source after the source's step: the channel spool and the channel stream of the output gate and the
+ * encoder, the mixer spool and the mixer stream of the mixer gate and the mixer pack */
 struct SpoolSource {
     const unsigned long long* mask; /* the gate's verdicts */
     const int* block_count;         /* ... and its per-workgroup counts */
     const uint8_t* audio;           /* the listed rows, encoded */
     const airband_hip_audio_row* info;
     int n, max_rows;                /* items (channels / mixers), the list's capacity */
-    int frames;                     /* wave_batch: `first` of a transmission without a stored row */
+    int frames;                     /* wave_batch: `first` of a transmission without a stored row; the frames of a row the RTP stream cuts */
+    int width;                      /* samples per frame: 1 for channels, the mixer gate's W */
 };
 
 #pragma GCC visibility push(hidden)
@@ -46,6 +47,20 @@ int spool_collect(airband_hip_handle* h, const TransmissionSpool& sp, const Spoo
 int spool_flush(airband_hip_handle* h, const TransmissionSpool& sp, const SpoolSource& src);
 int spool_counters(airband_hip_handle* h, const TransmissionSpool& sp, airband_hip_spool_counters* out);
 void spool_device_views(const TransmissionSpool& sp, void** d_export_audio, airband_hip_transmission** d_export_records, int32_t** d_n_export);
+/* driver_gate.cpp: the RTP stream's host side over an RtpStream and its source, ONE path for the channel stream and the mixer stream (driver_mix.cpp): a set
+ * call's checks with allocate and initialise (`gate`: the source's gate bytes; `item`: "channel" / "mixer"; `what` ends with ": "), the step, the flush step,
+ * collect (the count, the records and slots it keeps, then `extra_bytes` from d_extra to `extra`: axcindicate / has_signal, ONE synchronize), state, counters,
+ * device views */
+int rtp_slot_bytes_checked(int32_t encoding, int32_t frame_samples, int32_t width);
+int rtp_build(airband_hip_handle* h, RtpStream& r, const airband_hip_rtp_source* sources, const std::vector<uint8_t>& gate, const char* item, int32_t encoding,
+              const SpoolSource& src, int32_t frame_samples, int64_t max_packets, const char* what);
+void rtp_step(RtpStream& r, const SpoolSource& src, hipStream_t s);
+int rtp_flush(airband_hip_handle* h, RtpStream& r, const SpoolSource& src);
+int rtp_collect(airband_hip_handle* h, const RtpStream& r, const SpoolSource& src, int64_t* n_packets, airband_hip_rtp_packet* records, void* packets,
+                const void* d_extra, void* extra, size_t extra_bytes);
+int rtp_state(airband_hip_handle* h, const RtpStream& r, const SpoolSource& src, int64_t first, int64_t n, airband_hip_rtp_state* state, const char* item);
+int rtp_counters(airband_hip_handle* h, const RtpStream& r, airband_hip_rtp_counters* out);
+void rtp_device_views(const RtpStream& r, int32_t** d_n_packets, airband_hip_rtp_packet** d_records, void** d_packets, airband_hip_rtp_state** d_state);
 /* driver_mix.cpp: what the batch's mixer sums are launched with; one mixer input switched on or off in the grouped arrays (airband_hip_device_enable) */
 MixArgs mix_args(const airband_hip_handle* h);
 hipError_t write_mix_input(airband_hip_handle* h, int k);
@@ -120,6 +135,7 @@ static inline bool has_spool(const airband_hip_handle* h) { return has_encoding(
 static inline bool has_rtp(const airband_hip_handle* h) { return has_encoding(h) && h->gate.enc.rtp.max_packets > 0; }
 static inline bool has_mixer_gate(const airband_hip_handle* h) { return h->mix.n_mixers > 0 && h->mix_gate.max_rows > 0; }
 static inline bool has_mixer_spool(const airband_hip_handle* h) { return has_mixer_gate(h) && h->mix_gate.spool.pool_rows > 0; }
+static inline bool has_mixer_rtp(const airband_hip_handle* h) { return has_mixer_gate(h) && h->mix_gate.rtp.max_packets > 0; }
 static inline bool has_scan_control(const airband_hip_handle* h) { return h->scan_ctl.idle_batches > 0; }
 constexpr const char* NO_SCOPE = "the handle has no band scope (airband_hip_set_band_scope)";
 constexpr const char* NO_SURVEY = "the handle has no band survey (airband_hip_set_band_survey)";
@@ -131,6 +147,7 @@ constexpr const char* NO_SPOOL = "the handle has no transmission spool (airband_
 constexpr const char* NO_RTP = "the handle has no RTP stream (airband_hip_set_rtp_stream)";
 constexpr const char* NO_MIXER_GATE = "the handle has no mixer gate (airband_hip_set_mixer_gate)";
 constexpr const char* NO_MIXER_SPOOL = "the handle has no mixer spool (airband_hip_set_mixer_spool)";
+constexpr const char* NO_MIXER_RTP = "the handle has no mixer RTP stream (airband_hip_set_mixer_rtp_stream)";
 constexpr const char* NO_SCAN_CONTROL = "scan control is off (airband_hip_set_scan_control)";
 
 /* they are set before the first batch (the message stays a literal at each fail(): "the band watch is set before the first batch") */

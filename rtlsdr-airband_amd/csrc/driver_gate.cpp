@@ -2,7 +2,9 @@
  * (airband_hip_set_output_gate / _set_output_encoding / _set_transmission_spool and their collect / device entry points), and their launches behind the emit and
  * mixer launches of a batch (hook of airband_hip.cpp: run_back_half).  The spool's host side is written over a TransmissionSpool and a SpoolSource: the mixer
  * spool (driver_mix.cpp: airband_hip_set_mixer_spool and its collect / flush / counters / device entry points) goes through the same functions.  The RTP packet
- * stream (airband_hip_set_rtp_stream and its collect / state / counters / device entry points) is a second reader of the encoder's rows, beside the spool. */
+ * stream (airband_hip_set_rtp_stream and its collect / state / counters / device entry points) is a second reader of the encoder's rows, beside the spool; its
+ * host side is written over an RtpStream and a SpoolSource in the same way, and the mixer RTP stream (driver_mix.cpp: airband_hip_set_mixer_rtp_stream and its
+ * entry points) goes through it. */
 #include "driver.h"
 
 using namespace airband;
@@ -58,6 +60,7 @@ static SpoolSource channel_spool_source(const airband_hip_handle* h) {
     src.n = h->plan.total_ch;
     src.max_rows = g.max_rows;
     src.frames = h->B;
+    src.width = 1;
     return src;
 }
 
@@ -218,8 +221,10 @@ void airband::spool_device_views(const TransmissionSpool& sp, void** d_export_au
 static bool audio_encoding_known(int32_t e) { return e == AIRBAND_AUDIO_S16 || e == AIRBAND_AUDIO_ULAW || e == AIRBAND_AUDIO_ALAW; }
 static size_t audio_sample_bytes(int e) { return e == AIRBAND_AUDIO_S16 ? 2 : 1; }
 
-/* ---- the RTP stream's host side, over an RtpStream and the source whose rows it frames ---- */
-static RtpArgs rtp_args(const RtpStream& r, const SpoolSource& src, uint32_t k) {
+/* ---- the RTP stream's host side, over an RtpStream and the source whose rows it frames: the channel stream (below) and the mixer stream (driver_mix.cpp) go
+ * through these ---- */
+/* k: the step's number; listed: false for the flush step, in which nobody is listed (no mask, no counts) */
+static RtpArgs rtp_args(const RtpStream& r, const SpoolSource& src, uint32_t k, bool listed) {
     RtpArgs a;
     a.sources = r.d_sources.p;
     a.state = r.d_state.p;
@@ -228,8 +233,8 @@ static RtpArgs rtp_args(const RtpStream& r, const SpoolSource& src, uint32_t k) 
     a.plan = r.d_plan.p;
     a.blocks = r.d_blocks.p;
     a.work = r.d_work.p;
-    a.gate_mask = src.mask;
-    a.gate_count = src.block_count;
+    a.gate_mask = listed ? src.mask : nullptr;
+    a.gate_count = listed ? src.block_count : nullptr;
     a.enc_audio = src.audio;
     a.records = r.d_records.p;
     a.packets = r.d_packets.p;
@@ -243,29 +248,159 @@ static RtpArgs rtp_args(const RtpStream& r, const SpoolSource& src, uint32_t k) 
     a.slot_bytes = r.slot_bytes;
     a.max_packets = r.max_packets;
     a.k = k;
+    a.width_shift = r.width == 2 ? 1 : 0;
     return a;
 }
 
 /* one step behind the source's rows on s (rtp_stream.hip) */
-static void rtp_step(RtpStream& r, const SpoolSource& src, hipStream_t s) {
-    launch_rtp_step(rtp_args(r, src, r.steps), r.write_grid, s);
+void airband::rtp_step(RtpStream& r, const SpoolSource& src, hipStream_t s) {
+    launch_rtp_step(rtp_args(r, src, r.steps, true), r.write_grid, s);
     r.steps++;
     r.steps_total++;
+    r.has_result = true;
 }
 
-/* the frame length's bounds (the header's): AIRBAND_HIP_OK, or the code with *why set */
-static int rtp_frame_check(int32_t encoding, int64_t frame_samples, int64_t wave_batch, const char** why) {
+/* the step in which nobody is listed, in stream order behind the steps enqueued so far; not a step: k does not advance */
+int airband::rtp_flush(airband_hip_handle* h, RtpStream& r, const SpoolSource& src) {
+    ON_OWN_STREAM(h, s);
+    launch_rtp_step(rtp_args(r, src, r.steps, false), r.write_grid, s);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
+    r.has_result = true;
+    /* a batch (or a step) that ran on a caller's stream: the next one there knows nothing of the handle's stream, so the flush is complete before this returns */
+    if (h->ev_last_pending) HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
+    return AIRBAND_HIP_OK;
+}
+
+/* the frame length's bounds (the header's): AIRBAND_HIP_OK, or the code with *why set.  width: samples per frame */
+static int rtp_frame_check(int32_t encoding, int64_t frame_samples, int64_t wave_batch, int64_t width, const char** why) {
     if (!audio_encoding_known(encoding)) {
         *why = "encoding is not AIRBAND_AUDIO_S16, _ULAW or _ALAW";
         return AIRBAND_HIP_EINVAL;
     }
-    *why = "frame_samples must be a multiple of 4 with 40 <= frame_samples <= wave_batch and 12 + frame_samples * sample_bytes <= 1472";
+    if (width != 1 && width != 2) {
+        *why = "width is neither 1 nor 2";
+        return AIRBAND_HIP_EINVAL;
+    }
+    *why = "frame_samples must be a multiple of 4 with 40 <= frame_samples <= wave_batch and 12 + frame_samples * width * sample_bytes <= 1472";
     if (frame_samples % 4 || frame_samples < 40 || (wave_batch > 0 && frame_samples > wave_batch)) return AIRBAND_HIP_EBADSIZE;
-    if (12 + frame_samples * (int64_t)audio_sample_bytes(encoding) > 1472) return AIRBAND_HIP_EBADSIZE;
+    if (12 + frame_samples * width * (int64_t)audio_sample_bytes(encoding) > 1472) return AIRBAND_HIP_EBADSIZE;
     return AIRBAND_HIP_OK;
 }
 
-static int rtp_slot_bytes(int32_t encoding, int32_t frame_samples) { return (int)((12 + (size_t)frame_samples * audio_sample_bytes(encoding) + 15) / 16 * 16); }
+static int rtp_slot_bytes(int32_t encoding, int32_t frame_samples, int32_t width) {
+    return (int)((12 + (size_t)frame_samples * width * audio_sample_bytes(encoding) + 15) / 16 * 16);
+}
+
+int airband::rtp_slot_bytes_checked(int32_t encoding, int32_t frame_samples, int32_t width) {
+    const char* why = "";
+    const int rc = rtp_frame_check(encoding, frame_samples, 0, width, &why);
+    return rc != AIRBAND_HIP_OK ? rc : rtp_slot_bytes(encoding, frame_samples, width);
+}
+
+/* the most packets one step can emit: every item a whole row behind the longest carry */
+static int64_t rtp_most_packets(const RtpStream& r, const SpoolSource& src) { return (int64_t)src.n * ((r.carry_cap + src.frames) / r.frame_samples); }
+
+/* a set call's arguments checked before the device is touched, then allocate and initialise: `r` is built beside what it will belong to and moved in whole by the
+ * caller, so a failed allocation leaves the handle as it was */
+int airband::rtp_build(airband_hip_handle* h, RtpStream& r, const airband_hip_rtp_source* sources, const std::vector<uint8_t>& gate, const char* item, int32_t encoding,
+                       const SpoolSource& src, int32_t frame_samples, int64_t max_packets, const char* what) {
+    const char* why = "";
+    int rc = rtp_frame_check(encoding, frame_samples, src.frames, src.width, &why);
+    if (rc != AIRBAND_HIP_OK) return fail(h, rc, why);
+    const int n = src.n, B = src.frames, F = frame_samples, sb = (int)audio_sample_bytes(encoding), slot = rtp_slot_bytes(encoding, F, src.width);
+    int gcd = B, rest = F;
+    while (rest) {
+        const int t = gcd % rest;
+        gcd = rest;
+        rest = t;
+    }
+    const int carry_cap = F - gcd; /* a carry is a multiple of gcd(B, F) below F */
+    const int64_t most = (int64_t)n * ((carry_cap + B) / F);
+    if (max_packets < 1 || max_packets > 0x7fffffff || most > 0x7fffffff) return fail(h, AIRBAND_HIP_EINVAL, "max_packets must be at least 1, and it and the most packets of a step small enough to index");
+    size_t n_streamed = 0;
+    for (int c = 0; c < n; c++) {
+        if (!sources[c].stream) continue;
+        n_streamed++;
+        if (sources[c].payload_type > 127) return fail(h, AIRBAND_HIP_EINVAL, std::string("payload_type of ") + item + " " + std::to_string(c) + " is above 127");
+        if (gate[c] == AIRBAND_GATE_NEVER) return fail(h, AIRBAND_HIP_EINVAL, std::string("streamed ") + item + " " + std::to_string(c) + " has gate AIRBAND_GATE_NEVER");
+    }
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    std::vector<airband_hip_rtp_source> host_src(sources, sources + n);
+    std::vector<airband_hip_rtp_state> state((size_t)n);
+    std::memset(state.data(), 0, state.size() * sizeof(state[0]));
+    for (int c = 0; c < n; c++)
+        if (host_src[c].stream) state[c].seq = host_src[c].seq0;
+    const size_t carry_stride = (size_t)carry_cap * sb * src.width;
+    hipError_t e = upload(r.d_sources, host_src);
+    if (e == hipSuccess) e = upload(r.d_state, state);
+    if (e == hipSuccess) e = r.d_carry.alloc_zeroed((size_t)n * carry_stride + 4);
+    if (e == hipSuccess) e = r.d_ctl.alloc_zeroed(1);
+    if (e == hipSuccess) e = r.d_plan.alloc_zeroed((size_t)n);
+    if (e == hipSuccess) e = r.d_blocks.alloc_zeroed((size_t)gate_blocks(n));
+    if (e == hipSuccess) e = r.d_work.alloc_zeroed((size_t)n);
+    if (e == hipSuccess) e = r.d_records.alloc_zeroed((size_t)max_packets);
+    if (e == hipSuccess) e = r.d_packets.alloc_zeroed((size_t)max_packets * slot);
+    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); /* the zeroes are there before a step on another stream reads them */
+    if (e != hipSuccess) return alloc_failed(h, e, what);
+    r.max_packets = (int)max_packets;
+    r.frame_samples = F;
+    r.sample_bytes = sb;
+    r.slot_bytes = slot;
+    r.carry_cap = carry_cap;
+    r.carry_stride = (int)carry_stride;
+    r.width = src.width;
+    r.write_grid = (int)(n_streamed < 1 ? 1 : (n_streamed < 8192 ? n_streamed : 8192));
+    return AIRBAND_HIP_OK;
+}
+
+/* how many packets there are is on the device: the count first, then exactly those records and slots and the caller's extra, ONE synchronize behind them; only
+ * then is the count reported */
+int airband::rtp_collect(airband_hip_handle* h, const RtpStream& r, const SpoolSource& src, int64_t* n_packets, airband_hip_rtp_packet* records, void* packets,
+                         const void* d_extra, void* extra, size_t extra_bytes) {
+    ON_OWN_STREAM(h, s);
+    int64_t count = 0;
+    int rc = collect_counted<int32_t>(h, &r.d_ctl.p->n_packets, rtp_most_packets(r, src), r.max_packets, "RTP packet count out of range: ", &count, nullptr, nullptr, s);
+    if (rc != AIRBAND_HIP_OK) return rc;
+    const size_t n = (size_t)(count < r.max_packets ? count : r.max_packets);
+    if (records && n) HIP_TRY(h, hipMemcpyAsync(records, r.d_records.p, n * sizeof(airband_hip_rtp_packet), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (packets && n) HIP_TRY(h, hipMemcpyAsync(packets, r.d_packets.p, n * (size_t)r.slot_bytes, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    if (extra) HIP_TRY(h, hipMemcpyAsync(extra, d_extra, extra_bytes, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    if (n_packets) *n_packets = count;
+    return AIRBAND_HIP_OK;
+}
+
+int airband::rtp_state(airband_hip_handle* h, const RtpStream& r, const SpoolSource& src, int64_t first, int64_t n, airband_hip_rtp_state* state, const char* item) {
+    if (!state) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    if (first < 0 || n < 0 || first + n > src.n) return fail(h, AIRBAND_HIP_EINVAL, std::string(item) + " range outside the handle's " + item + "s");
+    if (n == 0) return AIRBAND_HIP_OK;
+    ON_OWN_STREAM(h, s);
+    HIP_TRY(h, hipMemcpyAsync(state, r.d_state.p + first, (size_t)n * sizeof(airband_hip_rtp_state), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    return AIRBAND_HIP_OK;
+}
+
+int airband::rtp_counters(airband_hip_handle* h, const RtpStream& r, airband_hip_rtp_counters* out) {
+    if (!out) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    ON_OWN_STREAM(h, s);
+    RtpCtl ctl;
+    HIP_TRY(h, hipMemcpyAsync(&ctl, r.d_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
+    out->steps = (int64_t)r.steps_total;
+    out->packets = (int64_t)ctl.packets;
+    out->dropped_packets = (int64_t)ctl.dropped;
+    out->octets = (int64_t)ctl.octets;
+    out->lost_rows = (int64_t)ctl.lost_rows;
+    return AIRBAND_HIP_OK;
+}
+
+void airband::rtp_device_views(const RtpStream& r, int32_t** d_n_packets, airband_hip_rtp_packet** d_records, void** d_packets, airband_hip_rtp_state** d_state) {
+    if (d_n_packets) *d_n_packets = &r.d_ctl.p->n_packets; /* RtpCtl's first member */
+    if (d_records) *d_records = r.d_records.p;
+    if (d_packets) *d_packets = r.d_packets.p;
+    if (d_state) *d_state = r.d_state.p;
+}
 
 /* What airband_hip_collect_active() and airband_hip_collect_active_encoded() share.  How many rows there are is on the device: the count first, then exactly those
  * rows -- the channel indices, what `rows(n, s)` enqueues of the call's own arrays, axcindicate of every channel, ONE synchronize.  Only then is the count
@@ -489,11 +624,7 @@ int airband_hip_device_transmission_spool(airband_hip_handle* h, void** d_export
     return AIRBAND_HIP_OK;
 }
 
-int airband_hip_rtp_slot_bytes(int32_t encoding, int32_t frame_samples) {
-    const char* why = "";
-    const int rc = rtp_frame_check(encoding, frame_samples, 0, &why);
-    return rc != AIRBAND_HIP_OK ? rc : rtp_slot_bytes(encoding, frame_samples);
-}
+int airband_hip_rtp_slot_bytes(int32_t encoding, int32_t frame_samples) { return rtp_slot_bytes_checked(encoding, frame_samples, 1); }
 
 int airband_hip_set_rtp_stream(airband_hip_handle* h, const airband_hip_rtp_source* sources, int32_t frame_samples, int64_t max_packets) {
     if (!h) return AIRBAND_HIP_EINVAL;
@@ -505,53 +636,10 @@ int airband_hip_set_rtp_stream(airband_hip_handle* h, const airband_hip_rtp_sour
         g.enc.rtp = RtpStream();
         return AIRBAND_HIP_OK;
     }
-    const char* why = "";
-    int rc = rtp_frame_check(g.enc.encoding, frame_samples, h->B, &why);
-    if (rc != AIRBAND_HIP_OK) return fail(h, rc, why);
-    const int n_ch = h->plan.total_ch, B = h->B, F = frame_samples, sb = (int)audio_sample_bytes(g.enc.encoding), slot = rtp_slot_bytes(g.enc.encoding, F);
-    int gcd = B, rest = F;
-    while (rest) {
-        const int t = gcd % rest;
-        gcd = rest;
-        rest = t;
-    }
-    const int carry_cap = F - gcd; /* a carry is a multiple of gcd(B, F) below F */
-    const int64_t most = (int64_t)n_ch * ((carry_cap + B) / F);
-    if (max_packets < 1 || max_packets > 0x7fffffff || most > 0x7fffffff) return fail(h, AIRBAND_HIP_EINVAL, "max_packets must be at least 1, and it and the most packets of a step small enough to index");
-    size_t n_streamed = 0;
-    for (int c = 0; c < n_ch; c++) {
-        if (!sources[c].stream) continue;
-        n_streamed++;
-        if (sources[c].payload_type > 127) return fail(h, AIRBAND_HIP_EINVAL, "payload_type of channel " + std::to_string(c) + " is above 127");
-        if (g.gate[c] == AIRBAND_GATE_NEVER) return fail(h, AIRBAND_HIP_EINVAL, "streamed channel " + std::to_string(c) + " has gate AIRBAND_GATE_NEVER");
-    }
-    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
     /* built beside the encoding and moved in whole: a failed allocation leaves the handle as it was */
     RtpStream r;
-    std::vector<airband_hip_rtp_source> src(sources, sources + n_ch);
-    std::vector<airband_hip_rtp_state> state((size_t)n_ch);
-    std::memset(state.data(), 0, state.size() * sizeof(state[0]));
-    for (int c = 0; c < n_ch; c++)
-        if (src[c].stream) state[c].seq = src[c].seq0;
-    const size_t carry_stride = (size_t)carry_cap * sb;
-    hipError_t e = upload(r.d_sources, src);
-    if (e == hipSuccess) e = upload(r.d_state, state);
-    if (e == hipSuccess) e = r.d_carry.alloc_zeroed((size_t)n_ch * carry_stride + 4);
-    if (e == hipSuccess) e = r.d_ctl.alloc_zeroed(1);
-    if (e == hipSuccess) e = r.d_plan.alloc_zeroed((size_t)n_ch);
-    if (e == hipSuccess) e = r.d_blocks.alloc_zeroed((size_t)gate_blocks(n_ch));
-    if (e == hipSuccess) e = r.d_work.alloc_zeroed((size_t)n_ch);
-    if (e == hipSuccess) e = r.d_records.alloc_zeroed((size_t)max_packets);
-    if (e == hipSuccess) e = r.d_packets.alloc_zeroed((size_t)max_packets * slot);
-    if (e == hipSuccess) e = hipStreamSynchronize(nullptr); /* the zeroes are there before a step on another stream reads them */
-    if (e != hipSuccess) return alloc_failed(h, e, "RTP stream buffers: ");
-    r.max_packets = (int)max_packets;
-    r.frame_samples = F;
-    r.sample_bytes = sb;
-    r.slot_bytes = slot;
-    r.carry_cap = carry_cap;
-    r.carry_stride = (int)carry_stride;
-    r.write_grid = (int)(n_streamed < 1 ? 1 : (n_streamed < 8192 ? n_streamed : 8192));
+    const int rc = rtp_build(h, r, sources, g.gate, "channel", g.enc.encoding, channel_spool_source(h), frame_samples, max_packets, "RTP stream buffers: ");
+    if (rc != AIRBAND_HIP_OK) return rc;
     g.enc.rtp = std::move(r);
     return AIRBAND_HIP_OK;
 }
@@ -560,19 +648,8 @@ int airband_hip_collect_rtp_packets(airband_hip_handle* h, int64_t* n_packets, a
     if (!h) return AIRBAND_HIP_EINVAL;
     if (!has_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_RTP);
     if (!h->results_ready || h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
-    const RtpStream& r = h->gate.enc.rtp;
-    ON_OWN_STREAM(h, s);
-    /* how many packets there are is on the device: the count first, then exactly those records and slots, ONE synchronize behind them */
-    int64_t count = 0;
-    const int64_t most = (int64_t)h->plan.total_ch * ((r.carry_cap + h->B) / r.frame_samples);
-    int rc = collect_counted<int32_t>(h, &r.d_ctl.p->n_packets, most, r.max_packets, "RTP packet count out of range: ", &count, nullptr, nullptr, s);
+    const int rc = rtp_collect(h, h->gate.enc.rtp, channel_spool_source(h), n_packets, records, packets, h->d_out_axc.p, axc_all, (size_t)h->plan.total_ch);
     if (rc != AIRBAND_HIP_OK) return rc;
-    const size_t n = (size_t)(count < r.max_packets ? count : r.max_packets);
-    if (records && n) HIP_TRY(h, hipMemcpyAsync(records, r.d_records.p, n * sizeof(airband_hip_rtp_packet), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (packets && n) HIP_TRY(h, hipMemcpyAsync(packets, r.d_packets.p, n * (size_t)r.slot_bytes, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    if (axc_all) HIP_TRY(h, hipMemcpyAsync(axc_all, h->d_out_axc.p, (size_t)h->plan.total_ch, hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    if (n_packets) *n_packets = count;
     h->results_ready = false;
     return AIRBAND_HIP_OK;
 }
@@ -580,40 +657,19 @@ int airband_hip_collect_rtp_packets(airband_hip_handle* h, int64_t* n_packets, a
 int airband_hip_collect_rtp_state(airband_hip_handle* h, int64_t first_channel, int64_t n_channels, airband_hip_rtp_state* state) {
     if (!h) return AIRBAND_HIP_EINVAL;
     if (!has_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_RTP);
-    if (!state) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
-    if (first_channel < 0 || n_channels < 0 || first_channel + n_channels > h->plan.total_ch) return fail(h, AIRBAND_HIP_EINVAL, "channel range outside the handle's channels");
-    if (n_channels == 0) return AIRBAND_HIP_OK;
-    ON_OWN_STREAM(h, s);
-    HIP_TRY(h, hipMemcpyAsync(state, h->gate.enc.rtp.d_state.p + first_channel, (size_t)n_channels * sizeof(airband_hip_rtp_state), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    return AIRBAND_HIP_OK;
+    return rtp_state(h, h->gate.enc.rtp, channel_spool_source(h), first_channel, n_channels, state, "channel");
 }
 
 int airband_hip_rtp_counters_get(airband_hip_handle* h, airband_hip_rtp_counters* out) {
     if (!h) return AIRBAND_HIP_EINVAL;
     if (!has_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_RTP);
-    if (!out) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
-    const RtpStream& r = h->gate.enc.rtp;
-    ON_OWN_STREAM(h, s);
-    RtpCtl ctl;
-    HIP_TRY(h, hipMemcpyAsync(&ctl, r.d_ctl.p, sizeof(ctl), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
-    HIP_TRY(h, hipStreamSynchronize(s), AIRBAND_HIP_ERUNTIME);
-    out->steps = (int64_t)r.steps_total;
-    out->packets = (int64_t)ctl.packets;
-    out->dropped_packets = (int64_t)ctl.dropped;
-    out->octets = (int64_t)ctl.octets;
-    out->lost_rows = (int64_t)ctl.lost_rows;
-    return AIRBAND_HIP_OK;
+    return rtp_counters(h, h->gate.enc.rtp, out);
 }
 
 int airband_hip_device_rtp_stream(airband_hip_handle* h, int32_t** d_n_packets, airband_hip_rtp_packet** d_records, void** d_packets, airband_hip_rtp_state** d_state) {
     if (!h) return AIRBAND_HIP_EINVAL;
     if (!has_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_RTP);
-    const RtpStream& r = h->gate.enc.rtp;
-    if (d_n_packets) *d_n_packets = &r.d_ctl.p->n_packets; /* RtpCtl's first member */
-    if (d_records) *d_records = r.d_records.p;
-    if (d_packets) *d_packets = r.d_packets.p;
-    if (d_state) *d_state = r.d_state.p;
+    rtp_device_views(h->gate.enc.rtp, d_n_packets, d_records, d_packets, d_state);
     return AIRBAND_HIP_OK;
 }
 

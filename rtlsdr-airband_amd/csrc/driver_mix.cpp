@@ -1,6 +1,7 @@
 /* csrc/driver_mix.cpp -- the mixers of the host driver: the wiring (airband_hip_set_mixers / _mixer_enable_input / _mixer_set_stereo / _collect_mixers), what the sums
  * behind a batch's demod kernels are launched with (run_back_half), their exchange between handles over librccl.so (airband_hip_comm_* / *_mixers), and the gated
- * mixer collect over the sums (airband_hip_set_mixer_gate / _mixer_gate_step / _collect_active_mixers / _device_active_mixers / _encode_mixer_audio). */
+ * mixer collect over the sums (airband_hip_set_mixer_gate / _mixer_gate_step / _collect_active_mixers / _device_active_mixers / _encode_mixer_audio) with the
+ * two readers of its encoded rows: the mixer spool and the mixer RTP stream, whose host sides are driver_gate.cpp's. */
 #include <dlfcn.h>
 
 #include "driver.h"
@@ -37,7 +38,7 @@ static bool mixer_encoding_known(int32_t e) { return e == AIRBAND_AUDIO_F32 || e
 static size_t mixer_sample_bytes(int e) { return e == AIRBAND_AUDIO_F32 ? 4 : (e == AIRBAND_AUDIO_S16 ? 2 : 1); }
 static int mixer_gate_blocks(int n_mixers) { return gate_blocks(n_mixers); } /* the passes are the channel gate's (gate_passes.h) */
 
-/* what the mixer spool reads: the mixer gate's verdicts and the pack's rows and records (airband_hip_set_mixer_spool) */
+/* what the mixer spool and the mixer RTP stream read: the mixer gate's verdicts and the pack's rows and records (airband_hip_set_mixer_spool, _set_mixer_rtp_stream) */
 static SpoolSource mixer_spool_source(const airband_hip_handle* h) {
     const MixerGate& g = h->mix_gate;
     SpoolSource src;
@@ -48,6 +49,7 @@ static SpoolSource mixer_spool_source(const airband_hip_handle* h) {
     src.n = h->mix.n_mixers;
     src.max_rows = g.max_rows;
     src.frames = h->B;
+    src.width = g.width;
     return src;
 }
 
@@ -85,6 +87,7 @@ void airband::launch_mixer_gate_step(airband_hip_handle* h, hipStream_t s) {
     launch_mixer_pack(p, 0, s);
     g.stepped = true;
     if (has_mixer_spool(h)) spool_step(g.spool, mixer_spool_source(h), s); /* ... and the mixer spool's step, once per gate step (tx_spool.hip) */
+    if (has_mixer_rtp(h)) rtp_step(g.rtp, mixer_spool_source(h), s);       /* ... and the mixer RTP stream's (rtp_stream.hip): another reader of the same rows */
 }
 
 /* position k of the grouped mixer-input arrays: the channel it reads, or -1 while the connection (airband_hip_mixer_enable_input) or its dongle
@@ -421,6 +424,61 @@ int airband_hip_device_mixer_spool(airband_hip_handle* h, void** d_export_audio,
     if (!h) return AIRBAND_HIP_EINVAL;
     if (!has_mixer_spool(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_SPOOL);
     spool_device_views(h->mix_gate.spool, d_export_audio, d_export_records, d_n_export);
+    return AIRBAND_HIP_OK;
+}
+
+/* ---- mixer RTP stream (include/airband_hip.h; the host side is driver_gate.cpp's, the kernels rtp_stream.hip's) ------------------------------------------- */
+int airband_hip_mixer_rtp_slot_bytes(int32_t encoding, int32_t frame_samples, int32_t width) { return rtp_slot_bytes_checked(encoding, frame_samples, width); }
+
+int airband_hip_set_mixer_rtp_stream(airband_hip_handle* h, const airband_hip_rtp_source* sources, int32_t frame_samples, int64_t max_packets) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_gate(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_GATE);
+    MixerGate& g = h->mix_gate;
+    if (g.encoding == AIRBAND_AUDIO_F32) return fail(h, AIRBAND_HIP_EINVAL, "the mixer RTP stream frames encoded rows: the mixer gate's encoding is AIRBAND_AUDIO_F32");
+    RtpStream r; /* built beside the gate and moved in whole: a failed allocation leaves the handle as it was; sources == NULL: an empty one, removed */
+    if (sources) {
+        const int rc = rtp_build(h, r, sources, g.gate, "mixer", g.encoding, mixer_spool_source(h), frame_samples, max_packets, "mixer RTP stream buffers: ");
+        if (rc != AIRBAND_HIP_OK) return rc;
+    } else {
+        HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    }
+    /* behind the last batch, as airband_hip_set_mixer_spool: a step under way still reads and writes the stream that is replaced here */
+    order_behind_last_batch(h);
+    HIP_TRY(h, hipStreamSynchronize(h->stream), AIRBAND_HIP_ERUNTIME);
+    g.rtp = std::move(r);
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_collect_mixer_rtp_packets(airband_hip_handle* h, int64_t* n_packets, airband_hip_rtp_packet* records, void* packets, uint8_t* signal_all) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_RTP);
+    if (!h->mix_gate.rtp.has_result) return AIRBAND_HIP_EAGAIN;
+    /* the batch is not marked as collected: airband_hip_collect_active_mixers() does not do that either */
+    return rtp_collect(h, h->mix_gate.rtp, mixer_spool_source(h), n_packets, records, packets, h->mix.d_signal.p, signal_all, (size_t)h->mix.n_mixers);
+}
+
+int airband_hip_collect_mixer_rtp_state(airband_hip_handle* h, int64_t first_mixer, int64_t n_mixers, airband_hip_rtp_state* state) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_RTP);
+    return rtp_state(h, h->mix_gate.rtp, mixer_spool_source(h), first_mixer, n_mixers, state, "mixer");
+}
+
+int airband_hip_mixer_rtp_counters_get(airband_hip_handle* h, airband_hip_rtp_counters* out) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_RTP);
+    return rtp_counters(h, h->mix_gate.rtp, out);
+}
+
+int airband_hip_mixer_rtp_flush(airband_hip_handle* h) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_RTP);
+    return rtp_flush(h, h->mix_gate.rtp, mixer_spool_source(h));
+}
+
+int airband_hip_device_mixer_rtp_stream(airband_hip_handle* h, int32_t** d_n_packets, airband_hip_rtp_packet** d_records, void** d_packets, airband_hip_rtp_state** d_state) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!has_mixer_rtp(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_MIXER_RTP);
+    rtp_device_views(h->mix_gate.rtp, d_n_packets, d_records, d_packets, d_state);
     return AIRBAND_HIP_OK;
 }
 

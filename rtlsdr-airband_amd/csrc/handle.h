@@ -116,6 +116,27 @@ struct TransmissionSpool {
     DevBuf<airband_hip_transmission> d_fin, d_exp_records;
 };
 
+/* what airband_hip_set_rtp_stream() set up, a part of the encoding whose rows it frames -- or airband_hip_set_mixer_rtp_stream(), a part of the mixer gate whose
+ * rows it frames: replaced as a whole, gone with the encoding (and so with the gate) or with the mixer gate, one without max_packets is an encoding or a mixer
+ * gate without a stream (nothing allocated, nothing launched).  Declared in front of both owners: a member's type has to be complete */
+struct RtpStream {
+    int max_packets = 0;       /* 0 = no stream */
+    int frame_samples = 0, sample_bytes = 0, slot_bytes = 0, carry_cap = 0, carry_stride = 0; /* frame_samples and carry_cap count frames */
+    int width = 1;             /* samples per frame: the source's when the stream was set */
+    int write_grid = 0;        /* workgroups of the write pass: min(streamed channels, one per wavefront slot of the GPU) */
+    uint32_t steps = 0;        /* steps enqueued so far: the next step's k */
+    uint64_t steps_total = 0;
+    bool has_result = false;   /* a step or a flush has been enqueued.  Read by the MIXER stream's collect only (its EAGAIN); the channel stream's result is tied to the batch (results_ready) */
+    DevBuf<airband_hip_rtp_source> d_sources;
+    DevBuf<airband_hip_rtp_state> d_state;
+    DevBuf<uint8_t> d_carry, d_packets;
+    DevBuf<RtpCtl> d_ctl;
+    DevBuf<RtpPlan> d_plan;
+    DevBuf<RtpBlock> d_blocks;
+    DevBuf<RtpWork> d_work;
+    DevBuf<airband_hip_rtp_packet> d_records;
+};
+
 /* what airband_hip_set_mixer_gate() set up over the wiring's sums: replaced as a whole, dropped by airband_hip_set_mixers(), one without max_rows is a handle
  * without a mixer gate (nothing allocated, nothing launched).  An encoded gate holds d_audio / d_info and no d_rows, a float gate d_rows alone. */
 struct MixerGate {
@@ -132,24 +153,7 @@ struct MixerGate {
     DevBuf<airband_hip_audio_row> d_info;
     std::vector<uint8_t> gate; /* the caller's bytes: a spooled mixer must be AIRBAND_GATE_SIGNAL */
     TransmissionSpool spool;   /* airband_hip_set_mixer_spool: an encoded gate's, gone with the gate */
-};
-
-/* what airband_hip_set_rtp_stream() set up, a part of the encoding whose rows it frames: replaced as a whole, gone with the encoding (and so with the gate), one
- * without max_packets is an encoding without a stream (nothing allocated, nothing launched) */
-struct RtpStream {
-    int max_packets = 0;       /* 0 = no stream */
-    int frame_samples = 0, sample_bytes = 0, slot_bytes = 0, carry_cap = 0, carry_stride = 0;
-    int write_grid = 0;        /* workgroups of the write pass: min(streamed channels, one per wavefront slot of the GPU) */
-    uint32_t steps = 0;        /* steps enqueued so far: the next step's k */
-    uint64_t steps_total = 0;
-    DevBuf<airband_hip_rtp_source> d_sources;
-    DevBuf<airband_hip_rtp_state> d_state;
-    DevBuf<uint8_t> d_carry, d_packets;
-    DevBuf<RtpCtl> d_ctl;
-    DevBuf<RtpPlan> d_plan;
-    DevBuf<RtpBlock> d_blocks;
-    DevBuf<RtpWork> d_work;
-    DevBuf<airband_hip_rtp_packet> d_records;
+    RtpStream rtp;             /* airband_hip_set_mixer_rtp_stream: an encoded gate's, gone with the gate */
 };
 
 /* what airband_hip_set_output_encoding() set up, a part of the gate whose list it reads: replaced as a whole, gone with the gate, AIRBAND_AUDIO_F32 is a gate

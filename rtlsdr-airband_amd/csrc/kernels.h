@@ -410,7 +410,8 @@ void launch_spool_flush(const SpoolArgs& a, hipStream_t stream);   /* two: scan,
 void launch_spool_collect(const SpoolArgs& a, hipStream_t stream); /* three: export, walk, gather */
 
 /* RTP packet stream (rtp_stream.hip): the encoded rows a gate lists cut into RTP packets of frame_samples, the remainder carried per channel, one record per
- * packet, ranked (channel, time) by prefix sums.  Written against "a mask, counts, encoded rows": the driver fills them from the output gate and the encoder */
+ * packet, ranked (channel, time) by prefix sums.  Written against "a mask, counts, encoded rows": the driver fills them from the output gate and the encoder, or
+ * from the mixer gate and the mixer pack ("channel" is then the mixer, a row wave_batch FRAMES of 1 << width_shift samples) */
 struct RtpPlan {
     int32_t np, row;                 /* packets the step gives the channel; its row in the encoder's buffer, -1: not listed */
 };
@@ -434,18 +435,19 @@ struct RtpArgs {
     RtpPlan* plan;                   /* [n_ch] */
     RtpBlock* blocks;                /* [gate_blocks(n_ch)] */
     RtpWork* work;                   /* [n_ch] */
-    const unsigned long long* gate_mask; /* the gate's verdicts and counts of this batch (GateArgs::mask, ::block_count) */
+    const unsigned long long* gate_mask; /* the gate's verdicts and counts of this step (GateArgs::mask, ::block_count; MixerGateArgs'), BOTH NULL: nobody is listed (the flush) */
     const int* gate_count;
-    const uint8_t* enc_audio;        /* the encoder's rows of this batch (AudioPackArgs::audio) */
+    const uint8_t* enc_audio;        /* the encoder's rows of this step (AudioPackArgs::audio, MixerPackArgs::out) */
     airband_hip_rtp_packet* records; /* [max_packets] */
     uint8_t* packets;                /* [max_packets][slot_bytes] */
     int n_ch, max_rows;              /* the gate's */
-    int wave_batch, frame_samples;   /* multiples of four */
+    int wave_batch, frame_samples;   /* FRAMES of a row and of a packet: multiples of four */
     int sample_bytes;                /* 1 or 2 */
-    int carry_cap;                   /* the longest carry in samples: frame_samples - gcd(wave_batch, frame_samples) */
-    int carry_stride;                /* bytes of a channel's carry buffer: carry_cap * sample_bytes */
+    int carry_cap;                   /* the longest carry in frames: frame_samples - gcd(wave_batch, frame_samples) */
+    int carry_stride;                /* bytes of a channel's carry buffer: carry_cap * (sample_bytes << width_shift) */
     int slot_bytes, max_packets;
-    uint32_t k;                      /* the step's number */
+    uint32_t k;                      /* the step's number; flush: the steps run so far */
+    int width_shift;                 /* a frame is 1 << width_shift samples: 0 (channels, mono mixer gates) or 1 (AIRBAND_MIXER_GATE_STEREO: L, R interleaved) */
 };
 void launch_rtp_step(const RtpArgs& a, int grid, hipStream_t stream); /* three launches: count, scan, write; grid: workgroups of the write pass, 0 = min(n_ch, one per wavefront slot of the GPU) */
 

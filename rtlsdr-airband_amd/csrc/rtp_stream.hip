@@ -4,12 +4,22 @@
  * capi.rtp_stream_reference() is the same in plain Python.  Integers only: packets, records and state are checked as bytes.
  *
  * The kernels are written against "a mask, its per-workgroup counts and encoded rows" (RtpArgs::gate_mask, ::gate_count, ::enc_audio): the driver fills them from
- * the output gate and the encoder (driver_gate.cpp, SpoolSource); a mixer gate's would fit the same way.
+ * the output gate and the encoder, or from the mixer gate and the mixer pack (driver_gate.cpp, rtp_args over a SpoolSource): the mixer RTP stream
+ * (airband_hip_set_mixer_rtp_stream) runs these same kernels, "channel" being the mixer.
  *
- * wave_batch B and frame_samples F are multiples of 4, so every carry length -- a multiple of gcd(B, F) below F -- is a multiple of 4 samples as well: a carry, a
- * row, a payload and a slot's payload offset (12) are whole dwords whatever the sample size.  ALL MOVES ARE WHOLE DWORDS, four-byte aligned at both ends.
+ * Frames.  A frame is W = 1 << width_shift samples (W = 2: a stereo mixer gate's L, R), FB = W * sample_bytes bytes: 1, 2 or 4.  Everything that counts time --
+ * B, F, a carry length, state.carry, ts_start, a packet's timestamp, packets = (carry + B) / F -- counts FRAMES; everything that moves bytes -- the row, the carry
+ * buffer, the payload dwords, `length`, octets -- multiplies by FB.
+ * wave_batch B and frame_samples F are multiples of 4 frames, so every carry length -- a multiple of gcd(B, F) below F -- is a multiple of 4 frames as well:
+ * 4 * FB bytes, which is 1, 2 or 4 whole dwords.  For W = 2: a carry of 4n frames is 8n bytes (G.711) or 16n bytes (S16), a packet's payload F * 2 * sample_bytes
+ * bytes with F = 4m is 8m or 16m, a row B * 2 * sample_bytes likewise, the channel's carry buffer starts at c * carry_cap * FB with carry_cap a multiple of 4,
+ * and a slot's payload starts at byte 12 of a 16-byte aligned slot.  So a carry, a row, a payload and a slot's payload offset are whole dwords whatever the
+ * frame size, and a dword never straddles two frames' samples of different packets.  ALL MOVES ARE WHOLE DWORDS, four-byte aligned at both ends.  The S16 byte
+ * swap is per 16-bit half of a dword and so does not care whether the halves are two mono samples or L and R of one frame.
  *
- * Three launches per batch on a handle with a stream, behind the encoder on the same stream (driver_gate.cpp, launch_gate_behind_mix); none on a handle without:
+ * Three launches per step on a handle with a stream, behind the encoder on the same stream (driver_gate.cpp, launch_gate_behind_mix; driver_mix.cpp,
+ * launch_mixer_gate_step); none on a handle without.  The flush (airband_hip_mixer_rtp_flush) is the same three launches with NO mask and no counts
+ * (gate_mask == gate_count == NULL): nobody is listed, every carrying channel emits its flush packet; no pass indexes with the null pointers:
  *   rtp_count_kernel   one lane per channel: the channel's rank in the gate's mask (its row, were the list endless), listed or not, and from its carry how many
  *                      packets the step gives it; a channel that is neither listed nor carrying stops talking here.  Per workgroup the sums of packets, channels
  *                      with work, lost rows and payload bytes;
@@ -53,7 +63,7 @@ constexpr int RTP_MAX_GRID = 8192; /* one-wavefront workgroups: 256 CUs x 32 wav
 
 __device__ __forceinline__ int rtp_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-/* the carry a state record names, as the kernels use it: whole dwords, inside the channel's carry buffer */
+/* the carry a state record names, in frames, as the kernels use it: whole dwords, inside the channel's carry buffer */
 __device__ __forceinline__ int rtp_carry(const RtpArgs& a, const airband_hip_rtp_state& st) { return rtp_clamp((int)(st.carry & ~3u), 0, a.carry_cap); }
 
 /* sum over the workgroup's lanes, called by all of them: shuffles, then the wavefronts' totals through LDS.  SET: every call site its own LDS */
@@ -99,16 +109,19 @@ __global__ __launch_bounds__(GATE_BLOCK) void rtp_count_kernel(RtpArgs a) {
     /* the channel's rank among the gate's verdicts (gate_index_pass's scheme): its row, had the list no end */
     if (threadIdx.x == 0) base = 0;
     __syncthreads();
+    const bool masked = a.gate_mask != nullptr && a.gate_count != nullptr; /* uniform; false: the flush, nobody is listed and neither pointer is followed */
     int before = 0;
-    for (int j = threadIdx.x; j < (int)blockIdx.x; j += GATE_BLOCK) before += a.gate_count[j];
+    if (masked)
+        for (int j = threadIdx.x; j < (int)blockIdx.x; j += GATE_BLOCK) before += a.gate_count[j];
     if (before) atomicAdd(&base, before);
-    const unsigned long long m = (c - lane) < a.n_ch ? a.gate_mask[c >> 6] : 0ull;
+    const unsigned long long m = (masked && (c - lane) < a.n_ch) ? a.gate_mask[c >> 6] : 0ull;
     if (lane == 0) wave_count[w] = __popcll(m);
     __syncthreads();
     int pos = base;
     for (int i = 0; i < w; i++) pos += wave_count[i];
     pos += __popcll(m & ((1ull << lane) - 1ull));
 
+    const int fb = a.sample_bytes << a.width_shift; /* bytes of a frame */
     int np = 0, row = -1, lost = 0, octets = 0;
     if (c < a.n_ch) {
         if (a.sources[c].stream) {
@@ -118,12 +131,12 @@ __global__ __launch_bounds__(GATE_BLOCK) void rtp_count_kernel(RtpArgs a) {
             if (selected && pos < a.max_rows) {
                 row = pos;
                 np = (cn + a.wave_batch) / a.frame_samples;
-                octets = np * a.frame_samples * a.sample_bytes;
+                octets = np * a.frame_samples * fb;
             } else {
                 lost = selected ? 1 : 0; /* selected by the rule, dropped past max_rows */
                 if (cn > 0) {
                     np = 1; /* the flush packet */
-                    octets = cn * a.sample_bytes;
+                    octets = cn * fb;
                 } else if (st.flags & 1u) {
                     a.state[c].flags = st.flags & ~1u; /* not listed, nothing carried: the talkspurt is over, nothing is emitted */
                 }
@@ -196,12 +209,14 @@ __global__ __launch_bounds__(GATE_BLOCK) void rtp_scan_kernel(RtpArgs a) {
     }
 }
 
-/* SB: bytes per sample, 1 (G.711: the encoder's bytes as they are) or 2 (L16 is network order: the encoder's little-endian int16 byte-swapped) */
-template <int SB>
+/* SB: bytes per sample, 1 (G.711: the encoder's bytes as they are) or 2 (L16 is network order: the encoder's little-endian int16 byte-swapped, L and R each);
+ * W: samples per frame.  FB = SB * W bytes per frame: B, F, cn, rem and the timestamps count frames, the dword counts (Bd, cd, per, rd) come from bytes */
+template <int SB, int W>
 __device__ __forceinline__ void rtp_write(const RtpArgs& a) {
+    constexpr int FB = SB * W;
     const int lane = threadIdx.x & 63;
     const int n_work = rtp_clamp(a.ctl->n_work, 0, a.n_ch);
-    const int B = a.wave_batch, F = a.frame_samples, Bd = B * SB / 4;
+    const int B = a.wave_batch, F = a.frame_samples, Bd = B * FB / 4;
     for (int w = blockIdx.x; w < n_work; w += gridDim.x) { /* wave-uniform */
         const RtpWork it = a.work[w];
         const int c = rtp_clamp(it.channel, 0, a.n_ch - 1);
@@ -209,13 +224,13 @@ __device__ __forceinline__ void rtp_write(const RtpArgs& a) {
         const int row = rtp_clamp(it.row, 0, a.max_rows - 1), first = rtp_clamp(it.first, 0, a.max_packets); /* at max_packets: nothing of it is written */
         const airband_hip_rtp_state st = a.state[c];
         const airband_hip_rtp_source src = a.sources[c];
-        const int cn = rtp_carry(a, st), cd = cn * SB / 4;
+        const int cn = rtp_carry(a, st), cd = cn * FB / 4;
         const int np = listed ? (cn + B) / F : (cn > 0 ? 1 : 0);
-        const int per = listed ? F * SB / 4 : cd; /* payload dwords of one packet */
+        const int per = listed ? F * FB / 4 : cd; /* payload dwords of one packet */
         const int nd = np * per;
         const uint32_t ts_start = src.ts0 + a.k * (uint32_t)B - (uint32_t)cn;
         unsigned* const carry = reinterpret_cast<unsigned*>(a.carry + (long)c * a.carry_stride);
-        const unsigned* const rowp = reinterpret_cast<const unsigned*>(a.enc_audio + (long)row * B * SB);
+        const unsigned* const rowp = reinterpret_cast<const unsigned*>(a.enc_audio + (long)row * B * FB);
         /* the payloads: dword d of the carry followed by the row is dword o of packet j.  Four passes at a time, their loads in flight together */
         if (nd > 0) {
             int j = lane / per, o = lane - j * per;
@@ -245,7 +260,7 @@ __device__ __forceinline__ void rtp_write(const RtpArgs& a) {
             }
         }
         /* lane j: packet j's header and record */
-        const unsigned length = 12u + (unsigned)(listed ? F : cn) * SB;
+        const unsigned length = 12u + (unsigned)(listed ? F : cn) * FB;
         for (int j = lane; j < np; j += 64) {
             if (first + j >= a.max_packets) continue;
             const unsigned seq = (st.seq + (unsigned)j) & 0xFFFFu, ts = ts_start + (uint32_t)(j * F);
@@ -262,8 +277,8 @@ __device__ __forceinline__ void rtp_write(const RtpArgs& a) {
             __builtin_nontemporal_store(rec, reinterpret_cast<rtp_v4u*>(a.records + (first + j)));
         }
         RTP_CARRY_READ(); /* every lane has read the state and what it needs of the old carry */
-        /* what is left of the row is the new carry: np >= 1 packets took at least F > cn samples, so it lies in the row */
-        const int rem = listed ? rtp_clamp(cn + B - np * F, 0, a.carry_cap) : 0, rd = rem * SB / 4;
+        /* what is left of the row is the new carry: np >= 1 packets took at least F > cn frames, so it lies in the row */
+        const int rem = listed ? rtp_clamp(cn + B - np * F, 0, a.carry_cap) : 0, rd = rem * FB / 4;
         for (int d = lane; d < rd; d += 64) carry[d] = __builtin_nontemporal_load(rowp + (Bd - rd) + d);
         if (lane == 0) {
             airband_hip_rtp_state n = st;
@@ -278,10 +293,17 @@ __device__ __forceinline__ void rtp_write(const RtpArgs& a) {
 }
 
 __global__ __launch_bounds__(64) void rtp_write_kernel(RtpArgs a) {
-    if (a.sample_bytes == 2)
-        rtp_write<2>(a);
-    else
-        rtp_write<1>(a);
+    /* uniform: one of four straight-line bodies, the frame size a compile-time constant in each */
+    if (a.width_shift) {
+        if (a.sample_bytes == 2)
+            rtp_write<2, 2>(a);
+        else
+            rtp_write<1, 2>(a);
+    } else if (a.sample_bytes == 2) {
+        rtp_write<2, 1>(a);
+    } else {
+        rtp_write<1, 1>(a);
+    }
 }
 
 void launch_rtp_step(const RtpArgs& a, int grid, hipStream_t stream) {
