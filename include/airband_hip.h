@@ -571,6 +571,60 @@ int airband_hip_device_active_encoded(airband_hip_handle* h, void** d_audio, air
  * AIRBAND_HIP_EINVAL for NULL rows, n_rows < 0 (or too many to index), encoding AIRBAND_AUDIO_F32 or unknown; n_rows == 0 is AIRBAND_HIP_OK. */
 int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const float* rows, int64_t n_rows, void* audio, airband_hip_audio_row* info);
 
+/* ---- output decimation ------------------------------------------------------------------------------------------------------------------
+ * "8 kHz mono is exactly RTP payload types 0 and 8" holds for the AM-only build (wave_rate 8000).  A fleet with an NFM channel runs at wave_rate 16000: a row is
+ * 2 000 samples, and its encoded rows, spool clips and RTP packets are 16 kHz G.711, which no stock receiver plays.  The reference never ships 16 kHz to a
+ * listener either: lame converts WAVE_RATE to MP3_RATE 8000 (src/output.cpp:155-161, src/rtl_airband.h:68-76).  A gated handle with an encoding and an output
+ * decimation by 2 does that on the GPU, behind the gate, in the encoder's place: a listed row of B = wave_batch float samples becomes B / 2 encoded samples --
+ * quantise, an integer half-band FIR with a per-channel history carried from batch to batch, every second sample kept, then S16 / mu-law / A-law.  The
+ * transmission spool and the RTP stream of such a handle work on the half-length rows; the full-rate encoded rows are not produced.
+ * The definition (normative).  Integers only behind q: two implementations of this text agree in every byte.
+ * q.     q(x) of "encoded audio collect" above: one float32 multiplication by 32767.0f, clamp, rintf; NaN gives 0; a clamped sample counts as clipped.
+ * Taps.  h[0 .. 46], a symmetric half-band FIR in Q15:
+ *          h[23] = 16384;
+ *          h[23 +- d] for d = 1, 3, .. 23  =  10383, -3332, 1853, -1178, 781, -520, 339, -213, 126, -68, 32, -11;
+ *          every other tap is 0.
+ *        sum h = 32768 and sum |h| = 54056; 54056 * 32767 + 16384 < 2^31, so an int32 accumulator cannot overflow and every summation order gives the same bits
+ *        (a polyphase form is allowed: 24 taps on the even-index samples plus 16384 * one odd-index sample).  The design is a Kaiser window (beta 5.5) on the
+ *        ideal half-band, rounded, the two inner taps adjusted so that the DC gain is exact: -0.019 .. +0.011 dB up to 3.4 kHz and <= -53.0 dB from 4.6 kHz at
+ *        16 kHz input (computed from this table on a 1 Hz grid).
+ * State per channel.  hist[46] holds q values, all zero when the decimation is set.
+ * Step, once per batch in every schedule, behind the gate's list.  "Listed" is the RTP stream's sense: the channel is among the first max_rows channels of the
+ *   batch's list.
+ *   Listed:  S = hist followed by q(row[0 .. B)), B + 46 values.  For n = 0 .. B / 2 - 1: acc = sum_{j = 0 .. 46} h[j] * S[2 n + j]; y = (acc + 16384) >> 15
+ *            (arithmetic shift); y clamps to +-32767.  New hist = S[B .. B + 46).
+ *   Not listed:  hist = 0.  A closed squelch leaves zeros in the row, so for a signal-gated channel this is literally its input; for a channel dropped past
+ *            max_rows, or on a switched-off dongle, it is the defined loss.
+ *   Consecutive listed batches are one uninterrupted convolution.  The constant delay is 23 input samples.
+ * Output.  The encoded row is y[0 .. B / 2) as little-endian int16, or the mu-law / A-law code of y by the text above.
+ * The record.  airband_hip_audio_row, its layout unchanged, computed on y: peak; first and end in OUTPUT-sample indices (B / 2 where there is none; 0 for end);
+ *   n_clipped = the row's clipped input samples (what the undecimated record holds) plus the output samples the +-32767 clamp changed; reserved = 0.
+ * Alignment: a lane of the kernel makes four outputs, so B / 2 must be a multiple of 4.  It is 500 or 1000.
+ * Downstream.  The spool's `audio` rows, `first` of a transmission without a stored row, and the RTP stream's bounds all read the ROW LENGTH for wave_batch:
+ *   40 <= frame_samples <= B / 2, timestamps ts0 + k * (B / 2), carry[F - 4] from the row length.  At wave_rate 16000 a decimated row is 1 000 samples of 8 kHz
+ *   audio: 6.25 frames of 160, payload types 0 and 8.
+ * Out of scope: mixer gates stay at full rate (the filter core, csrc/audio_decimate.h, is written over "S in LDS -> four outputs per lane", so the mixer
+ *   gate's pack can follow); factors other than 2; raw-I/Q rows.
+ * A handle without a decimation allocates nothing for this, launches nothing new and returns the same bits. */
+#define AIRBAND_AUDIO_DECIMATE_TAPS 47
+
+/* factor = 2, or 1 to remove it.  After airband_hip_set_output_encoding() and before the first batch; calling it again before then replaces the setting.
+ * airband_hip_set_output_encoding() or airband_hip_set_output_gate() called again drops it, and setting it drops a transmission spool and an RTP stream on the
+ * handle, as re-setting the encoding does: set those afterwards.  Validated before the device is touched: AIRBAND_HIP_EINVAL for a NULL handle, a handle without an
+ * encoding, any other factor, a batch already enqueued; AIRBAND_HIP_EBADSIZE where wave_batch / 2 is no multiple of 4.  Buffers: [total_channels][46] int16 and
+ * [total_channels] uint32; AIRBAND_HIP_ENOMEM when they cannot be had -- the handle then runs on as it was. */
+int airband_hip_set_output_decimation(airband_hip_handle* h, int32_t factor);
+
+/* Samples of an encoded row: wave_batch, or wave_batch / 2 on a decimating handle; AIRBAND_HIP_EINVAL (negative) for a NULL handle or one without an encoding.
+ * What airband_hip_collect_active_encoded()'s and airband_hip_device_active_encoded()'s `audio`, the spool's `audio` and the RTP stream's bounds are sized by. */
+int airband_hip_encoded_row_samples(const airband_hip_handle* h);
+
+/* The same kernel on caller-provided HOST rows [n_rows][wave_batch] float32, the decimating twin of airband_hip_encode_audio() with the same error rules (and
+ * AIRBAND_HIP_EBADSIZE as above): audio [n_rows][wave_batch / 2] int16 or bytes, info [n_rows] with info[i].channel = i (either may be NULL).
+ * history [n_rows][46] is read and written back, so that a second call on the rows that follow continues the convolution; NULL means zeros in and nothing out.
+ * Needs no gate and touches no handle state; synchronous. */
+int airband_hip_decimate_audio(airband_hip_handle* h, int32_t encoding, const float* rows, int64_t n_rows, int16_t* history, void* audio, airband_hip_audio_row* info);
+
 /* ---- RTP packet stream ------------------------------------------------------------------------------------------------------------------
  * airband_hip_collect_active_encoded() hands the host rows of wave_batch samples -- 1 000 or 2 000, which is 6.25 RTP frames of 20 ms.  The reference's live
  * sink (src/udp_stream.cpp:68-84) sends one float32 datagram per batch: above any MTU, without sequence number, timestamp or stream identity.  A host that

@@ -36,6 +36,7 @@ EXPORTS = [
     "airband_hip_set_scan_control", "airband_hip_scan_hold", "airband_hip_collect_scan_events", "airband_hip_collect_scan_state", "airband_hip_device_scan_control",
     "airband_hip_set_output_gate", "airband_hip_collect_active", "airband_hip_device_active",
     "airband_hip_set_output_encoding", "airband_hip_collect_active_encoded", "airband_hip_device_active_encoded", "airband_hip_encode_audio",
+    "airband_hip_set_output_decimation", "airband_hip_encoded_row_samples", "airband_hip_decimate_audio",
     "airband_hip_set_mixer_gate", "airband_hip_mixer_gate_step", "airband_hip_collect_active_mixers", "airband_hip_device_active_mixers", "airband_hip_encode_mixer_audio",
     "airband_hip_set_transmission_spool", "airband_hip_collect_transmissions", "airband_hip_spool_flush", "airband_hip_spool_counters_get", "airband_hip_device_transmission_spool",
     "airband_hip_set_rtp_stream", "airband_hip_collect_rtp_packets", "airband_hip_collect_rtp_state", "airband_hip_rtp_counters_get", "airband_hip_device_rtp_stream", "airband_hip_rtp_slot_bytes",
@@ -117,7 +118,7 @@ def load_library() -> C.CDLL:
     L.airband_hip_set_output_gate.argtypes = [vp, vp, i64]
     L.airband_hip_collect_active.argtypes = [vp, C.POINTER(i64), vp, vp, vp, vp]
     L.airband_hip_device_active.argtypes = [vp] + [C.POINTER(vp)] * 4
-    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()) + list(capi.TABLES_PROTOTYPES.items()) + list(capi.MIXER_GATE_PROTOTYPES.items()) + list(capi.MIXER_SPOOL_PROTOTYPES.items()) + list(capi.RTP_STREAM_PROTOTYPES.items()) + list(capi.MIXER_RTP_PROTOTYPES.items()):
+    for name, argtypes in list(capi.BAND_SCOPE_PROTOTYPES.items()) + list(capi.BAND_SURVEY_PROTOTYPES.items()) + list(capi.BAND_WATCH_PROTOTYPES.items()) + list(capi.BAND_FOLLOW_PROTOTYPES.items()) + list(capi.AUDIO_ENCODING_PROTOTYPES.items()) + list(capi.AUDIO_DECIMATION_PROTOTYPES.items()) + list(capi.SCAN_CONTROL_PROTOTYPES.items()) + list(capi.TRANSMISSION_SPOOL_PROTOTYPES.items()) + list(capi.TABLES_PROTOTYPES.items()) + list(capi.MIXER_GATE_PROTOTYPES.items()) + list(capi.MIXER_SPOOL_PROTOTYPES.items()) + list(capi.RTP_STREAM_PROTOTYPES.items()) + list(capi.MIXER_RTP_PROTOTYPES.items()):
         if hasattr(L, name):  # (AIRBAND_HIP_LIB may name an older build for an A/B measurement: scripts/band_scope_profile.py --parent-lib)
             getattr(L, name).argtypes = argtypes
     L.airband_hip_collect_mixers.argtypes = [vp, vp, vp, vp]
@@ -365,6 +366,7 @@ class AirbandHip:
         self.gate_rows = rows
         self.gate_bytes = gate.copy()  # set_rtp_stream()'s default sources: every channel whose gate is not NEVER
         self.audio_encoding = capi.AUDIO_F32  # a new gate drops the encoding
+        self.audio_decimation = 1  # ... and its decimation
         self.rtp = None  # ... and the RTP stream with it
 
     def collect_active(self, *, iq: bool = False) -> dict:
@@ -396,15 +398,34 @@ class AirbandHip:
         enc = capi.AUDIO_F32 if encoding is None else capi.audio_encoding_value(encoding)
         self._check(self.L.airband_hip_set_output_encoding(self.h, enc))
         self.audio_encoding = enc
-        self.rtp = None  # a new encoding drops the RTP stream
+        self.audio_decimation = 1  # a new encoding drops the decimation
+        self.rtp = None  # ... and the RTP stream
+
+    def set_output_decimation(self, factor):
+        """factor: 2, or None / 1 to remove it (airband_hip_set_output_decimation): behind the gate a listed row of B samples becomes B / 2 encoded samples through
+        an integer half-band FIR with a per-channel history.  After set_output_encoding(), before the first batch; it drops a transmission spool and an RTP stream."""
+        f = 1 if factor is None else int(factor)
+        self._check(self.L.airband_hip_set_output_decimation(self.h, f))
+        self.audio_decimation = f
+        self.rtp = None
+        self.spool_export_rows = self.spool_max_records = 0
+
+    def encoded_row_samples(self) -> int:
+        """Samples of an encoded row (airband_hip_encoded_row_samples): B, or B / 2 on a decimating handle."""
+        return self._check(self.L.airband_hip_encoded_row_samples(self.h))
+
+    def _encoded_row(self) -> int:
+        """encoded_row_samples() for sizing a collect's arrays; B on a handle without an encoding (the call then reports the error itself)"""
+        n = self.L.airband_hip_encoded_row_samples(self.h) if hasattr(self.L, "airband_hip_encoded_row_samples") else self.B
+        return n if n > 0 else self.B
 
     def _audio_dtype(self, enc):
         return np.dtype("<i2") if enc == capi.AUDIO_S16 else np.dtype(np.uint8)
 
     def collect_active_encoded(self) -> dict:
         """collect_active() with encoded rows (airband_hip_collect_active_encoded): n_active, channels [n] ascending, audio [n][B] int16 ("s16") or uint8 (G.711),
-        info [n] of capi.AUDIO_ROW_DTYPE, axcindicate of every channel."""
-        rows, B = max(self.gate_rows, 1), self.B
+        info [n] of capi.AUDIO_ROW_DTYPE, axcindicate of every channel.  On a decimating handle the rows are encoded_row_samples() = B / 2 long."""
+        rows, B = max(self.gate_rows, 1), self._encoded_row()
         n = C.c_int64(0)
         idx = np.empty((rows,), np.int32)
         audio = np.empty((rows, B), self._audio_dtype(getattr(self, "audio_encoding", capi.AUDIO_F32)))
@@ -433,6 +454,22 @@ class AirbandHip:
         self._check(self.L.airband_hip_encode_audio(self.h, enc, rows.ctypes.data, n, audio.ctypes.data, info.ctypes.data))
         return audio, info
 
+    def decimate_audio(self, rows, encoding, history=None):
+        """The decimating kernel on host rows [n][B] float32 (airband_hip_decimate_audio): (audio [n][B / 2] int16 or uint8, info [n] of capi.AUDIO_ROW_DTYPE,
+        history [n][46] int16 to hand to the next call on the rows that follow; None in means zeros)."""
+        enc = capi.audio_encoding_value(encoding)
+        rows = np.ascontiguousarray(rows, np.float32)
+        if rows.ndim != 2 or rows.shape[1] != self.B:
+            raise ValueError("rows must be [n][%d], got shape %r" % (self.B, rows.shape))
+        n = rows.shape[0]
+        hist = np.zeros((n, capi.AUDIO_DECIMATE_HISTORY), "<i2") if history is None else np.array(history, "<i2", order="C")
+        if hist.shape != (n, capi.AUDIO_DECIMATE_HISTORY):
+            raise ValueError("history must be [%d][%d], got shape %r" % (n, capi.AUDIO_DECIMATE_HISTORY, hist.shape))
+        audio = np.empty((n, self.B // 2), self._audio_dtype(enc))
+        info = np.empty((n,), capi.AUDIO_ROW_DTYPE)
+        self._check(self.L.airband_hip_decimate_audio(self.h, enc, rows.ctypes.data, n, hist.ctypes.data, audio.ctypes.data, info.ctypes.data))
+        return audio, info, hist
+
     def set_transmission_spool(self, pool_rows, export_rows=None, max_records=None, mask=None, min_batches=8, idle_batches=4, max_batches=480):
         """Transmission spool (airband_hip_set_transmission_spool): the GPU keeps the encoded rows of every open transmission and hands over finished ones.
         export_rows: default max(pool_rows, max_batches + 1); max_records: default the channel count; mask: one byte per channel (None = every SIGNAL channel).
@@ -451,7 +488,7 @@ class AirbandHip:
         [sum of n_rows][B] int16 ("s16") or uint8 (G.711) -- transmission i's rows are audio[row_offset : row_offset + n_rows] -- and n_waiting."""
         enc = getattr(self, "audio_encoding", capi.AUDIO_F32)
         records = np.empty((max(getattr(self, "spool_max_records", 0), 1),), capi.TRANSMISSION_DTYPE)
-        audio = np.empty((max(getattr(self, "spool_export_rows", 0), 1), self.B), self._audio_dtype(enc))
+        audio = np.empty((max(getattr(self, "spool_export_rows", 0), 1), self._encoded_row()), self._audio_dtype(enc))
         n, n_rows, n_waiting = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         self._check(self.L.airband_hip_collect_transmissions(self.h, C.byref(n), records.ctypes.data, audio.ctypes.data, C.byref(n_rows), C.byref(n_waiting)))
         return dict(records=records[:n.value], audio=audio[:n_rows.value], n_waiting=int(n_waiting.value))
@@ -484,7 +521,8 @@ class AirbandHip:
             self.rtp = None
             return
         enc = getattr(self, "audio_encoding", capi.AUDIO_F32)
-        F = int(self.geometry.wave_rate) // 50 if frame_samples is None else int(frame_samples)
+        row = self._encoded_row()  # B, or B / 2 behind the output decimation: 20 ms are half as many samples there
+        F = int(self.geometry.wave_rate) * row // self.B // 50 if frame_samples is None else int(frame_samples)
         if sources is None:
             src = np.zeros(self.total_channels, capi.RTP_SOURCE_DTYPE)
             src["ssrc"] = np.arange(self.total_channels)
@@ -495,7 +533,7 @@ class AirbandHip:
             if src.shape != (self.total_channels,):
                 raise ValueError("sources needs one record per channel (%d), got shape %r" % (self.total_channels, src.shape))
         if max_packets is None:
-            max_packets = max(1, int(np.count_nonzero(src["stream"])) * ((max(F, 4) - 4 + self.B) // max(F, 1)))
+            max_packets = max(1, int(np.count_nonzero(src["stream"])) * ((max(F, 4) - 4 + row) // max(F, 1)))
         self._check(self.L.airband_hip_set_rtp_stream(self.h, src.ctypes.data, F, int(max_packets)))
         self.rtp = dict(frame_samples=F, max_packets=int(max_packets), slot_bytes=self._check(self.L.airband_hip_rtp_slot_bytes(enc, F)), sources=src)
 

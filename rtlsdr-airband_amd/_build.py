@@ -41,6 +41,7 @@ HIP_SOURCES = {
     "demod.hip": ["-O3", "-ffp-contract=off", "-fhip-fp32-correctly-rounded-divide-sqrt"],
     "gate.hip": ["-O3"],  # signal-gated collect: integer passes and a row copy
     "audio_pack.hip": ["-O3", "-ffp-contract=off"],  # encoded audio collect: one float multiplication per sample, then integers (int16 / G.711) and a row record
+    "audio_decimate.hip": ["-O3", "-ffp-contract=off"],  # output decimation by 2: the encoder's float step, then an integer half-band FIR over LDS, int16 / G.711 and the row record
     "mixer_gate.hip": ["-O3", "-ffp-contract=off"],  # gated mixer collect: the gate's integer passes over the mixers, then the encoder's arithmetic on frames of left / right
     "tx_spool.hip": ["-O3"],  # transmission spool: integer passes over per-channel records, a row pool and row copies
     "rtp_stream.hip": ["-O3"],  # RTP packet stream: integer passes over per-channel sender state, prefix sums, and dword copies of rows into packet slots

@@ -520,6 +520,62 @@ def audio_decode_reference(codes, encoding):
     raise ValueError("unknown encoding: %r" % (encoding,))
 
 
+# the output decimation's (same header)
+AUDIO_DECIMATION_PROTOTYPES = {
+    "airband_hip_set_output_decimation": [_vp, _i32],
+    "airband_hip_encoded_row_samples": [_vp],
+    "airband_hip_decimate_audio": [_vp, _i32, _vp, _i64, _vp, _vp, _vp],
+}
+AUDIO_DECIMATE_HISTORY = 46  # q values a channel carries from batch to batch
+_DECIMATE_SIDE = (10383, -3332, 1853, -1178, 781, -520, 339, -213, 126, -68, 32, -11)  # h[23 +- d], d = 1, 3, .. 23
+
+
+def _decimate_taps():
+    import numpy as np
+
+    h = np.zeros(47, np.int64)
+    h[23] = 16384
+    for i, t in enumerate(_DECIMATE_SIDE):
+        h[23 + 2 * i + 1] = h[23 - 2 * i - 1] = t
+    h.setflags(write=False)
+    return h
+
+
+AUDIO_DECIMATE_TAPS = _decimate_taps()  # h[0 .. 46] in Q15 (AIRBAND_AUDIO_DECIMATE_TAPS values)
+
+
+def audio_decimate_reference(rows, encoding, history=None):
+    """The output decimation's definition (include/airband_hip.h) in numpy.  rows [n][B] float32 (B even), encoding "s16" / "ulaw" / "alaw" or an AUDIO_* value,
+    history [n][46] int16 (None: zeros) -> (audio [n][B / 2] int16 or uint8, info [n] of AUDIO_ROW_DTYPE with channel = the row's number, history_out [n][46] int16)."""
+    import numpy as np
+
+    enc = audio_encoding_value(encoding)
+    rows = np.ascontiguousarray(rows, np.float32)
+    n, B = rows.shape
+    if B % 2:
+        raise ValueError("rows of an odd length: %d" % B)
+    H, Bo = AUDIO_DECIMATE_HISTORY, B // 2
+    hist = np.zeros((n, H), np.int64) if history is None else np.asarray(history).astype(np.int64).reshape(n, H)
+    q, clipped = audio_quantize_reference(rows)
+    S = np.concatenate([hist, q.astype(np.int64)], axis=1)
+    acc = np.zeros((n, Bo), np.int64)
+    for j, t in enumerate(AUDIO_DECIMATE_TAPS):
+        if t:
+            acc += int(t) * S[:, j:j + B:2]
+    r = (acc + 16384) >> 15
+    y = np.clip(r, -32767, 32767)
+    audio = y.astype("<i2") if enc == AUDIO_S16 else audio_law_reference(y.astype(np.int32), enc)
+    info = np.zeros(n, AUDIO_ROW_DTYPE)
+    info["channel"] = np.arange(n)
+    nz = y != 0
+    some = nz.any(axis=1)
+    info["peak"] = np.abs(y).max(axis=1) if Bo else 0
+    info["n_clipped"] = clipped.sum(axis=1) + (y != r).sum(axis=1)
+    info["first"] = np.where(some, nz.argmax(axis=1), Bo)
+    info["end"] = np.where(some, Bo - nz[:, ::-1].argmax(axis=1), 0)
+    return audio, info, S[:, B:].astype("<i2")
+
+
 # the gated mixer collect's (same header)
 MIXER_GATE_STEREO, MIXER_GATE_MANUAL_STEP = 0x1, 0x2
 MIXER_GATE_PROTOTYPES = {

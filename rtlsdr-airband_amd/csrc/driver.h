@@ -131,6 +131,7 @@ static inline bool has_watch(const airband_hip_handle* h) { return has_survey(h)
 static inline bool has_follow(const airband_hip_handle* h) { return has_watch(h) && h->scope.survey.watch.follow.max_changes > 0; }
 static inline bool has_gate(const airband_hip_handle* h) { return h->gate.max_rows > 0; }
 static inline bool has_encoding(const airband_hip_handle* h) { return has_gate(h) && h->gate.enc.encoding != AIRBAND_AUDIO_F32; }
+static inline bool has_decimation(const airband_hip_handle* h) { return has_encoding(h) && h->gate.enc.dec.factor == 2; }
 static inline bool has_spool(const airband_hip_handle* h) { return has_encoding(h) && h->gate.enc.spool.pool_rows > 0; }
 static inline bool has_rtp(const airband_hip_handle* h) { return has_encoding(h) && h->gate.enc.rtp.max_packets > 0; }
 static inline bool has_mixer_gate(const airband_hip_handle* h) { return h->mix.n_mixers > 0 && h->mix_gate.max_rows > 0; }

@@ -4,7 +4,9 @@
  * spool (driver_mix.cpp: airband_hip_set_mixer_spool and its collect / flush / counters / device entry points) goes through the same functions.  The RTP packet
  * stream (airband_hip_set_rtp_stream and its collect / state / counters / device entry points) is a second reader of the encoder's rows, beside the spool; its
  * host side is written over an RtpStream and a SpoolSource in the same way, and the mixer RTP stream (driver_mix.cpp: airband_hip_set_mixer_rtp_stream and its
- * entry points) goes through it. */
+ * entry points) goes through it.  The output decimation (airband_hip_set_output_decimation / _encoded_row_samples / _decimate_audio) halves the encoder's rows:
+ * its kernel is launched in the encoder's place, and the spool and the stream read rows of half the length. */
+#include "audio_decimate.h" /* AUDIO_DECIMATE_HIST */
 #include "driver.h"
 
 using namespace airband;
@@ -49,6 +51,31 @@ static AudioPackArgs audio_pack_args(const airband_hip_handle* h) {
     return a;
 }
 
+/* samples of an encoded row: wave_batch, or half of it behind the output decimation (airband_hip_encoded_row_samples) */
+static int encoded_row_samples(const airband_hip_handle* h) { return has_decimation(h) ? h->B / 2 : h->B; }
+
+/* the same list, count and source rows, the channels' carried values; k: the step's number (airband_hip_set_output_decimation) */
+static AudioDecimateArgs audio_decimate_args(const airband_hip_handle* h, uint32_t k) {
+    const OutputGate& g = h->gate;
+    AudioDecimateArgs a;
+    a.index = g.d_index.p;
+    a.count = g.d_count.p;
+    a.n_rows = 0;
+    a.max_rows = g.max_rows;
+    a.n_ch = h->plan.total_ch;
+    a.src = h->d_out_wave.p;
+    a.src_stride = h->wave_stride;
+    a.src_pad = AB_OUT_PAD;
+    a.audio = g.enc.d_audio.p;
+    a.info = g.enc.d_info.p;
+    a.hist = g.enc.dec.d_hist.p;
+    a.stamp = g.enc.dec.d_stamp.p;
+    a.k = k;
+    a.wave_batch = h->B;
+    a.encoding = g.enc.encoding;
+    return a;
+}
+
 /* what the channel spool reads: the output gate's verdicts and the encoder's rows (airband_hip_set_transmission_spool) */
 static SpoolSource channel_spool_source(const airband_hip_handle* h) {
     const OutputGate& g = h->gate;
@@ -59,7 +86,7 @@ static SpoolSource channel_spool_source(const airband_hip_handle* h) {
     src.info = g.enc.d_info.p;
     src.n = h->plan.total_ch;
     src.max_rows = g.max_rows;
-    src.frames = h->B;
+    src.frames = encoded_row_samples(h);
     src.width = 1;
     return src;
 }
@@ -426,7 +453,8 @@ static int collect_active_rows(airband_hip_handle* h, int64_t* n_active, int32_t
 /* behind the emit / mixer launches of a gated handle's batch: its active channels and their rows, packed (gate.hip) ... */
 void airband::launch_gate_behind_mix(airband_hip_handle* h, hipStream_t s) {
     launch_gate(gate_args(h), s);
-    if (has_encoding(h)) launch_audio_pack(audio_pack_args(h), 0, s); /* ... and encoded (audio_pack.hip) */
+    if (has_decimation(h)) launch_audio_decimate(audio_decimate_args(h, ++h->gate.enc.dec.steps), 0, s); /* ... and encoded at half the rate (audio_decimate.hip) */
+    else if (has_encoding(h)) launch_audio_pack(audio_pack_args(h), 0, s); /* ... or encoded as they are (audio_pack.hip) */
     if (has_spool(h)) spool_step(h->gate.enc.spool, channel_spool_source(h), s); /* ... and the spool's step of this batch (tx_spool.hip) */
     if (has_rtp(h)) rtp_step(h->gate.enc.rtp, channel_spool_source(h), s);       /* ... and the RTP stream's (rtp_stream.hip): another reader of the same rows */
 }
@@ -520,7 +548,7 @@ int airband_hip_collect_active_encoded(airband_hip_handle* h, int64_t* n_active,
     if (!has_encoding(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_ENCODING);
     if (!h->results_ready || h->batches_done == 0) return AIRBAND_HIP_EAGAIN;
     return collect_active_rows(h, n_active, channel_index, axc_all, [&](size_t n, hipStream_t s) -> int {
-        if (audio && n) HIP_TRY(h, hipMemcpyAsync(audio, g.enc.d_audio.p, n * h->B * audio_sample_bytes(g.enc.encoding), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
+        if (audio && n) HIP_TRY(h, hipMemcpyAsync(audio, g.enc.d_audio.p, n * encoded_row_samples(h) * audio_sample_bytes(g.enc.encoding), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
         if (info && n) HIP_TRY(h, hipMemcpyAsync(info, g.enc.d_info.p, n * sizeof(airband_hip_audio_row), hipMemcpyDeviceToHost, s), AIRBAND_HIP_ERUNTIME);
         return AIRBAND_HIP_OK;
     });
@@ -575,6 +603,81 @@ int airband_hip_encode_audio(airband_hip_handle* h, int32_t encoding, const floa
     return AIRBAND_HIP_OK;
 }
 
+int airband_hip_set_output_decimation(airband_hip_handle* h, int32_t factor) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    OutputGate& g = h->gate;
+    if (!has_encoding(h)) return fail(h, AIRBAND_HIP_EINVAL, NO_ENCODING);
+    if (factor != 1 && factor != 2) return fail(h, AIRBAND_HIP_EINVAL, "the output decimation's factor is 1 or 2");
+    if (started(h)) return fail(h, AIRBAND_HIP_EINVAL, "the output decimation is set before the first batch");
+    if (factor == 2 && h->B % 8) return fail(h, AIRBAND_HIP_EBADSIZE, "a lane makes four outputs: WAVE_BATCH / 2 must be a multiple of four");
+    /* built beside the encoding and moved in whole: a failed allocation leaves the handle as it was */
+    OutputDecimation dec;
+    if (factor == 2) {
+        HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+        hipError_t e = dec.d_hist.alloc_zeroed((size_t)h->plan.total_ch * AUDIO_DECIMATE_HIST);
+        if (e == hipSuccess) e = dec.d_stamp.alloc_zeroed((size_t)h->plan.total_ch);
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr); /* the zeroes are there before a step on another stream reads them */
+        if (e != hipSuccess) return alloc_failed(h, e, "output decimation buffers: ");
+        dec.factor = 2;
+    }
+    g.enc.dec = std::move(dec);
+    g.enc.spool = TransmissionSpool(); /* they were sized for rows of the other length */
+    g.enc.rtp = RtpStream();
+    return AIRBAND_HIP_OK;
+}
+
+int airband_hip_encoded_row_samples(const airband_hip_handle* h) {
+    if (!h || !has_encoding(h)) return AIRBAND_HIP_EINVAL;
+    return encoded_row_samples(h);
+}
+
+int airband_hip_decimate_audio(airband_hip_handle* h, int32_t encoding, const float* rows, int64_t n_rows, int16_t* history, void* audio, airband_hip_audio_row* info) {
+    if (!h) return AIRBAND_HIP_EINVAL;
+    if (!rows) return fail(h, AIRBAND_HIP_EINVAL, "NULL argument");
+    if (!audio_encoding_known(encoding)) return fail(h, AIRBAND_HIP_EINVAL, "encoding is not AIRBAND_AUDIO_S16, _ULAW or _ALAW");
+    if (n_rows < 0 || n_rows > 0x7fffffff / 4) return fail(h, AIRBAND_HIP_EINVAL, "n_rows out of range");
+    if (h->B % 8) return fail(h, AIRBAND_HIP_EBADSIZE, "a lane makes four outputs: WAVE_BATCH / 2 must be a multiple of four");
+    if (n_rows == 0) return AIRBAND_HIP_OK;
+    HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
+    /* buffers of the call's own, on the null stream: nothing of the handle is read or written */
+    const size_t n = (size_t)n_rows, B = (size_t)h->B, row_bytes = B / 2 * audio_sample_bytes(encoding), hist_bytes = n * AUDIO_DECIMATE_HIST * sizeof(int16_t);
+    DevBuf<float> d_rows;
+    DevBuf<uint8_t> d_audio;
+    DevBuf<airband_hip_audio_row> d_info;
+    DevBuf<int16_t> d_hist;
+    hipError_t e = d_rows.alloc(n * B);
+    if (e == hipSuccess) e = d_audio.alloc(n * row_bytes);
+    if (e == hipSuccess) e = d_info.alloc(n);
+    if (e == hipSuccess && history) e = d_hist.alloc(n * AUDIO_DECIMATE_HIST);
+    if (e != hipSuccess) return alloc_failed(h, e, "decimate_audio buffers: ");
+    HIP_TRY(h, hipMemcpy(d_rows.p, rows, n * B * sizeof(float), hipMemcpyHostToDevice), AIRBAND_HIP_ERUNTIME);
+    if (history) HIP_TRY(h, hipMemcpy(d_hist.p, history, hist_bytes, hipMemcpyHostToDevice), AIRBAND_HIP_ERUNTIME);
+    AudioDecimateArgs a;
+    a.index = nullptr;
+    a.count = nullptr;
+    a.n_rows = (int)n_rows;
+    a.max_rows = (int)n_rows;
+    a.n_ch = (int)n_rows;
+    a.src = d_rows.p;
+    a.src_stride = (long)B;
+    a.src_pad = 0;
+    a.audio = d_audio.p;
+    a.info = d_info.p;
+    a.hist = history ? d_hist.p : nullptr;
+    a.stamp = nullptr;
+    a.k = 0;
+    a.wave_batch = h->B;
+    a.encoding = encoding;
+    launch_audio_decimate(a, 0, nullptr);
+    e = hipGetLastError();
+    if (e != hipSuccess) return fail(h, AIRBAND_HIP_ERUNTIME, std::string("kernel launch: ") + hipGetErrorString(e));
+    if (audio) HIP_TRY(h, hipMemcpy(audio, d_audio.p, n * row_bytes, hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
+    if (info) HIP_TRY(h, hipMemcpy(info, d_info.p, n * sizeof(airband_hip_audio_row), hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
+    if (history) HIP_TRY(h, hipMemcpy(history, d_hist.p, hist_bytes, hipMemcpyDeviceToHost), AIRBAND_HIP_ERUNTIME);
+    HIP_TRY(h, hipStreamSynchronize(nullptr), AIRBAND_HIP_ERUNTIME); /* the buffers go with this call */
+    return AIRBAND_HIP_OK;
+}
+
 int airband_hip_set_transmission_spool(airband_hip_handle* h, const uint8_t* spool, int64_t pool_rows, int64_t export_rows, int64_t max_records, int32_t min_batches, int32_t idle_batches, int32_t max_batches) {
     if (!h) return AIRBAND_HIP_EINVAL;
     OutputGate& g = h->gate;
@@ -592,7 +695,7 @@ int airband_hip_set_transmission_spool(airband_hip_handle* h, const uint8_t* spo
     HIP_TRY(h, hipSetDevice(h->hip_device), AIRBAND_HIP_ENODEV);
     /* built beside the encoding and moved in whole: a failed allocation leaves the handle as it was */
     TransmissionSpool sp;
-    rc = spool_build(h, sp, mask, g.max_rows, (size_t)h->B * audio_sample_bytes(g.enc.encoding), pool_rows, export_rows, max_records, min_batches, idle_batches, max_batches,
+    rc = spool_build(h, sp, mask, g.max_rows, (size_t)encoded_row_samples(h) * audio_sample_bytes(g.enc.encoding), pool_rows, export_rows, max_records, min_batches, idle_batches, max_batches,
                      "transmission spool buffers: ");
     if (rc != AIRBAND_HIP_OK) return rc;
     g.enc.spool = std::move(sp);

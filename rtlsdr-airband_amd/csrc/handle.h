@@ -158,9 +158,19 @@ struct MixerGate {
 
 /* what airband_hip_set_output_encoding() set up, a part of the gate whose list it reads: replaced as a whole, gone with the gate, AIRBAND_AUDIO_F32 is a gate
  * without an encoding (nothing allocated, nothing launched) */
+/* what airband_hip_set_output_decimation() set up, a part of the encoding whose rows it halves: the channels' carried filter values and the step that listed
+ * each last.  The encoding's d_audio keeps its size; its rows are wave_batch / 2 samples long then */
+struct OutputDecimation {
+    int factor = 1;            /* 1 = none (nothing allocated, audio_pack.hip encodes); 2: audio_decimate.hip in its place, rows of wave_batch / 2 */
+    uint32_t steps = 0;        /* steps enqueued so far; step numbers start at 1 (kernels.h: AudioDecimateArgs::k) */
+    DevBuf<int16_t> d_hist;    /* [total_ch][46] */
+    DevBuf<uint32_t> d_stamp;  /* [total_ch] */
+};
+
 struct OutputEncoding {
     TransmissionSpool spool;
     RtpStream rtp;
+    OutputDecimation dec;      /* airband_hip_set_output_decimation: replaced as a whole, gone with the encoding */
     int encoding = AIRBAND_AUDIO_F32;
     DevBuf<uint8_t> d_audio; /* [max_rows][wave_batch] bytes, or int16 for S16 */
     DevBuf<airband_hip_audio_row> d_info;

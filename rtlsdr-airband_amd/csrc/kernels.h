@@ -327,6 +327,27 @@ struct AudioPackArgs {
 };
 void launch_audio_pack(const AudioPackArgs& a, int grid, hipStream_t stream); /* grid: workgroups, 0 = min(max_rows, one per wavefront slot of the GPU) */
 
+/* output decimation by 2 (audio_decimate.hip), in launch_audio_pack's place on a decimating handle: rows of wave_batch / 2 samples as int16 or G.711 bytes and
+ * one record per row, through the half-band FIR of audio_decimate.h with 46 carried values per channel; the same shape of launch */
+struct AudioDecimateArgs {
+    const int* index;         /* [max_rows] row r is channel index[r] (the gate's list); null: row r is source row r (airband_hip_decimate_audio) */
+    const int* count;         /* [1] on the device: the gate's count (may exceed max_rows); null: n_rows */
+    int n_rows;
+    int max_rows, n_ch;       /* the clamps: rows written, source rows (and histories) there are */
+    const float* src;         /* source row c starts at src + c * src_stride + src_pad, 16-byte aligned */
+    long src_stride;
+    int src_pad;
+    void* audio;              /* [max_rows][wave_batch / 2] int16 (S16) or bytes (G.711) */
+    airband_hip_audio_row* info; /* [max_rows] */
+    int16_t* hist;            /* [n_ch][46] the q values a channel carries, read and written back; null: zeros in, nothing out */
+    uint32_t* stamp;          /* [n_ch] the last step that listed the channel: its history counts only if that is k - 1; null: it always counts */
+    uint32_t k;               /* the step's number, 1, 2, ... (a zeroed stamp is "listed in step 0", with the zeroed history every channel starts from) */
+    int wave_batch;           /* a multiple of eight */
+    int encoding;             /* AIRBAND_AUDIO_S16 / _ULAW / _ALAW */
+};
+size_t audio_decimate_lds_bytes(int wave_batch); /* the launch's dynamic LDS */
+void launch_audio_decimate(const AudioDecimateArgs& a, int grid, hipStream_t stream); /* grid: as launch_audio_pack's */
+
 /* gated mixer collect (mixer_gate.hip): the batch's active mixers, ascending (gate_passes.h), and their rows packed as float32, int16 or G.711 frames */
 struct MixerGateArgs {
     const uint8_t* gate;       /* [n_mixers] AIRBAND_GATE_* */
